@@ -2,6 +2,7 @@
 """bench.py — audio-seconds/sec of WavTokenizer encode_infer + decode on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--arch hop600|hop320] [--clips 64]
+                    [--dump-outputs DIR]
 
 One "step" = one encode_infer + decode round trip of `--clips` independent 3 s / 24 kHz clips
 per GPU (BASELINE.json configs[1]: WavTokenizer-small-600, batch 64 x 3 s), inputs already
@@ -11,9 +12,16 @@ torch.distributed.run; clips shard across ranks with no collective on the data p
 scaling) and the per-step codes all-gather + waveform gather to rank 0 over RCCL is inside the
 timed region.  Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then R blocks of exactly K steps, each block bracketed by a barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  `ms_per_step` / `value` are
-the MEDIAN block (a single 0.13 s block is a thin basis: the min / max over the blocks are on the line too).
+Timing: W warm-up steps, then exactly K timed steps in one block bracketed by a barrier +
+torch.cuda.synchronize() on both sides and reduced with MAX over ranks.  `--repeats R` times R such
+blocks of K steps instead; `ms_per_step` / `value` are then the MEDIAN block (the min / max over the
+blocks are on the line too).
+
+--dump-outputs DIR: after the timed steps, what the headline's last step handed its caller (codes and
+reconstructed waveforms; at N > 1 with the gather, rank 0's gathered batch) is written as DIR/codes.npy
+(float64, exact) and DIR/waveform.npy (float32).  Inputs and weights come from fixed seeds, so two
+builds run with the same arguments can be compared output for output.  Above 64 MB in all, both keep
+the same fixed, seeded sample of clips (`outputs.clips_kept` on the line).
 
 Schedule of the headline (config.lanes): at N = 1 the K steps of a block are issued alternately on TWO HIP streams
 (sharding.StepRunner(lanes=2): step i+1's encode_infer runs beside step i's decode and fills its launch gaps and last-round
@@ -159,6 +167,34 @@ def pmc_traffic(arch_name, B, clip_seconds):
     return None
 
 
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs writes less than this in all
+
+
+def dump_outputs(out_dir, codes, wav):
+    """--dump-outputs: codes (K, B, L) as float64 (exact) and waveforms (B, T') as float32 under out_dir.  If both together
+    would exceed DUMP_BYTES, the same fixed, seeded sample of clips is kept in both.  Returns what was written."""
+    import numpy as np
+    arrays = {"codes": codes.cpu().numpy().astype(np.float64)}
+    if wav is not None:
+        arrays["waveform"] = wav.cpu().numpy().astype(np.float32)
+    n = arrays["codes"].shape[1]
+    per_clip = sum(a.nbytes for a in arrays.values()) // n
+    keep = min(n, (DUMP_BYTES - 4096) // per_clip)          # 4096: room for the .npy headers
+    if keep < 1:
+        raise SystemExit(f"--dump-outputs: one clip's outputs ({per_clip} bytes) exceed {DUMP_BYTES} bytes")
+    clips = "all"
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays["codes"] = arrays["codes"][:, idx]
+        if "waveform" in arrays:
+            arrays["waveform"] = arrays["waveform"][idx]
+        clips = idx.tolist()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "shapes": {k: list(a.shape) for k, a in arrays.items()}, "clips_kept": clips}
+
+
 def make_model(arch_name, dev):
     from wavtokenizer_amd import WavTokenizer, NAMED_ARCHS, synth
     arch = NAMED_ARCHS[arch_name]
@@ -175,9 +211,11 @@ def make_model(arch_name, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (per block)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; the line carries the median block")
+    ap.add_argument("--repeats", type=int, default=1, help="timed blocks of --steps steps; the line carries the median block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's last-step outputs as DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--arch", default="hop600", choices=["hop600", "hop320"])
     ap.add_argument("--clips", type=int, default=64, help="clips per GPU per step")
     ap.add_argument("--clip-seconds", type=int, default=3, help="clip length (BASELINE configs[4] uses 30 s clips)")
@@ -195,6 +233,8 @@ def main():
                     help="nccl = RCCL over xGMI (the measured path); gloo only rehearses the N>1 flow on a box with "
                          "fewer GPUs than ranks (ranks share GPUs, collectives go through host memory)")
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1 or args.warmup < 0:
+        raise SystemExit("--steps and --repeats must be >= 1, --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -251,8 +291,8 @@ def main():
             barrier()
             t0 = time.perf_counter()
             for _ in range(steps):
-                runner.step()
-            runner.drain()
+                last = runner.step()
+            drained = runner.drain()
             barrier()
             dt = time.perf_counter() - t0
             runner.own_blocks.append(dt)                    # this rank's own clock; the line carries the MAX over ranks
@@ -263,6 +303,9 @@ def main():
             _capi.check(_capi.lib.wt_plan_read_timing(time_plan[0], ctypes.byref(tot_ms), ctypes.byref(n_l), 1), "wt_plan_read_timing")
             _capi.lib.wt_plan_set_timing(time_plan[0], b"")
             kern = (tot_ms.value, n_l.value)
+        # what the caller of the last timed step receives: (codes, waveforms) of this rank's clips, or with the exchange
+        # the gathered batch that drain() collects (waveforms on rank 0 only)
+        runner.last_outputs = drained if drained is not None else last[:2]
         return blocks, kern
 
     # ------------------------------------------------------------------------------ the headline workload
@@ -291,6 +334,9 @@ def main():
         blocks, _ = run_blocks(runner, args.steps, max(lanes, args.warmup), args.repeats)
         model.check_status()
     own_blocks = list(runner.own_blocks)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *runner.last_outputs)
 
     # N > 1: what every rank saw, so that the first run on a real multi-GPU node explains itself (rank 0 prints it)
     ranks_info = None
@@ -339,7 +385,8 @@ def main():
                           "on the plain fp32 MFMA chain is other_configs.fp32_gemm_chain_64x3s; measured error of both against a float64 "
                           "run of the oracle: tests/test_gpu_parity.py::test_precision_against_float64 (profiles/r03_gpu_parity_summary.json)",
             "data": "synthetic",
-            "timing": {"blocks": len(per_step), "steps_per_block": args.steps, "statistic": "median block",
+            "timing": {"blocks": len(per_step), "steps_per_block": args.steps,
+                       "statistic": "median block" if len(per_step) > 1 else "one block",
                        "ms_per_step_min": round(per_step[0], 3), "ms_per_step_max": round(per_step[-1], 3),
                        "ms_per_step_blocks": [round(x, 3) for x in per_step],
                        "value_min": round(world * B * clip_s / (per_step[-1] * 1e-3), 1),
@@ -380,6 +427,8 @@ def main():
                          "end_to_end_tflops": round(e2e_tflops, 2),
                          "end_to_end_frac": round(e2e_tflops / PEAK_F16X3_TFLOPS, 4)},
         }
+        if dumped is not None:
+            line["outputs"] = dumped
 
     # ------------------------------------------------------------------------------ other configs (N = 1)
     if world == 1 and rank == 0 and not args.no_other_configs and args.arch == "hop600" and clip_s == 3:

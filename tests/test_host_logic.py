@@ -283,6 +283,36 @@ def test_bench_finds_the_dominant_kernel_in_the_committed_pmc_summary():
     assert t is not None and 101e6 < t < 400e6, t
 
 
+def test_bench_dump_outputs_exact_and_bounded(tmp_path):
+    """bench.py --dump-outputs: codes exact as float64, waveforms float32; a batch over the size bound keeps the same
+    seeded clips in both arrays, identically from call to call, and stays under the bound."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    codes = torch.randint(0, 4096, (1, 8, 120), generator=g)
+    wav = torch.randn(8, 72000, generator=g)
+    info = bench.dump_outputs(str(tmp_path / "small"), codes, wav)
+    assert info["clips_kept"] == "all"
+    c, w = np.load(tmp_path / "small" / "codes.npy"), np.load(tmp_path / "small" / "waveform.npy")
+    assert c.dtype == np.float64 and np.array_equal(c, codes.numpy())
+    assert w.dtype == np.float32 and np.array_equal(w, wav.numpy())
+    # 64 clips of 30 s: 184 MB of waveforms
+    codes = torch.randint(0, 4096, (1, 64, 1200), generator=g)
+    wav = torch.zeros(64, 720000)
+    wav[:, 0] = torch.arange(64, dtype=torch.float32)
+    runs = [bench.dump_outputs(str(tmp_path / d), codes, wav) for d in ("a", "b")]
+    assert runs[0] == {**runs[1], "dir": runs[0]["dir"]}
+    kept = runs[0]["clips_kept"]
+    assert 0 < len(kept) < 64 and kept == sorted(kept)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in ("codes.npy", "waveform.npy"))
+    assert total <= bench.DUMP_BYTES, total
+    c, w = np.load(tmp_path / "a" / "codes.npy"), np.load(tmp_path / "a" / "waveform.npy")
+    assert np.array_equal(c, codes.numpy()[:, kept]) and np.array_equal(w[:, 0], np.array(kept, np.float32))
+
+
 # ------------------------------------------------------------------------------------------ round 3
 class _RecordingCodec:
     """Deterministic stand-in for the GPU model in the world-2 test of the step runner: per-clip, batch-independent

@@ -150,7 +150,8 @@ def test_istft_center_padding_fixture():
         with torch.inference_mode():
             got = orc.decode(feats, torch.tensor([0])).numpy()
         assert got.shape == want.shape == (feats.shape[0], (feats.shape[2] - 1) * arch.hop_length)
-        assert np.array_equal(got, want), tag
+        # bit-identical on the host that wrote the fixture (make_golden_center.py asserts it); elsewhere the module's rule
+        assert rel_l2(got, want) < FLOAT_TOL, tag
 
 
 def test_codes_to_features_with_several_codebooks():

@@ -27,16 +27,42 @@ static int gemm_auto(const wt_plan* P, const GemmArgs& a, int pro, int epi, hipS
     return launch_gemm(a, pro, epi, s);
 }
 
+static bool has_s32(const wt_model* M, std::initializer_list<const float*> ws) {
+    for (const float* w : ws)
+        if (!M->s32.count(w)) return false;
+    return true;
+}
+
+// The S32 copy of weight w (null: none), and into *acc_scale the factor that undoes its storage scale (model.h)
+static const void* s32_copy(const wt_model* M, const float* w, float* acc_scale) {
+    auto it = M->s32.find(w);
+    if (it == M->s32.end()) return nullptr;
+    auto sc = M->s32_acc_scale.find(w);
+    if (sc != M->s32_acc_scale.end()) *acc_scale = sc->second;
+    return it->second;
+}
+
 // Both operands pre-split (S32): the activations were written in S32 by their producer, the weight has an S32 copy
 static int gemm_s32(const wt_plan* P, const GemmArgs& a, int epi, int out, hipStream_t s) {
-    auto it = P->model->s32.find(a.W);
-    if (it == P->model->s32.end()) { set_error("internal: no S32 copy of this weight"); return WT_ERR_INVALID; }
     GemmArgs b = a;
-    b.W_hi = it->second;
+    b.W_hi = s32_copy(P->model, a.W, &b.acc_scale);
+    if (!b.W_hi) { set_error("internal: no S32 copy of this weight"); return WT_ERR_INVALID; }
     b.tap_pair = P->model->s32_tap_pair.count(a.W) ? 1 : 0;
-    auto sc = P->model->s32_acc_scale.find(a.W);
-    if (sc != P->model->s32_acc_scale.end()) b.acc_scale = sc->second;
     return launch_gemm16s(b, epi, out, s);
+}
+
+// One GEMM step of a layer that runs on either operand form: S32 on gemm16s.hip (`out`: Out16s) or fp32 on gemm.hip
+// (`pro`: its operand prologue)
+static int dense(const wt_plan* P, bool s32, const GemmArgs& a, int pro, int epi, int out, hipStream_t s) {
+    return s32 ? gemm_s32(P, a, epi, out, s) : gemm_auto(P, a, pro, epi, s);
+}
+
+// Activation x activation (attention S and O): the B operand is a plan buffer, S32 in W_hi on gemm16s.hip, fp32 in W on
+// gemm.hip
+static int dense_act(const wt_plan* P, bool s32, GemmArgs a, const float* b_op, int epi, int out, hipStream_t s) {
+    if (s32) { a.W_hi = b_op; return launch_gemm16s(a, epi, out, s); }
+    a.W = b_op;
+    return gemm_auto(P, a, PRO_NONE, epi, s);
 }
 
 // SConv1d geometry (encoder/modules/conv.py:195-211, 54-61), non-causal.
@@ -147,8 +173,7 @@ static int plan_lstm(wt_plan* P, const LstmW& w, int B, int L, int H, int xin, c
     const int xsrc = xin_s32 >= 0 ? xin_s32 : xin;
     P->step({xsrc, xg}, [=](const RunCtx& c) {
         GemmArgs a = ax; a.A = P->ptr(c, xsrc); a.C = P->ptr(c, xg);
-        if (xin_s32 >= 0) return gemm_s32(P, a, EPI_BIAS, OUT_F32, c.stream);
-        return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
+        return dense(P, xin_s32 >= 0, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
     });
     // one persistent launch for the whole recurrence (lstm_persist.hip) when the batch fits its per-XCD clip groups and
     // the device is a full MI355X (256 CUs: one resident workgroup per CU, 32 per XCD)
@@ -189,9 +214,10 @@ static int plan_lstm(wt_plan* P, const LstmW& w, int B, int L, int H, int xin, c
 }
 
 // Unfused SEANetResnetBlock with every operand pre-split: x arrives as S32(x) (shortcut) and S32(elu(x)) (conv3),
-// the hidden activation and the output are written as S32(elu(.)); returns the output buffer
-static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& c1, const ConvW& sc, int B, long T, int x_raw,
-                             int x_elu, const std::string& name, long x_off = 0, long x_bstride = 0, const ConvW* cat = nullptr) {
+// the hidden activation and the output are written as S32(elu(.)); returns the output buffer, or -1 (set_error)
+static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const ConvW& cat, int B, long T, int x_raw,
+                             int x_elu, const std::string& name, long x_off = 0, long x_bstride = 0) {
+    if (!has_s32(P->model, {cat.w})) { set_error("internal: unfused S32 resblock without an S32 shortcut + conv1 weight"); return -1; }
     const int C = sc.cout;
     const int h = P->buf(name + ".h", (size_t)B * T * (C / 2), BUF_S32 | BUF_ELU);
     GemmArgs a3 = sconv_args(c3, B, T, 1, 1);
@@ -200,33 +226,16 @@ static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& c1, const
         if (x_bstride) a.a_bstride = x_bstride;
         return gemm_s32(P, a, EPI_BIAS_ELU, OUT_S32, c.stream);
     });
-    const bool cat_env = [] { const char* e = lab_env("WT_RESBLOCK_CAT"); return !e || e[0] != '0'; }();      // A/B timing (LAB builds)
-    if (cat && cat->w && cat_env && P->model->s32.count(cat->w)) {
-        // shortcut + conv1 as one GEMM over K = [x (C) | elu(h) (C/2)] (GemmArgs::A2): the fp32 shortcut tensor is neither
-        // written nor read back, and the output goes through the staged full-line epilogue
-        const int o = P->buf(name, (size_t)B * T * C, BUF_S32 | BUF_ELU);
-        GemmArgs ac = sconv_args(sc, B, T, 1, 1);
-        ac.W = cat->w; ac.w_rstride = cat->cin; ac.bias = cat->b; ac.K = cat->cin; ac.Cin = cat->cin;
-        ac.K1 = C; ac.a2_bstride = T * (C / 2); ac.a2_rstride = C / 2;
-        P->step({x_raw, h, o}, [=](const RunCtx& c) {
-            GemmArgs a = ac; a.A = P->ptr(c, x_raw) + x_off; a.A2 = P->ptr(c, h); a.C = P->ptr(c, o);
-            if (x_bstride) a.a_bstride = x_bstride;
-            return gemm_s32(P, a, EPI_BIAS_ELU, OUT_S32, c.stream);
-        });
-        return o;
-    }
-    const int y = P->buf(name + ".sc", (size_t)B * T * C);
+    // shortcut + conv1 as one GEMM over K = [x (C) | elu(h) (C/2)] (GemmArgs::A2, weight `cat`: weights.cpp build_cat): the
+    // fp32 shortcut tensor is neither written nor read back, and the output goes through the staged full-line epilogue
     const int o = P->buf(name, (size_t)B * T * C, BUF_S32 | BUF_ELU);
-    GemmArgs as = sconv_args(sc, B, T, 1, 1);
-    P->step({x_raw, y}, [=](const RunCtx& c) {
-        GemmArgs a = as; a.A = P->ptr(c, x_raw) + x_off; a.C = P->ptr(c, y);
+    GemmArgs ac = sconv_args(sc, B, T, 1, 1);
+    ac.W = cat.w; ac.w_rstride = cat.cin; ac.bias = cat.b; ac.K = cat.cin; ac.Cin = cat.cin;
+    ac.K1 = C; ac.a2_bstride = T * (C / 2); ac.a2_rstride = C / 2;
+    P->step({x_raw, h, o}, [=](const RunCtx& c) {
+        GemmArgs a = ac; a.A = P->ptr(c, x_raw) + x_off; a.A2 = P->ptr(c, h); a.C = P->ptr(c, o);
         if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_s32(P, a, EPI_BIAS, OUT_F32, c.stream);
-    });
-    GemmArgs a1 = sconv_args(c1, B, T, 1, 1);
-    P->step({h, y, o}, [=](const RunCtx& c) {
-        GemmArgs a = a1; a.A = P->ptr(c, h); a.C = P->ptr(c, o); a.R = P->ptr(c, y); a.r_rstride = C;
-        return gemm_s32(P, a, EPI_BIAS_RES_ELU, OUT_S32, c.stream);
+        return gemm_s32(P, a, EPI_BIAS_ELU, OUT_S32, c.stream);
     });
     return o;
 }
@@ -249,31 +258,43 @@ int build_encode(wt_plan* P) {
     // ELU is applied once by the producer wherever its only consumer is "ELU -> conv" (resblock
     // output -> down conv, LSTM output -> last conv); the unfused debug plan keeps raw tensors instead
     const bool fuse_elu = !plan_unfused(P);
-    long Tc = T;
-    int idx = 1;
     // S32 mode (default): from the first fused stage on, every GEMM operand of the encoder is written pre-split by
     // its producer and multiplied by gemm16s.hip; tensors that fp32 kernels read too (fused resblock input, LSTM
     // skip, embeddings) are written in both forms by the producing GEMM
     const bool s32 = plan_s32(P);
-    int x_raw = -1, x_elu = -1;          // current stage input as S32(x) and S32(elu(x)) (unfused S32 stages)
-    int x_s32 = -1;                      // S32 copy of the last down conv output (LSTM input projection)
-    for (size_t si = 0; si < M->stages.size(); ++si) {
+    // Route of every stage, decided before any step is added: the fused resblock kernel or the unfused GEMMs, the down conv
+    // folded into the fused kernel or not, and whether the stage's GEMMs take S32 operands
+    struct Route { bool fused, down, s32; };
+    std::vector<Route> route(M->stages.size());
+    for (size_t si = 0; si < route.size(); ++si) {
         const ResStage& st = M->stages[si];
-        const bool fused = resblock_fusable(st.C) && !plan_unfused(P);
+        Route& r = route[si];
+        r.fused = resblock_fusable(st.C) && !plan_unfused(P);
         // a fused stage only needs the S32 down-conv weights (its own convs run inside resblock16); an unfused one
-        // needs S32 copies of all four
-        const bool ws32 = s32 && (st.C % 32 == 0) && M->s32.count(st.down.w) &&
-                          (fused || (M->s32.count(st.c3.w) && M->s32.count(st.c1.w) && M->s32.count(st.sc.w)));
-        bool x_is_s32;                   // the resblock output (elu'd) is S32
+        // needs S32 copies of all four, and its input in S32 from the stage before
+        r.s32 = s32 && st.C % 32 == 0 && has_s32(M, {st.down.w}) &&
+                (r.fused || (si > 0 && route[si - 1].s32 && has_s32(M, {st.c3.w, st.c1.w, st.sc.w})));
         // stage 1 of the shipped plan: first conv + resblock + ELU + down conv in ONE kernel, the stage's activations never
-        // leave LDS (resblock16.hip, DOWN).  WT_RB16_DOWN=0 keeps the two launches (A/B timing).
-        const bool down_env = [] { const char* e = lab_env("WT_RB16_DOWN"); return !e || e[0] != '0'; }();
-        const bool fuse_down = down_env && fused && idx == 1 && fold_e0 && ws32 &&
-                               si + 1 < M->stages.size() && resblock_fusable(M->stages[si + 1].C) && st.down.cin == 32 &&
-                               st.down.cout == 64 && resblock16_down_fusable(st.C, Tc, st.r, st.down.k);
-        if (fuse_down) {
-            const long Td = sconv_args(st.down, B, Tc, st.r, 1).T_out;      // ceil(Tc / r)
-            const int y = P->buf("enc." + std::to_string(idx + 2), (size_t)B * Td * st.down.cout);
+        // leave LDS (resblock16.hip, DOWN)
+        r.down = si == 0 && fold_e0 && r.fused && r.s32 && route.size() > 1 && resblock_fusable(M->stages[1].C) &&
+                 st.down.cin == 32 && st.down.cout == 64 && resblock16_down_fusable(st.C, T, st.r, st.down.k);
+    }
+    // after the last stage the LSTM reads fp32 (skip) and, on S32 operands, an S32 copy (input projection)
+    const bool lstm_s32 = !route.empty() && route.back().s32 && has_s32(M, {M->enc_lstm.Wih0});
+    const bool tail_s32 = lstm_s32 && has_s32(M, {M->enc_final.w, M->embed});
+    long Tc = T;
+    int idx = 1;
+    int x_elu = -1;                      // S32(elu(x)) beside S32(x) for an unfused S32 stage
+    int x_s32 = -1;                      // S32 copy of the last down conv output (LSTM input projection)
+    for (size_t si = 0; si < route.size(); ++si) {
+        const ResStage& st = M->stages[si];
+        const Route r = route[si];
+        const bool last = si + 1 == route.size();
+        GemmArgs ad = sconv_args(st.down, B, Tc, st.r, 1);
+        const size_t ynum = (size_t)B * ad.T_out * st.down.cout;
+        const std::string out = "enc." + std::to_string(idx + 2);
+        if (r.down) {
+            const int y = P->buf(out, ynum);
             P->step({-1, y}, [=](const RunCtx& c) {
                 ResblockArgs a{};
                 a.wav = c.in_f; a.e0_w = M->e0_w; a.e0_b = M->e0_b;
@@ -282,50 +303,35 @@ int build_encode(wt_plan* P) {
                 a.B = B; a.T = (int)Tc; a.C = st.C;
                 return launch_resblock16_down(a, c.stream);
             }, 1, "resblock.fused_down");
-            x_raw = x_elu = -1;
-            x = y; Tc = Td; idx += 3;
+            x = y; Tc = ad.T_out; idx += 3;
             continue;
         }
-        if (fused) {
-            x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, "enc." + std::to_string(idx), fuse_elu,
-                              (idx == 1 && fold_e0) ? M : nullptr, 0, 0, ws32);
-            x_is_s32 = ws32;
-        } else if (ws32 && x_raw >= 0) {
-            x = plan_resblock_s32(P, st.c3, st.c1, st.sc, B, Tc, x_raw, x_elu, "enc." + std::to_string(idx), 0, 0, &st.cat);
-            x_is_s32 = true;
-        } else {
-            x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, "enc." + std::to_string(idx), fuse_elu, nullptr);
-            x_is_s32 = false;
-        }
-        x_raw = x_elu = -1;
-        GemmArgs ad = sconv_args(st.down, B, Tc, st.r, 1);
-        const size_t ynum = (size_t)B * ad.T_out * st.down.cout;
+        const std::string name = "enc." + std::to_string(idx);
+        if (r.fused)
+            x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, name, fuse_elu, (si == 0 && fold_e0) ? M : nullptr, 0, 0, r.s32);
+        else if (r.s32)
+            x = plan_resblock_s32(P, st.c3, st.sc, st.cat, B, Tc, x, x_elu, name);
+        else
+            x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, name, fuse_elu);
+        if (x < 0) return WT_ERR_INVALID;
+        // what the next consumer wants: a fused resblock reads fp32, an unfused S32 stage S32 raw + S32 elu
+        const bool next_s32 = !last && !route[si + 1].fused && route[si + 1].s32;
+        const int y = P->buf(out, ynum, next_s32 ? BUF_S32 : BUF_F32);
+        const int y2 = (next_s32 || (last && lstm_s32)) ? P->buf(out + ".s32", ynum, BUF_S32 | (next_s32 ? BUF_ELU : 0)) : -1;
         const int xin = x;
-        const bool last = si + 1 == M->stages.size();
-        // what the next consumer wants: a fused resblock reads fp32; an unfused S32 stage reads S32 raw + S32 elu; after
-        // the last stage the LSTM reads fp32 (skip) and its input projection S32
-        const bool next_s32_stage = !last && x_is_s32 && (st.down.cout % 32 == 0) &&
-                                    !(resblock_fusable(M->stages[si + 1].C) && !plan_unfused(P)) &&
-                                    M->s32.count(M->stages[si + 1].c3.w) && M->s32.count(M->stages[si + 1].sc.w) &&
-                                    M->s32.count(M->stages[si + 1].c1.w) && M->s32.count(M->stages[si + 1].down.w);
-        const bool lstm_s32 = last && x_is_s32 && M->s32.count(M->enc_lstm.Wih0);
-        const int y = P->buf("enc." + std::to_string(idx + 2), ynum, next_s32_stage ? BUF_S32 : BUF_F32);
-        const int y2 = (next_s32_stage || lstm_s32) ? P->buf("enc." + std::to_string(idx + 2) + ".s32", ynum, BUF_S32 | (next_s32_stage ? BUF_ELU : 0)) : -1;
         P->step({xin, y, y2}, [=](const RunCtx& c) {
             GemmArgs a = ad; a.A = P->ptr(c, xin); a.C = P->ptr(c, y);
             if (y2 >= 0) a.C2 = P->ptr(c, y2);
-            if (x_is_s32)
-                return gemm_s32(P, a, EPI_BIAS, next_s32_stage ? OUT_S32_DUAL_ELU : (lstm_s32 ? OUT_F32_AND_S32 : OUT_F32), c.stream);
-            return gemm_auto(P, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, c.stream);
+            return dense(P, r.s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS,
+                         next_s32 ? OUT_S32_DUAL_ELU : (y2 >= 0 ? OUT_F32_AND_S32 : OUT_F32), c.stream);
         });
-        if (next_s32_stage) { x_raw = y; x_elu = y2; }
-        if (lstm_s32) x_s32 = y2;
+        if (next_s32) x_elu = y2;
+        if (last) x_s32 = y2;
         x = y; Tc = ad.T_out; idx += 3;
     }
     const int L = (int)Tc;
     if (L != P->L) { set_error("internal: frame count mismatch"); return WT_ERR_INVALID; }
     const int H = M->H;
-    const bool tail_s32 = s32 && x_s32 >= 0 && M->s32.count(M->enc_final.w) && M->s32.count(M->embed);
     x = plan_lstm(P, M->enc_lstm, B, L, H, x, "enc." + std::to_string(idx), fuse_elu, x_s32, tail_s32);
     GemmArgs af = sconv_args(M->enc_final, B, L, 1, 1);
     const int emb = P->buf("enc." + std::to_string(idx + 2), (size_t)B * L * 512);
@@ -334,8 +340,8 @@ int build_encode(wt_plan* P) {
         const int xin = x;
         P->step({xin, emb, emb_s32}, [=](const RunCtx& c) {
             GemmArgs a = af; a.A = P->ptr(c, xin); a.C = P->ptr(c, emb);
-            if (tail_s32) { a.C2 = P->ptr(c, emb_s32); return gemm_s32(P, a, EPI_BIAS, OUT_F32_AND_S32, c.stream); }
-            return gemm_auto(P, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, c.stream);
+            if (emb_s32 >= 0) a.C2 = P->ptr(c, emb_s32);
+            return dense(P, tail_s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, OUT_F32_AND_S32, c.stream);
         });
     }
     // ---- VQ (core_vq.py:175-183, 206-231)
@@ -352,8 +358,7 @@ int build_encode(wt_plan* P) {
         GemmArgs a = av; a.A = P->ptr(c, tail_s32 ? emb_s32 : emb);
         a.vq_xx = P->ptr(c, xx); a.vq_ee = M->ee; a.vq_pval = P->ptr(c, pv);
         a.vq_pidx = reinterpret_cast<int*>(P->ptr(c, pi)); a.vq_nparts = np;
-        if (tail_s32) return gemm_s32(P, a, EPI_ARGMAX, OUT_F32, c.stream);
-        return gemm_auto(P, a, PRO_NONE, EPI_ARGMAX, c.stream);
+        return dense(P, tail_s32, a, PRO_NONE, EPI_ARGMAX, OUT_F32, c.stream);
     }, 1, "vq.argmin");
     P->step({pv, pi, emb}, [=](const RunCtx& c) {
         if (int rc = launch_vq_finalize(P->ptr(c, pv), reinterpret_cast<int*>(P->ptr(c, pi)), np, M->embed, c.codes,
@@ -377,8 +382,7 @@ static void plan_head(wt_plan* P, int xo, bool s32) {
     GemmArgs ah = linear_args(M->head_W, M->head_b, Mrows, 2 * Kb, D);
     P->step({xo, spec}, [=](const RunCtx& c) {
         GemmArgs a = ah; a.A = P->ptr(c, xo); a.C = P->ptr(c, spec); a.c_rstride = 2 * Kb; a.head_kb = Kb;
-        if (s32) return gemm_s32(P, a, EPI_HEAD, 1, c.stream);                // spectrum pre-split for the ISTFT GEMM
-        return gemm_auto(P, a, PRO_NONE, EPI_HEAD, c.stream);
+        return dense(P, s32, a, PRO_NONE, EPI_HEAD, OUT_S32, c.stream);        // spectrum pre-split for the ISTFT GEMM
     }, 1, "head.out");
     const int Kq = M->Kq;
     const int parts = P->buf("head.parts", (size_t)4 * Mrows * Kq);       // Ce, Co, Se, So: [4][M][Kq]
@@ -387,8 +391,7 @@ static void plan_head(wt_plan* P, int xo, bool s32) {
         a.A = P->ptr(c, spec); a.a_rstride = 2 * Kb; a.zA = Kq;              // z picks the spectrum quarter
         a.zW = (long)Kq * Kq; a.nz = 4;
         a.C = P->ptr(c, parts); a.c_rstride = Kq; a.zC = (long)Mrows * Kq;
-        if (s32) return gemm_s32(P, a, EPI_BIAS, 0, c.stream);
-        return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
+        return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
     }, 1, "head.istft");
     P->step({parts}, [=](const RunCtx& c) {
         return launch_istft_ola(P->ptr(c, parts), M->win, M->wsq, c.out_f, B, L, ar.n_fft, hop, Kq, ar.padding_same ? 0 : 1, c.stream);
@@ -414,8 +417,7 @@ int build_decode(wt_plan* P) {
     GemmArgs ae = zconv_args(M->bb_embed, B, L);
     P->step({x0, x}, [=](const RunCtx& c) {
         GemmArgs a = ae; a.A = P->ptr(c, x0); a.C = P->ptr(c, x);
-        if (s32_e) return gemm_s32(P, a, EPI_BIAS, 0, c.stream);
-        return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
+        return dense(P, s32_e, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
     });
     const bool keep = P->flags & WT_PLAN_FLAG_KEEP_STAGES;
     auto snapshot = [&](const std::string& name) {   // debug taps of the in-place residual stream
@@ -445,8 +447,7 @@ int build_decode(wt_plan* P) {
         GemmArgs a1 = zconv_args(r.c1, B, L);
         P->step({h1, h2}, [=](const RunCtx& c) {
             GemmArgs a = a1; a.A = P->ptr(c, h1); a.C = P->ptr(c, h2);
-            if (s32) return gemm_s32(P, a, EPI_BIAS, 0, c.stream);
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
+            return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
         }, 1, "res.conv1");
         P->step({h2, sc, sh, h1, gp}, [=](const RunCtx& c) {
             return launch_gn_apply(P->ptr(c, h2), r.n2w, r.n2b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
@@ -454,104 +455,61 @@ int build_decode(wt_plan* P) {
         GemmArgs a2 = zconv_args(r.c2, B, L);
         P->step({h1, x}, [=](const RunCtx& c) {
             GemmArgs a = a2; a.A = P->ptr(c, h1); a.C = P->ptr(c, x); a.R = P->ptr(c, x); a.r_rstride = D;
-            if (s32) return gemm_s32(P, a, EPI_BIAS_RES, 0, c.stream);
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS_RES, c.stream);
+            return dense(P, s32, a, PRO_NONE, EPI_BIAS_RES, OUT_F32, c.stream);
         }, 1, "res.conv2");
         snapshot(name);
     };
     resnet(M->res[0], "bb.pos_net.0", SITE_RES0);
     resnet(M->res[1], "bb.pos_net.1", SITE_RES1);
-    P->cur_site = SITE_ATTN;
-    if (s32_at(SITE_ATTN) && M->s32.count(M->at_Wqk) && M->s32.count(M->at_Wv) && M->s32.count(M->at_Wp)) {
-        P->bufs[h1].fmt = BUF_S32;
-        // AttnBlock (models.py:107-127), single head of width D, every product on split-f16 MFMAs: the normalised
-        // input, q | k, V^T, the probabilities and the attention output are all written pre-split by their producers
-        const int qk = P->buf("bb.attn.qk", (size_t)Mrows * 2 * D, BUF_S32);          // S32 [M][q | k]
-        const int vt = P->buf("bb.attn.vt", (size_t)B * D * Lp, BUF_S32);              // S32 [B][D][Lp]
-        const int S = P->buf("bb.attn.s", (size_t)Mrows * Lp);                // fp32 scores
-        const int Ps = P->buf("bb.attn.p", (size_t)Mrows * Lp, BUF_S32);               // S32 probabilities
-        const int o = P->buf("bb.attn.o", (size_t)Mrows * D, BUF_S32);                 // S32
+    {   // AttnBlock (models.py:107-127), single head of width D.  On S32 operands every product runs on split-f16 MFMAs:
+        // the normalised input, q | k, V^T, the probabilities and the attention output are written pre-split by their
+        // producers.  On fp32 operands softmax turns the scores into probabilities in place.
+        P->cur_site = SITE_ATTN;
+        const bool s32 = s32_at(SITE_ATTN) && has_s32(M, {M->at_Wqk, M->at_Wv, M->at_Wp});
+        const int fmt = s32 ? BUF_S32 : BUF_F32;
+        P->bufs[h1].fmt = fmt;
+        const int qk = P->buf("bb.attn.qk", (size_t)Mrows * 2 * D, fmt);             // [M][q | k]
+        const int vt = P->buf("bb.attn.vt", (size_t)B * D * Lp, fmt);                 // [B][D][Lp]
+        const int S = P->buf("bb.attn.s", (size_t)Mrows * Lp);                        // fp32 scores
+        const int Ps = s32 ? P->buf("bb.attn.p", (size_t)Mrows * Lp, BUF_S32) : S;    // probabilities
+        const int o = P->buf("bb.attn.o", (size_t)Mrows * D, fmt);
         P->step({x, sc, sh, gp, h1}, [=](const RunCtx& c) {
-            return launch_gn_apply(P->ptr(c, x), M->at_nw, M->at_nb, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 0, B, L, D, 32, 1e-6f, c.stream, 1, P->ptr(c, gp));
+            return launch_gn_apply(P->ptr(c, x), M->at_nw, M->at_nb, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 0, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
         }, 1, "attn.gn");
         GemmArgs aqk = linear_args(M->at_Wqk, M->at_bqk, Mrows, 2 * D, D);
         P->step({h1, qk}, [=](const RunCtx& c) {
             GemmArgs a = aqk; a.A = P->ptr(c, h1); a.C = P->ptr(c, qk);
-            return gemm_s32(P, a, EPI_BIAS, OUT_S32, c.stream);
+            return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_S32, c.stream);
         }, 1, "attn.qk");
         P->step({h1, vt}, [=](const RunCtx& c) {     // V^T[b] = Wv . hn[b]^T + bv   (D x L, pitch Lp; pad columns stay zero)
             if (int rc = launch_fill_u32(P->ptr(c, vt), 0u, (size_t)B * D * Lp * sizeof(float), c.stream)) return rc;
-            GemmArgs a = linear_args(P->ptr(c, h1), M->at_bv, D, L, D);
-            a.A = reinterpret_cast<const float*>(M->s32.at(M->at_Wv)); a.zA = 0;
-            if (M->s32_acc_scale.count(M->at_Wv)) a.acc_scale = M->s32_acc_scale.at(M->at_Wv);
-            a.W_hi = P->ptr(c, h1); a.zW = (long)L * D; a.nz = B;
+            GemmArgs a = linear_args(nullptr, M->at_bv, D, L, D);
+            a.A = s32 ? static_cast<const float*>(s32_copy(M, M->at_Wv, &a.acc_scale)) : M->at_Wv; a.zA = 0;
+            a.zW = (long)L * D; a.nz = B;
             a.C = P->ptr(c, vt); a.c_rstride = Lp; a.zC = (long)D * Lp;
-            return launch_gemm16s(a, EPI_BIAS_ROW, OUT_S32, c.stream);
+            return dense_act(P, s32, a, P->ptr(c, h1), EPI_BIAS_ROW, OUT_S32, c.stream);
         }, 2, "attn.vt");
         P->step({qk, S}, [=](const RunCtx& c) {      // S[b] = q[b] . k[b]^T * D^-0.5
             GemmArgs a = linear_args(nullptr, nullptr, L, L, D);
             a.A = P->ptr(c, qk); a.a_rstride = 2 * D; a.zA = (long)L * 2 * D;
-            a.W_hi = P->ptr(c, qk) + D; a.w_rstride = 2 * D; a.zW = (long)L * 2 * D; a.nz = B;
+            a.w_rstride = 2 * D; a.zW = (long)L * 2 * D; a.nz = B;
             a.C = P->ptr(c, S); a.c_rstride = Lp; a.zC = (long)L * Lp;
             a.alpha = (float)std::pow((double)D, -0.5);
-            return launch_gemm16s(a, EPI_SCALE, OUT_F32, c.stream);
+            return dense_act(P, s32, a, P->ptr(c, qk) + D, EPI_SCALE, OUT_F32, c.stream);
         }, 1, "attn.s");
-        P->step({S, Ps}, [=](const RunCtx& c) { return launch_softmax(P->ptr(c, S), (int)Mrows, L, Lp, c.stream, P->ptr(c, Ps)); });
+        P->step({S, Ps}, [=](const RunCtx& c) { return launch_softmax(P->ptr(c, S), (int)Mrows, L, Lp, c.stream, s32 ? P->ptr(c, Ps) : nullptr); });
         P->step({Ps, vt, o}, [=](const RunCtx& c) {  // O[b] = P[b] . V[b]
             GemmArgs a = linear_args(nullptr, nullptr, L, D, Lp);
             a.A = P->ptr(c, Ps); a.zA = (long)L * Lp;
-            a.W_hi = P->ptr(c, vt); a.zW = (long)D * Lp; a.nz = B;
+            a.zW = (long)D * Lp; a.nz = B;
             a.C = P->ptr(c, o); a.c_rstride = D; a.zC = (long)L * D;
-            return launch_gemm16s(a, EPI_BIAS, OUT_S32, c.stream);
+            return dense_act(P, s32, a, P->ptr(c, vt), EPI_BIAS, OUT_S32, c.stream);
         }, 1, "attn.o");
         GemmArgs ap = linear_args(M->at_Wp, M->at_bp, Mrows, D, D);
         P->step({o, x}, [=](const RunCtx& c) {
             GemmArgs a = ap; a.A = P->ptr(c, o); a.C = P->ptr(c, x); a.R = P->ptr(c, x); a.r_rstride = D;
-            return gemm_s32(P, a, EPI_BIAS_RES, OUT_F32, c.stream);
+            return dense(P, s32, a, PRO_NONE, EPI_BIAS_RES, OUT_F32, c.stream);
         }, 1, "attn.proj");
-        snapshot("bb.pos_net.2");
-    } else
-    {   // AttnBlock (models.py:107-127), single head of width D
-        P->bufs[h1].fmt = BUF_F32;
-        const int qk = P->buf("bb.attn.qk", (size_t)Mrows * 2 * D);
-        const int vt = P->buf("bb.attn.vt", (size_t)B * D * Lp);
-        const int S = P->buf("bb.attn.s", (size_t)Mrows * Lp);
-        const int o = P->buf("bb.attn.o", (size_t)Mrows * D);
-        P->step({x, sc, sh, gp, h1}, [=](const RunCtx& c) {
-            return launch_gn_apply(P->ptr(c, x), M->at_nw, M->at_nb, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 0, B, L, D, 32, 1e-6f, c.stream, 0, P->ptr(c, gp));
-        }, 1, "attn.gn");
-        GemmArgs aqk = linear_args(M->at_Wqk, M->at_bqk, Mrows, 2 * D, D);
-        P->step({h1, qk}, [=](const RunCtx& c) {
-            GemmArgs a = aqk; a.A = P->ptr(c, h1); a.C = P->ptr(c, qk);
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
-        });
-        P->step({h1, vt}, [=](const RunCtx& c) {     // V^T[b] = Wv . hn[b]^T + bv   (D x L, pitch Lp)
-            if (int rc = launch_fill_u32(P->ptr(c, vt), 0u, (size_t)B * D * Lp * sizeof(float), c.stream)) return rc;
-            GemmArgs a = linear_args(P->ptr(c, h1), M->at_bv, D, L, D);
-            a.A = M->at_Wv; a.zA = 0; a.zW = (long)L * D; a.nz = B;
-            a.C = P->ptr(c, vt); a.c_rstride = Lp; a.zC = (long)D * Lp;
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS_ROW, c.stream);
-        }, 2);
-        P->step({qk, S}, [=](const RunCtx& c) {      // S[b] = q[b] . k[b]^T * D^-0.5
-            GemmArgs a = linear_args(P->ptr(c, qk) + D, nullptr, L, L, D);
-            a.A = P->ptr(c, qk); a.a_rstride = 2 * D; a.zA = (long)L * 2 * D;
-            a.w_rstride = 2 * D; a.zW = (long)L * 2 * D; a.nz = B;
-            a.C = P->ptr(c, S); a.c_rstride = Lp; a.zC = (long)L * Lp;
-            a.alpha = (float)std::pow((double)D, -0.5);
-            return gemm_auto(P, a, PRO_NONE, EPI_SCALE, c.stream);
-        });
-        P->step({S}, [=](const RunCtx& c) { return launch_softmax(P->ptr(c, S), (int)Mrows, L, Lp, c.stream); });
-        P->step({S, vt, o}, [=](const RunCtx& c) {   // O[b] = P[b] . V[b]
-            GemmArgs a = linear_args(P->ptr(c, vt), nullptr, L, D, Lp);
-            a.A = P->ptr(c, S); a.zA = (long)L * Lp; a.zW = (long)D * Lp; a.nz = B;
-            a.C = P->ptr(c, o); a.c_rstride = D; a.zC = (long)L * D;
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
-        });
-        GemmArgs ap = linear_args(M->at_Wp, M->at_bp, Mrows, D, D);
-        P->step({o, x}, [=](const RunCtx& c) {
-            GemmArgs a = ap; a.A = P->ptr(c, o); a.C = P->ptr(c, x); a.R = P->ptr(c, x); a.r_rstride = D;
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS_RES, c.stream);
-        });
         snapshot("bb.pos_net.2");
     }
     resnet(M->res[2], "bb.pos_net.3", SITE_RES2);
@@ -588,14 +546,12 @@ int build_decode(wt_plan* P) {
         GemmArgs a1 = linear_args(cb.W1, cb.b1, Mrows, I, D);
         P->step({nrm, mid}, [=](const RunCtx& c) {
             GemmArgs a = a1; a.A = P->ptr(c, nrm); a.C = P->ptr(c, mid);
-            if (s32) return gemm_s32(P, a, EPI_BIAS_GELU, 1, c.stream);       // GELU output pre-split for pwconv2
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS_GELU, c.stream);
+            return dense(P, s32, a, PRO_NONE, EPI_BIAS_GELU, OUT_S32, c.stream);     // GELU output pre-split for pwconv2
         }, 1, "cnx.pwconv1");
         GemmArgs a2 = linear_args(cb.W2, cb.b2, Mrows, D, I);
         P->step({mid, xc}, [=](const RunCtx& c) {
             GemmArgs a = a2; a.A = P->ptr(c, mid); a.C = P->ptr(c, xc); a.R = P->ptr(c, xc); a.r_rstride = D; a.gamma = cb.gamma;
-            if (s32) return gemm_s32(P, a, EPI_BIAS_GAMMA_RES, 0, c.stream);
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS_GAMMA_RES, c.stream);
+            return dense(P, s32, a, PRO_NONE, EPI_BIAS_GAMMA_RES, OUT_F32, c.stream);
         }, 1, "cnx.pwconv2");
         if (keep && (i == 0 || i == ar.num_layers / 2 - 1 || i == ar.num_layers - 1)) {
             const int s = P->buf("bb.convnext." + std::to_string(i), (size_t)Mrows * D);
@@ -627,7 +583,7 @@ int build_head(wt_plan* P) {
     const int B = P->B, L = (int)P->L, D = M->arch.dim;
     const long Mrows = (long)B * L;
     P->cur_site = SITE_HEAD;
-    const bool s32 = plan_s32(P) && (D % 32 == 0) && M->s32.count(M->head_W) && M->s32.count(M->istft_W);
+    const bool s32 = plan_s32(P) && (D % 32 == 0) && has_s32(M, {M->head_W, M->istft_W});
     const int xo = P->buf("head.in", (size_t)Mrows * D, s32 ? BUF_S32 : BUF_F32);
     P->step({xo}, [=](const RunCtx& c) {
         if (s32) return launch_split_s32(c.in_f, P->ptr(c, xo), Mrows * D, c.stream);
@@ -638,91 +594,39 @@ int build_head(wt_plan* P) {
     return 0;
 }
 
-// SEANetDecoder on S32 operands (the default): every GEMM operand is written pre-split by its producer, as in
-// build_encode.  z -> S32 -> conv k7 (fp32 for the LSTM skip + S32 for its input projection) -> LSTM (S32(elu) out)
-// -> per stage: transposed conv as r phase GEMMs over (x[t-1], x[t]) -> resblock (fused resblock16 reads fp32 and
-// writes S32(elu); an unfused one reads S32 raw + S32 elu, both written by the phase GEMM) -> ... -> last conv.
+// The SEANetDecoder runs on S32 operands (the default) when every GEMM weight it needs has an S32 copy
 static bool seadec_s32_ok(const wt_plan* P) {
     const wt_model* M = P->model;
-    if (!plan_s32(P) || M->sd_stages.empty() || !M->s32.count(M->sd_first.w) || !M->s32.count(M->sd_lstm.Wih0)) return false;
+    if (!plan_s32(P) || M->sd_stages.empty() || !has_s32(M, {M->sd_first.w, M->sd_lstm.Wih0})) return false;
     for (const SeaDecStage& st : M->sd_stages) {
-        if (!st.tr_wp || !M->s32.count(st.tr_wp) || st.cout % 32) return false;
-        if (!resblock_fusable(st.cout) && !(M->s32.count(st.c3.w) && M->s32.count(st.c1.w) && M->s32.count(st.sc.w))) return false;
+        if (!has_s32(M, {st.tr_wp}) || st.cout % 32) return false;
+        if (!resblock_fusable(st.cout) && !has_s32(M, {st.c3.w, st.c1.w, st.sc.w})) return false;
     }
     return resblock_fusable(M->sd_stages.back().cout);      // the last conv reads fp32
 }
 
-static int build_seanet_decoder_s32(wt_plan* P) {
-    const wt_model* M = P->model;
-    const int B = P->B, L = (int)P->L, H = M->H;
-    const int x0 = P->buf("sdec.in", (size_t)B * L * 512);
-    P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, 512, L, c.stream, 1); });
-    const int xf = P->buf("sdec.0", (size_t)B * L * H);
-    const int xs = P->buf("sdec.0.s32", (size_t)B * L * H);
-    GemmArgs a0 = sconv_args(M->sd_first, B, L, 1, 1);
-    P->step({x0, xf, xs}, [=](const RunCtx& c) {
-        GemmArgs a = a0; a.A = P->ptr(c, x0); a.C = P->ptr(c, xf); a.C2 = P->ptr(c, xs);
-        return gemm_s32(P, a, EPI_BIAS, OUT_F32_AND_S32, c.stream);
-    });
-    int x = plan_lstm(P, M->sd_lstm, B, L, H, xf, "sdec.1", true, xs, true);        // S32(elu(lstm(x) + x))
-    long Tc = L;
-    int di = 2;
-    for (size_t si = 0; si < M->sd_stages.size(); ++si) {
-        const SeaDecStage st = M->sd_stages[si];
-        const long To = Tc * st.r;
-        const int xin = x;
-        const int Tin = (int)Tc;
-        const bool fused = resblock_fusable(st.cout);
-        const bool last = si + 1 == M->sd_stages.size();
-        // SConvTranspose1d (conv.py:232-253), k = 2*stride: see build_seanet_decoder
-        const int trim_l = (st.k - st.r) - (st.k - st.r) / 2;
-        const size_t ynum = (size_t)B * (Tin + 1) * st.r * st.cout;
-        const int y = P->buf("sdec." + std::to_string(di + 1), ynum);
-        const int y2 = fused ? -1 : P->buf("sdec." + std::to_string(di + 1) + ".elu", ynum);
-        const long y_off = (long)trim_l * st.cout, y_bs = (long)(Tin + 1) * st.r * st.cout;
-        P->step({xin, y, y2}, [=](const RunCtx& c) {
-            GemmArgs a;
-            a.A = P->ptr(c, xin); a.a_bstride = (long)Tin * st.cin; a.a_rstride = st.cin;
-            a.T_in = Tin; a.T_out = Tin + 1; a.Cin = st.cin; a.taps = 2; a.pad_left = 1; a.pad_mode = PAD_ZERO;
-            a.W = st.tr_wp; a.w_rstride = 2L * st.cin; a.zW = (long)st.cout * 2 * st.cin; a.bias = st.tr_b;
-            a.M = B * (Tin + 1); a.N = st.cout; a.K = 2 * st.cin;
-            a.C = P->ptr(c, y); a.c_rstride = (long)st.r * st.cout; a.zC = st.cout; a.nz = st.r;
-            if (y2 >= 0) a.C2 = P->ptr(c, y2);
-            return gemm_s32(P, a, EPI_BIAS, fused ? OUT_F32 : OUT_S32_DUAL_ELU, c.stream);
-        }, 1, "sdec.convtr");
-        if (fused)
-            x = plan_resblock(P, st.c3, st.c1, st.sc, B, To, y, "sdec." + std::to_string(di + 2), true, nullptr, y_off, y_bs, !last);
-        else
-            x = plan_resblock_s32(P, st.c3, st.c1, st.sc, B, To, y, y2, "sdec." + std::to_string(di + 2), y_off, y_bs, &st.cat);
-        Tc = To; di += 3;
-    }
-    const int xin = x;
-    const long Tf = Tc;
-    P->step({xin}, [=](const RunCtx& c) {
-        return launch_conv_last(P->ptr(c, xin), M->sd_last_w, M->sd_last_b, c.out_f, B, Tf, 32, 7, 0, c.stream);
-    }, 1, "sdec.last");
-    return 0;
-}
-
+// SEANetDecoder: z -> conv k7 -> LSTM -> per stage: transposed conv -> resblock -> ... -> last conv.  On S32 operands every
+// GEMM operand is written pre-split by its producer, as in build_encode: the first conv writes fp32 for the LSTM skip +
+// S32 for its input projection, the LSTM S32(elu), each phase GEMM fp32 for a fused resblock (resblock16 reads fp32 and
+// writes S32(elu)) or S32 raw + S32 elu for an unfused one.
 int build_seanet_decoder(wt_plan* P) {
     const wt_model* M = P->model;
     if (!M->has_seadec) { set_error("checkpoint holds no SEANetDecoder weights"); return WT_ERR_MISSING_TENSOR; }
     const int B = P->B, L = (int)P->L, H = M->H;
     P->cur_site = SITE_SEADEC;
-    if (seadec_s32_ok(P)) return build_seanet_decoder_s32(P);
-    const int x0 = P->buf("sdec.in", (size_t)B * L * 512);
-    P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, 512, L, c.stream); });
-    int x = P->buf("sdec.0", (size_t)B * L * H);
-    GemmArgs a0 = sconv_args(M->sd_first, B, L, 1, 1);
-    {
-        const int y = x;
-        P->step({x0, y}, [=](const RunCtx& c) {
-            GemmArgs a = a0; a.A = P->ptr(c, x0); a.C = P->ptr(c, y);
-            return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
-        });
-    }
+    const bool s32 = seadec_s32_ok(P);
     const bool fuse_elu = !plan_unfused(P);      // producers store elu(.) for "ELU -> conv" consumers
-    x = plan_lstm(P, M->sd_lstm, B, L, H, x, "sdec.1", fuse_elu);
+    const int x0 = P->buf("sdec.in", (size_t)B * L * 512);
+    P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, 512, L, c.stream, s32); });
+    const int xf = P->buf("sdec.0", (size_t)B * L * H);
+    const int xs = s32 ? P->buf("sdec.0.s32", (size_t)B * L * H) : -1;
+    GemmArgs a0 = sconv_args(M->sd_first, B, L, 1, 1);
+    P->step({x0, xf, xs}, [=](const RunCtx& c) {
+        GemmArgs a = a0; a.A = P->ptr(c, x0); a.C = P->ptr(c, xf);
+        if (xs >= 0) a.C2 = P->ptr(c, xs);
+        return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_F32_AND_S32, c.stream);
+    });
+    int x = plan_lstm(P, M->sd_lstm, B, L, H, xf, "sdec.1", fuse_elu, xs, s32);
     long Tc = L;
     int di = 2;
     for (size_t si = 0; si < M->sd_stages.size(); ++si) {
@@ -730,7 +634,10 @@ int build_seanet_decoder(wt_plan* P) {
         const long To = Tc * st.r;
         const int xin = x;
         const int Tin = (int)Tc;
-        int y;
+        const bool unfused_s32 = s32 && !resblock_fusable(st.cout);
+        const bool last = si + 1 == M->sd_stages.size();
+        const std::string name = "sdec." + std::to_string(di + 1);
+        int y, y2 = -1;
         long y_off = 0, y_bs = 0;
         if (st.tr_wp) {
             // SConvTranspose1d (conv.py:232-253) with k = 2*stride: output sample u' = t*stride + r gets
@@ -738,26 +645,34 @@ int build_seanet_decoder(wt_plan* P) {
             // frames as K (zero beyond the clip); the phases are the batch dimension and interleave in the
             // untrimmed output, of which the following resblock reads the trimmed view.
             const int trim_l = (st.k - st.r) - (st.k - st.r) / 2;
-            y = P->buf("sdec." + std::to_string(di + 1), (size_t)B * (Tin + 1) * st.r * st.cout);
+            const size_t ynum = (size_t)B * (Tin + 1) * st.r * st.cout;
+            y = P->buf(name, ynum);
+            if (unfused_s32) y2 = P->buf(name + ".elu", ynum);
             y_off = (long)trim_l * st.cout;
             y_bs = (long)(Tin + 1) * st.r * st.cout;
-            P->step({xin, y}, [=](const RunCtx& c) {
+            P->step({xin, y, y2}, [=](const RunCtx& c) {
                 GemmArgs a;
                 a.A = P->ptr(c, xin); a.a_bstride = (long)Tin * st.cin; a.a_rstride = st.cin;
                 a.T_in = Tin; a.T_out = Tin + 1; a.Cin = st.cin; a.taps = 2; a.pad_left = 1; a.pad_mode = PAD_ZERO;
                 a.W = st.tr_wp; a.w_rstride = 2L * st.cin; a.zW = (long)st.cout * 2 * st.cin; a.bias = st.tr_b;
                 a.M = B * (Tin + 1); a.N = st.cout; a.K = 2 * st.cin;
                 a.C = P->ptr(c, y); a.c_rstride = (long)st.r * st.cout; a.zC = st.cout; a.nz = st.r;
-                return gemm_auto(P, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, c.stream);
+                if (y2 >= 0) a.C2 = P->ptr(c, y2);
+                return dense(P, s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, y2 >= 0 ? OUT_S32_DUAL_ELU : OUT_F32, c.stream);
             }, 1, "sdec.convtr");
         } else {
-            y = P->buf("sdec." + std::to_string(di + 1), (size_t)B * To * st.cout);
+            y = P->buf(name, (size_t)B * To * st.cout);
             P->step({xin, y}, [=](const RunCtx& c) {
                 return launch_convtr(P->ptr(c, xin), st.tr_w, st.tr_b, P->ptr(c, y), B, Tin, st.cin, st.cout, st.k, st.r,
                                      fuse_elu ? 0 : 1, c.stream);
             }, 1, "sdec.convtr");
         }
-        x = plan_resblock(P, st.c3, st.c1, st.sc, B, To, y, "sdec." + std::to_string(di + 2), fuse_elu, nullptr, y_off, y_bs);
+        const std::string rname = "sdec." + std::to_string(di + 2);
+        if (unfused_s32)
+            x = plan_resblock_s32(P, st.c3, st.sc, st.cat, B, To, y, y2, rname, y_off, y_bs);
+        else
+            x = plan_resblock(P, st.c3, st.c1, st.sc, B, To, y, rname, fuse_elu, nullptr, y_off, y_bs, s32 && !last);
+        if (x < 0) return WT_ERR_INVALID;
         Tc = To; di += 3;
     }
     const int xin = x;
@@ -802,7 +717,7 @@ void plan_end(wt_plan* P) {
 int build_unit_lstm(wt_plan* P) {
     const wt_model* M = P->model;
     const int B = P->B, L = (int)P->L, H = M->H;
-    const bool s32 = plan_s32(P) && M->s32.count(M->enc_lstm.Wih0);
+    const bool s32 = plan_s32(P) && has_s32(M, {M->enc_lstm.Wih0});
     const int x = P->buf("lstm.in", (size_t)B * L * H);
     const int xs = s32 ? P->buf("lstm.in.s32", (size_t)B * L * H, BUF_S32) : -1;
     P->step({x, xs}, [=](const RunCtx& c) {

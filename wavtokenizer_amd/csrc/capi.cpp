@@ -622,7 +622,7 @@ int wt_codes_to_features(const wt_model* m, const int64_t* codes, int32_t K, int
     if (K < 1 || K > m->arch.num_quantizers) { set_error("wt_codes_to_features: K exceeds the number of codebooks"); return WT_ERR_INVALID; }
     DeviceGuard dg(m->device);
     if (!dg.ok) { set_error("hipSetDevice failed"); return WT_ERR_HIP; }
-    return launch_codes_to_features(codes, m->embed, K, m->arch.vq_bins, B, L, 512, features, static_cast<hipStream_t>(stream),
+    return launch_codes_to_features(codes, m->embed.w, K, m->arch.vq_bins, B, L, 512, features, static_cast<hipStream_t>(stream),
                                     m->bad_codes_dev);
 }
 

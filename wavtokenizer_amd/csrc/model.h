@@ -19,13 +19,26 @@
 namespace wt {
 
 // ------------------------------------------------------------------------------------- model
+// S32 copy of a GEMM weight (gemm16s.hip: 128-byte groups [32 x f16 hi | 32 x f16 lo], same footprint as the fp32 array),
+// held by the weight it stands for; p = null: none (weights.cpp add_s32)
+struct S32Copy {
+    const void* p = nullptr;
+    float acc_scale = 1.f;     // undoes the copy's power-of-two storage scale (GemmArgs::acc_scale)
+    bool tap_pair = false;     // the copy holds its taps in paired order (GemmArgs::tap_pair)
+};
 struct ConvW {
     float* w = nullptr;   // [cout][k][cin]
     float* b = nullptr;   // [cout]
     int cout = 0, cin = 0, k = 0;
+    S32Copy s32;
+};
+struct GemmW {            // the W operand of plain GEMMs (linear_args)
+    float* w = nullptr;   // [rows][cols]: the extent its GEMMs read, and that of its S32 copy
+    int rows = 0, cols = 0;
+    S32Copy s32;
 };
 struct LstmW {
-    float* Wih0 = nullptr;  // [4H][H] rows in packed gate order
+    GemmW Wih0;             // [4H][H] rows in packed gate order
     float* b0 = nullptr;    // [4H]  b_ih_l0 + b_hh_l0, packed
     float* W0 = nullptr;    // [4H][H]  W_hh_l0 packed
     float* W1 = nullptr;    // [4H][2H] [W_ih_l1 | W_hh_l1] packed
@@ -44,11 +57,12 @@ struct PosRes {
     ConvW c1, c2;
 };
 struct CnxBlock {
-    float *dw_w, *dw_b, *ada_s, *ada_h, *W1, *b1, *W2, *b2, *gamma;
+    float *dw_w, *dw_b, *ada_s, *ada_h, *b1, *b2, *gamma;
+    GemmW W1, W2;
 };
 struct SeaDecStage {
     float* tr_w = nullptr;  // [k][cin][cout]
-    float* tr_wp = nullptr; // [stride phases][cout][2 taps][cin]: tap 0 <-> frame t-1 (kernel index r+stride), tap 1 <-> frame t (index r)
+    GemmW tr_wp;            // [stride phases][cout][2 taps][cin]: tap 0 <-> frame t-1 (kernel index r+stride), tap 1 <-> frame t (index r)
     float* tr_b = nullptr;
     int cin = 0, cout = 0, k = 0, r = 0;
     ConvW c3, c1, sc;
@@ -66,27 +80,25 @@ struct wt_model {
     std::vector<void*> allocs;
     std::vector<size_t> alloc_bytes;     // size of each allocation (the packed image stores them in this order)
     int64_t weight_bytes = 0;
-    // S32 copies (gemm16s.hip: 128-byte groups [32 x f16 hi | 32 x f16 lo], same footprint as fp32) of the weights
-    // whose GEMMs take pre-split activations, keyed by the fp32 device pointer the plans already use
-    std::map<const float*, void*> s32;
-    std::map<const float*, bool> s32_tap_pair;       // that S32 copy holds its taps in paired order (GemmArgs::tap_pair)
     // encoder
     float *e0_w = nullptr, *e0_b = nullptr;   // [7][32], [32]
     int e0_k = 7, e0_c = 32;
     std::vector<wt::ResStage> stages;
     wt::LstmW enc_lstm;
     wt::ConvW enc_final;
-    float *embed = nullptr, *ee = nullptr;
+    wt::GemmW embed;                          // [num_quantizers][vq_bins][512]; rows = vq_bins: the GEMM (and S32 copy) is codebook 0
+    float* ee = nullptr;
     // backbone
     wt::ConvW bb_embed;
     wt::PosRes res[4];
-    float *at_nw, *at_nb, *at_Wqk, *at_bqk, *at_Wv, *at_bv, *at_Wp, *at_bp;
+    float *at_nw, *at_nb, *at_bqk, *at_bv, *at_bp;
+    wt::GemmW at_Wqk, at_Wv, at_Wp;
     float *gn5w, *gn5b, *ada_s, *ada_h;
     std::vector<wt::CnxBlock> cnx;
     float *fln_w, *fln_b;
-    float *head_W = nullptr, *head_b = nullptr;
+    wt::GemmW head_W, istft_W;                // istft_W: [4 quarters][Kq][Kq], one batched GEMM of N = K = Kq
+    float *head_b = nullptr, *wsq = nullptr, *win = nullptr;
     int Kb = 0, Kq = 0, bins_f = 0, R = 0;
-    float *istft_W = nullptr, *wsq = nullptr, *win = nullptr;
     // SEANetDecoder (present iff the checkpoint holds it)
     bool has_seadec = false;
     wt::ConvW sd_first;
@@ -107,9 +119,6 @@ struct wt_model {
     std::vector<LazyF32> lazy_f32;
     mutable std::atomic<bool> f32_stale{false};          // the arrays of lazy_f32 hold nothing yet (packed import)
     mutable std::mutex f32_mu;
-    // per-weight power-of-two scale of the S32 copy (tensors whose largest magnitude is far from 1 are stored as
-    // w * 2^e; the GEMM brings its accumulators back with acc_scale = 2^-e); absent = 1
-    std::map<const float*, float> s32_acc_scale;
     // host-mapped word for wt_codes_to_features: set by the kernel when it meets an index outside the codebook
     unsigned* bad_codes_host = nullptr;
     unsigned* bad_codes_dev = nullptr;
@@ -328,6 +337,7 @@ SConvGeom sconv_geom(long T, int k, int stride, int dil);
 GemmArgs sconv_args(const ConvW& w, int B, long T, int stride, int dil);
 GemmArgs zconv_args(const ConvW& w, int B, int L);
 GemmArgs linear_args(const float* W, const float* bias, long M, int N, int K);
+GemmArgs linear_args(const GemmW& W, const float* bias, long M, int N, int K);
 int build_encode(wt_plan* P);
 int build_decode(wt_plan* P);
 int build_head(wt_plan* P);

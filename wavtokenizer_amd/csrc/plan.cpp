@@ -27,34 +27,21 @@ static int gemm_auto(const wt_plan* P, const GemmArgs& a, int pro, int epi, hipS
     return launch_gemm(a, pro, epi, s);
 }
 
-static bool has_s32(const wt_model* M, std::initializer_list<const float*> ws) {
-    for (const float* w : ws)
-        if (!M->s32.count(w)) return false;
-    return true;
-}
-
-// The S32 copy of weight w (null: none), and into *acc_scale the factor that undoes its storage scale (model.h)
-static const void* s32_copy(const wt_model* M, const float* w, float* acc_scale) {
-    auto it = M->s32.find(w);
-    if (it == M->s32.end()) return nullptr;
-    auto sc = M->s32_acc_scale.find(w);
-    if (sc != M->s32_acc_scale.end()) *acc_scale = sc->second;
-    return it->second;
+// The weight's S32 copy as the W operand of gemm16s.hip (the argument builders set it; gemm.hip ignores these fields)
+static void set_s32(GemmArgs& a, const S32Copy& c) {
+    a.W_hi = c.p; a.acc_scale = c.acc_scale; a.tap_pair = c.tap_pair ? 1 : 0;
 }
 
 // Both operands pre-split (S32): the activations were written in S32 by their producer, the weight has an S32 copy
-static int gemm_s32(const wt_plan* P, const GemmArgs& a, int epi, int out, hipStream_t s) {
-    GemmArgs b = a;
-    b.W_hi = s32_copy(P->model, a.W, &b.acc_scale);
-    if (!b.W_hi) { set_error("internal: no S32 copy of this weight"); return WT_ERR_INVALID; }
-    b.tap_pair = P->model->s32_tap_pair.count(a.W) ? 1 : 0;
-    return launch_gemm16s(b, epi, out, s);
+static int gemm_s32(const GemmArgs& a, int epi, int out, hipStream_t s) {
+    if (!a.W_hi) { set_error("internal: no S32 copy of this weight"); return WT_ERR_INVALID; }
+    return launch_gemm16s(a, epi, out, s);
 }
 
 // One GEMM step of a layer that runs on either operand form: S32 on gemm16s.hip (`out`: Out16s) or fp32 on gemm.hip
 // (`pro`: its operand prologue)
 static int dense(const wt_plan* P, bool s32, const GemmArgs& a, int pro, int epi, int out, hipStream_t s) {
-    return s32 ? gemm_s32(P, a, epi, out, s) : gemm_auto(P, a, pro, epi, s);
+    return s32 ? gemm_s32(a, epi, out, s) : gemm_auto(P, a, pro, epi, s);
 }
 
 // Activation x activation (attention S and O): the B operand is a plan buffer, S32 in W_hi on gemm16s.hip, fp32 in W on
@@ -94,6 +81,7 @@ GemmArgs sconv_args(const ConvW& w, int B, long T, int stride, int dil) {
     a.W = w.w; a.w_rstride = (long)w.k * w.cin; a.bias = w.b;
     a.M = B * g.Tout; a.N = w.cout; a.K = w.k * w.cin;
     a.c_rstride = w.cout;
+    set_s32(a, w.s32);
     return a;
 }
 // zero-padded 'same' Conv1d (decoder/models.py:29-43,177): k odd, padding (k-1)/2
@@ -103,6 +91,7 @@ GemmArgs zconv_args(const ConvW& w, int B, int L) {
     a.T_in = L; a.T_out = L; a.Cin = w.cin; a.taps = w.k; a.pad_left = (w.k - 1) / 2; a.pad_mode = PAD_ZERO;
     a.W = w.w; a.w_rstride = (long)w.k * w.cin; a.bias = w.b;
     a.M = B * L; a.N = w.cout; a.K = w.k * w.cin; a.c_rstride = w.cout;
+    set_s32(a, w.s32);
     return a;
 }
 // plain X[M][K] . W[N][K]^T
@@ -111,6 +100,9 @@ GemmArgs linear_args(const float* W, const float* bias, long M, int N, int K) {
     a.a_bstride = 0; a.a_rstride = K; a.T_in = (int)M; a.T_out = (int)M; a.Cin = K; a.taps = 1;
     a.W = W; a.w_rstride = K; a.bias = bias; a.M = (int)M; a.N = N; a.K = K; a.c_rstride = N;
     return a;
+}
+GemmArgs linear_args(const GemmW& W, const float* bias, long M, int N, int K) {
+    GemmArgs a = linear_args(W.w, bias, M, N, K); set_s32(a, W.s32); return a;
 }
 
 // SEANetResnetBlock (seanet.py:62-63): y = shortcut(x) + conv1(elu(conv3(elu(x)))); returns y's buffer
@@ -217,25 +209,26 @@ static int plan_lstm(wt_plan* P, const LstmW& w, int B, int L, int H, int xin, c
 // the hidden activation and the output are written as S32(elu(.)); returns the output buffer, or -1 (set_error)
 static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const ConvW& cat, int B, long T, int x_raw,
                              int x_elu, const std::string& name, long x_off = 0, long x_bstride = 0) {
-    if (!has_s32(P->model, {cat.w})) { set_error("internal: unfused S32 resblock without an S32 shortcut + conv1 weight"); return -1; }
+    if (!cat.s32.p) { set_error("internal: unfused S32 resblock without an S32 shortcut + conv1 weight"); return -1; }
     const int C = sc.cout;
     const int h = P->buf(name + ".h", (size_t)B * T * (C / 2), BUF_S32 | BUF_ELU);
     GemmArgs a3 = sconv_args(c3, B, T, 1, 1);
     P->step({x_elu, h}, [=](const RunCtx& c) {
         GemmArgs a = a3; a.A = P->ptr(c, x_elu) + x_off; a.C = P->ptr(c, h);
         if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_s32(P, a, EPI_BIAS_ELU, OUT_S32, c.stream);
+        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream);
     });
     // shortcut + conv1 as one GEMM over K = [x (C) | elu(h) (C/2)] (GemmArgs::A2, weight `cat`: weights.cpp build_cat): the
     // fp32 shortcut tensor is neither written nor read back, and the output goes through the staged full-line epilogue
     const int o = P->buf(name, (size_t)B * T * C, BUF_S32 | BUF_ELU);
     GemmArgs ac = sconv_args(sc, B, T, 1, 1);
     ac.W = cat.w; ac.w_rstride = cat.cin; ac.bias = cat.b; ac.K = cat.cin; ac.Cin = cat.cin;
+    set_s32(ac, cat.s32);
     ac.K1 = C; ac.a2_bstride = T * (C / 2); ac.a2_rstride = C / 2;
     P->step({x_raw, h, o}, [=](const RunCtx& c) {
         GemmArgs a = ac; a.A = P->ptr(c, x_raw) + x_off; a.A2 = P->ptr(c, h); a.C = P->ptr(c, o);
         if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_s32(P, a, EPI_BIAS_ELU, OUT_S32, c.stream);
+        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream);
     });
     return o;
 }
@@ -272,16 +265,16 @@ int build_encode(wt_plan* P) {
         r.fused = resblock_fusable(st.C) && !plan_unfused(P);
         // a fused stage only needs the S32 down-conv weights (its own convs run inside resblock16); an unfused one
         // needs S32 copies of all four, and its input in S32 from the stage before
-        r.s32 = s32 && st.C % 32 == 0 && has_s32(M, {st.down.w}) &&
-                (r.fused || (si > 0 && route[si - 1].s32 && has_s32(M, {st.c3.w, st.c1.w, st.sc.w})));
+        r.s32 = s32 && st.C % 32 == 0 && st.down.s32.p &&
+                (r.fused || (si > 0 && route[si - 1].s32 && st.c3.s32.p && st.c1.s32.p && st.sc.s32.p));
         // stage 1 of the shipped plan: first conv + resblock + ELU + down conv in ONE kernel, the stage's activations never
         // leave LDS (resblock16.hip, DOWN)
         r.down = si == 0 && fold_e0 && r.fused && r.s32 && route.size() > 1 && resblock_fusable(M->stages[1].C) &&
                  st.down.cin == 32 && st.down.cout == 64 && resblock16_down_fusable(st.C, T, st.r, st.down.k);
     }
     // after the last stage the LSTM reads fp32 (skip) and, on S32 operands, an S32 copy (input projection)
-    const bool lstm_s32 = !route.empty() && route.back().s32 && has_s32(M, {M->enc_lstm.Wih0});
-    const bool tail_s32 = lstm_s32 && has_s32(M, {M->enc_final.w, M->embed});
+    const bool lstm_s32 = !route.empty() && route.back().s32 && M->enc_lstm.Wih0.s32.p;
+    const bool tail_s32 = lstm_s32 && M->enc_final.s32.p && M->embed.s32.p;
     long Tc = T;
     int idx = 1;
     int x_elu = -1;                      // S32(elu(x)) beside S32(x) for an unfused S32 stage
@@ -361,7 +354,7 @@ int build_encode(wt_plan* P) {
         return dense(P, tail_s32, a, PRO_NONE, EPI_ARGMAX, OUT_F32, c.stream);
     }, 1, "vq.argmin");
     P->step({pv, pi, emb}, [=](const RunCtx& c) {
-        if (int rc = launch_vq_finalize(P->ptr(c, pv), reinterpret_cast<int*>(P->ptr(c, pi)), np, M->embed, c.codes,
+        if (int rc = launch_vq_finalize(P->ptr(c, pv), reinterpret_cast<int*>(P->ptr(c, pi)), np, M->embed.w, c.codes,
                                         c.out_f, B, L, 512, bins, c.stream)) return rc;
         if (c.aux) return launch_transpose(P->ptr(c, emb), c.aux, B, L, 512, c.stream);
         return 0;
@@ -465,7 +458,7 @@ int build_decode(wt_plan* P) {
         // the normalised input, q | k, V^T, the probabilities and the attention output are written pre-split by their
         // producers.  On fp32 operands softmax turns the scores into probabilities in place.
         P->cur_site = SITE_ATTN;
-        const bool s32 = s32_at(SITE_ATTN) && has_s32(M, {M->at_Wqk, M->at_Wv, M->at_Wp});
+        const bool s32 = s32_at(SITE_ATTN) && M->at_Wqk.s32.p && M->at_Wv.s32.p && M->at_Wp.s32.p;
         const int fmt = s32 ? BUF_S32 : BUF_F32;
         P->bufs[h1].fmt = fmt;
         const int qk = P->buf("bb.attn.qk", (size_t)Mrows * 2 * D, fmt);             // [M][q | k]
@@ -484,7 +477,7 @@ int build_decode(wt_plan* P) {
         P->step({h1, vt}, [=](const RunCtx& c) {     // V^T[b] = Wv . hn[b]^T + bv   (D x L, pitch Lp; pad columns stay zero)
             if (int rc = launch_fill_u32(P->ptr(c, vt), 0u, (size_t)B * D * Lp * sizeof(float), c.stream)) return rc;
             GemmArgs a = linear_args(nullptr, M->at_bv, D, L, D);
-            a.A = s32 ? static_cast<const float*>(s32_copy(M, M->at_Wv, &a.acc_scale)) : M->at_Wv; a.zA = 0;
+            a.A = s32 ? static_cast<const float*>(M->at_Wv.s32.p) : M->at_Wv.w; a.acc_scale = M->at_Wv.s32.acc_scale; a.zA = 0;
             a.zW = (long)L * D; a.nz = B;
             a.C = P->ptr(c, vt); a.c_rstride = Lp; a.zC = (long)D * Lp;
             return dense_act(P, s32, a, P->ptr(c, h1), EPI_BIAS_ROW, OUT_S32, c.stream);
@@ -583,7 +576,7 @@ int build_head(wt_plan* P) {
     const int B = P->B, L = (int)P->L, D = M->arch.dim;
     const long Mrows = (long)B * L;
     P->cur_site = SITE_HEAD;
-    const bool s32 = plan_s32(P) && (D % 32 == 0) && has_s32(M, {M->head_W, M->istft_W});
+    const bool s32 = plan_s32(P) && (D % 32 == 0) && M->head_W.s32.p && M->istft_W.s32.p;
     const int xo = P->buf("head.in", (size_t)Mrows * D, s32 ? BUF_S32 : BUF_F32);
     P->step({xo}, [=](const RunCtx& c) {
         if (s32) return launch_split_s32(c.in_f, P->ptr(c, xo), Mrows * D, c.stream);
@@ -597,10 +590,10 @@ int build_head(wt_plan* P) {
 // The SEANetDecoder runs on S32 operands (the default) when every GEMM weight it needs has an S32 copy
 static bool seadec_s32_ok(const wt_plan* P) {
     const wt_model* M = P->model;
-    if (!plan_s32(P) || M->sd_stages.empty() || !has_s32(M, {M->sd_first.w, M->sd_lstm.Wih0})) return false;
+    if (!plan_s32(P) || M->sd_stages.empty() || !M->sd_first.s32.p || !M->sd_lstm.Wih0.s32.p) return false;
     for (const SeaDecStage& st : M->sd_stages) {
-        if (!has_s32(M, {st.tr_wp}) || st.cout % 32) return false;
-        if (!resblock_fusable(st.cout) && !has_s32(M, {st.c3.w, st.c1.w, st.sc.w})) return false;
+        if (!st.tr_wp.s32.p || st.cout % 32) return false;
+        if (!resblock_fusable(st.cout) && !(st.c3.s32.p && st.c1.s32.p && st.sc.s32.p)) return false;
     }
     return resblock_fusable(M->sd_stages.back().cout);      // the last conv reads fp32
 }
@@ -639,7 +632,7 @@ int build_seanet_decoder(wt_plan* P) {
         const std::string name = "sdec." + std::to_string(di + 1);
         int y, y2 = -1;
         long y_off = 0, y_bs = 0;
-        if (st.tr_wp) {
+        if (st.tr_wp.w) {
             // SConvTranspose1d (conv.py:232-253) with k = 2*stride: output sample u' = t*stride + r gets
             // x[t].W[r] + x[t-1].W[r+stride], i.e. per phase r one GEMM over rows t = 0..Tin with the two
             // frames as K (zero beyond the clip); the phases are the batch dimension and interleave in the
@@ -654,9 +647,10 @@ int build_seanet_decoder(wt_plan* P) {
                 GemmArgs a;
                 a.A = P->ptr(c, xin); a.a_bstride = (long)Tin * st.cin; a.a_rstride = st.cin;
                 a.T_in = Tin; a.T_out = Tin + 1; a.Cin = st.cin; a.taps = 2; a.pad_left = 1; a.pad_mode = PAD_ZERO;
-                a.W = st.tr_wp; a.w_rstride = 2L * st.cin; a.zW = (long)st.cout * 2 * st.cin; a.bias = st.tr_b;
+                a.W = st.tr_wp.w; a.w_rstride = 2L * st.cin; a.zW = (long)st.cout * 2 * st.cin; a.bias = st.tr_b;
                 a.M = B * (Tin + 1); a.N = st.cout; a.K = 2 * st.cin;
                 a.C = P->ptr(c, y); a.c_rstride = (long)st.r * st.cout; a.zC = st.cout; a.nz = st.r;
+                set_s32(a, st.tr_wp.s32);
                 if (y2 >= 0) a.C2 = P->ptr(c, y2);
                 return dense(P, s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, y2 >= 0 ? OUT_S32_DUAL_ELU : OUT_F32, c.stream);
             }, 1, "sdec.convtr");
@@ -717,7 +711,7 @@ void plan_end(wt_plan* P) {
 int build_unit_lstm(wt_plan* P) {
     const wt_model* M = P->model;
     const int B = P->B, L = (int)P->L, H = M->H;
-    const bool s32 = plan_s32(P) && has_s32(M, {M->enc_lstm.Wih0});
+    const bool s32 = plan_s32(P) && M->enc_lstm.Wih0.s32.p;
     const int x = P->buf("lstm.in", (size_t)B * L * H);
     const int xs = s32 ? P->buf("lstm.in.s32", (size_t)B * L * H, BUF_S32) : -1;
     P->step({x, xs}, [=](const RunCtx& c) {

@@ -69,6 +69,13 @@ static int load_vec(wt_model* M, TensorMap& tm, const std::string& key, int64_t 
     if (!p) return WT_ERR_MISSING_TENSOR;
     return upload_raw(M, p, n, out);
 }
+// a GEMM weight [rows][cols] (GemmW)
+static int upload_gemm(wt_model* M, const std::vector<float>& h, int rows, int cols, GemmW* out) {
+    out->rows = rows; out->cols = cols; return upload(M, h, &out->w);
+}
+static int load_gemm(wt_model* M, TensorMap& tm, const std::string& key, int rows, int cols, GemmW* out) {
+    out->rows = rows; out->cols = cols; return load_vec(M, tm, key, (int64_t)rows * cols, &out->w);
+}
 
 // nn.LSTM weights -> packed gate order: packed row (j/4)*16 + g*4 + j%4  <-  row g*H + j
 static int load_lstm(wt_model* M, TensorMap& tm, const std::string& prefix, int H, LstmW* out, bool* split_ok) {
@@ -135,7 +142,7 @@ static int load_lstm(wt_model* M, TensorMap& tm, const std::string& prefix, int 
             b0[dst] = bih0[src] + bhh0[src];
             b1[dst] = bih1[src] + bhh1[src];
         }
-    if (int rc = upload(M, Wih0, &out->Wih0)) return rc;
+    if (int rc = upload_gemm(M, Wih0, 4 * H, H, &out->Wih0)) return rc;
     if (int rc = upload(M, b0, &out->b0)) return rc;
     if (int rc = upload(M, W0, &out->W0)) return rc;
     if (int rc = upload(M, W1, &out->W1)) return rc;
@@ -234,7 +241,8 @@ int build_model(wt_model* M, TensorMap& tm) {
             if (!eq) return WT_ERR_MISSING_TENSOR;
             std::memcpy(all.data() + (size_t)q * a.vq_bins * 512, eq, (size_t)a.vq_bins * 512 * sizeof(float));
         }
-        if (int rc = upload(M, all, &M->embed)) return rc;
+        M->embed.rows = a.vq_bins; M->embed.cols = 512;
+        if (int rc = upload(M, all, &M->embed.w)) return rc;
         std::vector<float> ee(a.vq_bins);
         for (int n = 0; n < a.vq_bins; ++n) {   // embed.pow(2).sum(0)
             float s = 0.f;
@@ -272,11 +280,11 @@ int build_model(wt_model* M, TensorMap& tm) {
         std::memcpy(&wqk[(size_t)D * D], wk, (size_t)D * D * sizeof(float));
         std::memcpy(&bqk[0], bq, D * sizeof(float));
         std::memcpy(&bqk[D], bk, D * sizeof(float));
-        if (int rc = upload(M, wqk, &M->at_Wqk)) return rc;
+        if (int rc = upload_gemm(M, wqk, 2 * D, D, &M->at_Wqk)) return rc;
         if (int rc = upload(M, bqk, &M->at_bqk)) return rc;
-        if (int rc = load_vec(M, tm, p + ".v.weight", (int64_t)D * D, &M->at_Wv)) return rc;
+        if (int rc = load_gemm(M, tm, p + ".v.weight", D, D, &M->at_Wv)) return rc;
         if (int rc = load_vec(M, tm, p + ".v.bias", D, &M->at_bv)) return rc;
-        if (int rc = load_vec(M, tm, p + ".proj_out.weight", (int64_t)D * D, &M->at_Wp)) return rc;
+        if (int rc = load_gemm(M, tm, p + ".proj_out.weight", D, D, &M->at_Wp)) return rc;
         if (int rc = load_vec(M, tm, p + ".proj_out.bias", D, &M->at_bp)) return rc;
     }
     if (int rc = load_vec(M, tm, "backbone.pos_net.5.weight", D, &M->gn5w)) return rc;
@@ -296,9 +304,9 @@ int build_model(wt_model* M, TensorMap& tm) {
         if (int rc = load_vec(M, tm, p + ".dwconv.bias", D, &c.dw_b)) return rc;
         if (int rc = load_vec(M, tm, p + ".norm.scale.weight", (int64_t)A * D, &c.ada_s)) return rc;
         if (int rc = load_vec(M, tm, p + ".norm.shift.weight", (int64_t)A * D, &c.ada_h)) return rc;
-        if (int rc = load_vec(M, tm, p + ".pwconv1.weight", (int64_t)I * D, &c.W1)) return rc;
+        if (int rc = load_gemm(M, tm, p + ".pwconv1.weight", I, D, &c.W1)) return rc;
         if (int rc = load_vec(M, tm, p + ".pwconv1.bias", I, &c.b1)) return rc;
-        if (int rc = load_vec(M, tm, p + ".pwconv2.weight", (int64_t)D * I, &c.W2)) return rc;
+        if (int rc = load_gemm(M, tm, p + ".pwconv2.weight", D, I, &c.W2)) return rc;
         if (int rc = load_vec(M, tm, p + ".pwconv2.bias", D, &c.b2)) return rc;
         if (int rc = load_vec(M, tm, p + ".gamma", D, &c.gamma)) return rc;
         M->cnx.push_back(c);
@@ -337,7 +345,7 @@ int build_model(wt_model* M, TensorMap& tm) {
             bp[pm] = b[f];
             bp[pp] = b[bins + f];
         }
-        if (int rc = upload(M, wp, &M->head_W)) return rc;
+        if (int rc = upload_gemm(M, wp, 2 * Kb, D, &M->head_W)) return rc;
         if (int rc = upload(M, bp, &M->head_b)) return rc;
         // Inverse real DFT, two radix-2 splits then dense: with theta = 2 pi f n / N,
         //   x[n] = C[n] - S[n], x[N-n] = C[n] + S[n]            (n <= N/2;  C = sum c_f Re cos, S = sum c_f Im sin, /N)
@@ -360,7 +368,7 @@ int build_model(wt_model* M, TensorMap& tm) {
                     basis[((size_t)3 * Kq + n) * Kq + g] = (float)(co * std::sin(tho));
                 }
             }
-        if (int rc = upload(M, basis, &M->istft_W)) return rc;
+        if (int rc = upload_gemm(M, basis, 4 * Kq, Kq, &M->istft_W)) return rc;
         if (int rc = upload_raw(M, win, N, &M->win)) return rc;
         std::vector<float> wsq(N);
         for (int n = 0; n < N; ++n) wsq[n] = win[n] * win[n];
@@ -398,7 +406,7 @@ int build_model(wt_model* M, TensorMap& tm) {
                             pp[(((size_t)ph * st.cout + co) * 2 + 0) * st.cin + ci] = w[((size_t)ci * st.cout + co) * st.k + ph + r];
                             pp[(((size_t)ph * st.cout + co) * 2 + 1) * st.cin + ci] = w[((size_t)ci * st.cout + co) * st.k + ph];
                         }
-                if (int rc = upload(M, pp, &st.tr_wp)) return rc;
+                if (int rc = upload_gemm(M, pp, r * st.cout, 2 * st.cin, &st.tr_wp)) return rc;
             }
             if (int rc = upload_raw(M, b, st.cout, &st.tr_b)) return rc;
             const std::string rp = std::string(DEC) + std::to_string(di + 2);
@@ -429,8 +437,8 @@ int build_model(wt_model* M, TensorMap& tm) {
 // largest magnitude is not far from 1 (x = hi + lo * 2^-11 has an absolute floor of 2^-36), so a tensor whose maximum
 // lies outside [2^-6, 2^12] is stored as w * 2^e (maximum brought into [1, 2)) and its GEMMs multiply their
 // accumulators by 2^-e (GemmArgs::acc_scale; powers of two: exact).  A non-finite weight cannot be split at all:
-// the model then runs on the fp32 MFMA chain (wt_model::s32_ok).
-static int add_s32(wt_model* M, const float* w, long n, bool* split_ok = nullptr, bool gemm_only = false) {
+// the model then runs on the fp32 MFMA chain (wt_model::s32_ok).  The copy goes into *out, the record of the weight.
+static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* split_ok = nullptr, bool gemm_only = false) {
     if (!w || n <= 0 || (n % 32)) return 0;
     if (!split_ok) split_ok = &M->s32_ok;
     std::vector<float> h((size_t)n);
@@ -453,7 +461,7 @@ static int add_s32(wt_model* M, const float* w, long n, bool* split_ok = nullptr
     float* scale_dev = nullptr;
     if (scale != 1.f) {
         if (int rc = upload(M, std::vector<float>{scale}, &scale_dev)) return rc;
-        M->s32_acc_scale[w] = 1.f / scale;
+        out->acc_scale = 1.f / scale;
     }
     void* d = nullptr;
     WT_HIP_CHECK(hipMalloc(&d, (size_t)n * 4));
@@ -461,20 +469,19 @@ static int add_s32(wt_model* M, const float* w, long n, bool* split_ok = nullptr
     M->alloc_bytes.push_back((size_t)n * 4);
     M->weight_bytes += n * 4;
     if (int rc = launch_split_s32(w, d, n, nullptr, scale_dev)) return rc;
-    M->s32[w] = d;
+    out->p = d;
     // gemm_only: nothing but a GEMM reads this fp32 array, and the default plans multiply by the S32 copy (wt_model::lazy_f32)
     if (gemm_only && finite) M->lazy_f32.push_back({w, d, (int64_t)n, scale});
     return 0;
 }
 
 int build_splits(wt_model* M) {
-    const wt_arch& a = M->arch;
-    const int D = a.dim, I = a.intermediate_dim;
-    auto conv32 = [&](const ConvW& c, bool gemm_only = true) { return (c.cin % 32) ? 0 : add_s32(M, c.w, (long)c.cout * c.k * c.cin, nullptr, gemm_only); };
+    auto conv32 = [&](ConvW& c, bool gemm_only = true) { return (c.cin % 32) ? 0 : add_s32(M, c.w, (long)c.cout * c.k * c.cin, &c.s32, nullptr, gemm_only); };
+    auto gemm32 = [&](GemmW& g, bool* split_ok = nullptr, bool gemm_only = true) { return add_s32(M, g.w, (long)g.rows * g.cols, &g.s32, split_ok, gemm_only); };
     // the SEANetDecoder's weights are all zeros -> NaN after the weight-norm fold when a checkpoint without them was
     // loaded into the full module tree: they only decide how the SEANetDecoder plan runs
-    auto conv32sd = [&](const ConvW& c) { return (c.cin % 32) ? 0 : add_s32(M, c.w, (long)c.cout * c.k * c.cin, &M->sd_s32_ok, true); };
-    for (const ResStage& st : M->stages) {      // encoder chain on S32 operands (build_encode)
+    auto conv32sd = [&](ConvW& c) { return (c.cin % 32) ? 0 : add_s32(M, c.w, (long)c.cout * c.k * c.cin, &c.s32, &M->sd_s32_ok, true); };
+    for (ResStage& st : M->stages) {            // encoder chain on S32 operands (build_encode)
         if (st.down.cin % 32 == 0 && st.down.k == 2 * st.r && st.down.k <= 32) {
             // k = 2 * stride: every input frame feeds two output frames (taps j and j + stride).  Packing the taps as
             // (0, r, 1, r+1, ...) puts those two reads in adjacent K steps
@@ -489,11 +496,9 @@ int build_splits(wt_model* M) {
                 }
             float* dpk = nullptr;
             if (int rc = upload(M, pk, &dpk)) return rc;
-            if (int rc = add_s32(M, dpk, n)) return rc;
+            if (int rc = add_s32(M, dpk, n, &st.down.s32)) return rc;
             M->lazy_f32.push_back({dpk, nullptr, (int64_t)n, 1.f});      // only the split above ever read the repacked copy
-            M->s32[st.down.w] = M->s32.at(dpk);
-            if (M->s32_acc_scale.count(dpk)) M->s32_acc_scale[st.down.w] = M->s32_acc_scale.at(dpk);
-            M->s32_tap_pair[st.down.w] = true;
+            st.down.s32.tap_pair = true;
         } else
         if (int rc = conv32(st.down, false)) return rc;
         // the fused resblock kernels (C = 32, 64) read their conv weights in fp32 and split them themselves
@@ -503,28 +508,28 @@ int build_splits(wt_model* M) {
         if (int rc = conv32(st.sc, !fused)) return rc;
         if (st.cat.w) if (int rc = conv32(st.cat)) return rc;
     }
-    if (int rc = add_s32(M, M->enc_lstm.Wih0, 4L * M->H * M->H, nullptr, true)) return rc;
+    if (int rc = gemm32(M->enc_lstm.Wih0)) return rc;
     if (int rc = conv32(M->enc_final)) return rc;
-    if (int rc = add_s32(M, M->embed, (long)a.vq_bins * 512)) return rc;        // (the gathers read the fp32 codebook)
+    if (int rc = gemm32(M->embed, nullptr, false)) return rc;        // codebook 0 (the gathers read the fp32 codebooks)
     if (int rc = conv32(M->bb_embed)) return rc;
     for (int i = 0; i < 4; ++i) {
         if (int rc = conv32(M->res[i].c1)) return rc;
         if (int rc = conv32(M->res[i].c2)) return rc;
     }
-    for (const CnxBlock& c : M->cnx) {
-        if (int rc = add_s32(M, c.W1, (long)I * D, nullptr, true)) return rc;
-        if (int rc = add_s32(M, c.W2, (long)D * I, nullptr, true)) return rc;
+    for (CnxBlock& c : M->cnx) {
+        if (int rc = gemm32(c.W1)) return rc;
+        if (int rc = gemm32(c.W2)) return rc;
     }
-    if (int rc = add_s32(M, M->head_W, 2L * M->Kb * D, nullptr, true)) return rc;
-    if (int rc = add_s32(M, M->istft_W, 4L * M->Kq * M->Kq, nullptr, true)) return rc;
-    if (int rc = add_s32(M, M->at_Wqk, 2L * D * D, nullptr, true)) return rc;
-    if (int rc = add_s32(M, M->at_Wv, (long)D * D, nullptr, true)) return rc;
-    if (int rc = add_s32(M, M->at_Wp, (long)D * D, nullptr, true)) return rc;
+    if (int rc = gemm32(M->head_W)) return rc;
+    if (int rc = gemm32(M->istft_W)) return rc;
+    if (int rc = gemm32(M->at_Wqk)) return rc;
+    if (int rc = gemm32(M->at_Wv)) return rc;
+    if (int rc = gemm32(M->at_Wp)) return rc;
     if (M->has_seadec) {
         if (int rc = conv32sd(M->sd_first)) return rc;
-        if (int rc = add_s32(M, M->sd_lstm.Wih0, 4L * M->H * M->H, &M->sd_s32_ok, true)) return rc;
-        for (const SeaDecStage& st : M->sd_stages) {
-            if (st.tr_wp && st.cin % 16 == 0) if (int rc = add_s32(M, st.tr_wp, (long)st.r * st.cout * 2 * st.cin, &M->sd_s32_ok, true)) return rc;
+        if (int rc = gemm32(M->sd_lstm.Wih0, &M->sd_s32_ok)) return rc;
+        for (SeaDecStage& st : M->sd_stages) {
+            if (st.tr_wp.w && st.cin % 16 == 0) if (int rc = gemm32(st.tr_wp, &M->sd_s32_ok)) return rc;
             if (resblock_fusable(st.cout)) continue;            // its convs run inside resblock16
             if (int rc = conv32sd(st.sc)) return rc;
             if (int rc = conv32sd(st.c3)) return rc;
@@ -544,7 +549,7 @@ int build_splits(wt_model* M) {
 // header (magic, version, the wt_arch and a hash of it) and the model struct with every pointer written as
 // (allocation index).  Loading it is allocate + upload + fix up pointers: nothing is folded, packed or split again.
 static constexpr uint32_t PACK_MAGIC = 0x4b505457u;     // "WTPK"
-static constexpr int32_t PACK_VERSION = 6;
+static constexpr int32_t PACK_VERSION = 7;
 
 static uint64_t arch_hash_of(const wt_arch& a) {        // FNV-1a over the architecture struct and the layout version
     uint64_t h = 1469598103934665603ull;
@@ -590,8 +595,10 @@ struct Archive {
             else p = reinterpret_cast<T*>(static_cast<char*>((*allocs)[idx]) + off);
         }
     }
-    void conv(ConvW& c) { ptr(c.w); ptr(c.b); pod(c.cout); pod(c.cin); pod(c.k); }
-    void lstm(LstmW& l) { ptr(l.Wih0); ptr(l.b0); ptr(l.W0); ptr(l.W1); ptr(l.b1); ptr(l.W0h); ptr(l.W1h); ptr(l.Wp); }
+    void s32(S32Copy& s) { ptr(s.p); pod(s.acc_scale); pod(s.tap_pair); }
+    void conv(ConvW& c) { ptr(c.w); ptr(c.b); pod(c.cout); pod(c.cin); pod(c.k); s32(c.s32); }
+    void gemm(GemmW& g) { ptr(g.w); pod(g.rows); pod(g.cols); s32(g.s32); }
+    void lstm(LstmW& l) { gemm(l.Wih0); ptr(l.b0); ptr(l.W0); ptr(l.W1); ptr(l.b1); ptr(l.W0h); ptr(l.W1h); ptr(l.Wp); }
 };
 
 static void archive_model(Archive& ar, wt_model* M) {
@@ -602,42 +609,25 @@ static void archive_model(Archive& ar, wt_model* M) {
     ar.ptr(M->e0_w); ar.ptr(M->e0_b); ar.pod(M->e0_k); ar.pod(M->e0_c);
     n = ar.count(M->stages.size(), 8); M->stages.resize(n);
     for (ResStage& st : M->stages) { ar.conv(st.c3); ar.conv(st.c1); ar.conv(st.sc); ar.conv(st.down); ar.conv(st.cat); ar.pod(st.C); ar.pod(st.r); }
-    ar.lstm(M->enc_lstm); ar.conv(M->enc_final); ar.ptr(M->embed); ar.ptr(M->ee);
+    ar.lstm(M->enc_lstm); ar.conv(M->enc_final); ar.gemm(M->embed); ar.ptr(M->ee);
     ar.conv(M->bb_embed);
     for (PosRes& r : M->res) { ar.ptr(r.n1w); ar.ptr(r.n1b); ar.ptr(r.n2w); ar.ptr(r.n2b); ar.conv(r.c1); ar.conv(r.c2); }
-    ar.ptr(M->at_nw); ar.ptr(M->at_nb); ar.ptr(M->at_Wqk); ar.ptr(M->at_bqk); ar.ptr(M->at_Wv); ar.ptr(M->at_bv); ar.ptr(M->at_Wp); ar.ptr(M->at_bp);
+    ar.ptr(M->at_nw); ar.ptr(M->at_nb); ar.gemm(M->at_Wqk); ar.ptr(M->at_bqk); ar.gemm(M->at_Wv); ar.ptr(M->at_bv); ar.gemm(M->at_Wp); ar.ptr(M->at_bp);
     ar.ptr(M->gn5w); ar.ptr(M->gn5b); ar.ptr(M->ada_s); ar.ptr(M->ada_h);
     n = ar.count(M->cnx.size(), 64); M->cnx.resize(n);
-    for (CnxBlock& c : M->cnx) { ar.ptr(c.dw_w); ar.ptr(c.dw_b); ar.ptr(c.ada_s); ar.ptr(c.ada_h); ar.ptr(c.W1); ar.ptr(c.b1); ar.ptr(c.W2); ar.ptr(c.b2); ar.ptr(c.gamma); }
-    ar.ptr(M->fln_w); ar.ptr(M->fln_b); ar.ptr(M->head_W); ar.ptr(M->head_b);
+    for (CnxBlock& c : M->cnx) { ar.ptr(c.dw_w); ar.ptr(c.dw_b); ar.ptr(c.ada_s); ar.ptr(c.ada_h); ar.gemm(c.W1); ar.ptr(c.b1); ar.gemm(c.W2); ar.ptr(c.b2); ar.ptr(c.gamma); }
+    ar.ptr(M->fln_w); ar.ptr(M->fln_b); ar.gemm(M->head_W); ar.ptr(M->head_b);
     ar.pod(M->Kb); ar.pod(M->Kq); ar.pod(M->bins_f); ar.pod(M->R);
-    ar.ptr(M->istft_W); ar.ptr(M->wsq); ar.ptr(M->win);
+    ar.gemm(M->istft_W); ar.ptr(M->wsq); ar.ptr(M->win);
     ar.pod(M->has_seadec); ar.conv(M->sd_first); ar.lstm(M->sd_lstm);
     n = ar.count(M->sd_stages.size(), 8); M->sd_stages.resize(n);
     for (SeaDecStage& st : M->sd_stages) {
-        ar.ptr(st.tr_w); ar.ptr(st.tr_wp); ar.ptr(st.tr_b); ar.pod(st.cin); ar.pod(st.cout); ar.pod(st.k); ar.pod(st.r);
+        ar.ptr(st.tr_w); ar.gemm(st.tr_wp); ar.ptr(st.tr_b); ar.pod(st.cin); ar.pod(st.cout); ar.pod(st.k); ar.pod(st.r);
         ar.conv(st.c3); ar.conv(st.c1); ar.conv(st.sc); ar.conv(st.cat);
     }
     ar.ptr(M->sd_last_w); ar.ptr(M->sd_last_b);
-    // the maps keyed by the fp32 weight pointer
-    auto map_ptr = [&](auto& m, auto value_io) {
-        const int32_t cnt = ar.count(m.size(), 1 << 16);
-        if (ar.saving) {
-            // in allocation order, not in address order: the image of a model does not depend on where hipMalloc put it
-            std::vector<const float*> keys;
-            for (auto& kv : m) keys.push_back(kv.first);
-            auto alloc_of = [&](const float* k) { auto it = ar.index->upper_bound(static_cast<const void*>(k)); return it == ar.index->begin() ? -1 : std::prev(it)->second; };
-            std::sort(keys.begin(), keys.end(), [&](const float* a, const float* b) { return alloc_of(a) < alloc_of(b); });
-            for (const float* k0 : keys) { const float* k = k0; ar.ptr(k); value_io(m.at(k0)); }
-        } else {
-            for (int i = 0; i < cnt && ar.ok; ++i) { const float* k = nullptr; ar.ptr(k); auto& v = m[k]; value_io(v); }
-        }
-    };
-    map_ptr(M->s32, [&](void*& v) { ar.ptr(v); });
     n = ar.count(M->lazy_f32.size(), 1 << 12); M->lazy_f32.resize(n);
     for (wt_model::LazyF32& z : M->lazy_f32) { ar.ptr(z.w); ar.ptr(z.s32); ar.pod(z.n); ar.pod(z.scale); }
-    map_ptr(M->s32_tap_pair, [&](bool& v) { ar.pod(v); });
-    map_ptr(M->s32_acc_scale, [&](float& v) { ar.pod(v); });
 }
 
 struct PackHeader {
@@ -788,12 +778,22 @@ static int validate_imported(const wt_model* M) {
         return false;
     };
     auto bad = [](const char* what) { set_error(std::string("packed image: ") + what + " does not match the architecture in its header"); return WT_ERR_INVALID; };
-    auto conv_ok = [&](const ConvW& c, int cout, int cin, int k) {
-        return c.cout == cout && c.cin == cin && c.k == k && fits(c.w, (size_t)cout * cin * k * 4) && fits(c.b, (size_t)cout * 4);
+    // an S32 copy has the footprint of the fp32 array it stands for; taps in paired order only where the plan packs them
+    // so (encoder down convs, k = 2r)
+    auto copy_ok = [&](const S32Copy& s, size_t bytes, bool pair_ok) {
+        return (!s.p || fits(s.p, bytes)) && s.acc_scale > 0.f && std::isfinite(s.acc_scale) && (pair_ok || !s.tap_pair);
+    };
+    auto conv_ok = [&](const ConvW& c, int cout, int cin, int k, bool pair_ok = false) {
+        const size_t bytes = (size_t)cout * cin * k * 4;
+        return c.cout == cout && c.cin == cin && c.k == k && fits(c.w, bytes) && fits(c.b, (size_t)cout * 4) && copy_ok(c.s32, bytes, pair_ok);
+    };
+    auto gemm_ok = [&](const GemmW& g, int rows, int cols) {
+        const size_t bytes = (size_t)rows * cols * 4;
+        return g.rows == rows && g.cols == cols && fits(g.w, bytes) && copy_ok(g.s32, bytes, false);
     };
     auto lstm_ok = [&](const LstmW& l, int H) {
         const size_t hh = (size_t)4 * H * H * 4;
-        return fits(l.Wih0, hh) && fits(l.b0, (size_t)16 * H) && fits(l.W0, hh) && fits(l.W1, 2 * hh) && fits(l.b1, (size_t)16 * H) &&
+        return gemm_ok(l.Wih0, 4 * H, H) && fits(l.b0, (size_t)16 * H) && fits(l.W0, hh) && fits(l.W1, 2 * hh) && fits(l.b1, (size_t)16 * H) &&
                (!l.W0h || fits(l.W0h, hh)) && (!l.W1h || fits(l.W1h, 2 * hh)) &&
                (!l.Wp || fits(l.Wp, (size_t)3 * 32 * 4 * 16 * 2 * 64 * 16));
     };
@@ -809,46 +809,42 @@ static int validate_imported(const wt_model* M) {
         const ResStage& st = M->stages[i];
         const int r = a.ratios[a.n_ratios - 1 - i], C = mult * nf;
         if (M->enc_ratios[i] != r || st.C != C || st.r != r || !conv_ok(st.c3, C / 2, C, 3) || !conv_ok(st.c1, C, C / 2, 1) || !conv_ok(st.sc, C, C, 1) ||
-            !conv_ok(st.down, 2 * C, C, 2 * r)) return bad("an encoder stage");
-        if (st.cat.w && !(st.cat.cout == C && st.cat.cin == C + C / 2 && st.cat.k == 1 && fits(st.cat.w, (size_t)C * (C + C / 2) * 4) && fits(st.cat.b, (size_t)C * 4)))
-            return bad("a fused shortcut weight");
+            !conv_ok(st.down, 2 * C, C, 2 * r, true)) return bad("an encoder stage");
+        if ((st.cat.w || st.cat.s32.p) && !conv_ok(st.cat, C, C + C / 2, 1)) return bad("a fused shortcut weight");
         mult *= 2;
     }
     if (mult * nf != H || !lstm_ok(M->enc_lstm, H) || !conv_ok(M->enc_final, 512, H, 7)) return bad("the encoder tail");
-    if (!fits(M->embed, (size_t)a.num_quantizers * a.vq_bins * 512 * 4) || !fits(M->ee, (size_t)a.vq_bins * 4)) return bad("the codebook");
+    if (!gemm_ok(M->embed, a.vq_bins, 512) || !fits(M->embed.w, (size_t)a.num_quantizers * a.vq_bins * 512 * 4) || !fits(M->ee, (size_t)a.vq_bins * 4)) return bad("the codebook");
     if (!conv_ok(M->bb_embed, D, 512, 7)) return bad("backbone.embed");
     for (const PosRes& r : M->res)
         if (!fits(r.n1w, D * 4) || !fits(r.n1b, D * 4) || !fits(r.n2w, D * 4) || !fits(r.n2b, D * 4) || !conv_ok(r.c1, D, D, 3) || !conv_ok(r.c2, D, D, 3)) return bad("a pos_net block");
-    if (!fits(M->at_nw, D * 4) || !fits(M->at_nb, D * 4) || !fits(M->at_Wqk, (size_t)2 * D * D * 4) || !fits(M->at_bqk, 2 * D * 4) || !fits(M->at_Wv, (size_t)D * D * 4) ||
-        !fits(M->at_bv, D * 4) || !fits(M->at_Wp, (size_t)D * D * 4) || !fits(M->at_bp, D * 4)) return bad("the attention block");
+    if (!fits(M->at_nw, D * 4) || !fits(M->at_nb, D * 4) || !gemm_ok(M->at_Wqk, 2 * D, D) || !fits(M->at_bqk, 2 * D * 4) || !gemm_ok(M->at_Wv, D, D) ||
+        !fits(M->at_bv, D * 4) || !gemm_ok(M->at_Wp, D, D) || !fits(M->at_bp, D * 4)) return bad("the attention block");
     const size_t ada = (size_t)a.adanorm_num_embeddings * D * 4;
     if (!fits(M->gn5w, D * 4) || !fits(M->gn5b, D * 4) || !fits(M->ada_s, ada) || !fits(M->ada_h, ada)) return bad("backbone.norm");
     if ((int)M->cnx.size() != a.num_layers) return bad("the ConvNeXt block count");
     for (const CnxBlock& c : M->cnx)
-        if (!fits(c.dw_w, (size_t)7 * D * 4) || !fits(c.dw_b, D * 4) || !fits(c.ada_s, ada) || !fits(c.ada_h, ada) || !fits(c.W1, (size_t)I * D * 4) || !fits(c.b1, I * 4) ||
-            !fits(c.W2, (size_t)D * I * 4) || !fits(c.b2, D * 4) || !fits(c.gamma, D * 4)) return bad("a ConvNeXt block");
+        if (!fits(c.dw_w, (size_t)7 * D * 4) || !fits(c.dw_b, D * 4) || !fits(c.ada_s, ada) || !fits(c.ada_h, ada) || !gemm_ok(c.W1, I, D) || !fits(c.b1, I * 4) ||
+            !gemm_ok(c.W2, D, I) || !fits(c.b2, D * 4) || !fits(c.gamma, D * 4)) return bad("a ConvNeXt block");
     const int N = a.n_fft;
     if (N % 4 || N % a.hop_length) return bad("n_fft / hop_length");
     const int Kq = ((N / 4 + 1 + 31) / 32) * 32, Kb = 2 * Kq;
     if (M->Kq != Kq || M->Kb != Kb || M->bins_f != N / 2 + 1 || M->R != N / a.hop_length) return bad("the ISTFT head's shape");
-    if (!fits(M->fln_w, D * 4) || !fits(M->fln_b, D * 4) || !fits(M->head_W, (size_t)2 * Kb * D * 4) || !fits(M->head_b, (size_t)2 * Kb * 4) ||
-        !fits(M->istft_W, (size_t)4 * Kq * Kq * 4) || !fits(M->win, (size_t)N * 4) || !fits(M->wsq, (size_t)N * 4)) return bad("the ISTFT head");
+    if (!fits(M->fln_w, D * 4) || !fits(M->fln_b, D * 4) || !gemm_ok(M->head_W, 2 * Kb, D) || !fits(M->head_b, (size_t)2 * Kb * 4) ||
+        !gemm_ok(M->istft_W, 4 * Kq, Kq) || !fits(M->win, (size_t)N * 4) || !fits(M->wsq, (size_t)N * 4)) return bad("the ISTFT head");
     if (M->has_seadec) {
         if ((int)M->sd_stages.size() != a.n_ratios || !conv_ok(M->sd_first, (1 << a.n_ratios) * nf, 512, 7) || !lstm_ok(M->sd_lstm, H)) return bad("the SEANetDecoder");
         int m2 = 1 << a.n_ratios;
         for (int i = 0; i < a.n_ratios; ++i) {
             const SeaDecStage& st = M->sd_stages[i];
             const int r = a.ratios[i], cin = m2 * nf, h = cin / 2;
-            if (st.cin != cin || st.cout != h || st.k != 2 * r || st.r != r || !fits(st.tr_w, (size_t)2 * r * cin * h * 4) || (st.tr_wp && !fits(st.tr_wp, (size_t)2 * r * cin * h * 4)) ||
+            if (st.cin != cin || st.cout != h || st.k != 2 * r || st.r != r || !fits(st.tr_w, (size_t)2 * r * cin * h * 4) || ((st.tr_wp.w || st.tr_wp.s32.p) && !gemm_ok(st.tr_wp, r * h, 2 * cin)) ||
                 !fits(st.tr_b, h * 4) || !conv_ok(st.c3, h / 2, h, 3) || !conv_ok(st.c1, h, h / 2, 1) || !conv_ok(st.sc, h, h, 1)) return bad("a SEANetDecoder stage");
-            if (st.cat.w && !(st.cat.cout == h && st.cat.cin == h + h / 2 && fits(st.cat.w, (size_t)h * (h + h / 2) * 4) && fits(st.cat.b, (size_t)h * 4))) return bad("a SEANetDecoder fused shortcut");
+            if ((st.cat.w || st.cat.s32.p) && !conv_ok(st.cat, h, h + h / 2, 1)) return bad("a SEANetDecoder fused shortcut");
             m2 /= 2;
         }
         if (!fits(M->sd_last_w, 7 * nf * 4) || !fits(M->sd_last_b, 4)) return bad("the SEANetDecoder's last conv");
     }
-    // S32 copies: same footprint as the fp32 array they stand for; keys must be weights the plans look up (checked by extent)
-    for (const auto& kv : M->s32) if (!kv.first || !kv.second || !fits(kv.first, 128) || !fits(kv.second, 128)) return bad("an S32 copy");
-    for (const auto& kv : M->s32_acc_scale) if (!(kv.second > 0.f) || !std::isfinite(kv.second)) return bad("an S32 scale");
     return WT_OK;
 }
 

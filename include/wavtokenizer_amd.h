@@ -283,6 +283,41 @@ int wt_vq_nearest(const float* x, const float* embed, int64_t N, int32_t D, int3
 int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
                       void* workspace, void* stream);
 
+/* One GEMM launch through the plans' own launchers, with every argument a plan sets: the unit tests' view of each
+ * (epilogue, output format) pair and of each tile form the launchers pick.  Operands are fp32 device arrays in the
+ * plans' layouts (activations time-major [clip][frame][channel], B operand [N][K] with K = taps * Cin).  engine 0
+ * (gemm16s.hip) splits them into the S32 form in the workspace as the plans hold them: a B operand that is a weight
+ * (b_is_act = 0) with its per-tensor power-of-two scale and acc_scale, activations (A, A2, a B operand with
+ * b_is_act = 1) unscaled (the weight is read back to choose its scale: the call waits for `stream` once); a tap-paired B operand (tap_pair = 1) must already be packed in the paired tap order.
+ * engine 1 (gemm.hip) reads the fp32 arrays directly.  epi / out / pro take the values of the library's Epi, Out16s,
+ * Pro enums (the argmax epilogue is reached through wt_vq_nearest instead).  C (and C2) are written in the format
+ * `out` names (S32: 128-byte groups [32 x f16 hi | 32 x f16 lo]).  status: optional device word that the S32
+ * producers OR WT_STATUS_BIT_RANGE into.  The whole descriptor is checked before any HIP call: a problem the
+ * launchers refuse returns WT_ERR_INVALID and touches no memory.  form (optional): the launch the launcher chose. */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_gemm_desc) */
+    int32_t engine, epi, out, pro, b_is_act;
+    int32_t M, N, K;                /* M = clips * T_out */
+    int32_t T_in, T_out, Cin, taps, stride, dil, pad_left, pad_mode, Tp;   /* gather; pad_mode 0 zero, 1 reflect */
+    int32_t K1, nz, tap_pair, head_kb;
+    float alpha;
+    int64_t a_bstride, a_rstride, a2_bstride, a2_rstride, w_rstride, c_rstride, r_rstride, zA, zW, zC;   /* elements */
+    const float* A;
+    const float* A2;                /* K columns [K1, K) (engine 0 only) */
+    const float* B;                 /* [N][K] (per z slice: + z * zW) */
+    const float* bias;
+    const float* R;
+    const float* gamma;
+    float* C;
+    float* C2;
+    uint32_t* status;
+} wt_gemm_desc;
+typedef struct {
+    int32_t BM, BN, waves_m, waves_n, stages, ks, prod, staged, bias_cache, G, tiles;   /* G < tiles: persistent grid */
+} wt_launch_form;
+size_t wt_gemm_probe_workspace_bytes(const wt_gemm_desc* d);
+int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, void* stream);
+
 /* Replaces: SEANetResnetBlock.forward (encoder/modules/seanet.py:62-63): y = shortcut(x) + conv1(elu(conv3(elu(x)))),
  * one fused launch, time-major x [B][T][C] -> y [B][T][C], C = 32 or 64; folded weights w3 [C/2][3][C], w1 [C][C/2],
  * ws [C][C].  wav != NULL (C = 32): x is not read; the tile is built from the waveform wav [B][T] through

@@ -21,7 +21,7 @@ EXPORTS = [
     "wt_plan_find_buffer", "wt_plan_buffer_info", "wt_plan_buffer_name", "wt_plan_status", "wt_plan_num_steps", "wt_plan_step_name",
     "wt_plan_set_timing", "wt_plan_read_timing", "wt_model_split_ok", "wt_model_status", "wt_model_take_bad_codes", "wt_encode", "wt_codes_to_features",
     "wt_decode", "wt_seanet_decode", "wt_head", "wt_unit_run", "wt_sconv1d", "wt_linear", "wt_conv1d_s32", "wt_vq_workspace_bytes",
-    "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down",
+    "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down", "wt_gemm_probe_workspace_bytes", "wt_gemm_probe",
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
     "wt_linear_overlap_add",
 ]
@@ -49,6 +49,22 @@ class WtArch(ctypes.Structure):
 
 class WtTensor(ctypes.Structure):
     _fields_ = [("name", c_char_p), ("data", POINTER(c_float)), ("numel", c_int64)]
+
+
+class WtGemmDesc(ctypes.Structure):
+    """wt_gemm_desc: one GEMM launch through the plans' launchers (wt_gemm_probe)."""
+    _fields_ = ([("size", c_int32), ("engine", c_int32), ("epi", c_int32), ("out", c_int32), ("pro", c_int32), ("b_is_act", c_int32),
+                 ("M", c_int32), ("N", c_int32), ("K", c_int32)]
+                + [(n, c_int32) for n in ("T_in", "T_out", "Cin", "taps", "stride", "dil", "pad_left", "pad_mode", "Tp",
+                                         "K1", "nz", "tap_pair", "head_kb")]
+                + [("alpha", c_float)]
+                + [(n, c_int64) for n in ("a_bstride", "a_rstride", "a2_bstride", "a2_rstride", "w_rstride", "c_rstride",
+                                         "r_rstride", "zA", "zW", "zC")]
+                + [(n, c_void_p) for n in ("A", "A2", "B", "bias", "R", "gamma", "C", "C2", "status")])
+
+
+class WtLaunchForm(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("BM", "BN", "waves_m", "waves_n", "stages", "ks", "prod", "staged", "bias_cache", "G", "tiles")]
 
 
 class WavTokError(RuntimeError):
@@ -136,6 +152,9 @@ def _load() -> ctypes.CDLL:
     lib.wt_vq_nearest_f32.argtypes = [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     lib.wt_resblock.argtypes = [c_void_p] * 11 + [c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]
     lib.wt_resblock_down.argtypes = [c_void_p] * 12 + [c_int32, c_int64, c_int32, c_void_p]
+    lib.wt_gemm_probe_workspace_bytes.argtypes = [POINTER(WtGemmDesc)]
+    lib.wt_gemm_probe_workspace_bytes.restype = c_size_t
+    lib.wt_gemm_probe.argtypes = [POINTER(WtGemmDesc), POINTER(WtLaunchForm), c_void_p, c_void_p]
     lib.wt_resampler_create.argtypes = [c_int32, c_int32, c_int32, POINTER(c_void_p)]
     lib.wt_resampler_destroy.argtypes = [c_void_p]
     lib.wt_resampler_destroy.restype = None

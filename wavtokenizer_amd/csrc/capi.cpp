@@ -681,6 +681,104 @@ int wt_conv1d_s32(const float* x, const float* w, const float* bias, float* y, i
 }
 
 static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+// wt_gemm_probe: the S32 copies of A, A2 and B in the workspace (same element offsets as the fp32 arrays), then the scale
+struct ProbeLayout { long nA = 0, nA2 = 0, nB = 0; size_t oA2 = 0, oB = 0, oScale = 0, total = 0; };
+static ProbeLayout probe_layout(const wt_gemm_desc& d) {
+    ProbeLayout L;
+    const long clips = d.M / d.T_out;
+    const long a_cols = d.A2 ? d.K1 : d.Cin;
+    L.nA = (d.nz - 1) * d.zA + (clips - 1) * d.a_bstride + (long)(d.T_in - 1) * d.a_rstride + a_cols;
+    if (d.A2) L.nA2 = (clips - 1) * d.a2_bstride + (long)(d.T_in - 1) * d.a2_rstride + (d.K - d.K1);
+    L.nB = (d.nz - 1) * d.zW + (long)(d.N - 1) * d.w_rstride + d.K;
+    L.oA2 = al256((size_t)L.nA * 4);
+    L.oB = L.oA2 + al256((size_t)L.nA2 * 4);
+    L.oScale = L.oB + al256((size_t)L.nB * 4);
+    L.total = L.oScale + 256;
+    return L;
+}
+// the descriptor as the launchers' arguments; every check that needs no HIP call (the launchers' own included)
+static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
+    if (!d || d->size != (int32_t)sizeof(wt_gemm_desc)) { set_error("wt_gemm_probe: descriptor missing or of another size"); return WT_ERR_INVALID; }
+    if (d->engine != 0 && d->engine != 1) { set_error("wt_gemm_probe: engine is 0 (gemm16s) or 1 (gemm)"); return WT_ERR_INVALID; }
+    if (!d->A || !d->B || !d->C) { set_error("wt_gemm_probe: A, B and C are required"); return WT_ERR_INVALID; }
+    if (d->epi == EPI_ARGMAX) { set_error("wt_gemm_probe: the argmax epilogue is reached through wt_vq_nearest"); return WT_ERR_INVALID; }
+    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->T_out <= 0 || d->T_in <= 0 || d->M % d->T_out || d->nz < 1 || d->taps < 1 ||
+        d->stride < 1 || d->dil < 1 || d->pad_left < 0 || (d->pad_mode != PAD_ZERO && d->pad_mode != PAD_REFLECT) ||
+        d->a_bstride < 0 || d->a_rstride < 0 || d->a2_bstride < 0 || d->a2_rstride < 0 || d->w_rstride < d->K ||
+        d->c_rstride < d->N || d->r_rstride < 0 || d->zA < 0 || d->zW < 0 || d->zC < 0 || (d->nz > 1 && d->zC <= 0)) {
+        set_error("wt_gemm_probe: bad extents or strides"); return WT_ERR_INVALID;
+    }
+    if (d->engine == 1 && (d->out != OUT_F32 || d->A2 || d->tap_pair)) {
+        set_error("wt_gemm_probe: gemm.hip writes fp32 and has no second K source or tap pairing"); return WT_ERR_INVALID;
+    }
+    if (d->engine == 0 && d->pro != PRO_NONE) { set_error("wt_gemm_probe: gemm16s has no operand prologue"); return WT_ERR_INVALID; }
+    if (d->tap_pair && (d->taps != 2 * d->stride || d->dil != 1)) { set_error("wt_gemm_probe: tap pairing needs k = 2 * stride, dilation 1"); return WT_ERR_INVALID; }
+    if (d->engine == 0 && (!ws || (reinterpret_cast<uintptr_t>(ws) & 255))) { set_error("wt_gemm_probe: gemm16s needs a 256-byte aligned workspace"); return WT_ERR_INVALID; }
+    a = GemmArgs{};
+    a.a_bstride = d->a_bstride; a.a_rstride = d->a_rstride; a.T_in = d->T_in; a.T_out = d->T_out; a.Cin = d->Cin; a.taps = d->taps;
+    a.stride = d->stride; a.dil = d->dil; a.pad_left = d->pad_left; a.pad_mode = d->pad_mode; a.Tp = d->Tp;
+    a.a2_bstride = d->a2_bstride; a.a2_rstride = d->a2_rstride; a.K1 = d->K1;
+    a.w_rstride = d->w_rstride; a.bias = d->bias; a.M = d->M; a.N = d->N; a.K = d->K;
+    a.C = d->C; a.c_rstride = d->c_rstride; a.C2 = d->C2; a.R = d->R; a.r_rstride = d->r_rstride; a.gamma = d->gamma;
+    a.alpha = d->alpha; a.nz = d->nz; a.zA = d->zA; a.zW = d->zW; a.zC = d->zC; a.head_kb = d->head_kb; a.tap_pair = d->tap_pair ? 1 : 0;
+    if (d->engine == 1) {
+        a.A = d->A; a.W = d->B;
+        return check_gemm(a, d->pro, d->epi) ? WT_ERR_INVALID : WT_OK;
+    }
+    const ProbeLayout L = probe_layout(*d);
+    a.A = reinterpret_cast<const float*>(ws);
+    a.A2 = d->A2 ? reinterpret_cast<const float*>(ws + L.oA2) : nullptr;
+    a.W = d->B; a.W_hi = ws + L.oB;
+    a.status = reinterpret_cast<unsigned*>(d->status);
+    return check_gemm16s(a, d->epi, d->out) ? WT_ERR_INVALID : WT_OK;
+}
+
+size_t wt_gemm_probe_workspace_bytes(const wt_gemm_desc* d) {
+    if (!d || d->size != (int32_t)sizeof(wt_gemm_desc) || d->engine != 0 || d->M <= 0 || d->T_out <= 0 || d->nz < 1) return 0;
+    return probe_layout(*d).total;
+}
+
+int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, void* stream) {
+    char* ws = static_cast<char*>(workspace);
+    GemmArgs a;
+    if (int rc = probe_args(d, ws, a)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LaunchForm lf;
+    a.form = &lf;
+    if (d->engine == 1) {
+        if (int rc = launch_gemm(a, d->pro, d->epi, s)) return rc;
+    } else {
+        const ProbeLayout L = probe_layout(*d);
+        float* scale_dev = reinterpret_cast<float*>(ws + L.oScale);
+        float scale = 1.f;
+        if (!d->b_is_act) {      // a weight: the plans' per-tensor power of two (weights.cpp add_s32), chosen over its logical rows
+            std::vector<float> h((size_t)L.nB);
+            WT_HIP_CHECK(hipMemcpyAsync(h.data(), d->B, (size_t)L.nB * 4, hipMemcpyDeviceToHost, s));
+            WT_HIP_CHECK(hipStreamSynchronize(s));
+            float amax = 0.f;
+            for (long z = 0; z < d->nz; ++z)
+                for (long n = 0; n < d->N; ++n)
+                    for (long k = 0; k < d->K; ++k) {
+                        const float v = std::fabs(h[(size_t)(z * d->zW + n * d->w_rstride + k)]);
+                        if (!(v <= 3.0e38f)) { set_error("wt_gemm_probe: a non-finite weight has no S32 copy"); return WT_ERR_INVALID; }
+                        amax = std::max(amax, v);
+                    }
+            scale = s32_weight_scale(amax);
+            uint32_t bits;
+            memcpy(&bits, &scale, 4);
+            if (int rc = launch_fill_u32(scale_dev, bits, 16, s)) return rc;
+            a.acc_scale = 1.f / scale;
+        }
+        if (int rc = launch_split_s32(d->B, ws + L.oB, L.nB, s, scale != 1.f ? scale_dev : nullptr)) return rc;
+        if (int rc = launch_split_s32(d->A, ws, L.nA, s)) return rc;
+        if (d->A2) if (int rc = launch_split_s32(d->A2, ws + L.oA2, L.nA2, s)) return rc;
+        if (int rc = launch_gemm16s(a, d->epi, d->out, s)) return rc;
+    }
+    if (form) *form = wt_launch_form{lf.BM, lf.BN, lf.waves_m, lf.waves_n, lf.stages, lf.ks, lf.prod, lf.staged, lf.bias_cache, lf.G, lf.tiles};
+    return WT_OK;
+}
+
 size_t wt_vq_workspace_bytes(int64_t N, int32_t D, int32_t bins) {
     const size_t np = std::max(gemm_vq_parts(bins), gemm16s_vq_parts(bins));
     return al256((size_t)N * D * 4) + al256((size_t)bins * D * 4) + al256((size_t)N * sizeof(float)) +

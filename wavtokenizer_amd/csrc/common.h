@@ -158,6 +158,14 @@ enum Out16s : int {
 };
 enum PadMode : int { PAD_ZERO = 0, PAD_REFLECT = 1 };
 
+// What a GEMM launcher chose for one launch (host only; GemmArgs::form, filled when set: wt_gemm_probe)
+struct LaunchForm {
+    int BM = 0, BN = 0, waves_m = 0, waves_n = 0, stages = 0;
+    int ks = 1, prod = 0;        // gemm16s: K tiles per barrier, loader-wave sets
+    int staged = 0, bias_cache = 0;   // gemm16s: epilogue staged through LDS; bias (and gamma) cached in LDS
+    int G = 0, tiles = 0;        // workgroups per z slice (grid.x) and output tiles per z slice: G < tiles = persistent
+};
+
 struct GemmArgs {
     // A gather
     const float* A = nullptr;
@@ -209,9 +217,13 @@ struct GemmArgs {
     const float* acc_scale_dev = nullptr;  // stored scaled) before bias / activation; the device copy, when set, wins
     unsigned* status = nullptr;            // gemm16s: call status word (range report of the S32 epilogues); launcher default: g_launch
     unsigned long long* dbg_stamps = nullptr;   // gemm16s timing-experiment builds: per workgroup {s_memtime, s_memrealtime} spans
+    LaunchForm* form = nullptr;            // host: when set, the launcher records the form it launched (plans leave it null)
 };
 
 int gemm_vq_parts(int N);   // partial (val, idx) slots per row written by EPI_ARGMAX
+// the launchers' argument checks on their own (no HIP call): 0 if launch_gemm / launch_gemm16s would launch this problem
+int check_gemm(const GemmArgs& a, int pro, int epi);
+int check_gemm16s(const GemmArgs& a, int epi, int out);
 int launch_gemm(const GemmArgs& a, int pro, int epi, hipStream_t s);
 // gemm16s.hip: both operands pre-split in the S32 layout (128-byte groups [32 x f16 hi | 32 x f16 lo], same
 // footprint and strides as the fp32 array); a.A / a.W_hi point at S32 data, out_s32 selects an S32 C

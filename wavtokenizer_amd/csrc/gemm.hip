@@ -335,6 +335,7 @@ static int launch_one(const GemmArgs& a, hipStream_t s) {
     })) return rc;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, a.nz);
+    if (a.form) *a.form = LaunchForm{BM, BN, WMs, WNs, 2, 1, 0, 0, 0, tiles_m * tiles_n, tiles_m * tiles_n};
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -417,24 +418,34 @@ static int check_args(const GemmArgs& a) {
     return 0;
 }
 
+// the (prologue, epilogue) pairs the plans use: the one list both the checks and the dispatch read
+#define WT_GEMM_PAIRS(X) \
+    X(PRO_NONE, EPI_BIAS) X(PRO_ELU, EPI_BIAS) X(PRO_ELU, EPI_BIAS_RES) X(PRO_ELU, EPI_BIAS_RES_ELU) X(PRO_NONE, EPI_BIAS_RES) \
+    X(PRO_NONE, EPI_BIAS_GELU) X(PRO_NONE, EPI_BIAS_GAMMA_RES) X(PRO_NONE, EPI_HEAD) X(PRO_NONE, EPI_ARGMAX) \
+    X(PRO_NONE, EPI_SCALE) X(PRO_NONE, EPI_BIAS_ROW)
+
+int check_gemm(const GemmArgs& a, int pro, int epi) {
+    bool known = false;
+#define WT_PAIR(P, E) known = known || (pro == P && epi == E);
+    WT_GEMM_PAIRS(WT_PAIR)
+#undef WT_PAIR
+    if (!known) { set_error("gemm: unsupported prologue/epilogue pair"); return -1; }
+    if (int rc = check_args(a)) return rc;
+    if ((!a.C && epi != EPI_ARGMAX) || ((epi == EPI_BIAS_RES || epi == EPI_BIAS_RES_ELU || epi == EPI_BIAS_GAMMA_RES) && !a.R) ||
+        (epi == EPI_BIAS_GAMMA_RES && !a.gamma) || ((epi == EPI_BIAS_ROW || epi == EPI_HEAD) && !a.bias) ||
+        (epi == EPI_HEAD && (a.N % 32 || a.head_kb <= 0))) {
+        set_error("gemm: this epilogue needs C and its R / gamma / bias operands (the head: N % 32 == 0 and head_kb)"); return -1;
+    }
+    return 0;
+}
+
 int launch_gemm(const GemmArgs& a_in, int pro, int epi, hipStream_t s) {
-    if (int rc = check_args(a_in)) return rc;
+    if (int rc = check_gemm(a_in, pro, epi)) return rc;
     GemmArgs a = a_in;
     a.group_m = pick_group_m(a);
 #define WT_CASE(P, E) \
     if (pro == P && epi == E) return launch_tiled<P, E>(a, s);
-    // the (prologue, epilogue) pairs the plans use
-    WT_CASE(PRO_NONE, EPI_BIAS)
-    WT_CASE(PRO_ELU, EPI_BIAS)
-    WT_CASE(PRO_ELU, EPI_BIAS_RES)
-    WT_CASE(PRO_ELU, EPI_BIAS_RES_ELU)
-    WT_CASE(PRO_NONE, EPI_BIAS_RES)
-    WT_CASE(PRO_NONE, EPI_BIAS_GELU)
-    WT_CASE(PRO_NONE, EPI_BIAS_GAMMA_RES)
-    WT_CASE(PRO_NONE, EPI_HEAD)
-    WT_CASE(PRO_NONE, EPI_ARGMAX)
-    WT_CASE(PRO_NONE, EPI_SCALE)
-    WT_CASE(PRO_NONE, EPI_BIAS_ROW)
+    WT_GEMM_PAIRS(WT_CASE)
 #undef WT_CASE
     set_error("gemm: unsupported prologue/epilogue pair");
     return -1;

@@ -1198,6 +1198,7 @@ static int launch16s_one(const GemmArgs& a, hipStream_t s) {
         b.stamp_start = g_launch.stamp_start; b.stamp_end = g_launch.stamp_end;
         g_launch.stamp_used = true;
     }
+    if (a.form) *a.form = LaunchForm{BM, BN, WMs, WNs, NSTAGE, KS, PROD, b.stage_epi, b.pc_off ? 1 : 0, G, ntiles};
     hipLaunchKernelGGL(kern, dim3(G, 1, a.nz), dim3(64 * WMs * WNs * (1 + PROD)), smem, s, b);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1267,11 +1268,21 @@ static int launch16s_tiled(const GemmArgs& a, hipStream_t s) {
 
 int gemm16s_vq_parts(int N) { return ((N + 191) / 192) * 2; }      // (column tiles of 192) x (2 wave columns)
 
+// The (epilogue, output format) pairs the plans use: the one list both the checks and the dispatch read
+#define WT_GEMM16S_PAIRS(X) \
+    X(EPI_BIAS, OUT_F32) X(EPI_BIAS, OUT_S32) X(EPI_BIAS, OUT_S32_DUAL_ELU) X(EPI_BIAS, OUT_F32_AND_S32) \
+    X(EPI_BIAS_RES, OUT_F32) X(EPI_BIAS_ELU, OUT_S32) X(EPI_BIAS_RES_ELU, OUT_S32) X(EPI_BIAS_GELU, OUT_S32) \
+    X(EPI_BIAS_GAMMA_RES, OUT_F32) X(EPI_HEAD, OUT_S32) X(EPI_ARGMAX, OUT_F32) X(EPI_SCALE, OUT_F32) X(EPI_BIAS_ROW, OUT_S32)
+
 // Contract: a.A = S32 activations (same strides as the fp32 array),
 // a.W_hi = S32 weights [N][K]; out_s32 selects an S32 C (c_rstride in fp32 elements either way).
-int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s) {
+int check_gemm16s(const GemmArgs& c, int epi, int out) {
+    bool known = false;
+#define WT_PAIR16S(E, O) known = known || (epi == E && out == O);
+    WT_GEMM16S_PAIRS(WT_PAIR16S)
+#undef WT_PAIR16S
+    if (!known) { set_error("gemm16s: unsupported epilogue / output-format pair"); return -1; }
     const bool out_s32 = out != OUT_F32;        // some S32 array is written: whole 32-column groups
-    const GemmArgs& c = a_in;
     if (c.M <= 0 || c.N <= 0 || c.K <= 0 || c.K % SBK || c.Cin % SBK || c.K != c.taps * c.Cin || c.T_out <= 0 ||
         c.M % c.T_out || c.taps > 32 || !c.W_hi || !c.A || (c.w_rstride % 32) || (c.zW % 32) || (c.a_rstride % 32) ||
         (c.a_bstride % 32) || (c.zA % 32) || ((c.N % 4) && !((epi == EPI_SCALE || epi == EPI_BIAS_ROW) && c.c_rstride >= ((c.N + 3) & ~3))) || (c.c_rstride % 4) || (c.zC % 4) || (c.r_rstride % 4) || (out_s32 && ((c.c_rstride % 32) || (c.zC % 32)))) {
@@ -1298,6 +1309,20 @@ int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s) {
             return -1;
         }
     }
+    if ((out == OUT_S32_DUAL_ELU || out == OUT_F32_AND_S32) && !c.C2) { set_error("gemm16s: this output format needs C2"); return -1; }
+    if (epi == EPI_HEAD && (!c.bias || c.N % 32 || c.head_kb <= 0)) { set_error("gemm16s: head epilogue needs a bias, N % 32 == 0 and head_kb"); return -1; }
+    if ((!c.C && epi != EPI_ARGMAX) || ((epi == EPI_BIAS_RES || epi == EPI_BIAS_RES_ELU || epi == EPI_BIAS_GAMMA_RES) && !c.R) ||
+        (epi == EPI_BIAS_GAMMA_RES && !c.gamma) || (epi == EPI_BIAS_ROW && !c.bias)) {
+        set_error("gemm16s: this epilogue needs C and its R / gamma / bias operands"); return -1;
+    }
+    if (epi == EPI_ARGMAX && (!c.vq_xx || !c.vq_ee || !c.vq_pval || !c.vq_pidx || c.vq_nparts != gemm16s_vq_parts(c.N))) {
+        set_error("gemm16s: argmax epilogue needs xx, ee and (value, index) slots for gemm16s_vq_parts(N) parts"); return -1;
+    }
+    return 0;
+}
+
+int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s) {
+    if (int rc = check_gemm16s(a_in, epi, out)) return rc;
     GemmArgs a = a_in;
     // Tile order.  An XCD runs 30 tiles at a time (240 persistent workgroups / 8); a round pulls the A panels of its row tiles
     // and the W panels of its column tiles through that XCD's L2 once.  Wide outputs (ConvNeXt pwconv1: 60 x 12 tiles) walk
@@ -1308,25 +1333,8 @@ int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s) {
     if (tiles_n192 >= 12 && tiles_n192 % 6 == 0 && a.nz == 1) { a.group_m = 5; a.group_n = 6; }
     if (const char* e = lab_env("WT_GEMM16S_GM")) { a.group_m = atoi(e) > 0 ? atoi(e) : a.group_m; a.group_n = 0; }      // sweeps (tools/gemm16s_bench.py)
     if (const char* e = lab_env("WT_GEMM16S_GN")) a.group_n = atoi(e);
-    if ((out == OUT_S32_DUAL_ELU || out == OUT_F32_AND_S32) && !c.C2) { set_error("gemm16s: this output format needs C2"); return -1; }
-    if (epi == EPI_HEAD && (!c.bias || c.N % 32 || c.head_kb <= 0)) { set_error("gemm16s: head epilogue needs a bias, N % 32 == 0 and head_kb"); return -1; }
-    if (epi == EPI_ARGMAX && (!c.vq_xx || !c.vq_ee || !c.vq_pval || !c.vq_pidx || c.vq_nparts != gemm16s_vq_parts(c.N))) {
-        set_error("gemm16s: argmax epilogue needs xx, ee and (value, index) slots for gemm16s_vq_parts(N) parts"); return -1;
-    }
 #define WT_CASE16S(E, O) if (epi == E && out == O) return launch16s_tiled<E, O>(a, s);
-    WT_CASE16S(EPI_BIAS, OUT_F32)
-    WT_CASE16S(EPI_BIAS, OUT_S32)
-    WT_CASE16S(EPI_BIAS, OUT_S32_DUAL_ELU)
-    WT_CASE16S(EPI_BIAS, OUT_F32_AND_S32)
-    WT_CASE16S(EPI_BIAS_RES, OUT_F32)
-    WT_CASE16S(EPI_BIAS_ELU, OUT_S32)
-    WT_CASE16S(EPI_BIAS_RES_ELU, OUT_S32)
-    WT_CASE16S(EPI_BIAS_GELU, OUT_S32)
-    WT_CASE16S(EPI_BIAS_GAMMA_RES, OUT_F32)
-    WT_CASE16S(EPI_HEAD, OUT_S32)
-    WT_CASE16S(EPI_ARGMAX, OUT_F32)
-    WT_CASE16S(EPI_SCALE, OUT_F32)
-    WT_CASE16S(EPI_BIAS_ROW, OUT_S32)
+    WT_GEMM16S_PAIRS(WT_CASE16S)
 #undef WT_CASE16S
     set_error("gemm16s: unsupported epilogue / output-format pair");
     return -1;

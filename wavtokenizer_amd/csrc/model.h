@@ -323,6 +323,9 @@ namespace wt {
 // weights.cpp
 int build_model(wt_model* M, TensorMap& tm);
 int build_splits(wt_model* M);
+// the power of two a weight whose largest |value| is amax is multiplied by in its S32 copy (1: stored as it is); the GEMMs that
+// read the copy take acc_scale = 1 / this
+float s32_weight_scale(float amax);
 // packed image of a model (weights.cpp): everything wt_model_create computes and uploads, ready to upload again
 size_t model_export_bytes(const wt_model* M);
 int model_export(const wt_model* M, void* buf, size_t n);

@@ -438,6 +438,12 @@ int build_model(wt_model* M, TensorMap& tm) {
 // lies outside [2^-6, 2^12] is stored as w * 2^e (maximum brought into [1, 2)) and its GEMMs multiply their
 // accumulators by 2^-e (GemmArgs::acc_scale; powers of two: exact).  A non-finite weight cannot be split at all:
 // the model then runs on the fp32 MFMA chain (wt_model::s32_ok).  The copy goes into *out, the record of the weight.
+float s32_weight_scale(float amax) {
+    if (!(amax > 0.f) || (amax >= 0x1p-6f && amax < 0x1p12f)) return 1.f;
+    int e = 0;
+    (void)std::frexp(amax, &e);                 // amax = m * 2^e, m in [0.5, 1)
+    return std::ldexp(1.f, 1 - e);              // amax * scale in [1, 2)
+}
 static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* split_ok = nullptr, bool gemm_only = false) {
     if (!w || n <= 0 || (n % 32)) return 0;
     if (!split_ok) split_ok = &M->s32_ok;
@@ -452,12 +458,7 @@ static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* spli
     }
     if (!finite) *split_ok = false;
     M->w_amax = std::max(M->w_amax, amax);
-    float scale = 1.f;
-    if (finite && amax > 0.f && (amax < 0x1p-6f || amax >= 0x1p12f)) {
-        int e = 0;
-        (void)std::frexp(amax, &e);                 // amax = m * 2^e, m in [0.5, 1)
-        scale = std::ldexp(1.f, 1 - e);             // amax * scale in [1, 2)
-    }
+    const float scale = finite ? s32_weight_scale(amax) : 1.f;
     float* scale_dev = nullptr;
     if (scale != 1.f) {
         if (int rc = upload(M, std::vector<float>{scale}, &scale_dev)) return rc;

@@ -105,9 +105,12 @@ enum {
                                       plan must not be run from two host threads at once */
     WT_PLAN_FLAG_FP32_GEMM = 2,    /* every dense layer on the fp32 MFMA chain; default: the fp32-equivalent
                                       split-f16 kernel (3 f16 MFMAs per product, fp32 accumulate) where covered */
-    WT_PLAN_FLAG_RANGE_REPORT = 32 /* diagnostic: behind every step, the largest magnitude held by each S32 (split-f16) buffer the
+    WT_PLAN_FLAG_RANGE_REPORT = 32,/* diagnostic: behind every step, the largest magnitude held by each S32 (split-f16) buffer the
                                       step touches is measured (wt_plan_range_report): the head-room of every dense layer's
                                       operands below the f16 limit 65504.  Costs a pass per buffer; never graph-replayed */
+    WT_PLAN_FLAG_MIXED_LENGTH = 64 /* WT_PLAN_ENCODE: clips of different lengths in one call (wt_encode_mixed); `len` is the padded
+                                      length.  Only the shipped route takes it: refused together with UNFUSED, FP32_GEMM,
+                                      KEEP_STAGES or RANGE_REPORT, with the encoder site on fp32, or for weights without S32 copies */
 };
 
 /* Range sites: the units in which a plan can leave the split-f16 form on its own (wt_plan_create_ex, wt_plan_range_sites).
@@ -218,6 +221,23 @@ int wt_plan_read_timing(const wt_plan* p, double* total_ms, int64_t* launches, i
  *   emb_out  optional [B][512][L] fp32: encoder output before quantisation (may be NULL) */
 int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* codes, float* emb_out,
               void* workspace, void* stream);
+
+/* A batch of clips of different lengths on a WT_PLAN_FLAG_MIXED_LENGTH plan (B, Tpad): clip b is lengths[b] samples long and
+ * gets exactly the codes and features a plan of its own length computes (the lengths are read on the device, so a recorded
+ * graph replays for any lengths).
+ *   wav      [B][Tpad] fp32 (device): samples past a clip's length are never read
+ *   lengths  [B] int32 (device), each in [wt_plan_min_clip_length(p), Tpad]
+ *   features [B][512][Lpad], codes [1][B][Lpad], emb_out (optional) [B][512][Lpad]: past a clip's L = ceil(length / hop) the
+ *            codes are -1 and the features (and emb_out) 0.  A clip whose length is outside the range gets -1 codes and NaN
+ *            features over its whole row; the other clips and the call's status are not affected.
+ * wt_encode refuses a mixed-length plan, and wt_encode_mixed every other plan. */
+int wt_encode_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, float* features, int64_t* codes, float* emb_out,
+                    void* workspace, void* stream);
+/* The shortest clip a mixed-length plan takes (samples); 0 for any other plan. */
+int64_t wt_plan_min_clip_length(const wt_plan* p);
+/* SConv1d geometry (encoder/modules/conv.py:54-61, 86-91, 195-211) of a non-causal conv over T samples, the function the plans
+ * (and the mixed-length geometry step on the device) use: out = {left pad, total right pad, output frames, reflect length}. */
+int wt_sconv_geometry(int64_t T, int32_t k, int32_t stride, int32_t dilation, int32_t out[4]);
 
 /* Replaces: WavTokenizer.codes_to_features (decoder/pretrained.py:209-239).
  *   codes [K][B][L] int64, features [B][512][L] fp32; K <= num_quantizers. */

@@ -23,7 +23,7 @@ EXPORTS = [
     "wt_decode", "wt_seanet_decode", "wt_head", "wt_unit_run", "wt_sconv1d", "wt_linear", "wt_conv1d_s32", "wt_vq_workspace_bytes",
     "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down", "wt_gemm_probe_workspace_bytes", "wt_gemm_probe",
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
-    "wt_linear_overlap_add",
+    "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -33,8 +33,10 @@ WT_PLAN_FLAG_STEP_LSTM = 4
 WT_PLAN_FLAG_GRAPH = 8
 WT_PLAN_FLAG_UNFUSED = 16
 WT_PLAN_FLAG_RANGE_REPORT = 32
+WT_PLAN_FLAG_MIXED_LENGTH = 64
 WT_SITE_ENCODER, WT_SITE_BB_EMBED, WT_SITE_RES0, WT_SITE_RES1, WT_SITE_ATTN, WT_SITE_RES2, WT_SITE_RES3 = 0, 1, 2, 3, 4, 5, 6
 WT_SITE_CNX0, WT_SITE_HEAD, WT_SITE_SEANET_DECODER = 7, 40, 41
+WT_ERR_INVALID = -1
 WT_ERR_RANGE, WT_ERR_LSTM_SYNC, WT_ERR_INDEX = -6, -7, -8
 WT_STATUS_BIT_LSTM, WT_STATUS_BIT_RANGE = 1, 2
 BUF_S32, BUF_ELU = 1, 2
@@ -137,6 +139,10 @@ def _load() -> ctypes.CDLL:
     lib.wt_plan_set_timing.argtypes = [c_void_p, c_char_p]
     lib.wt_plan_read_timing.argtypes = [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]
     lib.wt_encode.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.wt_encode_mixed.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.wt_plan_min_clip_length.argtypes = [c_void_p]
+    lib.wt_plan_min_clip_length.restype = c_int64
+    lib.wt_sconv_geometry.argtypes = [c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]
     lib.wt_codes_to_features.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]
     lib.wt_decode.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.wt_seanet_decode.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]

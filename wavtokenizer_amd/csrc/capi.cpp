@@ -172,6 +172,9 @@ int wt_plan_create_ex(const wt_model* m, int32_t kind, int32_t B, int64_t len, i
     if (!m || !out) { set_error("wt_plan_create: null argument"); return WT_ERR_INVALID; }
     if (m->arch.num_layers > SITE_HEAD - SITE_CNX0) { set_error("wt_plan_create: more ConvNeXt blocks than range sites"); return WT_ERR_INVALID; }
     if (B < 1 || len < 1) { set_error("wt_plan_create: B and len must be >= 1"); return WT_ERR_INVALID; }
+    if ((flags & WT_PLAN_FLAG_MIXED_LENGTH) && kind != WT_PLAN_ENCODE) {
+        set_error("wt_plan_create: WT_PLAN_FLAG_MIXED_LENGTH is an encode-plan flag"); return WT_ERR_INVALID;
+    }
     if ((len + (kind == WT_PLAN_ENCODE ? m->hop - 1 : 0)) / (kind == WT_PLAN_ENCODE ? m->hop : 1) > 12000) {
         set_error("clips longer than 12000 frames are not supported by one plan; split the clip"); return WT_ERR_INVALID;
     }
@@ -237,6 +240,16 @@ void wt_plan_destroy(wt_plan* p) {
 }
 size_t wt_plan_workspace_bytes(const wt_plan* p) { return p ? p->ws_bytes : 0; }
 int64_t wt_plan_frames(const wt_plan* p) { return p ? p->L : 0; }
+int64_t wt_plan_min_clip_length(const wt_plan* p) { return p && (p->flags & WT_PLAN_FLAG_MIXED_LENGTH) ? p->min_clip : 0; }
+int wt_sconv_geometry(int64_t T, int32_t k, int32_t stride, int32_t dilation, int32_t out[4]) {
+    if (!out || T < 1 || k < 1 || stride < 1 || dilation < 1 || (int64_t)(k - 1) * dilation + 1 < stride || T >= INT_MAX) {
+        set_error("wt_sconv_geometry: needs T, k, stride, dilation >= 1 and an effective kernel no shorter than the stride");
+        return WT_ERR_INVALID;
+    }
+    const SConvGeom g = sconv_geom((long)T, k, stride, dilation);
+    out[0] = g.pl; out[1] = g.pr_total; out[2] = g.Tout; out[3] = g.Tp;
+    return WT_OK;
+}
 int wt_plan_num_launches(const wt_plan* p) { return p ? p->n_launches : 0; }
 
 int wt_plan_find_buffer(const wt_plan* p, const char* name, size_t* offset, size_t* numel) {
@@ -364,7 +377,7 @@ static int run_plan(const wt_plan* p, const RunCtx& c) {
 static int run_plan_locked(const wt_plan* p, const RunCtx& c) {
     const bool timing = !p->timing_filter.empty();
     if ((p->flags & WT_PLAN_FLAG_GRAPH) && !timing && !p->graph_failed && !p->range_dev) {
-        const wt_plan::GraphKey key{c.ws, c.in_f, c.out_f, c.codes, c.aux, c.bw_id};
+        const wt_plan::GraphKey key{c.ws, c.in_f, c.out_f, c.codes, c.aux, c.lengths, c.bw_id};
         if (p->graph_exec && key == p->graph_key) {
             WT_HIP_CHECK(hipGraphLaunch(p->graph_exec, c.stream));
             ++p->graph_replays;
@@ -579,8 +592,19 @@ int wt_plan_read_timing(const wt_plan* p, double* total_ms, int64_t* launches, i
 int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* codes, float* emb_out, void* workspace,
               void* stream) {
     if (!p || p->kind != WT_PLAN_ENCODE) { set_error("wt_encode: not an encode plan"); return WT_ERR_INVALID; }
+    if (p->flags & WT_PLAN_FLAG_MIXED_LENGTH) { set_error("wt_encode: a mixed-length plan runs through wt_encode_mixed"); return WT_ERR_INVALID; }
     if (!wav || !codes || !workspace) { set_error("wt_encode: null buffer"); return WT_ERR_INVALID; }
     RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), wav, features, codes, emb_out, 0};
+    return run_plan(p, c);
+}
+
+int wt_encode_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, float* features, int64_t* codes, float* emb_out,
+                    void* workspace, void* stream) {
+    if (!p || p->kind != WT_PLAN_ENCODE || !(p->flags & WT_PLAN_FLAG_MIXED_LENGTH)) {
+        set_error("wt_encode_mixed: not a mixed-length encode plan (WT_PLAN_FLAG_MIXED_LENGTH)"); return WT_ERR_INVALID;
+    }
+    if (!wav || !lengths || !codes || !workspace) { set_error("wt_encode_mixed: null buffer"); return WT_ERR_INVALID; }
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), wav, features, codes, emb_out, 0, lengths};
     return run_plan(p, c);
 }
 

@@ -129,6 +129,40 @@ __device__ __forceinline__ void range_report(unsigned* status, float amax) {
 #endif
 
 // ---------------------------------------------------------------------------------------------
+// SConv1d geometry (encoder/modules/conv.py:195-211, 54-61), non-causal: left pad, total right pad (incl. the extra padding that
+// completes the last window), output frames, and the reflect length max(T, max_pad + 1) (conv.py:86-91).  One function for the
+// host planner and the device step that turns the clip lengths of a mixed-length plan into its geometry table (mixed.hip)
+struct SConvGeom { int pl, pr_total, Tout, Tp; };
+__host__ __device__ inline SConvGeom sconv_geom(long T, int k, int stride, int dil) {
+    const int keff = (k - 1) * dil + 1;
+    const int pt = keff - stride;
+    const long nfr_num = T - keff + pt;                 // n_frames = nfr_num/stride + 1
+    const long nfr = (nfr_num + stride - 1) / stride + 1;   // ceil (nfr_num >= 0 here since pt = keff - stride)
+    const long ideal = (nfr - 1) * stride + (keff - pt);
+    const int extra = (int)(ideal - T);
+    SConvGeom g;
+    const int pr = pt / 2;
+    g.pl = pt - pr;
+    g.pr_total = pr + extra;
+    g.Tout = (int)((T + pt + extra - keff) / stride + 1);
+    const int maxpad = g.pl > g.pr_total ? g.pl : g.pr_total;
+    g.Tp = T > maxpad ? (int)T : maxpad + 1;
+    return g;
+}
+
+// Mixed-length encode plans (WT_PLAN_FLAG_MIXED_LENGTH): per clip, GEOM_WORDS int32 words of geometry in the workspace, written
+// by the plan's first step from the caller's lengths.  A conv's entry is the triple {T_in, Tp, T_out}; per encoder stage s the
+// triples of its k3 conv, its 1x1 shortcut (+ conv1) and its down conv start at GEOM_STAGE0 + s * GEOM_STAGE_WORDS, then the final
+// conv's triple and L.  A clip whose length lies outside [min clip length, padded length] is invalid: its geometry is that of the
+// shortest clip, its readable length 0 (no sample of it is read), and its outputs are -1 / NaN.
+enum : int {
+    GEOM_WORDS = 64, GEOM_VALID = 0, GEOM_T = 1, GEOM_TREAD = 2, GEOM_STAGE0 = 3, GEOM_STAGE_WORDS = 9,
+    GEOM_C3 = 0, GEOM_SC = 3, GEOM_DOWN = 6, GEOM_MAX_STAGES = 6
+};
+inline int geom_final(int n_stages) { return GEOM_STAGE0 + n_stages * GEOM_STAGE_WORDS; }
+inline int geom_L(int n_stages) { return geom_final(n_stages) + 3; }
+
+// ---------------------------------------------------------------------------------------------
 // The one dense-contraction kernel of the path: C = epilogue(prologue(gather(A)) . W^T)
 //   A  : activations, time-major rows [clip][time][channel]; a row of the im2col matrix for
 //        output frame t is the `taps` input rows (t*stride + tap*dil - pad_left), each `Cin` long,
@@ -223,11 +257,14 @@ struct GemmArgs {
 int gemm_vq_parts(int N);   // partial (val, idx) slots per row written by EPI_ARGMAX
 // the launchers' argument checks on their own (no HIP call): 0 if launch_gemm / launch_gemm16s would launch this problem
 int check_gemm(const GemmArgs& a, int pro, int epi);
-int check_gemm16s(const GemmArgs& a, int epi, int out);
+// mix_geom (mixed-length plans): clip 0's {T_in, Tp, T_out} triple of this conv in the geometry table (clip stride GEOM_WORDS).  A
+// clip's row t < T_out gathers reflect-about-Tp positions below T_in, its rows past T_out gather nothing (zero operands); the
+// GemmArgs extents are then the padded ones (strides and M).  Reflect-padded convs and the encoder's pairs only
+int check_gemm16s(const GemmArgs& a, int epi, int out, const int* mix_geom = nullptr);
 int launch_gemm(const GemmArgs& a, int pro, int epi, hipStream_t s);
 // gemm16s.hip: both operands pre-split in the S32 layout (128-byte groups [32 x f16 hi | 32 x f16 lo], same
 // footprint and strides as the fp32 array); a.A / a.W_hi point at S32 data, out_s32 selects an S32 C
-int launch_gemm16s(const GemmArgs& a, int epi, int out, hipStream_t s);     // out: Out16s
+int launch_gemm16s(const GemmArgs& a, int epi, int out, hipStream_t s, const int* mix_geom = nullptr);     // out: Out16s
 int gemm16s_vq_parts(int N);
 int launch_split_s32(const float* x, void* out, long n, hipStream_t s, const float* scale_dev = nullptr);
 int launch_unsplit_s32(const void* s32, float* out, long n, float inv_scale, hipStream_t s);     // fp32 = (hi + lo * 2^-11) * inv_scale
@@ -327,11 +364,24 @@ struct ResblockArgs {
     float* y_down;
     int R;
 };
+// mixed-length plans (resblock16 only): clip 0's length word and readable-length word in the geometry table (clip stride
+// GEOM_WORDS); ResblockArgs::T is then the padded length (the row stride of x / wav / y, of y_down through ceil(T / R))
+struct ResblockMix {
+    const int* T = nullptr;
+    const int* Tread = nullptr;
+};
 bool resblock_fusable(int C);
 int launch_resblock(const ResblockArgs& a, hipStream_t s);      // fp32 MFMA chain (resblock.hip)
-int launch_resblock16(const ResblockArgs& a, hipStream_t s);    // split-f16 MFMAs, fp32-equivalent (resblock16.hip)
+int launch_resblock16(const ResblockArgs& a, hipStream_t s, const ResblockMix* mix = nullptr);    // split-f16 MFMAs, fp32-equivalent (resblock16.hip)
 bool resblock16_down_fusable(int C, long T, int r, int k);
-int launch_resblock16_down(const ResblockArgs& a, hipStream_t s);   // stage 1 + ELU + down conv in one launch
+int launch_resblock16_down(const ResblockArgs& a, hipStream_t s, const ResblockMix* mix = nullptr);   // stage 1 + ELU + down conv in one launch
+// mixed.hip (mixed-length encode plans): the geometry table from the clip lengths (n_st encoder stages with down-conv kernel
+// sizes kd[] and strides rd[]; the final conv has kernel kf), and the padding rule of the outputs (codes -1 and features / emb 0
+// past a clip's L; -1 and NaN over the whole row of an invalid clip)
+int launch_mixed_geometry(const int* lengths, int* geom, int B, long Tpad, int tmin, int n_st, const int* kd, const int* rd,
+                          int kf, hipStream_t s);
+int launch_mixed_pad(const int* geom, int l_word, int64_t* codes, float* feat_ncl, float* emb_ncl, int B, int L, int D,
+                     hipStream_t s);
 int launch_convtr(const float* x, const float* w /*[k][Cin][Cout]*/, const float* bias, float* y, int B, int Tin,
                   int Cin, int Cout, int k, int stride, int elu_in, hipStream_t s);
 

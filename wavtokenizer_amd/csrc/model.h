@@ -157,6 +157,7 @@ struct RunCtx {
     int64_t* codes;
     float* aux;              // emb_out (encode) / backbone_out (decode)
     int bw_id;
+    const int* lengths = nullptr;    // mixed-length encode: the clip lengths (device int32 [B])
 };
 // Range sites (wt_plan_create_ex, wt_plan_range_sites): the units in which a plan can leave the split-f16 (S32) form.  Every
 // S32 tensor is produced and consumed inside ONE site, so a site can run on fp32 operands (gemm.hip) on its own while the
@@ -233,16 +234,20 @@ struct wt_plan {
     unsigned* status_dev = nullptr;       // device address of status_host
     int ctl = -1;                         // buffer id of the control block
     bool uses_persist = false;            // some step launches lstm_persist_kernel (while wt_model::persist_ok holds)
+    // WT_PLAN_FLAG_MIXED_LENGTH encode plans: T / L are the padded extents; the geometry table (buffer id) holds every clip's
+    // own (common.h GEOM_*); min_clip is the shortest clip the plan's route accepts
+    int mix_geom = -1;
+    int64_t min_clip = 0;
     mutable bool graph_persist = false;   // the recorded graph holds a persistent LSTM launch
     // one host call at a time per plan (graph capture state, timing events and persist_ok are per plan)
     mutable std::mutex mu;
     // WT_PLAN_FLAG_GRAPH: the launch sequence of a call, captured once and replayed with hipGraphLaunch while the
     // caller passes the same buffers (small batches are bound by the host's launch rate, not by the GPU)
     struct GraphKey {
-        const void *ws = nullptr, *in = nullptr, *out = nullptr, *codes = nullptr, *aux = nullptr;
+        const void *ws = nullptr, *in = nullptr, *out = nullptr, *codes = nullptr, *aux = nullptr, *lengths = nullptr;
         int bw = -1;
         bool operator==(const GraphKey& o) const {
-            return ws == o.ws && in == o.in && out == o.out && codes == o.codes && aux == o.aux && bw == o.bw;
+            return ws == o.ws && in == o.in && out == o.out && codes == o.codes && aux == o.aux && lengths == o.lengths && bw == o.bw;
         }
     };
     mutable GraphKey graph_key, last_key;
@@ -335,8 +340,6 @@ int ensure_f32_weights(const wt_model* M);                        // fills the l
 size_t packed_bytes(const void* buf, size_t n);                  // exact length of the image at buf (0: bad header)
 int packed_verify(const void* buf, size_t n);                    // header + bounds + content hash; needs no GPU
 // plan.cpp
-struct SConvGeom { int pl, pr_total, Tout, Tp; };
-SConvGeom sconv_geom(long T, int k, int stride, int dil);
 GemmArgs sconv_args(const ConvW& w, int B, long T, int stride, int dil);
 GemmArgs zconv_args(const ConvW& w, int B, int L);
 GemmArgs linear_args(const float* W, const float* bias, long M, int N, int K);

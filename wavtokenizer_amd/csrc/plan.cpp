@@ -33,15 +33,17 @@ static void set_s32(GemmArgs& a, const S32Copy& c) {
 }
 
 // Both operands pre-split (S32): the activations were written in S32 by their producer, the weight has an S32 copy
-static int gemm_s32(const GemmArgs& a, int epi, int out, hipStream_t s) {
+// (mix: a mixed-length plan's geometry triple of this conv, launch_gemm16s)
+static int gemm_s32(const GemmArgs& a, int epi, int out, hipStream_t s, const int* mix = nullptr) {
     if (!a.W_hi) { set_error("internal: no S32 copy of this weight"); return WT_ERR_INVALID; }
-    return launch_gemm16s(a, epi, out, s);
+    return launch_gemm16s(a, epi, out, s, mix);
 }
 
 // One GEMM step of a layer that runs on either operand form: S32 on gemm16s.hip (`out`: Out16s) or fp32 on gemm.hip
 // (`pro`: its operand prologue)
-static int dense(const wt_plan* P, bool s32, const GemmArgs& a, int pro, int epi, int out, hipStream_t s) {
-    return s32 ? gemm_s32(a, epi, out, s) : gemm_auto(P, a, pro, epi, s);
+static int dense(const wt_plan* P, bool s32, const GemmArgs& a, int pro, int epi, int out, hipStream_t s, const int* mix = nullptr) {
+    if (mix && !s32) { set_error("internal: a mixed-length conv off the S32 route"); return WT_ERR_INVALID; }
+    return s32 ? gemm_s32(a, epi, out, s, mix) : gemm_auto(P, a, pro, epi, s);
 }
 
 // Activation x activation (attention S and O): the B operand is a plan buffer, S32 in W_hi on gemm16s.hip, fp32 in W on
@@ -52,24 +54,7 @@ static int dense_act(const wt_plan* P, bool s32, GemmArgs a, const float* b_op, 
     return gemm_auto(P, a, PRO_NONE, epi, s);
 }
 
-// SConv1d geometry (encoder/modules/conv.py:195-211, 54-61), non-causal.
-
-SConvGeom sconv_geom(long T, int k, int stride, int dil) {
-    const int keff = (k - 1) * dil + 1;
-    const int pt = keff - stride;
-    const long nfr_num = T - keff + pt;                 // n_frames = nfr_num/stride + 1
-    const long nfr = (nfr_num + stride - 1) / stride + 1;   // ceil (nfr_num >= 0 here since pt = keff - stride)
-    const long ideal = (nfr - 1) * stride + (keff - pt);
-    const int extra = (int)(ideal - T);
-    SConvGeom g;
-    const int pr = pt / 2;
-    g.pl = pt - pr;
-    g.pr_total = pr + extra;
-    g.Tout = (int)((T + pt + extra - keff) / stride + 1);
-    const int maxpad = std::max(g.pl, g.pr_total);
-    g.Tp = T > maxpad ? (int)T : maxpad + 1;
-    return g;
-}
+// SConv1d geometry: sconv_geom (common.h, shared with the mixed-length geometry step)
 
 // x [B][T][cin] (time-major) -> y [B][Tout][cout]; reflect-padded SConv1d as one implicit GEMM
 GemmArgs sconv_args(const ConvW& w, int B, long T, int stride, int dil) {
@@ -108,13 +93,16 @@ GemmArgs linear_args(const GemmW& W, const float* bias, long M, int N, int K) {
 // SEANetResnetBlock (seanet.py:62-63): y = shortcut(x) + conv1(elu(conv3(elu(x)))); returns y's buffer
 static int plan_resblock(wt_plan* P, const ConvW& c3, const ConvW& c1, const ConvW& sc, int B, long T, int xin,
                          const std::string& name, bool elu_out = false, const wt_model* e0 = nullptr, long x_off = 0,
-                         long x_bstride = 0, bool out_s32 = false) {
+                         long x_bstride = 0, bool out_s32 = false, int mix_word = -1) {
     const int C = sc.cout;
     if (resblock_fusable(C) && !plan_unfused(P)) {
         // one fused kernel (resblock.hip); with e0 set, xin is unused and the tile is built from the waveform
         const int y = P->buf(name, (size_t)B * T * C, (out_s32 && !plan_fp32(P) ? BUF_S32 : BUF_F32) | (elu_out ? BUF_ELU : 0));
-        P->step({e0 ? -1 : xin, y}, [=](const RunCtx& c) {
+        const int geom = mix_word >= 0 ? P->mix_geom : -1;
+        P->step({e0 ? -1 : xin, y, geom}, [=](const RunCtx& c) {
             ResblockArgs a{};
+            ResblockMix mix;
+            if (geom >= 0) mix.T = mix.Tread = reinterpret_cast<const int*>(P->ptr(c, geom)) + mix_word;
             a.x = e0 ? nullptr : P->ptr(c, xin) + x_off;
             a.x_bstride = x_bstride;
             a.wav = e0 ? c.in_f : nullptr;
@@ -123,7 +111,7 @@ static int plan_resblock(wt_plan* P, const ConvW& c3, const ConvW& c1, const Con
             a.y = P->ptr(c, y); a.B = B; a.T = (int)T; a.C = C; a.elu_out = elu_out ? 1 : 0;
             if (plan_fp32(P)) return launch_resblock(a, c.stream);
             a.out_s32 = out_s32 ? 1 : 0;
-            return launch_resblock16(a, c.stream);
+            return launch_resblock16(a, c.stream, geom >= 0 ? &mix : nullptr);
         }, 1, "resblock.fused");
         return y;
     }
@@ -208,15 +196,17 @@ static int plan_lstm(wt_plan* P, const LstmW& w, int B, int L, int H, int xin, c
 // Unfused SEANetResnetBlock with every operand pre-split: x arrives as S32(x) (shortcut) and S32(elu(x)) (conv3),
 // the hidden activation and the output are written as S32(elu(.)); returns the output buffer, or -1 (set_error)
 static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const ConvW& cat, int B, long T, int x_raw,
-                             int x_elu, const std::string& name, long x_off = 0, long x_bstride = 0) {
+                             int x_elu, const std::string& name, long x_off = 0, long x_bstride = 0, int mix_word = -1) {
     if (!cat.s32.p) { set_error("internal: unfused S32 resblock without an S32 shortcut + conv1 weight"); return -1; }
     const int C = sc.cout;
     const int h = P->buf(name + ".h", (size_t)B * T * (C / 2), BUF_S32 | BUF_ELU);
     GemmArgs a3 = sconv_args(c3, B, T, 1, 1);
-    P->step({x_elu, h}, [=](const RunCtx& c) {
+    const int geom = mix_word >= 0 ? P->mix_geom : -1;
+    P->step({geom, x_elu, h}, [=](const RunCtx& c) {
         GemmArgs a = a3; a.A = P->ptr(c, x_elu) + x_off; a.C = P->ptr(c, h);
         if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream);
+        const int* mix = geom >= 0 ? reinterpret_cast<const int*>(P->ptr(c, geom)) + mix_word + GEOM_C3 : nullptr;
+        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream, mix);
     });
     // shortcut + conv1 as one GEMM over K = [x (C) | elu(h) (C/2)] (GemmArgs::A2, weight `cat`: weights.cpp build_cat): the
     // fp32 shortcut tensor is neither written nor read back, and the output goes through the staged full-line epilogue
@@ -225,10 +215,11 @@ static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const
     ac.W = cat.w; ac.w_rstride = cat.cin; ac.bias = cat.b; ac.K = cat.cin; ac.Cin = cat.cin;
     set_s32(ac, cat.s32);
     ac.K1 = C; ac.a2_bstride = T * (C / 2); ac.a2_rstride = C / 2;
-    P->step({x_raw, h, o}, [=](const RunCtx& c) {
+    P->step({geom, x_raw, h, o}, [=](const RunCtx& c) {
         GemmArgs a = ac; a.A = P->ptr(c, x_raw) + x_off; a.A2 = P->ptr(c, h); a.C = P->ptr(c, o);
         if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream);
+        const int* mix = geom >= 0 ? reinterpret_cast<const int*>(P->ptr(c, geom)) + mix_word + GEOM_SC : nullptr;
+        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream, mix);
     });
     return o;
 }
@@ -275,6 +266,35 @@ int build_encode(wt_plan* P) {
     // after the last stage the LSTM reads fp32 (skip) and, on S32 operands, an S32 copy (input projection)
     const bool lstm_s32 = !route.empty() && route.back().s32 && M->enc_lstm.Wih0.s32.p;
     const bool tail_s32 = lstm_s32 && M->enc_final.s32.p && M->embed.s32.p;
+    // Mixed-length plan (WT_PLAN_FLAG_MIXED_LENGTH): T is the padded length, every clip brings its own.  Only the shipped route
+    // takes per-clip lengths (stage 1 fused with its down conv, the 64-channel fused resblock, S32 GEMMs everywhere else)
+    const bool mixed = P->flags & WT_PLAN_FLAG_MIXED_LENGTH;
+    const int n_st = (int)route.size();
+    int geom = -1;
+    if (mixed) {
+        bool ok = s32 && !(P->flags & (WT_PLAN_FLAG_KEEP_STAGES | WT_PLAN_FLAG_RANGE_REPORT)) && tail_s32 &&
+                  n_st >= 2 && n_st <= GEOM_MAX_STAGES && route[0].down;
+        for (int si = 1; si < n_st && ok; ++si)
+            ok = route[si].s32 && (route[si].fused ? M->stages[si].C == 64 : M->stages[si].cat.s32.p != nullptr);
+        for (const ResStage& st : M->stages) ok = ok && st.c3.k == 3 && st.sc.k == 1;     // (the geometry step's k3 / 1x1 convs)
+        if (!ok) {
+            set_error("mixed-length plans run only the shipped split-f16 encoder route: not with WT_PLAN_FLAG_UNFUSED, "
+                      "FP32_GEMM, KEEP_STAGES or RANGE_REPORT, an encoder range site on fp32, or weights without S32 copies");
+            return WT_ERR_INVALID;
+        }
+        P->min_clip = 1024;              // resblock16_down_fusable: the fused stage-1 kernel's shortest clip
+        if (T < P->min_clip) { set_error("mixed-length plans need a padded length of at least 1024 samples"); return WT_ERR_INVALID; }
+        geom = P->mix_geom = P->buf("mix.geom", (size_t)B * GEOM_WORDS);
+        std::vector<int> kd, rd;
+        for (const ResStage& st : M->stages) { kd.push_back(st.down.k); rd.push_back(st.r); }
+        const int kf = M->enc_final.k;
+        const int tmin = (int)P->min_clip;
+        P->step({geom}, [=](const RunCtx& c) {
+            return launch_mixed_geometry(c.lengths, reinterpret_cast<int*>(P->ptr(c, geom)), B, T, tmin, n_st, kd.data(),
+                                         rd.data(), kf, c.stream);
+        }, 1, "mix.geom");
+    }
+    auto mix_ptr = [=](const RunCtx& c, int word) { return reinterpret_cast<const int*>(P->ptr(c, geom)) + word; };
     long Tc = T;
     int idx = 1;
     int x_elu = -1;                      // S32(elu(x)) beside S32(x) for an unfused S32 stage
@@ -288,22 +308,26 @@ int build_encode(wt_plan* P) {
         const std::string out = "enc." + std::to_string(idx + 2);
         if (r.down) {
             const int y = P->buf(out, ynum);
-            P->step({-1, y}, [=](const RunCtx& c) {
+            P->step({-1, y, geom}, [=](const RunCtx& c) {
                 ResblockArgs a{};
+                ResblockMix mix;
+                if (geom >= 0) { mix.T = mix_ptr(c, GEOM_T); mix.Tread = mix_ptr(c, GEOM_TREAD); }
                 a.wav = c.in_f; a.e0_w = M->e0_w; a.e0_b = M->e0_b;
                 a.W3 = st.c3.w; a.b3 = st.c3.b; a.W1 = st.c1.w; a.b1 = st.c1.b; a.Ws = st.sc.w; a.bs = st.sc.b;
                 a.Wd = st.down.w; a.bd = st.down.b; a.y_down = P->ptr(c, y); a.R = st.r;
                 a.B = B; a.T = (int)Tc; a.C = st.C;
-                return launch_resblock16_down(a, c.stream);
+                return launch_resblock16_down(a, c.stream, geom >= 0 ? &mix : nullptr);
             }, 1, "resblock.fused_down");
             x = y; Tc = ad.T_out; idx += 3;
             continue;
         }
         const std::string name = "enc." + std::to_string(idx);
+        const int stage_word = GEOM_STAGE0 + (int)si * GEOM_STAGE_WORDS;     // (mixed-length plans)
         if (r.fused)
-            x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, name, fuse_elu, (si == 0 && fold_e0) ? M : nullptr, 0, 0, r.s32);
+            x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, name, fuse_elu, (si == 0 && fold_e0) ? M : nullptr, 0, 0, r.s32,
+                              mixed ? stage_word + GEOM_C3 : -1);
         else if (r.s32)
-            x = plan_resblock_s32(P, st.c3, st.sc, st.cat, B, Tc, x, x_elu, name);
+            x = plan_resblock_s32(P, st.c3, st.sc, st.cat, B, Tc, x, x_elu, name, 0, 0, mixed ? stage_word : -1);
         else
             x = plan_resblock(P, st.c3, st.c1, st.sc, B, Tc, x, name, fuse_elu);
         if (x < 0) return WT_ERR_INVALID;
@@ -312,11 +336,12 @@ int build_encode(wt_plan* P) {
         const int y = P->buf(out, ynum, next_s32 ? BUF_S32 : BUF_F32);
         const int y2 = (next_s32 || (last && lstm_s32)) ? P->buf(out + ".s32", ynum, BUF_S32 | (next_s32 ? BUF_ELU : 0)) : -1;
         const int xin = x;
-        P->step({xin, y, y2}, [=](const RunCtx& c) {
+        P->step({geom, xin, y, y2}, [=](const RunCtx& c) {
             GemmArgs a = ad; a.A = P->ptr(c, xin); a.C = P->ptr(c, y);
             if (y2 >= 0) a.C2 = P->ptr(c, y2);
             return dense(P, r.s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS,
-                         next_s32 ? OUT_S32_DUAL_ELU : (y2 >= 0 ? OUT_F32_AND_S32 : OUT_F32), c.stream);
+                         next_s32 ? OUT_S32_DUAL_ELU : (y2 >= 0 ? OUT_F32_AND_S32 : OUT_F32), c.stream,
+                         geom >= 0 ? mix_ptr(c, stage_word + GEOM_DOWN) : nullptr);
         });
         if (next_s32) x_elu = y2;
         if (last) x_s32 = y2;
@@ -331,10 +356,11 @@ int build_encode(wt_plan* P) {
     const int emb_s32 = tail_s32 ? P->buf("enc." + std::to_string(idx + 2) + ".s32", (size_t)B * L * 512, BUF_S32) : -1;
     {
         const int xin = x;
-        P->step({xin, emb, emb_s32}, [=](const RunCtx& c) {
+        P->step({geom, xin, emb, emb_s32}, [=](const RunCtx& c) {
             GemmArgs a = af; a.A = P->ptr(c, xin); a.C = P->ptr(c, emb);
             if (emb_s32 >= 0) a.C2 = P->ptr(c, emb_s32);
-            return dense(P, tail_s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, OUT_F32_AND_S32, c.stream);
+            return dense(P, tail_s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, OUT_F32_AND_S32, c.stream,
+                         geom >= 0 ? mix_ptr(c, geom_final(n_st)) : nullptr);
         });
     }
     // ---- VQ (core_vq.py:175-183, 206-231)
@@ -353,12 +379,14 @@ int build_encode(wt_plan* P) {
         a.vq_pidx = reinterpret_cast<int*>(P->ptr(c, pi)); a.vq_nparts = np;
         return dense(P, tail_s32, a, PRO_NONE, EPI_ARGMAX, OUT_F32, c.stream);
     }, 1, "vq.argmin");
-    P->step({pv, pi, emb}, [=](const RunCtx& c) {
+    P->step({geom, pv, pi, emb}, [=](const RunCtx& c) {
         if (int rc = launch_vq_finalize(P->ptr(c, pv), reinterpret_cast<int*>(P->ptr(c, pi)), np, M->embed.w, c.codes,
                                         c.out_f, B, L, 512, bins, c.stream)) return rc;
-        if (c.aux) return launch_transpose(P->ptr(c, emb), c.aux, B, L, 512, c.stream);
+        if (c.aux) if (int rc = launch_transpose(P->ptr(c, emb), c.aux, B, L, 512, c.stream)) return rc;
+        // mixed-length plans: codes -1 and features (and emb_out) 0 past each clip's L; -1 / NaN for an invalid length
+        if (geom >= 0) return launch_mixed_pad(mix_ptr(c, 0), geom_L(n_st), c.codes, c.out_f, c.aux, B, L, 512, c.stream);
         return 0;
-    }, 2);
+    }, mixed ? 3 : 2);
     return 0;
 }
 

@@ -1,0 +1,52 @@
+"""Grouping policy of WavTokenizer.encode_infer_many: which clips share a mixed-length encode call, and how long its padded
+staging tensor is.  Pure functions of the clip lengths (no GPU), so the policy is tested on its own.
+
+A mixed-length call returns for every clip the bits a call of its own length returns (the kernels read each clip's length on
+the device), so grouping and bucketing change only the cost: a bucket is a coarse padded length that many calls share, which
+lets them reuse one plan (and, for small groups, one recorded graph) instead of building one per length."""
+from __future__ import annotations
+
+from typing import List, Sequence, Tuple
+
+MAX_FRAMES = 12000       # frames per clip of one plan (wt_plan_create): a bucket never goes past it
+MIN_CLIP = 1024          # the shortest clip a mixed-length plan takes (wt_plan_min_clip_length: the fused stage-1 kernel)
+MAX_GROUP = 64           # clips per call: up to 64 the persistent LSTM gives every clip the bits of a call of its own (above
+                         # 64 it still runs, up to 128, but its results move by an ulp against a solo call's)
+BUCKET_STEPS = 8         # buckets per octave of length: at most 1/8 of a call is padding from the bucket
+
+
+def bucket_length(T: int, hop: int) -> int:
+    """T rounded up to a multiple of hop * 2^e, with e chosen so that there are BUCKET_STEPS such multiples per octave
+    (at least one hop): 3 s at hop 320 (48 000 samples) -> 51 200 (ten multiples of 5 120)."""
+    if T < 1 or hop < 1:
+        raise ValueError("length and hop must be positive")
+    q = hop
+    while (T + q - 1) // q > 2 * BUCKET_STEPS - 1:
+        q *= 2
+    return -(-T // q) * q
+
+
+def group_clips(lengths: Sequence[int], hop: int, min_clip: int = MIN_CLIP, max_group: int = MAX_GROUP
+                ) -> Tuple[List[Tuple[int, List[int]]], List[int]]:
+    """(groups, solo): groups = [(padded length, clip indices)], solo = indices of the clips shorter than min_clip (they run
+    one at a time through encode_infer).  Clips are taken in order of length (ties in input order); a group closes at
+    max_group clips or when the next clip's bucket is more than twice the group's first clip (more than half of the call
+    would be padding).  Every clip index appears exactly once."""
+    def padded(T: int) -> int:
+        return max(T, min(bucket_length(T, hop), MAX_FRAMES * hop))
+
+    order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
+    solo = [i for i in order if int(lengths[i]) < min_clip]
+    groups: List[Tuple[int, List[int]]] = []
+    cur: List[int] = []
+    for i in order:
+        T = int(lengths[i])
+        if T < min_clip:
+            continue
+        if cur and (len(cur) >= max_group or bucket_length(T, hop) > 2 * int(lengths[cur[0]])):
+            groups.append((padded(int(lengths[cur[-1]])), cur))
+            cur = []
+        cur.append(i)
+    if cur:
+        groups.append((padded(int(lengths[cur[-1]])), cur))
+    return groups, solo

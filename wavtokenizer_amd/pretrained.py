@@ -13,7 +13,7 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -768,6 +768,97 @@ class WavTokenizer(nn.Module):
 
         return self._guarded(dev, lambda: self._engine.plan(_capi.WT_PLAN_ENCODE, B, T, self._graph_flags(B), dev,
                                                             self._sites(_capi.WT_PLAN_ENCODE)), launch, self._is_strict(B))
+
+    def _run_encode_mixed(self, wavs: List[torch.Tensor], T_pad: int, dev: torch.device):
+        """One mixed-length encode call (WT_PLAN_FLAG_MIXED_LENGTH) on clips of at least MIN_CLIP samples and at most T_pad:
+        returns (features [B, 512, L_pad], codes [1, B, L_pad]) with -1 / 0 past each clip's frames, or None when the
+        current flags or fp32 sites keep the encoder off the route a mixed-length plan takes (_mixed_route_ok; the caller
+        then encodes the clips one at a time).  Any other refusal of the plan raises."""
+        B = len(wavs)
+        L = self._arch.frames(T_pad)
+        lengths = [int(w.shape[0]) for w in wavs]
+        key_flags = lambda: self._graph_flags(B) | _capi.WT_PLAN_FLAG_MIXED_LENGTH
+
+        class _Refused(Exception):
+            pass
+
+        def get_plan():
+            # checked on every attempt: a range fallback inside _guarded can put the encoder site on fp32
+            if not self._mixed_route_ok():
+                raise _Refused()
+            return self._engine.plan(_capi.WT_PLAN_ENCODE, B, T_pad, key_flags(), dev, self._sites(_capi.WT_PLAN_ENCODE))
+
+        def fill(buf: torch.Tensor, lens: torch.Tensor):
+            for j, w in enumerate(wavs):
+                buf[j, :lengths[j]].copy_(w)
+            lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)
+
+        def launch(plan, ws):
+            flags = key_flags()
+            if flags & _capi.WT_PLAN_FLAG_GRAPH:
+                io = self._engine.staging(_capi.WT_PLAN_ENCODE, B, T_pad, flags, lambda: {
+                    "in": torch.zeros((B, T_pad), dtype=torch.float32, device=dev),
+                    "len": torch.zeros((B,), dtype=torch.int32, device=dev),
+                    "feats": torch.empty((B, 512, L), dtype=torch.float32, device=dev),
+                    "codes": torch.empty((1, B, L), dtype=torch.int64, device=dev)}, dev, self._sites(_capi.WT_PLAN_ENCODE))
+                fill(io["in"], io["len"])
+                check(lib.wt_encode_mixed(plan, _ptr(io["in"]), _ptr(io["len"]), _ptr(io["feats"]), _ptr(io["codes"]), _ptr(None),
+                                          _ptr(ws), _stream_ptr(dev)), "wt_encode_mixed")
+                return io["feats"].clone(), io["codes"].clone()
+            wav = torch.empty((B, T_pad), dtype=torch.float32, device=dev)      # (samples past a clip's length are never read)
+            lens = torch.empty((B,), dtype=torch.int32, device=dev)
+            fill(wav, lens)
+            feats = torch.empty((B, 512, L), dtype=torch.float32, device=dev)
+            codes = torch.empty((1, B, L), dtype=torch.int64, device=dev)
+            check(lib.wt_encode_mixed(plan, _ptr(wav), _ptr(lens), _ptr(feats), _ptr(codes), _ptr(None), _ptr(ws), _stream_ptr(dev)),
+                  "wt_encode_mixed")
+            return feats, codes
+
+        try:
+            return self._guarded(dev, get_plan, launch, self._is_strict(B))
+        except _Refused:
+            return None
+
+    def _mixed_route_ok(self) -> bool:
+        """Whether the encoder runs the route a mixed-length plan takes (the shipped split-f16 one): no fp32 GEMMs, no unfused
+        debug plan, no debug taps or range report, the encoder range site not on fp32, and weights that fit the split-f16 form
+        (the conditions build_encode checks; a plan refused in spite of them is an error, not a fallback)."""
+        off_route = (_capi.WT_PLAN_FLAG_FP32_GEMM | _capi.WT_PLAN_FLAG_UNFUSED | _capi.WT_PLAN_FLAG_KEEP_STAGES |
+                     _capi.WT_PLAN_FLAG_RANGE_REPORT)
+        return (not (self._plan_flags & off_route) and not self._sites(_capi.WT_PLAN_ENCODE) and
+                bool(lib.wt_model_split_ok(self._engine.model)))
+
+    @torch.inference_mode()
+    def encode_infer_many(self, wavs: Sequence[torch.Tensor], bandwidth_id=None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """encode_infer over clips of different lengths (the reference's infer.py loop, one call per file) in a few batched
+        calls: returns [(features [1, 512, L_i], codes [1, 1, L_i])] in input order, L_i = arch.frames(len(wavs[i])), each the
+        same bits as encode_infer(wavs[i][None]).  Clips are sorted by length and grouped (mixed_length.group_clips: at most
+        64 per call, padded to a coarse bucket so that calls share plans and graphs); clips shorter than the mixed-length
+        plan's minimum, and every clip while the encoder runs off its shipped route (set_gemm_precision("f32"), an fp32
+        encoder site after a range fallback, the unfused debug plans), run one at a time through encode_infer."""
+        from .mixed_length import group_clips
+        dev = self._ensure_engine()
+        if bandwidth_id is not None:
+            _ = self.feature_extractor.bandwidths[self._bandwidth_index(bandwidth_id)]
+        wavs = list(wavs)
+        for w in wavs:
+            if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] < 1:
+                raise ValueError("encode_infer_many takes a sequence of non-empty 1-D tensors")
+        wavs = [self._as_input(w, dev) for w in wavs]
+        out: List[Optional[Tuple[torch.Tensor, torch.Tensor]]] = [None] * len(wavs)
+        groups, solo = group_clips([int(w.shape[0]) for w in wavs], self._arch.hop)
+        for T_pad, idx in groups:
+            res = self._run_encode_mixed([wavs[i] for i in idx], T_pad, dev)
+            if res is None:
+                solo.extend(idx)
+                continue
+            feats, codes = res
+            for j, i in enumerate(idx):
+                L_i = self._arch.frames(int(wavs[i].shape[0]))
+                out[i] = (feats[j:j + 1, :, :L_i].clone(), codes[:, j:j + 1, :L_i].clone())
+        for i in sorted(solo):
+            out[i] = self.encode_infer(wavs[i][None], bandwidth_id=bandwidth_id)
+        return out  # type: ignore[return-value]
 
     def _bandwidth_index(self, bandwidth_id) -> int:
         if bandwidth_id is None:

@@ -2,7 +2,7 @@
 """bench.py — audio-seconds/sec of WavTokenizer encode_infer + decode on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--arch hop600|hop320] [--clips 64]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-other-configs]]
 
 One "step" = one encode_infer + decode round trip of `--clips` independent 3 s / 24 kHz clips
 per GPU (BASELINE.json configs[1]: WavTokenizer-small-600, batch 64 x 3 s), inputs already
@@ -26,11 +26,17 @@ the same fixed, seeded sample of clips (`outputs.clips_kept` on the line).
 Schedule of the headline (config.lanes): at N = 1 the K steps of a block are issued alternately on TWO HIP streams
 (sharding.StepRunner(lanes=2): step i+1's encode_infer runs beside step i's decode and fills its launch gaps and last-round
 tails; every step is still one full encode_infer + decode of the batch and all K complete inside the bracket; same kernels,
-same bits).  The one-stream schedule is measured in the same run (config.one_lane) and is what the roofline launch is timed
-in, so that a second stream never lengthens the launch being measured.  `--lanes 1` makes the one-stream schedule the
-headline.  N > 1 keeps one lane (the end-of-step exchange is ordered against the persistent LSTM on one stream: DESIGN 6).
+same bits).  With --full the one-stream schedule is measured in the same run first (config.one_lane) and is what the roofline
+launch is timed in, so that a second stream never lengthens the launch being measured.  `--lanes 1` makes the one-stream
+schedule the headline.  N > 1 keeps one lane (the end-of-step exchange is ordered against the persistent LSTM on one stream:
+DESIGN 6).
 
-Extra objects on the line:
+A plain run does only what the headline needs: model set-up, the warm-up and timed steps of the headline schedule,
+--dump-outputs, and the line.  --full adds everything else the benchmark measures (the objects below).  When the headline
+itself is the one-stream schedule (--lanes 1, N > 1), its timed steps carry the roofline launch timing in either mode, so
+roofline and config.one_lane are on a plain line too.
+
+Extra objects on the line (--full):
   roofline      — dominant kernel (ConvNeXt pwconv1 GEMM + GELU, 12 launches per step): achieved =
                   algorithmic 2*M*N*K per launch / mean launch duration of those launches during the timed
                   steps.  The duration is taken ON THE DEVICE (wt_plan_set_timing("@cnx.pwconv1"): every
@@ -219,12 +225,16 @@ def main():
     ap.add_argument("--arch", default="hop600", choices=["hop600", "hop320"])
     ap.add_argument("--clips", type=int, default=64, help="clips per GPU per step")
     ap.add_argument("--clip-seconds", type=int, default=3, help="clip length (BASELINE configs[4] uses 30 s clips)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: the one-stream block with the roofline launch timing "
+                         "(config.one_lane, roofline), the p50 encode_infer latency of >= 30 s clips, other_configs and "
+                         "cpu_baseline (the last two can be left out with --no-other-configs / --no-cpu-baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: leave out other_configs")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--lanes", type=int, default=2, help="N = 1 only: steps in flight on separate HIP streams (StepRunner(lanes=...)); "
-                    "default 2 (config.lanes says so); the one-stream schedule is always measured too (config.one_lane) and "
-                    "carries the roofline launch timing; --lanes 1 makes it the headline")
+                    "default 2 (config.lanes says so); with --full the one-stream schedule is measured too (config.one_lane) "
+                    "and carries the roofline launch timing; --lanes 1 makes it the headline")
     ap.add_argument("--force-collectives", action="store_true",
                     help="N = 1: create a world-1 RCCL process group and run the end-of-step exchange (all_gather_into_tensor + "
                          "gather, async) inside the timed steps anyway: exercises library load, stream semantics and the "
@@ -318,14 +328,17 @@ def main():
     L = arch.frames(T)
     forced = args.force_collectives and world == 1
     lanes = args.lanes if (world == 1 and not forced) else 1
-    # one stream first: the schedule the roofline launch is timed in (and the headline with --lanes 1 / N > 1)
-    runner = Runner(model, wav, bw, dist, world, rank, not args.no_gather, args.backend, lanes=1, force_collectives=forced)
-    runner.step()                                                  # creates the plans
-    runner.drain()
-    dplan = next(p for k, (p, _w) in model._engine.plans.items() if k == (_capi.WT_PLAN_DECODE, B, L, model._graph_flags(B)))
-    blocks, kern = run_blocks(runner, args.steps, max(0, args.warmup - 1), args.repeats, (dplan, b"cnx.pwconv1" if os.environ.get("WT_BENCH_TIMING") == "events" else b"@cnx.pwconv1"))     # (events: tools/trace_vs_events.sh only)
-    model.check_status()
-    one_lane_blocks = sorted(1e3 * b / args.steps for b in blocks)
+    # one stream first: the schedule the roofline launch is timed in (and the headline with --lanes 1 / N > 1); a plain
+    # run with two lanes skips it
+    kern = one_lane_blocks = None
+    if args.full or lanes <= 1:
+        runner = Runner(model, wav, bw, dist, world, rank, not args.no_gather, args.backend, lanes=1, force_collectives=forced)
+        runner.step()                                                  # creates the plans
+        runner.drain()
+        dplan = next(p for k, (p, _w) in model._engine.plans.items() if k == (_capi.WT_PLAN_DECODE, B, L, model._graph_flags(B)))
+        blocks, kern = run_blocks(runner, args.steps, max(0, args.warmup - 1), args.repeats, (dplan, b"cnx.pwconv1" if os.environ.get("WT_BENCH_TIMING") == "events" else b"@cnx.pwconv1"))     # (events: tools/trace_vs_events.sh only)
+        model.check_status()
+        one_lane_blocks = sorted(1e3 * b / args.steps for b in blocks)
     if lanes > 1:
         runner = Runner(model, wav, bw, None, 1, 0, False, args.backend, lanes=lanes)
         for _ in range(lanes):
@@ -353,7 +366,7 @@ def main():
         ranks_info = gathered
 
     p50_encode_ms = None
-    if clip_s >= 30:       # BASELINE configs[4] also asks for the p50 latency of one encode_infer call
+    if args.full and clip_s >= 30:       # BASELINE configs[4] also asks for the p50 latency of one encode_infer call
         lat = []
         for _ in range(7):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -370,10 +383,26 @@ def main():
         ms_per_step = statistics.median(per_step)
         value = world * B * clip_s / (ms_per_step * 1e-3)
         Mrows = B * L
-        flops = 2.0 * Mrows * arch.intermediate_dim * arch.dim
-        kern_ms = kern[0] / max(1, kern[1])
-        achieved = flops / (kern_ms * 1e-3) / 1e12
         e2e_tflops = gflop_per_clip(args.arch, arch, clip_s) * B * 1e9 / (ms_per_step * 1e-3) / 1e12
+        roofline = None
+        if kern is not None:
+            flops = 2.0 * Mrows * arch.intermediate_dim * arch.dim
+            kern_ms = kern[0] / max(1, kern[1])
+            achieved = flops / (kern_ms * 1e-3) / 1e12
+            roofline = {"bound": "mfma",
+                        "kernel": "wt::gemm16s_kernel<128,192,4,2,3,EPI_BIAS_GELU=2,OUT_S32=1> (ConvNeXt pwconv1 GEMM %dx%dx%d + GELU, "
+                                  "split-f16: 3 x v_mfma_f32_16x16x32_f16 per fp32-equivalent product)" % (Mrows, arch.intermediate_dim, arch.dim),
+                        "achieved": round(achieved, 2), "peak": round(PEAK_F16X3_TFLOPS, 1), "unit": "TFLOP/s",
+                        "frac": round(achieved / PEAK_F16X3_TFLOPS, 4), "traffic": pmc_traffic(args.arch, B, clip_s),
+                        "peak_note": "algorithmic fp32-equivalent FLOP/s; peak = %.1f TF dense f16 MFMA / 3 MFMAs per product; the kernel "
+                                     "issues %.0f TF/s of f16 MFMA work" % (PEAK_F16_MFMA_TFLOPS, 3 * achieved),
+                        "algorithmic_bytes_per_launch": 4 * (Mrows * arch.dim + arch.intermediate_dim * arch.dim + Mrows * arch.intermediate_dim),
+                        "flops_per_launch": flops, "avg_launch_ms": round(kern_ms, 4), "launches_timed": kern[1],
+                        "launch_timing": "device clock (s_memrealtime, 100 MHz) of the launch's first workgroup entry to its last exit, every "
+                                         "pwconv1 launch of the timed ONE-LANE steps (config.one_lane); no events in the stream "
+                                         "(profiles/r03_trace_vs_stamps.txt compares it with the rocprofv3 trace and with bracketing HIP events in one run)",
+                        "end_to_end_tflops": round(e2e_tflops, 2),
+                        "end_to_end_frac": round(e2e_tflops / PEAK_F16X3_TFLOPS, 4)}
         line = {
             "metric": "audio-seconds/sec encode+decode, 24 kHz %d s clips" % clip_s,
             "value": round(value, 1), "unit": "audio-s/s", "n_gpus": world, "steps": args.steps,
@@ -382,7 +411,7 @@ def main():
             "dtype_note": "fp32 accumulation everywhere; residual streams, norm / LSTM-cell arithmetic and outputs are fp32; every operand of a "
                           "dense layer is STORED between layers as a split pair of f16 numbers (S32: x = hi + lo * 2^-11, 22 significant "
                           "bits, f16 exponent range guarded by a status word) and each product is formed by 3 f16 MFMAs; the same workload "
-                          "on the plain fp32 MFMA chain is other_configs.fp32_gemm_chain_64x3s; measured error of both against a float64 "
+                          "on the plain fp32 MFMA chain is other_configs.fp32_gemm_chain_64x3s (--full); measured error of both against a float64 "
                           "run of the oracle: tests/test_gpu_parity.py::test_precision_against_float64 (profiles/r03_gpu_parity_summary.json)",
             "data": "synthetic",
             "timing": {"blocks": len(per_step), "steps_per_block": args.steps,
@@ -401,10 +430,10 @@ def main():
                        "schedule": ("the K steps of a block are issued alternately on %d HIP streams (step i+1's encode_infer beside step i's decode); "
                                     "each step is one full encode_infer + decode of the batch; all K complete inside the timed bracket" % runner.lanes)
                                    if runner.lanes > 1 else "one step after the other on one HIP stream",
-                       "one_lane": {"ms_per_step": round(statistics.median(one_lane_blocks), 3), "ms_per_step_blocks": [round(x, 3) for x in one_lane_blocks],
-                                    "audio_s_per_s": round(world * B * clip_s / (statistics.median(one_lane_blocks) * 1e-3), 1),
-                                    "what": "the same workload, one step after the other on one stream (the r01-r03 headline schedule); "
-                                            "the roofline launch is timed in this block"},
+                       **({"one_lane": {"ms_per_step": round(statistics.median(one_lane_blocks), 3), "ms_per_step_blocks": [round(x, 3) for x in one_lane_blocks],
+                                        "audio_s_per_s": round(world * B * clip_s / (statistics.median(one_lane_blocks) * 1e-3), 1),
+                                        "what": "the same workload, one step after the other on one stream (the r01-r03 headline schedule); "
+                                                "the roofline launch is timed in this block"}} if one_lane_blocks is not None else {}),
                        "persistent_lstm": bool(model.persistent_lstm),
                        **({"forced_collectives": "world-1 RCCL process group: codes all_gather_into_tensor + waveform gather (async_op) "
                                                  "inside every timed step"} if forced else {}),
@@ -412,26 +441,13 @@ def main():
                        "gather": ("codes all_gather + waveform gather to rank 0 (%s), asynchronous: step i's exchange runs beside step i+1's decode "
                                   "(never beside the persistent LSTM), all finished inside the timed region" % ("RCCL" if args.backend == "nccl" else "gloo rehearsal"))
                        if world > 1 and not args.no_gather else "none"},
-            "roofline": {"bound": "mfma",
-                         "kernel": "wt::gemm16s_kernel<128,192,4,2,3,EPI_BIAS_GELU=2,OUT_S32=1> (ConvNeXt pwconv1 GEMM %dx%dx%d + GELU, "
-                                   "split-f16: 3 x v_mfma_f32_16x16x32_f16 per fp32-equivalent product)" % (Mrows, arch.intermediate_dim, arch.dim),
-                         "achieved": round(achieved, 2), "peak": round(PEAK_F16X3_TFLOPS, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_F16X3_TFLOPS, 4), "traffic": pmc_traffic(args.arch, B, clip_s),
-                         "peak_note": "algorithmic fp32-equivalent FLOP/s; peak = %.1f TF dense f16 MFMA / 3 MFMAs per product; the kernel "
-                                      "issues %.0f TF/s of f16 MFMA work" % (PEAK_F16_MFMA_TFLOPS, 3 * achieved),
-                         "algorithmic_bytes_per_launch": 4 * (Mrows * arch.dim + arch.intermediate_dim * arch.dim + Mrows * arch.intermediate_dim),
-                         "flops_per_launch": flops, "avg_launch_ms": round(kern_ms, 4), "launches_timed": kern[1],
-                         "launch_timing": "device clock (s_memrealtime, 100 MHz) of the launch's first workgroup entry to its last exit, every "
-                                          "pwconv1 launch of the timed ONE-LANE steps (config.one_lane); no events in the stream "
-                                          "(profiles/r03_trace_vs_stamps.txt compares it with the rocprofv3 trace and with bracketing HIP events in one run)",
-                         "end_to_end_tflops": round(e2e_tflops, 2),
-                         "end_to_end_frac": round(e2e_tflops / PEAK_F16X3_TFLOPS, 4)},
+            **({"roofline": roofline} if roofline is not None else {}),
         }
         if dumped is not None:
             line["outputs"] = dumped
 
-    # ------------------------------------------------------------------------------ other configs (N = 1)
-    if world == 1 and rank == 0 and not args.no_other_configs and args.arch == "hop600" and clip_s == 3:
+    # ------------------------------------------------------------------------------ other configs (--full, N = 1)
+    if args.full and world == 1 and rank == 0 and not args.no_other_configs and args.arch == "hop600" and clip_s == 3:
         other = {}
         # the reference's own usage (infer.py:44-70): one clip per call, a different length per file, bandwidth_id built
         # on the GPU once; >= 20 distinct lengths between 1 and 10 s
@@ -639,7 +655,7 @@ def main():
         line["other_configs"] = other
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.arch, sd, clips_np, clip_s)
             line["speedup_vs_cpu"] = round(line["value"] / line["cpu_baseline"]["value"], 1)
         print(json.dumps(line), flush=True)

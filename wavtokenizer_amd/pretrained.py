@@ -167,7 +167,7 @@ class _Engine:
         self.max_streams = int(os.environ.get("WAVTOK_MAX_STREAMS", "4"))
         self.stream_lru: List[int] = []
         self.plans: Dict[tuple, Tuple[ctypes.c_void_p, torch.Tensor]] = {}
-        self.io: Dict[Tuple[int, int, int, int], Dict[str, torch.Tensor]] = {}     # fixed I/O buffers of graph plans
+        self.io: Dict[int, tuple] = {}     # staging buffers of graph plans by plan handle: (inputs, outputs) of WavTokenizer._call
         self.device_index = -1
         self._keepalive: List[Any] = []
 
@@ -258,9 +258,9 @@ class _Engine:
         need = lib.wt_plan_workspace_bytes(p)
         while self.plans and (len(self.plans) >= self.max_plans or
                               sum(w.numel() for _p, w in self.plans.values()) + need > self.max_ws_bytes):
-            old = next(iter(self.plans))              # LRU: the least recently used plan + workspace
-            lib.wt_plan_destroy(self.plans.pop(old)[0])
-            self.io.pop(old, None)
+            old = self.plans.pop(next(iter(self.plans)))[0]      # LRU: the least recently used plan + workspace
+            lib.wt_plan_destroy(old)
+            self.io.pop(old.value, None)
         ws = torch.empty(need, dtype=torch.uint8, device=device)
         self.plans[key] = (p, ws)
         return p, ws
@@ -268,17 +268,9 @@ class _Engine:
     def drop(self, pred):
         """Destroys the cached plans (and their workspaces) whose key (kind, B, length, flags) satisfies pred."""
         for k in [k for k in self.plans if pred(k)]:
-            lib.wt_plan_destroy(self.plans.pop(k)[0])
-            self.io.pop(k, None)
-
-    def staging(self, kind: int, B: int, length: int, flags: int, make, device=None, sites: int = 0) -> Dict[str, torch.Tensor]:
-        """Fixed input/output tensors of a graph plan: a recorded hipGraph replays fixed addresses, so calls copy their
-        input in and hand out copies of the results (a few hundred KB at the batch sizes graphs are used for)."""
-        key = self._key(kind, B, length, flags, device, sites)
-        io = self.io.get(key)
-        if io is None:
-            io = self.io[key] = make()
-        return io
+            plan = self.plans.pop(k)[0]
+            lib.wt_plan_destroy(plan)
+            self.io.pop(plan.value, None)
 
 
 def site_name(site: int) -> str:
@@ -298,6 +290,26 @@ def _stream_ptr(device: torch.device) -> ctypes.c_void_p:
 
 def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _fill(src, buf: torch.Tensor) -> torch.Tensor:
+    """Writes one input of WavTokenizer._call into buf: a tensor is copied, a (shape, dtype, fill) input runs fill(buf)."""
+    if isinstance(src, torch.Tensor):
+        buf.copy_(src)
+    else:
+        src[2](buf)
+    return buf
+
+
+def _take_status(read, handle) -> int:
+    """Reads and clears a status word: read is lib.wt_plan_status (handle: a plan) or lib.wt_model_status (the model)."""
+    bits = ctypes.c_int32()
+    check(read(handle, ctypes.byref(bits), 1), read.__name__)
+    return bits.value
+
+
+class _OffRoute(Exception):
+    """A mixed-length call found the encoder off the route mixed-length plans take (WavTokenizer._mixed_route_ok)."""
 
 
 # ------------------------------------------------------------------------------ public class
@@ -538,18 +550,15 @@ class WavTokenizer(nn.Module):
         # the model's word first: it is what decides (every plan's guard step reports into it, and it outlives plans the
         # LRU has destroyed); the plans' own words only say which plans reported since the last check and may hold
         # failures that a later call has already consumed and answered by falling back
-        mbits = ctypes.c_int32()
-        if self._engine.model:
-            check(lib.wt_model_status(self._engine.model, ctypes.byref(mbits), 1), "wt_model_status")
+        mbits = _take_status(lib.wt_model_status, self._engine.model) if self._engine.model else 0
         seen = []
         for key, (plan, _ws) in self._engine.plans.items():
-            bits = ctypes.c_int32()
-            check(lib.wt_plan_status(plan, ctypes.byref(bits), 1), "wt_plan_status")
-            if bits.value:
-                seen.append((key, bits.value))
-        if mbits.value & _capi.WT_STATUS_BIT_RANGE:
+            bits = _take_status(lib.wt_plan_status, plan)
+            if bits:
+                seen.append((key, bits))
+        if mbits & _capi.WT_STATUS_BIT_RANGE:
             self._answer_range()
-        bad = (seen or [("model", mbits.value)]) if mbits.value else []
+        bad = (seen or [("model", mbits)]) if mbits else []
         events, self.fallback_events = self.fallback_events, []
         if events and not bad:
             raise WavTokError("device-side failures since the last check, already answered by a fallback: %s" % events)
@@ -611,13 +620,12 @@ class WavTokenizer(nn.Module):
             return self._plan_flags | _capi.WT_PLAN_FLAG_GRAPH
         return self._plan_flags
 
-    def _guarded(self, dev: torch.device, get_plan, launch, strict: bool = False):
-        """Runs launch(plan, ws) with the fallbacks for device-side failures (set_strict_status).  get_plan() builds the
-        plan from the CURRENT flags and fp32 sites, so a fallback that changes them re-plans."""
+    def _guarded(self, dev: torch.device, call, strict: bool = False):
+        """Runs call() -> (outputs, plan), one _call, with the fallbacks for device-side failures (set_strict_status) and
+        returns the outputs.  call() plans from the CURRENT flags and fp32 sites, so a fallback that changes them re-plans."""
         for attempt in range(8):
-            plan, ws = get_plan()
             try:
-                out = launch(plan, ws)
+                out, plan = call()
             except WavTokError as e:
                 if e.status == _capi.WT_ERR_LSTM_SYNC and attempt < 7:
                     self.fallback_events.append("persistent LSTM lost co-residency in an earlier call (its outputs were poisoned): "
@@ -631,12 +639,11 @@ class WavTokenizer(nn.Module):
             if not strict:
                 return out
             torch.cuda.current_stream(dev).synchronize()
-            bits = ctypes.c_int32()
-            check(lib.wt_plan_status(plan, ctypes.byref(bits), 1), "wt_plan_status")
-            if not bits.value:
+            bits = _take_status(lib.wt_plan_status, plan)
+            if not bits:
                 return out
-            what = self._answer_range() if bits.value & _capi.WT_STATUS_BIT_RANGE else "launch-per-step LSTM"
-            self.fallback_events.append("strict mode: the call failed on the device (status bits %d) and was repeated on the fallback path: %s" % (bits.value, what))
+            what = self._answer_range() if bits & _capi.WT_STATUS_BIT_RANGE else "launch-per-step LSTM"
+            self.fallback_events.append("strict mode: the call failed on the device (status bits %d) and was repeated on the fallback path: %s" % (bits, what))
         raise WavTokError("the call kept failing on the device after the fp32 / step-LSTM fallbacks")
 
     def _sites(self, kind: int) -> int:
@@ -660,12 +667,7 @@ class WavTokenizer(nn.Module):
         dev = self._ensure_engine()
         bw = self._bandwidth_index(bandwidth_id if bandwidth_id is not None else torch.tensor([0]))
         audio = self._as_input(audio_input, dev)
-        B, T = audio.shape
-        L = self._arch.frames(T)
         flags = (self._plan_flags | _capi.WT_PLAN_FLAG_RANGE_REPORT) & ~_capi.WT_PLAN_FLAG_GRAPH
-        feats = torch.empty((B, 512, L), dtype=torch.float32, device=dev)
-        codes = torch.empty((1, B, L), dtype=torch.int64, device=dev)
-        wav = torch.empty((B, self._wave_len(L)), dtype=torch.float32, device=dev)
         out: List[Dict[str, Any]] = []
 
         def collect(plan, what):
@@ -677,21 +679,18 @@ class WavTokenizer(nn.Module):
                             "headroom_bits": (math.log2(65504.0 / a) if 0.0 < a < float("inf") else (float("inf") if a == 0.0 else float("-inf")))})
                 i += 1
 
-        pe, wse = self._engine.plan(_capi.WT_PLAN_ENCODE, B, T, flags, dev, self._sites(_capi.WT_PLAN_ENCODE))
-        check(lib.wt_encode(pe, _ptr(audio), _ptr(feats), _ptr(codes), _ptr(None), _ptr(wse), _stream_ptr(dev)), "wt_encode")
+        (feats, _codes, _emb), pe = self._encode(audio, flags, dev, want_emb=False)
         collect(pe, "encode")
         # the decoder is measured on the features the codes select (finite even if the encoder's own report shows an overflow)
         torch.cuda.current_stream(dev).synchronize()
-        bits = ctypes.c_int32()
-        check(lib.wt_plan_status(pe, ctypes.byref(bits), 1), "wt_plan_status")
-        check(lib.wt_model_status(self._engine.model, ctypes.byref(bits), 1), "wt_model_status")
-        pd, wsd = self._engine.plan(_capi.WT_PLAN_DECODE, B, L, flags, dev, self._sites(_capi.WT_PLAN_DECODE))
+        _take_status(lib.wt_plan_status, pe)
+        _take_status(lib.wt_model_status, self._engine.model)
         fin = feats if torch.isfinite(feats).all() else torch.zeros_like(feats)
-        check(lib.wt_decode(pd, _ptr(fin), bw, _ptr(wav), _ptr(None), _ptr(wsd), _stream_ptr(dev)), "wt_decode")
+        _outs, pd = self._decode(fin, bw, flags, dev, want_backbone=False)
         collect(pd, "decode")
         torch.cuda.current_stream(dev).synchronize()
-        check(lib.wt_plan_status(pd, ctypes.byref(bits), 1), "wt_plan_status")
-        check(lib.wt_model_status(self._engine.model, ctypes.byref(bits), 1), "wt_model_status")
+        _take_status(lib.wt_plan_status, pd)
+        _take_status(lib.wt_model_status, self._engine.model)
         m = ctypes.c_uint64()
         for p in (pe, pd):
             check(lib.wt_plan_range_sites(p, ctypes.byref(m), 1), "wt_plan_range_sites")
@@ -740,34 +739,48 @@ class WavTokenizer(nn.Module):
         return x.to(dtype).contiguous()
 
     # -- kernels ------------------------------------------------------------------------------------
+    def _call(self, entry, kind: int, B: int, length: int, flags: int, dev: torch.device, ins, outs, scalars=()):
+        """One call of a C run entry point, entry(plan, inputs..., scalars..., outputs..., workspace, stream), on the plan
+        (kind, B, length, flags) with the kind's fp32 sites.  ins: per input the tensor itself, or (shape, dtype, fill) for a
+        buffer that fill(buffer) writes.  outs: per output (shape, dtype, wanted), or None for a null pointer; a direct call
+        passes null for an unwanted output too.  Returns (outputs, None where not wanted; plan)."""
+        plan, ws = self._engine.plan(kind, B, length, flags, dev, self._sites(kind))
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        graph = flags & _capi.WT_PLAN_FLAG_GRAPH
+        if graph:
+            # a recorded hipGraph replays fixed addresses: the plan keeps staging buffers, the inputs are copied in and the
+            # results handed out as copies.  Every output buffer is passed, wanted or not: the recording is keyed by the
+            # pointers (wt_plan::GraphKey), so encode_infer (no emb) and SEANetEncoder.forward (emb) alternating on one
+            # plan would otherwise record it again on every call
+            io = self._engine.io.get(plan.value)
+            if io is None:
+                io = self._engine.io[plan.value] = (
+                    [new(x.shape, x.dtype) if isinstance(x, torch.Tensor) else new(*x[:2]) for x in ins],
+                    [new(*o[:2]) if o is not None else None for o in outs])
+            bufs, obufs = io
+            for x, buf in zip(ins, bufs):
+                _fill(x, buf)
+        else:
+            bufs = [x if isinstance(x, torch.Tensor) else _fill(x, new(*x[:2])) for x in ins]
+            obufs = [new(*o[:2]) if o is not None and o[2] else None for o in outs]
+        check(entry(plan, *map(_ptr, bufs), *scalars, *map(_ptr, obufs), _ptr(ws), _stream_ptr(dev)), entry.__name__)
+        if graph:
+            return tuple(b.clone() if o is not None and o[2] else None for o, b in zip(outs, obufs)), plan
+        return tuple(obufs), plan
+
+    def _encode(self, audio: torch.Tensor, flags: int, dev: torch.device, want_emb: bool):
+        """The encode call of _run_encode and range_report: ((features, codes, emb), plan)."""
+        B, T = audio.shape
+        L = self._arch.frames(T)
+        return self._call(lib.wt_encode, _capi.WT_PLAN_ENCODE, B, T, flags, dev, (audio,),
+                          (((B, 512, L), torch.float32, True), ((1, B, L), torch.int64, True), ((B, 512, L), torch.float32, want_emb)))
+
     def _run_encode(self, audio: torch.Tensor, want_emb: bool = True):
         dev = self._ensure_engine()
         assert audio.dim() == 2, "expected audio of shape (B, T)"
         audio = self._as_input(audio, dev)
-        B, T = audio.shape
-        L = self._arch.frames(T)
-
-        def launch(plan, ws):
-            flags = self._graph_flags(B)
-            if flags & _capi.WT_PLAN_FLAG_GRAPH:
-                io = self._engine.staging(_capi.WT_PLAN_ENCODE, B, T, flags, lambda: {
-                    "in": torch.empty((B, T), dtype=torch.float32, device=dev),
-                    "feats": torch.empty((B, 512, L), dtype=torch.float32, device=dev),
-                    "codes": torch.empty((1, B, L), dtype=torch.int64, device=dev),
-                    "emb": torch.empty((B, 512, L), dtype=torch.float32, device=dev)}, dev, self._sites(_capi.WT_PLAN_ENCODE))
-                io["in"].copy_(audio)
-                check(lib.wt_encode(plan, _ptr(io["in"]), _ptr(io["feats"]), _ptr(io["codes"]), _ptr(io["emb"]), _ptr(ws),
-                                    _stream_ptr(dev)), "wt_encode")
-                return io["feats"].clone(), io["codes"].clone(), (io["emb"].clone() if want_emb else None)
-            feats = torch.empty((B, 512, L), dtype=torch.float32, device=dev)
-            codes = torch.empty((1, B, L), dtype=torch.int64, device=dev)
-            emb = torch.empty((B, 512, L), dtype=torch.float32, device=dev) if want_emb else None
-            check(lib.wt_encode(plan, _ptr(audio), _ptr(feats), _ptr(codes), _ptr(emb), _ptr(ws), _stream_ptr(dev)),
-                  "wt_encode")
-            return feats, codes, emb
-
-        return self._guarded(dev, lambda: self._engine.plan(_capi.WT_PLAN_ENCODE, B, T, self._graph_flags(B), dev,
-                                                            self._sites(_capi.WT_PLAN_ENCODE)), launch, self._is_strict(B))
+        B = audio.shape[0]
+        return self._guarded(dev, lambda: self._encode(audio, self._graph_flags(B), dev, want_emb), self._is_strict(B))
 
     def _run_encode_mixed(self, wavs: List[torch.Tensor], T_pad: int, dev: torch.device):
         """One mixed-length encode call (WT_PLAN_FLAG_MIXED_LENGTH) on clips of at least MIN_CLIP samples and at most T_pad:
@@ -777,46 +790,25 @@ class WavTokenizer(nn.Module):
         B = len(wavs)
         L = self._arch.frames(T_pad)
         lengths = [int(w.shape[0]) for w in wavs]
-        key_flags = lambda: self._graph_flags(B) | _capi.WT_PLAN_FLAG_MIXED_LENGTH
 
-        class _Refused(Exception):
-            pass
-
-        def get_plan():
-            # checked on every attempt: a range fallback inside _guarded can put the encoder site on fp32
-            if not self._mixed_route_ok():
-                raise _Refused()
-            return self._engine.plan(_capi.WT_PLAN_ENCODE, B, T_pad, key_flags(), dev, self._sites(_capi.WT_PLAN_ENCODE))
-
-        def fill(buf: torch.Tensor, lens: torch.Tensor):
+        def fill_wav(buf: torch.Tensor):        # (samples past a clip's length are never read)
             for j, w in enumerate(wavs):
                 buf[j, :lengths[j]].copy_(w)
-            lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)
 
-        def launch(plan, ws):
-            flags = key_flags()
-            if flags & _capi.WT_PLAN_FLAG_GRAPH:
-                io = self._engine.staging(_capi.WT_PLAN_ENCODE, B, T_pad, flags, lambda: {
-                    "in": torch.zeros((B, T_pad), dtype=torch.float32, device=dev),
-                    "len": torch.zeros((B,), dtype=torch.int32, device=dev),
-                    "feats": torch.empty((B, 512, L), dtype=torch.float32, device=dev),
-                    "codes": torch.empty((1, B, L), dtype=torch.int64, device=dev)}, dev, self._sites(_capi.WT_PLAN_ENCODE))
-                fill(io["in"], io["len"])
-                check(lib.wt_encode_mixed(plan, _ptr(io["in"]), _ptr(io["len"]), _ptr(io["feats"]), _ptr(io["codes"]), _ptr(None),
-                                          _ptr(ws), _stream_ptr(dev)), "wt_encode_mixed")
-                return io["feats"].clone(), io["codes"].clone()
-            wav = torch.empty((B, T_pad), dtype=torch.float32, device=dev)      # (samples past a clip's length are never read)
-            lens = torch.empty((B,), dtype=torch.int32, device=dev)
-            fill(wav, lens)
-            feats = torch.empty((B, 512, L), dtype=torch.float32, device=dev)
-            codes = torch.empty((1, B, L), dtype=torch.int64, device=dev)
-            check(lib.wt_encode_mixed(plan, _ptr(wav), _ptr(lens), _ptr(feats), _ptr(codes), _ptr(None), _ptr(ws), _stream_ptr(dev)),
-                  "wt_encode_mixed")
-            return feats, codes
+        ins = (((B, T_pad), torch.float32, fill_wav),
+               ((B,), torch.int32, lambda lens: lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)))
+        outs = (((B, 512, L), torch.float32, True), ((1, B, L), torch.int64, True), None)      # (no emb output)
+
+        def call():
+            # checked on every attempt: a range fallback inside _guarded can put the encoder site on fp32
+            if not self._mixed_route_ok():
+                raise _OffRoute()
+            return self._call(lib.wt_encode_mixed, _capi.WT_PLAN_ENCODE, B, T_pad,
+                              self._graph_flags(B) | _capi.WT_PLAN_FLAG_MIXED_LENGTH, dev, ins, outs)
 
         try:
-            return self._guarded(dev, get_plan, launch, self._is_strict(B))
-        except _Refused:
+            return self._guarded(dev, call, self._is_strict(B))[:2]
+        except _OffRoute:
             return None
 
     def _mixed_route_ok(self) -> bool:
@@ -887,61 +879,43 @@ class WavTokenizer(nn.Module):
         assert features.dim() == 3 and features.shape[1] == self._arch.input_channels, "expected features (B, 512, L)"
         bw = self._bandwidth_index(bandwidth_id)
         features = self._as_input(features, dev)
+        B = features.shape[0]
+        # a call that wants the backbone output is never graph-replayed
+        return self._guarded(dev, lambda: self._decode(features, bw, self._plan_flags if want_backbone else self._graph_flags(B),
+                                                       dev, want_backbone), self._is_strict(B))
+
+    def _decode(self, features: torch.Tensor, bw: int, flags: int, dev: torch.device, want_backbone: bool):
+        """The decode call of _run_decode and range_report: ((waveform, backbone output), plan)."""
         B, _, L = features.shape
-        cur_flags = lambda: self._graph_flags(B) if not want_backbone else self._plan_flags
-
-        def launch(plan, ws):
-            flags = cur_flags()
-            if flags & _capi.WT_PLAN_FLAG_GRAPH:
-                io = self._engine.staging(_capi.WT_PLAN_DECODE, B, L, flags, lambda: {
-                    "in": torch.empty((B, self._arch.input_channels, L), dtype=torch.float32, device=dev),
-                    "wav": torch.empty((B, self._wave_len(L)), dtype=torch.float32, device=dev)}, dev, self._sites(_capi.WT_PLAN_DECODE))
-                io["in"].copy_(features)
-                check(lib.wt_decode(plan, _ptr(io["in"]), bw, _ptr(io["wav"]), _ptr(None), _ptr(ws), _stream_ptr(dev)), "wt_decode")
-                return io["wav"].clone(), None
-            wav = torch.empty((B, self._wave_len(L)), dtype=torch.float32, device=dev)
-            bb = torch.empty((B, L, self._arch.dim), dtype=torch.float32, device=dev) if want_backbone else None
-            check(lib.wt_decode(plan, _ptr(features), bw, _ptr(wav), _ptr(bb), _ptr(ws), _stream_ptr(dev)), "wt_decode")
-            return wav, bb
-
-        return self._guarded(dev, lambda: self._engine.plan(_capi.WT_PLAN_DECODE, B, L, cur_flags(), dev, self._sites(_capi.WT_PLAN_DECODE)),
-                             launch, self._is_strict(B))
+        # no backbone buffer at all unless asked for: a graph plan's staging has none
+        bb = ((B, L, self._arch.dim), torch.float32, True) if want_backbone else None
+        return self._call(lib.wt_decode, _capi.WT_PLAN_DECODE, B, L, flags, dev, (features,),
+                          (((B, self._wave_len(L)), torch.float32, True), bb), (bw,))
 
     def _run_head(self, x: torch.Tensor) -> torch.Tensor:
         dev = self._ensure_engine()
         assert x.dim() == 3 and x.shape[2] == self._arch.dim, "expected the backbone output (B, L, dim)"
         x = self._as_input(x, dev)
         B, L, _ = x.shape
-
-        def launch(plan, ws):
-            wav = torch.empty((B, self._wave_len(L)), dtype=torch.float32, device=dev)
-            check(lib.wt_head(plan, _ptr(x), _ptr(wav), _ptr(ws), _stream_ptr(dev)), "wt_head")
-            return wav
-
-        return self._guarded(dev, lambda: self._engine.plan(_capi.WT_PLAN_HEAD, B, L, self._plan_flags, dev, self._sites(_capi.WT_PLAN_HEAD)),
-                             launch, self._is_strict(B))
+        outs = (((B, self._wave_len(L)), torch.float32, True),)
+        return self._guarded(dev, lambda: self._call(lib.wt_head, _capi.WT_PLAN_HEAD, B, L, self._plan_flags, dev, (x,), outs),
+                             self._is_strict(B))[0]
 
     def _run_seanet_decoder(self, z: torch.Tensor) -> torch.Tensor:
         dev = self._ensure_engine()
         z = self._as_input(z, dev)
         B, _, L = z.shape
-
-        def launch(plan, ws):
-            out = torch.empty((B, 1, L * self._arch.hop), dtype=torch.float32, device=dev)
-            check(lib.wt_seanet_decode(plan, _ptr(z), _ptr(out), _ptr(ws), _stream_ptr(dev)), "wt_seanet_decode")
-            return out
-
-        return self._guarded(dev, lambda: self._engine.plan(_capi.WT_PLAN_SEANET_DECODER, B, L, self._plan_flags, dev,
-                                                            self._sites(_capi.WT_PLAN_SEANET_DECODER)), launch, self._is_strict(B))
+        outs = (((B, 1, L * self._arch.hop), torch.float32, True),)
+        return self._guarded(dev, lambda: self._call(lib.wt_seanet_decode, _capi.WT_PLAN_SEANET_DECODER, B, L, self._plan_flags,
+                                                     dev, (z,), outs), self._is_strict(B))[0]
 
     def _run_unit_lstm(self, x: torch.Tensor) -> torch.Tensor:
         """Unit tests: the encoder's SLSTM alone, x (B, L, 512) time-major -> lstm(x) + x, on the plan's kernels."""
         dev = self._ensure_engine()
         x = self._as_input(x, dev)
         B, L, _ = x.shape
-        plan, ws = self._engine.plan(_capi.WT_PLAN_UNIT_LSTM, B, L, self._plan_flags, dev, self._sites(_capi.WT_PLAN_UNIT_LSTM))
-        y = torch.empty_like(x)
-        check(lib.wt_unit_run(plan, _ptr(x), _ptr(y), _ptr(ws), _stream_ptr(dev)), "wt_unit_run")
+        (y,), _plan = self._call(lib.wt_unit_run, _capi.WT_PLAN_UNIT_LSTM, B, L, self._plan_flags, dev, (x,),
+                                 ((x.shape, torch.float32, True),))
         return y
 
     def debug_stage(self, kind: int, B: int, length: int, name: str, rows: Optional[int] = None):

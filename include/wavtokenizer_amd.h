@@ -338,6 +338,55 @@ typedef struct {
 size_t wt_gemm_probe_workspace_bytes(const wt_gemm_desc* d);
 int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, void* stream);
 
+/* One launch of one non-GEMM kernel through the plans' own launcher (the unit tests' view of GroupNorm, the row norms,
+ * softmax, the ISTFT tail, the Cin = 1 / Cout = 1 convs, ConvTranspose1d, the transposes and the two reductions).
+ * All arrays are fp32 device arrays in the plans' layouts, activations time-major [clip][frame][channel]; 16-byte
+ * aligned (the softmax scores: 4-byte).  Per op (unused fields are ignored):
+ *   GN_APPLY   x [B][L][C], p0 gamma [C], p1 beta [C] -> y [B][L][C] (out_s32: S32 rows), y2 scale [B][C], y3 shift [B][C];
+ *              groups, eps, flag = swish, p2 = chunk scratch of B * groups * ceil(L / 128) * 2 floats (optional)
+ *   GN_STATS   the same without y, flag and out_s32
+ *   ROWNORM    x [B][L][C] -> y [B][L][C] (out_s32: S32 rows); mode 0 dwconv k7 p3 + LayerNorm (p0 dw_w [7][C], p1 dw_b [C]),
+ *              1 LayerNorm, 2 per-clip affine (p2 in_scale [B][C], p3 in_shift [B][C]) + LayerNorm; p4 out_scale [C],
+ *              p5 out_shift [C], eps
+ *   SOFTMAX    x scores [n][ld], L valid columns, in place; y (optional): S32 probabilities [n][ld] instead
+ *   ISTFT_OLA  x quarter transforms [4][B * L][Kq], p0 window [n_fft], p1 window^2 [n_fft] -> y [B][hop * L] (flag = 1,
+ *              "center": [B][hop * (L - 1)])
+ *   CONV_FIRST x wav [B][L], p0 w [k][Cout], p1 bias [Cout] -> y [B][L][Cout]
+ *   CONV_LAST  x [B][L][C], p0 w [k][C], p1 bias [1] -> y [B][L]; flag = ELU on the input
+ *   TRANSPOSE  x [B][L][C] -> y [B][C][L] (out_s32: S32 rows of L)
+ *   CONVTR     x [B][L][C], p0 w [k][C][Cout], p1 bias [Cout] -> y [B][L * stride][Cout]; flag = ELU on the input
+ *   ROW_SUMSQ  x [n][C] -> y [n]
+ *   S32_AMAX   x S32 array of n values -> y: one uint32 word, atomic max of the bit pattern of max |value|
+ * status: optional device word that the S32 producers OR WT_STATUS_BIT_RANGE into (the launch context's status word is
+ * set for the call and restored).  The descriptor is checked before any HIP call: whatever the launcher refuses returns
+ * WT_ERR_INVALID with its message and touches no memory.  form (optional): the launch the launcher chose. */
+enum { WT_OP_GN_APPLY = 0, WT_OP_GN_STATS = 1, WT_OP_ROWNORM = 2, WT_OP_SOFTMAX = 3, WT_OP_ISTFT_OLA = 4, WT_OP_CONV_FIRST = 5,
+       WT_OP_CONV_LAST = 6, WT_OP_TRANSPOSE = 7, WT_OP_CONVTR = 8, WT_OP_ROW_SUMSQ = 9, WT_OP_S32_AMAX = 10 };
+/* wt_op_form.kernel */
+enum { WT_OPK_GN_TILE = 1, WT_OPK_GN_CHUNK = 2, WT_OPK_GN_STATS = 3, WT_OPK_ROWNORM = 4, WT_OPK_DWCONV_LN = 5,
+       WT_OPK_SOFTMAX_REG = 6, WT_OPK_SOFTMAX_RMW = 7, WT_OPK_ISTFT_OLA = 8, WT_OPK_CONV_FIRST = 9, WT_OPK_CONV_LAST32 = 10,
+       WT_OPK_CONV_LAST = 11, WT_OPK_TRANSPOSE = 12, WT_OPK_CONVTR = 13, WT_OPK_ROW_SUMSQ = 14, WT_OPK_S32_AMAX = 15 };
+typedef struct {
+    int32_t size;                   /* sizeof(wt_op_desc) */
+    int32_t op;
+    int32_t B, L, C;                /* clips, frames (rows) per clip, channels */
+    int32_t groups, mode, flag, out_s32;
+    int32_t ld, k, stride, Cout, n_fft, hop, Kq;
+    float eps;
+    int64_t n;                      /* SOFTMAX / ROW_SUMSQ rows, S32_AMAX values */
+    const void* x;
+    const void *p0, *p1, *p2, *p3, *p4, *p5;
+    void *y, *y2, *y3;
+    uint32_t* status;
+} wt_op_desc;
+typedef struct {
+    int32_t kernel;                 /* WT_OPK_* */
+    int32_t variant;                /* gn_*: APPLY / SWISH template value; rownorm, dwconv_ln: NV; softmax_reg: NV4 */
+    int32_t variant2;               /* dwconv_ln: R; rownorm: MODE; gn_tile: waves per group */
+    int32_t grid_x, grid_y, grid_z, block, lds;     /* gn_chunk: the apply launch */
+} wt_op_form;
+int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream);
+
 /* Replaces: SEANetResnetBlock.forward (encoder/modules/seanet.py:62-63): y = shortcut(x) + conv1(elu(conv3(elu(x)))),
  * one fused launch, time-major x [B][T][C] -> y [B][T][C], C = 32 or 64; folded weights w3 [C/2][3][C], w1 [C][C/2],
  * ws [C][C].  wav != NULL (C = 32): x is not read; the tile is built from the waveform wav [B][T] through

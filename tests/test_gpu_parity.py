@@ -727,6 +727,26 @@ def test_decode_long_sequences_against_oracle(gpu_model):
         assert rel_l2(got.cpu().numpy(), want.numpy()) < WAV_REL_TOL, (B, L)
 
 
+def test_decode_across_launch_form_boundaries_against_oracle(gpu_model):
+    """decode at the lengths where the non-GEMM launchers switch forms: the 128-row GroupNorm chunks and the one-slab limit
+    (127 .. 129, 255 .. 257), the softmax pitches (513 -> 544: softmax_reg<5>; 2049 -> 2080: the read-modify-write kernel,
+    the only case that takes a pitch above 2048 through the attention GEMMs too) and, with B = 9, B L across 2048
+    (dwconv_ln<3, 1> -> <3, 4>, tail rows for L % 4 != 0)."""
+    from tests import parity_log
+    name, m, sd = gpu_model
+    orc = _oracle(name, sd)
+    cases = [(1, L) for L in (127, 128, 129, 255, 256, 257, 513, 2049)] + [(9, L) for L in (127, 128, 129, 255, 256, 257)]
+    for i, (B, L) in enumerate(cases):
+        feats = torch.randn(B, 512, L, generator=torch.Generator().manual_seed(5100 + i)) * 0.5
+        with torch.inference_mode():
+            want = orc.decode(feats, BW)
+        got = m.decode(feats.cuda(), bandwidth_id=BW)
+        assert tuple(got.shape) == tuple(want.shape)
+        err = rel_l2(got.cpu().numpy(), want.numpy())
+        parity_log.record(f"decode_form_boundaries[{name}-B{B}-L{L}]", wav_rel_l2=err)
+        assert err < WAV_REL_TOL, (B, L, err)
+
+
 # ------------------------------------------------------ shipped kernels, one at a time, against the oracle
 def _fold(sd, prefix):
     """weight_norm fold as wt_model_create does it (fp64): w = g * v / ||v|| (conv.py:25-34); returns [Cout][k][Cin]."""

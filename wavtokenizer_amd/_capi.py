@@ -21,7 +21,7 @@ EXPORTS = [
     "wt_plan_find_buffer", "wt_plan_buffer_info", "wt_plan_buffer_name", "wt_plan_status", "wt_plan_num_steps", "wt_plan_step_name",
     "wt_plan_set_timing", "wt_plan_read_timing", "wt_model_split_ok", "wt_model_status", "wt_model_take_bad_codes", "wt_encode", "wt_codes_to_features",
     "wt_decode", "wt_seanet_decode", "wt_head", "wt_unit_run", "wt_sconv1d", "wt_linear", "wt_conv1d_s32", "wt_vq_workspace_bytes",
-    "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down", "wt_gemm_probe_workspace_bytes", "wt_gemm_probe",
+    "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down", "wt_gemm_probe_workspace_bytes", "wt_gemm_probe", "wt_op_probe",
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry",
 ]
@@ -67,6 +67,25 @@ class WtGemmDesc(ctypes.Structure):
 
 class WtLaunchForm(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("BM", "BN", "waves_m", "waves_n", "stages", "ks", "prod", "staged", "bias_cache", "G", "tiles")]
+
+
+WT_OP_GN_APPLY, WT_OP_GN_STATS, WT_OP_ROWNORM, WT_OP_SOFTMAX, WT_OP_ISTFT_OLA, WT_OP_CONV_FIRST = 0, 1, 2, 3, 4, 5
+WT_OP_CONV_LAST, WT_OP_TRANSPOSE, WT_OP_CONVTR, WT_OP_ROW_SUMSQ, WT_OP_S32_AMAX = 6, 7, 8, 9, 10
+WT_OPK_NAMES = {1: "gn_tile", 2: "gn_chunk", 3: "gn_stats", 4: "rownorm", 5: "dwconv_ln", 6: "softmax_reg", 7: "softmax_rmw",
+                8: "istft_ola", 9: "conv_first", 10: "conv_last32", 11: "conv_last", 12: "transpose", 13: "convtr",
+                14: "row_sumsq", 15: "s32_amax"}
+
+
+class WtOpDesc(ctypes.Structure):
+    """wt_op_desc: one launch of one non-GEMM kernel through the plans' launcher (wt_op_probe)."""
+    _fields_ = ([(n, c_int32) for n in ("size", "op", "B", "L", "C", "groups", "mode", "flag", "out_s32", "ld", "k", "stride",
+                                        "Cout", "n_fft", "hop", "Kq")]
+                + [("eps", c_float), ("n", c_int64)]
+                + [(n, c_void_p) for n in ("x", "p0", "p1", "p2", "p3", "p4", "p5", "y", "y2", "y3", "status")])
+
+
+class WtOpForm(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("kernel", "variant", "variant2", "grid_x", "grid_y", "grid_z", "block", "lds")]
 
 
 class WavTokError(RuntimeError):
@@ -161,6 +180,7 @@ def _load() -> ctypes.CDLL:
     lib.wt_gemm_probe_workspace_bytes.argtypes = [POINTER(WtGemmDesc)]
     lib.wt_gemm_probe_workspace_bytes.restype = c_size_t
     lib.wt_gemm_probe.argtypes = [POINTER(WtGemmDesc), POINTER(WtLaunchForm), c_void_p, c_void_p]
+    lib.wt_op_probe.argtypes = [POINTER(WtOpDesc), POINTER(WtOpForm), c_void_p]
     lib.wt_resampler_create.argtypes = [c_int32, c_int32, c_int32, POINTER(c_void_p)]
     lib.wt_resampler_destroy.argtypes = [c_void_p]
     lib.wt_resampler_destroy.restype = None

@@ -803,6 +803,119 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
     return WT_OK;
 }
 
+// wt_op_probe: every check that needs no HIP call and that the launchers do not make themselves (they trust the plans)
+static int op_probe_check(const wt_op_desc* d) {
+    auto bad = [](const char* m) { set_error(std::string("wt_op_probe: ") + m); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_op_desc)) return bad("descriptor missing or of another size");
+    if (d->op < WT_OP_GN_APPLY || d->op > WT_OP_S32_AMAX) return bad("unknown op");
+    auto al16 = [](const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); };
+    const void* ptrs[] = {d->p0, d->p1, d->p2, d->p3, d->p4, d->p5, d->y, d->y2, d->y3};
+    for (const void* p : ptrs) if (!al16(p)) return bad("arrays must be 16-byte aligned");
+    if (!d->x || (reinterpret_cast<uintptr_t>(d->x) & (d->op == WT_OP_SOFTMAX ? 3 : 15))) return bad("x missing or misaligned");
+    if (reinterpret_cast<uintptr_t>(d->status) & 3) return bad("status misaligned");
+    const bool shaped = d->op != WT_OP_SOFTMAX && d->op != WT_OP_ROW_SUMSQ && d->op != WT_OP_S32_AMAX;
+    if (shaped && (d->B <= 0 || d->L <= 0)) return bad("extents must be positive");
+    if (shaped && d->op != WT_OP_CONV_FIRST && d->op != WT_OP_ISTFT_OLA && (d->C <= 0 || (long)d->L * d->C >= (long)INT_MAX)) return bad("extents must be positive (and L * C < 2^31)");
+    switch (d->op) {
+    case WT_OP_GN_APPLY: case WT_OP_GN_STATS:
+        if (!d->p0 || !d->p1 || !d->y2 || !d->y3 || (d->op == WT_OP_GN_APPLY && !d->y)) return bad("null argument");
+        if (d->groups <= 0 || d->C % d->groups || d->C / d->groups > 256 || d->B > 65535) return bad("GroupNorm needs C % groups == 0, at most 256 channels per group, B <= 65535");
+        break;
+    case WT_OP_ROWNORM:
+        if (!d->y || !d->p4 || !d->p5) return bad("null argument");
+        if (d->mode < RN_DWCONV || d->mode > RN_AFFINE_IN) return bad("rownorm mode is 0, 1 or 2");
+        if (d->mode == RN_DWCONV && (!d->p0 || !d->p1)) return bad("null argument");
+        if (d->mode == RN_AFFINE_IN && (!d->p2 || !d->p3)) return bad("null argument");
+        break;
+    case WT_OP_SOFTMAX:
+        if (d->n <= 0 || d->n > INT_MAX || d->L <= 0 || d->ld < d->L) return bad("softmax needs rows > 0 and 0 < L <= ld");
+        break;
+    case WT_OP_ISTFT_OLA:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->n_fft <= 0 || d->hop <= 0 || d->n_fft % 4 || d->n_fft % d->hop || (d->n_fft - d->hop) % 2 || d->Kq < d->n_fft / 4 + 1)
+            return bad("the ISTFT tail needs n_fft % 4 == 0, n_fft % hop == 0 and Kq > n_fft / 4");
+        break;
+    case WT_OP_CONV_FIRST:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->k <= 0 || d->Cout <= 0 || d->Cout % 4) return bad("conv_first needs k > 0 and Cout % 4 == 0");
+        break;
+    case WT_OP_CONV_LAST:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->k <= 0) return bad("conv_last needs k > 0");
+        break;
+    case WT_OP_TRANSPOSE:
+        if (!d->y) return bad("null argument");
+        if (d->B > 65535 || (d->L + 31) / 32 > 65535) return bad("transpose: too many tiles for one launch");
+        break;
+    case WT_OP_CONVTR:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->stride <= 0 || d->k < d->stride || d->Cout <= 0 || d->Cout % 4) return bad("convtr needs k >= stride > 0 and Cout % 4 == 0");
+        break;
+    case WT_OP_ROW_SUMSQ:
+        if (!d->y) return bad("null argument");
+        if (d->n <= 0 || d->C <= 0 || d->C % 4) return bad("row_sumsq needs rows > 0 and C % 4 == 0");
+        break;
+    case WT_OP_S32_AMAX:
+        if (!d->y) return bad("null argument");
+        if (d->n <= 0 || d->n % 32) return bad("s32_amax needs whole S32 groups of 32 values");
+        break;
+    }
+    return WT_OK;
+}
+
+int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream) {
+    if (int rc = op_probe_check(d)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto F = [](const void* p) { return static_cast<const float*>(p); };
+    auto W = [](void* p) { return static_cast<float*>(p); };
+    OpForm lf;
+    const LaunchCtx saved = g_launch;
+    g_launch.status = reinterpret_cast<unsigned*>(d->status);
+    g_launch.form = &lf;
+    int rc = 0;
+    switch (d->op) {
+    case WT_OP_GN_APPLY:
+        rc = launch_gn_apply(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), W(d->y), d->flag ? 1 : 0, d->B, d->L, d->C, d->groups, d->eps, s,
+                             d->out_s32 ? 1 : 0, const_cast<float*>(F(d->p2)));
+        break;
+    case WT_OP_GN_STATS:
+        rc = launch_gn_stats(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), d->B, d->L, d->C, d->groups, d->eps, s, const_cast<float*>(F(d->p2)));
+        break;
+    case WT_OP_ROWNORM:
+        rc = launch_rownorm(d->mode, F(d->x), W(d->y), d->B, d->L, d->C, F(d->p0), F(d->p1), F(d->p2), F(d->p3), F(d->p4), F(d->p5), d->eps, s,
+                            d->out_s32 ? 1 : 0);
+        break;
+    case WT_OP_SOFTMAX:
+        rc = launch_softmax(const_cast<float*>(F(d->x)), (int)d->n, d->L, d->ld, s, W(d->y));
+        break;
+    case WT_OP_ISTFT_OLA:
+        rc = launch_istft_ola(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->n_fft, d->hop, d->Kq, d->flag ? 1 : 0, s);
+        break;
+    case WT_OP_CONV_FIRST:
+        rc = launch_conv_first(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->k, d->Cout, s);
+        break;
+    case WT_OP_CONV_LAST:
+        rc = launch_conv_last(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->C, d->k, d->flag ? 1 : 0, s);
+        break;
+    case WT_OP_TRANSPOSE:
+        rc = launch_transpose(F(d->x), W(d->y), d->B, d->L, d->C, s, d->out_s32 ? 1 : 0);
+        break;
+    case WT_OP_CONVTR:
+        rc = launch_convtr(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->C, d->Cout, d->k, d->stride, d->flag ? 1 : 0, s);
+        break;
+    case WT_OP_ROW_SUMSQ:
+        rc = launch_row_sumsq(F(d->x), W(d->y), d->n, d->C, s);
+        break;
+    case WT_OP_S32_AMAX:
+        rc = launch_s32_amax(d->x, d->n, static_cast<unsigned*>(d->y), s);
+        break;
+    }
+    g_launch = saved;
+    if (rc) return rc;
+    if (form) *form = wt_op_form{lf.kernel, lf.variant, lf.variant2, (int32_t)lf.grid[0], (int32_t)lf.grid[1], (int32_t)lf.grid[2], (int32_t)lf.block, (int32_t)lf.lds};
+    return WT_OK;
+}
+
 size_t wt_vq_workspace_bytes(int64_t N, int32_t D, int32_t bins) {
     const size_t np = std::max(gemm_vq_parts(bins), gemm16s_vq_parts(bins));
     return al256((size_t)N * D * 4) + al256((size_t)bins * D * 4) + al256((size_t)N * sizeof(float)) +

@@ -49,8 +49,22 @@ enum : unsigned { WT_STATUS_LSTM = 1u, WT_STATUS_RANGE = 2u };
 // stamp_start / stamp_end: when set (wt_plan_set_timing("@name")), the next gemm16s launch records its own duration on the
 // device: every workgroup takes the constant 100 MHz clock (s_memrealtime) on entry and on exit, atomic min / max into the two
 // words; stamp_used reports that a launch took them.  No packet is added to the stream, so the neighbours do not move
+// form: when set (wt_op_probe), a non-GEMM launcher records the launch it chose (plans leave it null)
+enum OpKernel : int {
+    OPK_NONE = 0, OPK_GN_TILE, OPK_GN_CHUNK, OPK_GN_STATS, OPK_ROWNORM, OPK_DWCONV_LN, OPK_SOFTMAX_REG, OPK_SOFTMAX_RMW,
+    OPK_ISTFT_OLA, OPK_CONV_FIRST, OPK_CONV_LAST32, OPK_CONV_LAST, OPK_TRANSPOSE, OPK_CONVTR, OPK_ROW_SUMSQ, OPK_S32_AMAX
+};
+struct OpForm {
+    int kernel = OPK_NONE;       // OpKernel
+    int variant = 0;             // gn_*: the APPLY / SWISH template value; rownorm, dwconv_ln: NV; softmax_reg: NV4; else 0
+    int variant2 = 0;            // dwconv_ln: R; rownorm: MODE; gn_tile: waves per group; else 0
+    unsigned grid[3] = {0, 0, 0};
+    unsigned block = 0;
+    unsigned lds = 0;            // dynamic LDS bytes
+};
 struct LaunchCtx {
     unsigned* status = nullptr;
+    OpForm* form = nullptr;
     unsigned long long* stamp_start = nullptr;
     unsigned long long* stamp_end = nullptr;
     bool stamp_used = false;

@@ -7,6 +7,11 @@ namespace wt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// wt_op_probe asks which launch a launcher chose (common.h OpForm); plans leave g_launch.form null
+static inline void note_form(int kernel, int variant, int variant2, dim3 grid, unsigned block, size_t lds = 0) {
+    if (OpForm* f = g_launch.form) *f = OpForm{kernel, variant, variant2, {grid.x, grid.y, grid.z}, block, (unsigned)lds};
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -79,6 +84,7 @@ int launch_conv_first(const float* wav, const float* w, const float* bias, float
     const int Tp = T > maxpad ? (int)T : maxpad + 1;
     long total = BT * (Cout / 4);
     int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    note_form(OPK_CONV_FIRST, 0, 0, dim3(blocks), 256);
     hipLaunchKernelGGL(conv_first_kernel, dim3(blocks), dim3(256), 0, s, wav, w, bias, y, BT, (int)T, k, Cout, Tp);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -178,6 +184,7 @@ int launch_conv_last(const float* x, const float* w, const float* bias, float* y
     const int maxpad = pl > pr ? pl : pr;
     const int Tp = T > maxpad ? (int)T : maxpad + 1;
     if (Cin == 32 && k == 7 && B <= 65535) {
+        note_form(OPK_CONV_LAST32, 0, 0, dim3((unsigned)((T + 255) / 256), B), 256);
         hipLaunchKernelGGL(conv_last32_kernel, dim3((unsigned)((T + 255) / 256), B), dim3(256), 0, s, x, w, bias, y, (int)T, Tp, elu_in);
         WT_HIP_CHECK(hipGetLastError());
         return 0;
@@ -185,6 +192,7 @@ int launch_conv_last(const float* x, const float* w, const float* bias, float* y
     if (Cin < 4 || Cin > 256 || (Cin & (Cin - 1))) { set_error("conv_last: Cin must be a power of two in [4, 256]"); return -1; }
     const long groups = (BT + (256 / (Cin / 4)) - 1) / (256 / (Cin / 4));
     int blocks = (int)(groups < 16384 ? groups : 16384);
+    note_form(OPK_CONV_LAST, 0, 0, dim3(blocks), 256);
     hipLaunchKernelGGL(conv_last_kernel, dim3(blocks), dim3(256), 0, s, x, w, bias, y, BT, (int)T, Cin, k, Tp, elu_in);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -217,6 +225,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict_
 int launch_transpose(const float* in, float* out, int B, int R, int C, hipStream_t s, int out_s32) {
     if (out_s32 && (R % 32)) { set_error("transpose: an S32 output needs rows in multiples of 32 elements"); return -1; }
     dim3 grid((C + 31) / 32, (R + 31) / 32, B);
+    note_form(OPK_TRANSPOSE, 0, 0, grid, 256);
     hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, s, in, out, R, C, out_s32, g_launch.status);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -292,6 +301,7 @@ int launch_gn_stats(const float* x, const float* gamma, const float* beta, float
     const int GBs = gn_slab_groups(C, groups), cgs = C / groups;
     if (part && L > 256 && GBs && (cgs % 4 == 0) && (C % 4 == 0) && GBs <= 8)
         return launch_gn_chunked(x, gamma, beta, scale, shift, nullptr, 0, B, L, C, groups, GBs, eps, s, 0, part);
+    note_form(OPK_GN_STATS, 0, 0, dim3(groups, B), 256);
     hipLaunchKernelGGL(gn_stats_kernel<0>, dim3(groups, B), dim3(256), 0, s, x, gamma, beta, scale, shift,
                        (float*)nullptr, L, C, C / groups, eps, 0, (unsigned*)nullptr);
     WT_HIP_CHECK(hipGetLastError());
@@ -514,6 +524,7 @@ static int launch_gn_chunked(const float* x, const float* gamma, const float* be
     if (int rc = attr_once.run([&]() -> int { WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_chunk_stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); return 0; })) return rc;
     hipLaunchKernelGGL(gn_chunk_stats_kernel, dim3(groups / GB, nch, B), dim3(256), smem, s, x, part, L, C, cg, GB, groups, nch);
     const dim3 grid(groups / GB, mode ? nch : 1, B);
+    note_form(OPK_GN_CHUNK, mode, 0, grid, 256, smem);       // the apply launch; the statistics launch has nch chunks in grid.y
     if (mode == 0) hipLaunchKernelGGL(gn_chunk_apply_kernel<0>, grid, dim3(256), 0, s, x, part, gamma, beta, scale, shift, y, L, C, cg, GB, groups, nch, eps, out_s32, g_launch.status);
     else if (mode == 1) hipLaunchKernelGGL(gn_chunk_apply_kernel<1>, grid, dim3(256), 0, s, x, part, gamma, beta, scale, shift, y, L, C, cg, GB, groups, nch, eps, out_s32, g_launch.status);
     else hipLaunchKernelGGL(gn_chunk_apply_kernel<2>, grid, dim3(256), 0, s, x, part, gamma, beta, scale, shift, y, L, C, cg, GB, groups, nch, eps, out_s32, g_launch.status);
@@ -548,6 +559,7 @@ int launch_gn_apply(const float* x, const float* gamma, const float* beta, float
         // of 3 s clips: 17.9 -> 15.3 us at B = 64, 14.8 -> 11.0 at B = 1).  The choice depends on the architecture alone, so a
         // clip's statistics are summed in the same order whatever the batch
         const int nt = GB == 4 ? 512 : 256;
+        note_form(OPK_GN_TILE, swish ? 1 : 0, (nt >> 6) == 2 * GB ? 2 : 1, grid, nt, smem);
         if (swish) hipLaunchKernelGGL(gn_tile_kernel<1>, grid, dim3(nt), smem, s, x, gamma, beta, scale, shift, y, L, C, cg, GB, eps, out_s32, g_launch.status);
         else hipLaunchKernelGGL(gn_tile_kernel<0>, grid, dim3(nt), smem, s, x, gamma, beta, scale, shift, y, L, C, cg, GB, eps, out_s32, g_launch.status);
         WT_HIP_CHECK(hipGetLastError());
@@ -555,6 +567,7 @@ int launch_gn_apply(const float* x, const float* gamma, const float* beta, float
     }
     if (part && GB && (cg % 4 == 0) && (C % 4 == 0) && GB * cg <= 128 && GB <= 8)
         return launch_gn_chunked(x, gamma, beta, scale, shift, y, swish ? 2 : 1, B, L, C, groups, GB, eps, s, out_s32, part);
+    note_form(OPK_GN_STATS, swish ? 2 : 1, 0, dim3(groups, B), 256);
     if (swish)
         hipLaunchKernelGGL(gn_stats_kernel<2>, dim3(groups, B), dim3(256), 0, s, x, gamma, beta, scale, shift, y, L, C,
                            C / groups, eps, out_s32, g_launch.status);
@@ -714,19 +727,24 @@ static int launch_rownorm_nv(int mode, const float* x, float* y, long M, int L, 
             // a few clips: one frame per wave (four frames per wave would be fewer waves than the chip has SIMDs, each walking
             // its rows alone: 9.4 us for 120 frames).  Same accumulation order per output: same bits
             const long waves = (long)B * L;
+            note_form(OPK_DWCONV_LN, NV, 1, dim3((unsigned)((waves + 3) / 4)), 256);
             hipLaunchKernelGGL((dwconv_ln_kernel<NV, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, y, B, L, dw_w, dw_b,
                                os, oh, eps, s32, g_launch.status);
         } else {
             constexpr int R = 4;
             const long waves = (long)B * ((L + R - 1) / R);
+            note_form(OPK_DWCONV_LN, NV, R, dim3((unsigned)((waves + 3) / 4)), 256);
             hipLaunchKernelGGL((dwconv_ln_kernel<NV, R>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, y, B, L, dw_w, dw_b,
                                os, oh, eps, s32, g_launch.status);
         }
     }
-    else if (mode == RN_PLAIN)
+    else if (mode == RN_PLAIN) {
+        note_form(OPK_ROWNORM, NV, RN_PLAIN, grid, 256);
         hipLaunchKernelGGL((rownorm_kernel<NV, RN_PLAIN>), grid, dim3(256), 0, s, x, y, M, L, dw_w, dw_b, is, ih, os, oh, eps, s32, g_launch.status);
-    else
+    } else {
+        note_form(OPK_ROWNORM, NV, RN_AFFINE_IN, grid, 256);
         hipLaunchKernelGGL((rownorm_kernel<NV, RN_AFFINE_IN>), grid, dim3(256), 0, s, x, y, M, L, dw_w, dw_b, is, ih, os, oh, eps, s32, g_launch.status);
+    }
     WT_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -755,18 +773,22 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ S, lon
     float mx = -INFINITY;
     for (int j = lane; j < L; j += 64) mx = fmaxf(mx, row[j]);
     mx = wave_max(mx);
+    // a lane owns columns 4 (lane + 64 i) + e, i ascending, like softmax_reg_kernel: the same partial sums in the same order
     float sum = 0.f;
-    for (int j = lane; j < L; j += 64) {
-        const float e = expf(row[j] - mx);
-        row[j] = e;
-        sum += e;
-    }
+    for (int j0 = 4 * lane; j0 < L; j0 += 256)
+        for (int j = j0; j < j0 + 4 && j < L; ++j) {
+            const float e = expf(row[j] - mx);
+            row[j] = e;
+            sum += e;
+        }
     sum = wave_sum(sum);
     if (P_s32) {        // probabilities for a split-f16 GEMM: S32 rows in a separate buffer (pad columns zero)
         float unused = 0.f;                                      // probabilities never leave [0, 1]
-        for (int j = lane; j < ld; j += 64) store_s32_1(P_s32 + r * ld, j, j < L ? row[j] / sum : 0.f, unused);
+        for (int j0 = 4 * lane; j0 < ld; j0 += 256)
+            for (int j = j0; j < j0 + 4 && j < ld; ++j) store_s32_1(P_s32 + r * ld, j, j < L ? row[j] / sum : 0.f, unused);
     } else {
-        for (int j = lane; j < ld; j += 64) row[j] = j < L ? row[j] / sum : 0.f;
+        for (int j0 = 4 * lane; j0 < ld; j0 += 256)
+            for (int j = j0; j < j0 + 4 && j < ld; ++j) row[j] = j < L ? row[j] / sum : 0.f;
     }
 }
 
@@ -820,6 +842,7 @@ int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s3
     if (P_s32 && (ld % 32)) { set_error("softmax: an S32 output needs a row pitch in multiples of 32"); return -1; }
     if (ld % 4 == 0 && ld <= 2048 && !(reinterpret_cast<uintptr_t>(S) & 15)) {
         const dim3 grid((rows + 3) / 4), block(256);
+        note_form(OPK_SOFTMAX_REG, ld <= 256 ? 1 : ld <= 512 ? 2 : ld <= 1280 ? 5 : 8, 0, grid, 256);
         if (ld <= 256) hipLaunchKernelGGL(softmax_reg_kernel<1>, grid, block, 0, s, S, (long)rows, L, ld, P_s32);
         else if (ld <= 512) hipLaunchKernelGGL(softmax_reg_kernel<2>, grid, block, 0, s, S, (long)rows, L, ld, P_s32);
         else if (ld <= 1280) hipLaunchKernelGGL(softmax_reg_kernel<5>, grid, block, 0, s, S, (long)rows, L, ld, P_s32);
@@ -827,6 +850,7 @@ int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s3
         WT_HIP_CHECK(hipGetLastError());
         return 0;
     }
+    note_form(OPK_SOFTMAX_RMW, 0, 0, dim3((rows + 3) / 4), 256);
     hipLaunchKernelGGL(softmax_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, S, (long)rows, L, ld, P_s32);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -884,6 +908,7 @@ int launch_istft_ola(const float* parts, const float* win, const float* wsq, flo
     if (total <= 0) return 0;
     const long blocks = (((total + 255) / 256) + 7) / 8 * 8;          // one 256-sample chunk per workgroup, a multiple of 8
     if (blocks > 0x7fffffffL) { set_error("istft_ola: too many samples for one launch"); return -1; }
+    note_form(OPK_ISTFT_OLA, 0, 0, dim3((unsigned)blocks), 256);
     hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)blocks), dim3(256), 0, s, parts, win, wsq, out, total, (long)B * L, L, n_fft,
                        hop, Kq, pad, Tout);
     WT_HIP_CHECK(hipGetLastError());
@@ -974,6 +999,7 @@ __global__ __launch_bounds__(256) void s32_amax_kernel(const _Float16* __restric
 int launch_s32_amax(const void* s32, long numel, unsigned* out_bits, hipStream_t s) {
     if (numel <= 0) return 0;
     const long blocks = (numel + 255) / 256 < 2048 ? (numel + 255) / 256 : 2048;
+    note_form(OPK_S32_AMAX, 0, 0, dim3((unsigned)blocks), 256);
     hipLaunchKernelGGL(s32_amax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const _Float16*>(s32), numel, out_bits);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -995,6 +1021,7 @@ __global__ __launch_bounds__(256) void row_sumsq_kernel(const float* __restrict_
 }
 
 int launch_row_sumsq(const float* x, float* out, long rows, int D, hipStream_t s) {
+    note_form(OPK_ROW_SUMSQ, 0, 0, dim3((unsigned)((rows + 3) / 4)), 256);
     hipLaunchKernelGGL(row_sumsq_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, out, rows, D);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1363,6 +1390,7 @@ int launch_convtr(const float* x, const float* w, const float* bias, float* y, i
     const int Tout = (Tin - 1) * stride + k - pad_total;    // = Tin*stride
     const long total = (long)B * Tout * (Cout / 4);
     int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    note_form(OPK_CONVTR, 0, 0, dim3(blocks), 256);
     hipLaunchKernelGGL(convtr_kernel, dim3(blocks), dim3(256), 0, s, x, w, bias, y, total, Tin, Tout, Cin, Cout, k,
                        stride, pl, elu_in);
     WT_HIP_CHECK(hipGetLastError());

@@ -1336,7 +1336,7 @@ def test_batch_beyond_the_persistent_lstm_limit(gpu_model):
 def test_two_lanes_match_one_stream(gpu_model):
     """One model called from two HIP streams at once (sharding.StepRunner(lanes=2): step i+1's encode_infer beside step i's
     decode).  Every stream gets its own plan and workspace (pretrained._Engine._key) and the library chains the persistent
-    LSTM launches across streams (capi.cpp LstmChain), so the results are those of the single-stream calls, bit for bit, for
+    LSTM launches across streams (run.cpp LstmChain), so the results are those of the single-stream calls, bit for bit, for
     the whole-batch form (B = 20, persistent LSTM) and for the graph-replay form (B = 2)."""
     from wavtokenizer_amd import synth
     from wavtokenizer_amd.sharding import StepRunner

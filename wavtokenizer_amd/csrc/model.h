@@ -1,5 +1,5 @@
 // Internal types of the host side of libwavtok_hip.so: the packed model (weights.cpp), launch plans (plan.cpp)
-// and what the extern "C" entry points (capi.cpp) share with them.
+// and what the extern "C" entry points (capi.cpp, run.cpp, probe.cpp) share with them.
 #pragma once
 #include "../../include/wavtokenizer_amd.h"
 #include "common.h"
@@ -184,6 +184,7 @@ struct BufSpec {
     size_t bytes = 0, numel = 0, off = 0;
     int first = INT_MAX, last = -1;
     int fmt = BUF_F32;
+    bool holds_s32 = false;     // declared BUF_F32, written in S32 (plan.cpp build_seanet_decoder; gemm_step's format check)
 };
 
 // current device switched for the duration of a call, restored on every exit path
@@ -204,12 +205,17 @@ struct wt_plan {
     int kind = 0, B = 0, flags = 0;
     int64_t len = 0, L = 0, T = 0;
     uint64_t fp32_sites = 0;              // sites (wt::Site) that run on fp32 operands (wt_plan_create_ex)
+    int whole_site = -1;                  // the site that stands for the plan as a whole (wt_plan_create_ex); -1: decided site by site
     int cur_site = 0;                     // site of the steps being added (plan.cpp)
+    // what a call writes, recorded by the plan's builder: elements of codes, out_f and aux (0: not an output of this kind);
+    // the guard step poisons exactly these
+    long n_codes = 0, n_out = 0, n_aux = 0;
+    int build_rc = 0;                     // first error a step helper met while the plan was built
     std::vector<wt::BufSpec> bufs;
     std::vector<std::function<int(const wt::RunCtx&)>> steps;
     std::vector<std::string> step_names;
     std::vector<int> step_sites;          // site of every step: its kernels report WT_STATUS_RANGE into ctl[CTL_SITE0 + site]
-    // WT_PLAN_FLAG_RANGE_REPORT: after every step, the largest magnitude in each S32 buffer the step touches (capi.cpp)
+    // WT_PLAN_FLAG_RANGE_REPORT: after every step, the largest magnitude in each S32 buffer the step touches (run.cpp)
     struct RangeEntry { int step, buf; };
     std::vector<RangeEntry> range_entries;
     unsigned* range_dev = nullptr;        // one word (fp32 bit pattern of the maximum) per entry
@@ -221,7 +227,7 @@ struct wt_plan {
     // leg); mutable profiling state, not thread-safe, off by default
     mutable std::string timing_filter;
     mutable std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_free;
-    // "@name" timing: device-side stamps of the gemm16s launches (capi.cpp): [0, STAMP_SLOTS) entry clocks, then exit clocks
+    // "@name" timing: device-side stamps of the gemm16s launches (run.cpp): [0, STAMP_SLOTS) entry clocks, then exit clocks
     static constexpr int STAMP_SLOTS = 8192;
     mutable unsigned long long* stamps = nullptr;
     mutable int stamp_next = 0;
@@ -339,6 +345,8 @@ int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint
 int ensure_f32_weights(const wt_model* M);                        // fills the lazy fp32 arrays of a packed model (first fp32 plan)
 size_t packed_bytes(const void* buf, size_t n);                  // exact length of the image at buf (0: bad header)
 int packed_verify(const void* buf, size_t n);                    // header + bounds + content hash; needs no GPU
+// capi.cpp: the device is a whole MI355X (256 CUs: the persistent LSTM's one resident workgroup per CU, 32 per XCD)
+bool full_chip(int device);
 // plan.cpp
 GemmArgs sconv_args(const ConvW& w, int B, long T, int stride, int dil);
 GemmArgs zconv_args(const ConvW& w, int B, int L);

@@ -9,11 +9,9 @@ namespace wt {
 static bool site_fp32(const wt_plan* P, int site) { return (P->fp32_sites >> site) & 1u; }
 static bool plan_fp32(const wt_plan* P) {
     if ((P->flags & WT_PLAN_FLAG_FP32_GEMM) || !P->model->s32_ok) return true;
-    // plans that are one range site as a whole (model.h Site); the decode plan decides site by site (build_decode)
-    if (P->kind == WT_PLAN_SEANET_DECODER) return !P->model->sd_s32_ok || site_fp32(P, SITE_SEADEC);
-    if (P->kind == WT_PLAN_ENCODE || P->kind == WT_PLAN_UNIT_LSTM) return site_fp32(P, SITE_ENC);
-    if (P->kind == WT_PLAN_HEAD) return site_fp32(P, SITE_HEAD);
-    return false;
+    if (P->whole_site == SITE_SEADEC && !P->model->sd_s32_ok) return true;
+    // plans that are one range site as a whole (wt_plan::whole_site); the decode plan decides site by site (build_decode)
+    return P->whole_site >= 0 && site_fp32(P, P->whole_site);
 }
 static bool plan_unfused(const wt_plan* P) { return P->flags & WT_PLAN_FLAG_UNFUSED; }
 static bool plan_s32(const wt_plan* P) { return !plan_unfused(P) && !plan_fp32(P); }
@@ -52,6 +50,55 @@ static int dense_act(const wt_plan* P, bool s32, GemmArgs a, const float* b_op, 
     if (s32) { a.W_hi = b_op; return launch_gemm16s(a, epi, out, s); }
     a.W = b_op;
     return gemm_auto(P, a, PRO_NONE, epi, s);
+}
+
+// The buffers of a GEMM step by id (-1: none), in the order the step lists them, bound to the prototype's pointers when it runs
+struct GemmBufs {
+    int A, A2, C, C2 = -1;
+    bool r_is_c = false;         // the residual operand R is the output (updated in place)
+    long x_off = 0;              // A starts this many elements into its buffer (the trimmed view of a transposed conv's output)
+    int mix_word = -1;           // mixed-length plans: the conv's triple in the geometry table (launch_gemm16s)
+};
+// One GEMM step: registers it with the buffers it touches (geometry table, A, A2, C, C2: the order names the step and orders
+// the range report), binds them at run time and calls dense().  Declared formats that disagree with what the step reads
+// and writes fail the plan's creation (wt_plan::build_rc); BufSpec::holds_s32 stands in for the declaration of the
+// SEANetDecoder buffers that wt_plan_buffer_info has always reported as fp32.
+static void gemm_step(wt_plan* P, bool s32, const GemmArgs& proto, const GemmBufs& b, int pro, int epi, int out,
+                      const std::string& name = "") {
+    auto is_s32 = [&](int id) { return (P->bufs[id].fmt & BUF_S32) != 0 || P->bufs[id].holds_s32; };
+    const int eff = s32 ? out : OUT_F32;         // gemm.hip writes fp32 whatever `out` says
+    const bool c_s32 = eff == OUT_S32 || eff == OUT_S32_DUAL_ELU, dual = eff == OUT_S32_DUAL_ELU || eff == OUT_F32_AND_S32;
+    const char* why = nullptr;
+    if (dual && b.C2 < 0) why = "a dual output without a second buffer";
+    else if (s32 && (!is_s32(b.A) || (b.A2 >= 0 && !is_s32(b.A2)))) why = "an S32 GEMM reads a buffer declared fp32";
+    else if ((is_s32(b.C) != c_s32 || (dual && !is_s32(b.C2)))) why = "the output format disagrees with the buffer's declaration";
+    if (why && !P->build_rc) {
+        set_error("internal: GEMM step into '" + P->bufs[b.C].name + "': " + why);
+        P->build_rc = WT_ERR_INVALID;
+    }
+    const int geom = b.mix_word >= 0 ? P->mix_geom : -1;
+    P->step({geom, b.A, b.A2, b.C, b.C2}, [=](const RunCtx& c) {
+        GemmArgs a = proto;
+        a.A = P->ptr(c, b.A) + b.x_off; a.C = P->ptr(c, b.C);
+        if (b.A2 >= 0) a.A2 = P->ptr(c, b.A2);
+        if (b.C2 >= 0) a.C2 = P->ptr(c, b.C2);
+        if (b.r_is_c) a.R = a.C;
+        return dense(P, s32, a, pro, epi, out, c.stream, geom >= 0 ? reinterpret_cast<const int*>(P->ptr(c, geom)) + b.mix_word : nullptr);
+    }, 1, name);
+}
+
+static GemmBufs in_place(int A, int C) { GemmBufs b{A, -1, C}; b.r_is_c = true; return b; }
+
+static int copy_f32(float* dst, const float* src, size_t numel, hipStream_t s) {
+    WT_HIP_CHECK(hipMemcpyAsync(dst, src, numel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+// A device-to-device copy as a step of its own: plan buffer to plan buffer, or (CALLER) from the call's input / into its output
+constexpr int CALLER = -1;
+static void copy_step(wt_plan* P, int src, int dst, size_t numel, const std::string& name = "") {
+    P->step({src, dst}, [=](const RunCtx& c) {
+        return copy_f32(dst == CALLER ? c.out_f : P->ptr(c, dst), src == CALLER ? c.in_f : P->ptr(c, src), numel, c.stream);
+    }, 1, name);
 }
 
 // SConv1d geometry: sconv_geom (common.h, shared with the mixed-length geometry step)
@@ -117,23 +164,15 @@ static int plan_resblock(wt_plan* P, const ConvW& c3, const ConvW& c1, const Con
     }
     const int h = P->buf(name + ".h", (size_t)B * T * (C / 2));
     const int y = P->buf(name, (size_t)B * T * C, elu_out ? BUF_ELU : BUF_F32);
-    GemmArgs a3 = sconv_args(c3, B, T, 1, 1);
-    P->step({xin, h}, [=](const RunCtx& c) {
-        GemmArgs a = a3; a.A = P->ptr(c, xin) + x_off; a.C = P->ptr(c, h);
-        if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_auto(P, a, PRO_ELU, EPI_BIAS, c.stream);
-    });
-    GemmArgs as = sconv_args(sc, B, T, 1, 1);
-    P->step({xin, y}, [=](const RunCtx& c) {
-        GemmArgs a = as; a.A = P->ptr(c, xin) + x_off; a.C = P->ptr(c, y);
-        if (x_bstride) a.a_bstride = x_bstride;
-        return gemm_auto(P, a, PRO_NONE, EPI_BIAS, c.stream);
-    });
-    GemmArgs a1 = sconv_args(c1, B, T, 1, 1);
-    P->step({h, y}, [=](const RunCtx& c) {
-        GemmArgs a = a1; a.A = P->ptr(c, h); a.C = P->ptr(c, y); a.R = P->ptr(c, y); a.r_rstride = C;
-        return gemm_auto(P, a, PRO_ELU, elu_out ? EPI_BIAS_RES_ELU : EPI_BIAS_RES, c.stream);
-    });
+    GemmArgs a3 = sconv_args(c3, B, T, 1, 1), as = sconv_args(sc, B, T, 1, 1), a1 = sconv_args(c1, B, T, 1, 1);
+    if (x_bstride) a3.a_bstride = as.a_bstride = x_bstride;
+    a1.r_rstride = C;
+    GemmBufs bx{xin, -1, h};
+    bx.x_off = x_off;
+    gemm_step(P, false, a3, bx, PRO_ELU, EPI_BIAS, OUT_F32);
+    bx.C = y;
+    gemm_step(P, false, as, bx, PRO_NONE, EPI_BIAS, OUT_F32);
+    gemm_step(P, false, a1, in_place(h, y), PRO_ELU, elu_out ? EPI_BIAS_RES_ELU : EPI_BIAS_RES, OUT_F32);
     return y;
 }
 
@@ -151,18 +190,12 @@ static int plan_lstm(wt_plan* P, const LstmW& w, int B, int L, int H, int xin, c
     GemmArgs ax = linear_args(w.Wih0, w.b0, (long)B * L, 4 * H, H);
     ax.T_in = B; ax.T_out = B; ax.a_bstride = H; ax.a_rstride = (long)L * H;
     const int xsrc = xin_s32 >= 0 ? xin_s32 : xin;
-    P->step({xsrc, xg}, [=](const RunCtx& c) {
-        GemmArgs a = ax; a.A = P->ptr(c, xsrc); a.C = P->ptr(c, xg);
-        return dense(P, xin_s32 >= 0, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
-    });
+    gemm_step(P, xin_s32 >= 0, ax, {xsrc, -1, xg}, PRO_NONE, EPI_BIAS, OUT_F32);
     // one persistent launch for the whole recurrence (lstm_persist.hip) when the batch fits its per-XCD clip groups and
     // the device is a full MI355X (256 CUs: one resident workgroup per CU, 32 per XCD)
     const bool persist_env = [] { const char* e = lab_env("WT_LSTM_PERSIST"); return !e || e[0] != '0'; }();       // (LAB builds; callers use WT_PLAN_FLAG_STEP_LSTM)
-    bool persist = persist_env && !plan_fp32(P) && !(P->flags & WT_PLAN_FLAG_STEP_LSTM) && w.Wp && H == 512 && B <= 128 && L < 65536;
-    if (persist) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, P->model->device) != hipSuccess || cus != 256) persist = false;
-    }
+    const bool persist = persist_env && !plan_fp32(P) && !(P->flags & WT_PLAN_FLAG_STEP_LSTM) && w.Wp && H == 512 && B <= 128 && L < 65536 &&
+                         full_chip(P->model->device);
     if (persist) P->uses_persist = true;
     const size_t hxn = lstm_persist_hx_bytes() / sizeof(float), ctn = lstm_persist_ctl_bytes() / sizeof(float);
     const int hx = persist ? P->buf(name + ".hx", hxn + ctn) : -1;
@@ -201,13 +234,10 @@ static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const
     const int C = sc.cout;
     const int h = P->buf(name + ".h", (size_t)B * T * (C / 2), BUF_S32 | BUF_ELU);
     GemmArgs a3 = sconv_args(c3, B, T, 1, 1);
-    const int geom = mix_word >= 0 ? P->mix_geom : -1;
-    P->step({geom, x_elu, h}, [=](const RunCtx& c) {
-        GemmArgs a = a3; a.A = P->ptr(c, x_elu) + x_off; a.C = P->ptr(c, h);
-        if (x_bstride) a.a_bstride = x_bstride;
-        const int* mix = geom >= 0 ? reinterpret_cast<const int*>(P->ptr(c, geom)) + mix_word + GEOM_C3 : nullptr;
-        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream, mix);
-    });
+    GemmBufs b3{x_elu, -1, h};
+    b3.x_off = x_off; b3.mix_word = mix_word >= 0 ? mix_word + GEOM_C3 : -1;
+    if (x_bstride) a3.a_bstride = x_bstride;
+    gemm_step(P, true, a3, b3, PRO_NONE, EPI_BIAS_ELU, OUT_S32);
     // shortcut + conv1 as one GEMM over K = [x (C) | elu(h) (C/2)] (GemmArgs::A2, weight `cat`: weights.cpp build_cat): the
     // fp32 shortcut tensor is neither written nor read back, and the output goes through the staged full-line epilogue
     const int o = P->buf(name, (size_t)B * T * C, BUF_S32 | BUF_ELU);
@@ -215,12 +245,10 @@ static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const
     ac.W = cat.w; ac.w_rstride = cat.cin; ac.bias = cat.b; ac.K = cat.cin; ac.Cin = cat.cin;
     set_s32(ac, cat.s32);
     ac.K1 = C; ac.a2_bstride = T * (C / 2); ac.a2_rstride = C / 2;
-    P->step({geom, x_raw, h, o}, [=](const RunCtx& c) {
-        GemmArgs a = ac; a.A = P->ptr(c, x_raw) + x_off; a.A2 = P->ptr(c, h); a.C = P->ptr(c, o);
-        if (x_bstride) a.a_bstride = x_bstride;
-        const int* mix = geom >= 0 ? reinterpret_cast<const int*>(P->ptr(c, geom)) + mix_word + GEOM_SC : nullptr;
-        return gemm_s32(a, EPI_BIAS_ELU, OUT_S32, c.stream, mix);
-    });
+    if (x_bstride) ac.a_bstride = x_bstride;
+    GemmBufs bc{x_raw, h, o};
+    bc.x_off = x_off; bc.mix_word = mix_word >= 0 ? mix_word + GEOM_SC : -1;
+    gemm_step(P, true, ac, bc, PRO_NONE, EPI_BIAS_ELU, OUT_S32);
     return o;
 }
 
@@ -335,34 +363,25 @@ int build_encode(wt_plan* P) {
         const bool next_s32 = !last && !route[si + 1].fused && route[si + 1].s32;
         const int y = P->buf(out, ynum, next_s32 ? BUF_S32 : BUF_F32);
         const int y2 = (next_s32 || (last && lstm_s32)) ? P->buf(out + ".s32", ynum, BUF_S32 | (next_s32 ? BUF_ELU : 0)) : -1;
-        const int xin = x;
-        P->step({geom, xin, y, y2}, [=](const RunCtx& c) {
-            GemmArgs a = ad; a.A = P->ptr(c, xin); a.C = P->ptr(c, y);
-            if (y2 >= 0) a.C2 = P->ptr(c, y2);
-            return dense(P, r.s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS,
-                         next_s32 ? OUT_S32_DUAL_ELU : (y2 >= 0 ? OUT_F32_AND_S32 : OUT_F32), c.stream,
-                         geom >= 0 ? mix_ptr(c, stage_word + GEOM_DOWN) : nullptr);
-        });
+        GemmBufs bd{x, -1, y, y2};
+        bd.mix_word = mixed ? stage_word + GEOM_DOWN : -1;
+        gemm_step(P, r.s32, ad, bd, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS,
+                  next_s32 ? OUT_S32_DUAL_ELU : (y2 >= 0 ? OUT_F32_AND_S32 : OUT_F32));
         if (next_s32) x_elu = y2;
         if (last) x_s32 = y2;
         x = y; Tc = ad.T_out; idx += 3;
     }
     const int L = (int)Tc;
     if (L != P->L) { set_error("internal: frame count mismatch"); return WT_ERR_INVALID; }
+    P->n_codes = (long)B * L; P->n_out = P->n_aux = (long)B * 512 * L;
     const int H = M->H;
     x = plan_lstm(P, M->enc_lstm, B, L, H, x, "enc." + std::to_string(idx), fuse_elu, x_s32, tail_s32);
     GemmArgs af = sconv_args(M->enc_final, B, L, 1, 1);
     const int emb = P->buf("enc." + std::to_string(idx + 2), (size_t)B * L * 512);
     const int emb_s32 = tail_s32 ? P->buf("enc." + std::to_string(idx + 2) + ".s32", (size_t)B * L * 512, BUF_S32) : -1;
-    {
-        const int xin = x;
-        P->step({geom, xin, emb, emb_s32}, [=](const RunCtx& c) {
-            GemmArgs a = af; a.A = P->ptr(c, xin); a.C = P->ptr(c, emb);
-            if (emb_s32 >= 0) a.C2 = P->ptr(c, emb_s32);
-            return dense(P, tail_s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, OUT_F32_AND_S32, c.stream,
-                         geom >= 0 ? mix_ptr(c, geom_final(n_st)) : nullptr);
-        });
-    }
+    GemmBufs bf{x, -1, emb, emb_s32};
+    bf.mix_word = mixed ? geom_final(n_st) : -1;
+    gemm_step(P, tail_s32, af, bf, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, OUT_F32_AND_S32);
     // ---- VQ (core_vq.py:175-183, 206-231)
     const int bins = M->arch.vq_bins;
     GemmArgs av = linear_args(M->embed, nullptr, (long)B * L, bins, 512);
@@ -401,19 +420,15 @@ static void plan_head(wt_plan* P, int xo, bool s32) {
     const int Kb = M->Kb, hop = ar.hop_length;
     const int spec = P->buf("head.spec", (size_t)Mrows * 2 * Kb, s32 ? BUF_S32 : BUF_F32);
     GemmArgs ah = linear_args(M->head_W, M->head_b, Mrows, 2 * Kb, D);
-    P->step({xo, spec}, [=](const RunCtx& c) {
-        GemmArgs a = ah; a.A = P->ptr(c, xo); a.C = P->ptr(c, spec); a.c_rstride = 2 * Kb; a.head_kb = Kb;
-        return dense(P, s32, a, PRO_NONE, EPI_HEAD, OUT_S32, c.stream);        // spectrum pre-split for the ISTFT GEMM
-    }, 1, "head.out");
+    ah.c_rstride = 2 * Kb; ah.head_kb = Kb;
+    gemm_step(P, s32, ah, {xo, -1, spec}, PRO_NONE, EPI_HEAD, OUT_S32, "head.out");        // spectrum pre-split for the ISTFT GEMM
     const int Kq = M->Kq;
     const int parts = P->buf("head.parts", (size_t)4 * Mrows * Kq);       // Ce, Co, Se, So: [4][M][Kq]
-    P->step({spec, parts}, [=](const RunCtx& c) {
-        GemmArgs a = linear_args(M->istft_W, nullptr, Mrows, Kq, Kq);
-        a.A = P->ptr(c, spec); a.a_rstride = 2 * Kb; a.zA = Kq;              // z picks the spectrum quarter
-        a.zW = (long)Kq * Kq; a.nz = 4;
-        a.C = P->ptr(c, parts); a.c_rstride = Kq; a.zC = (long)Mrows * Kq;
-        return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
-    }, 1, "head.istft");
+    GemmArgs ai = linear_args(M->istft_W, nullptr, Mrows, Kq, Kq);
+    ai.a_rstride = 2 * Kb; ai.zA = Kq;              // z picks the spectrum quarter
+    ai.zW = (long)Kq * Kq; ai.nz = 4;
+    ai.c_rstride = Kq; ai.zC = (long)Mrows * Kq;
+    gemm_step(P, s32, ai, {spec, -1, parts}, PRO_NONE, EPI_BIAS, OUT_F32, "head.istft");
     P->step({parts}, [=](const RunCtx& c) {
         return launch_istft_ola(P->ptr(c, parts), M->win, M->wsq, c.out_f, B, L, ar.n_fft, hop, Kq, ar.padding_same ? 0 : 1, c.stream);
     }, 1, "head.ola");
@@ -425,6 +440,7 @@ int build_decode(wt_plan* P) {
     const int B = P->B, L = (int)P->L, D = ar.dim, I = ar.intermediate_dim, Cin = ar.input_channels;
     const long Mrows = (long)B * L;
     const int Lp = ((L + 31) / 32) * 32;
+    P->n_out = B * wave_samples(M, L); P->n_aux = Mrows * D;
     // S32 mode: every operand of the dense chain is written pre-split by its producer (transpose, norm kernels,
     // GELU / head epilogues) and multiplied by gemm16s.hip; the residual stream and the norm inputs stay fp32
     const bool s32_plan = plan_s32(P) && (Cin % 32 == 0) && (D % 32 == 0) && (I % 32 == 0);
@@ -435,21 +451,12 @@ int build_decode(wt_plan* P) {
     const int x0 = P->buf("bb.in", (size_t)Mrows * Cin, s32_e ? BUF_S32 : BUF_F32);
     P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, Cin, L, c.stream, s32_e); });
     const int x = P->buf("bb.x", (size_t)Mrows * D);       // residual stream, updated in place
-    GemmArgs ae = zconv_args(M->bb_embed, B, L);
-    P->step({x0, x}, [=](const RunCtx& c) {
-        GemmArgs a = ae; a.A = P->ptr(c, x0); a.C = P->ptr(c, x);
-        return dense(P, s32_e, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
-    });
+    gemm_step(P, s32_e, zconv_args(M->bb_embed, B, L), {x0, -1, x}, PRO_NONE, EPI_BIAS, OUT_F32);
     const bool keep = P->flags & WT_PLAN_FLAG_KEEP_STAGES;
-    auto snapshot = [&](const std::string& name) {   // debug taps of the in-place residual stream
-        if (!keep) return;
-        const int s = P->buf(name, (size_t)Mrows * D);
-        P->step({x, s}, [=](const RunCtx& c) {
-            WT_HIP_CHECK(hipMemcpyAsync(P->ptr(c, s), P->ptr(c, x), (size_t)Mrows * D * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-            return 0;
-        });
+    auto snapshot = [&](int src, const std::string& name) {   // WT_PLAN_FLAG_KEEP_STAGES: debug taps of the in-place residual streams
+        if (keep) copy_step(P, src, P->buf(name, (size_t)Mrows * D), (size_t)Mrows * D);
     };
-    snapshot("bb.embed");
+    snapshot(x, "bb.embed");
     const int sc = P->buf("bb.gn_scale", (size_t)B * D), sh = P->buf("bb.gn_shift", (size_t)B * D);
     const int gp = P->buf("bb.gn_part", gn_part_floats(B, L, 32));       // chunk statistics (long clips)
     const int h1 = P->buf("bb.h1", (size_t)Mrows * D, s32_plan ? BUF_S32 : BUF_F32);
@@ -465,20 +472,14 @@ int build_decode(wt_plan* P) {
         P->step({x, sc, sh, h1, gp}, [=](const RunCtx& c) {
             return launch_gn_apply(P->ptr(c, x), r.n1w, r.n1b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
         }, 1, "res.gn1");
-        GemmArgs a1 = zconv_args(r.c1, B, L);
-        P->step({h1, h2}, [=](const RunCtx& c) {
-            GemmArgs a = a1; a.A = P->ptr(c, h1); a.C = P->ptr(c, h2);
-            return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_F32, c.stream);
-        }, 1, "res.conv1");
+        gemm_step(P, s32, zconv_args(r.c1, B, L), {h1, -1, h2}, PRO_NONE, EPI_BIAS, OUT_F32, "res.conv1");
         P->step({h2, sc, sh, h1, gp}, [=](const RunCtx& c) {
             return launch_gn_apply(P->ptr(c, h2), r.n2w, r.n2b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
         }, 1, "res.gn2");
         GemmArgs a2 = zconv_args(r.c2, B, L);
-        P->step({h1, x}, [=](const RunCtx& c) {
-            GemmArgs a = a2; a.A = P->ptr(c, h1); a.C = P->ptr(c, x); a.R = P->ptr(c, x); a.r_rstride = D;
-            return dense(P, s32, a, PRO_NONE, EPI_BIAS_RES, OUT_F32, c.stream);
-        }, 1, "res.conv2");
-        snapshot(name);
+        a2.r_rstride = D;
+        gemm_step(P, s32, a2, in_place(h1, x), PRO_NONE, EPI_BIAS_RES, OUT_F32, "res.conv2");
+        snapshot(x, name);
     };
     resnet(M->res[0], "bb.pos_net.0", SITE_RES0);
     resnet(M->res[1], "bb.pos_net.1", SITE_RES1);
@@ -497,11 +498,7 @@ int build_decode(wt_plan* P) {
         P->step({x, sc, sh, gp, h1}, [=](const RunCtx& c) {
             return launch_gn_apply(P->ptr(c, x), M->at_nw, M->at_nb, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 0, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
         }, 1, "attn.gn");
-        GemmArgs aqk = linear_args(M->at_Wqk, M->at_bqk, Mrows, 2 * D, D);
-        P->step({h1, qk}, [=](const RunCtx& c) {
-            GemmArgs a = aqk; a.A = P->ptr(c, h1); a.C = P->ptr(c, qk);
-            return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_S32, c.stream);
-        }, 1, "attn.qk");
+        gemm_step(P, s32, linear_args(M->at_Wqk, M->at_bqk, Mrows, 2 * D, D), {h1, -1, qk}, PRO_NONE, EPI_BIAS, OUT_S32, "attn.qk");
         P->step({h1, vt}, [=](const RunCtx& c) {     // V^T[b] = Wv . hn[b]^T + bv   (D x L, pitch Lp; pad columns stay zero)
             if (int rc = launch_fill_u32(P->ptr(c, vt), 0u, (size_t)B * D * Lp * sizeof(float), c.stream)) return rc;
             GemmArgs a = linear_args(nullptr, M->at_bv, D, L, D);
@@ -527,11 +524,9 @@ int build_decode(wt_plan* P) {
             return dense_act(P, s32, a, P->ptr(c, vt), EPI_BIAS, OUT_S32, c.stream);
         }, 1, "attn.o");
         GemmArgs ap = linear_args(M->at_Wp, M->at_bp, Mrows, D, D);
-        P->step({o, x}, [=](const RunCtx& c) {
-            GemmArgs a = ap; a.A = P->ptr(c, o); a.C = P->ptr(c, x); a.R = P->ptr(c, x); a.r_rstride = D;
-            return dense(P, s32, a, PRO_NONE, EPI_BIAS_RES, OUT_F32, c.stream);
-        }, 1, "attn.proj");
-        snapshot("bb.pos_net.2");
+        ap.r_rstride = D;
+        gemm_step(P, s32, ap, in_place(o, x), PRO_NONE, EPI_BIAS_RES, OUT_F32, "attn.proj");
+        snapshot(x, "bb.pos_net.2");
     }
     resnet(M->res[2], "bb.pos_net.3", SITE_RES2);
     resnet(M->res[3], "bb.pos_net.4", SITE_RES3);
@@ -545,13 +540,7 @@ int build_decode(wt_plan* P) {
         return launch_rownorm(RN_AFFINE_IN, P->ptr(c, x), P->ptr(c, xc), B, L, D, nullptr, nullptr, P->ptr(c, sc),
                               P->ptr(c, sh), M->ada_s + (size_t)c.bw_id * D, M->ada_h + (size_t)c.bw_id * D, 1e-6f, c.stream);
     });
-    if (keep) {
-        const int sn = P->buf("bb.norm", (size_t)Mrows * D);
-        P->step({xc, sn}, [=](const RunCtx& c) {
-            WT_HIP_CHECK(hipMemcpyAsync(P->ptr(c, sn), P->ptr(c, xc), (size_t)Mrows * D * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-            return 0;
-        });
-    }
+    snapshot(xc, "bb.norm");
     // ConvNeXt blocks (modules.py:43-60); xc is the residual stream from here on
     const int nrm = P->buf("bb.cnx.norm", (size_t)Mrows * D, s32_plan ? BUF_S32 : BUF_F32);
     const int mid = P->buf("bb.cnx.mid", (size_t)Mrows * I, s32_plan ? BUF_S32 : BUF_F32);
@@ -564,23 +553,12 @@ int build_decode(wt_plan* P) {
             return launch_rownorm(RN_DWCONV, P->ptr(c, xc), P->ptr(c, nrm), B, L, D, cb.dw_w, cb.dw_b, nullptr, nullptr,
                                   cb.ada_s + (size_t)c.bw_id * D, cb.ada_h + (size_t)c.bw_id * D, 1e-6f, c.stream, s32);
         });
-        GemmArgs a1 = linear_args(cb.W1, cb.b1, Mrows, I, D);
-        P->step({nrm, mid}, [=](const RunCtx& c) {
-            GemmArgs a = a1; a.A = P->ptr(c, nrm); a.C = P->ptr(c, mid);
-            return dense(P, s32, a, PRO_NONE, EPI_BIAS_GELU, OUT_S32, c.stream);     // GELU output pre-split for pwconv2
-        }, 1, "cnx.pwconv1");
+        // GELU output pre-split for pwconv2
+        gemm_step(P, s32, linear_args(cb.W1, cb.b1, Mrows, I, D), {nrm, -1, mid}, PRO_NONE, EPI_BIAS_GELU, OUT_S32, "cnx.pwconv1");
         GemmArgs a2 = linear_args(cb.W2, cb.b2, Mrows, D, I);
-        P->step({mid, xc}, [=](const RunCtx& c) {
-            GemmArgs a = a2; a.A = P->ptr(c, mid); a.C = P->ptr(c, xc); a.R = P->ptr(c, xc); a.r_rstride = D; a.gamma = cb.gamma;
-            return dense(P, s32, a, PRO_NONE, EPI_BIAS_GAMMA_RES, OUT_F32, c.stream);
-        }, 1, "cnx.pwconv2");
-        if (keep && (i == 0 || i == ar.num_layers / 2 - 1 || i == ar.num_layers - 1)) {
-            const int s = P->buf("bb.convnext." + std::to_string(i), (size_t)Mrows * D);
-            P->step({xc, s}, [=](const RunCtx& c) {
-                WT_HIP_CHECK(hipMemcpyAsync(P->ptr(c, s), P->ptr(c, xc), (size_t)Mrows * D * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-                return 0;
-            });
-        }
+        a2.r_rstride = D; a2.gamma = cb.gamma;
+        gemm_step(P, s32, a2, in_place(mid, xc), PRO_NONE, EPI_BIAS_GAMMA_RES, OUT_F32, "cnx.pwconv2");
+        if (i == 0 || i == ar.num_layers / 2 - 1 || i == ar.num_layers - 1) snapshot(xc, "bb.convnext." + std::to_string(i));
     }
     P->cur_site = SITE_HEAD;
     const bool s32 = s32_at(SITE_HEAD);
@@ -591,8 +569,7 @@ int build_decode(wt_plan* P) {
         if (c.aux && s32)      // the caller wants the backbone output: a second, fp32 pass straight into its buffer
             return launch_rownorm(RN_PLAIN, P->ptr(c, xc), c.aux, B, L, D, nullptr, nullptr, nullptr, nullptr, M->fln_w,
                                   M->fln_b, 1e-6f, c.stream, 0);
-        if (c.aux) WT_HIP_CHECK(hipMemcpyAsync(c.aux, P->ptr(c, xo), (size_t)Mrows * D * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-        return 0;
+        return c.aux ? copy_f32(c.aux, P->ptr(c, xo), (size_t)Mrows * D, c.stream) : 0;
     });
     plan_head(P, xo, s32);
     return 0;
@@ -603,14 +580,11 @@ int build_head(wt_plan* P) {
     const wt_model* M = P->model;
     const int B = P->B, L = (int)P->L, D = M->arch.dim;
     const long Mrows = (long)B * L;
-    P->cur_site = SITE_HEAD;
     const bool s32 = plan_s32(P) && (D % 32 == 0) && M->head_W.s32.p && M->istft_W.s32.p;
     const int xo = P->buf("head.in", (size_t)Mrows * D, s32 ? BUF_S32 : BUF_F32);
-    P->step({xo}, [=](const RunCtx& c) {
-        if (s32) return launch_split_s32(c.in_f, P->ptr(c, xo), Mrows * D, c.stream);
-        WT_HIP_CHECK(hipMemcpyAsync(P->ptr(c, xo), c.in_f, (size_t)Mrows * D * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-        return 0;
-    });
+    if (s32) P->step({xo}, [=](const RunCtx& c) { return launch_split_s32(c.in_f, P->ptr(c, xo), Mrows * D, c.stream); });
+    else copy_step(P, CALLER, xo, (size_t)Mrows * D);
+    P->n_out = P->B * wave_samples(M, L);
     plan_head(P, xo, s32);
     return 0;
 }
@@ -634,19 +608,17 @@ int build_seanet_decoder(wt_plan* P) {
     const wt_model* M = P->model;
     if (!M->has_seadec) { set_error("checkpoint holds no SEANetDecoder weights"); return WT_ERR_MISSING_TENSOR; }
     const int B = P->B, L = (int)P->L, H = M->H;
-    P->cur_site = SITE_SEADEC;
+    P->n_out = (long)B * L * M->hop;
     const bool s32 = seadec_s32_ok(P);
     const bool fuse_elu = !plan_unfused(P);      // producers store elu(.) for "ELU -> conv" consumers
     const int x0 = P->buf("sdec.in", (size_t)B * L * 512);
     P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, 512, L, c.stream, s32); });
     const int xf = P->buf("sdec.0", (size_t)B * L * H);
     const int xs = s32 ? P->buf("sdec.0.s32", (size_t)B * L * H) : -1;
-    GemmArgs a0 = sconv_args(M->sd_first, B, L, 1, 1);
-    P->step({x0, xf, xs}, [=](const RunCtx& c) {
-        GemmArgs a = a0; a.A = P->ptr(c, x0); a.C = P->ptr(c, xf);
-        if (xs >= 0) a.C2 = P->ptr(c, xs);
-        return dense(P, s32, a, PRO_NONE, EPI_BIAS, OUT_F32_AND_S32, c.stream);
-    });
+    // these and an unfused stage's transposed-conv outputs hold S32 under a BUF_F32 declaration (kept: wt_plan_buffer_info)
+    P->bufs[x0].holds_s32 = s32;
+    if (xs >= 0) P->bufs[xs].holds_s32 = true;
+    gemm_step(P, s32, sconv_args(M->sd_first, B, L, 1, 1), {x0, -1, xf, xs}, PRO_NONE, EPI_BIAS, OUT_F32_AND_S32);
     int x = plan_lstm(P, M->sd_lstm, B, L, H, xf, "sdec.1", fuse_elu, xs, s32);
     long Tc = L;
     int di = 2;
@@ -668,20 +640,17 @@ int build_seanet_decoder(wt_plan* P) {
             const int trim_l = (st.k - st.r) - (st.k - st.r) / 2;
             const size_t ynum = (size_t)B * (Tin + 1) * st.r * st.cout;
             y = P->buf(name, ynum);
-            if (unfused_s32) y2 = P->buf(name + ".elu", ynum);
+            if (unfused_s32) { y2 = P->buf(name + ".elu", ynum); P->bufs[y].holds_s32 = P->bufs[y2].holds_s32 = true; }
             y_off = (long)trim_l * st.cout;
             y_bs = (long)(Tin + 1) * st.r * st.cout;
-            P->step({xin, y, y2}, [=](const RunCtx& c) {
-                GemmArgs a;
-                a.A = P->ptr(c, xin); a.a_bstride = (long)Tin * st.cin; a.a_rstride = st.cin;
-                a.T_in = Tin; a.T_out = Tin + 1; a.Cin = st.cin; a.taps = 2; a.pad_left = 1; a.pad_mode = PAD_ZERO;
-                a.W = st.tr_wp.w; a.w_rstride = 2L * st.cin; a.zW = (long)st.cout * 2 * st.cin; a.bias = st.tr_b;
-                a.M = B * (Tin + 1); a.N = st.cout; a.K = 2 * st.cin;
-                a.C = P->ptr(c, y); a.c_rstride = (long)st.r * st.cout; a.zC = st.cout; a.nz = st.r;
-                set_s32(a, st.tr_wp.s32);
-                if (y2 >= 0) a.C2 = P->ptr(c, y2);
-                return dense(P, s32, a, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, y2 >= 0 ? OUT_S32_DUAL_ELU : OUT_F32, c.stream);
-            }, 1, "sdec.convtr");
+            GemmArgs a;
+            a.a_bstride = (long)Tin * st.cin; a.a_rstride = st.cin;
+            a.T_in = Tin; a.T_out = Tin + 1; a.Cin = st.cin; a.taps = 2; a.pad_left = 1; a.pad_mode = PAD_ZERO;
+            a.W = st.tr_wp.w; a.w_rstride = 2L * st.cin; a.zW = (long)st.cout * 2 * st.cin; a.bias = st.tr_b;
+            a.M = B * (Tin + 1); a.N = st.cout; a.K = 2 * st.cin;
+            a.c_rstride = (long)st.r * st.cout; a.zC = st.cout; a.nz = st.r;
+            set_s32(a, st.tr_wp.s32);
+            gemm_step(P, s32, a, {xin, -1, y, y2}, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, y2 >= 0 ? OUT_S32_DUAL_ELU : OUT_F32, "sdec.convtr");
         } else {
             y = P->buf(name, (size_t)B * To * st.cout);
             P->step({xin, y}, [=](const RunCtx& c) {
@@ -717,19 +686,11 @@ void plan_begin(wt_plan* P) {
 
 void plan_end(wt_plan* P) {
     const wt_model* M = P->model;
-    const int ctl = P->ctl, kind = P->kind;
-    const long B = P->B, L = P->L, hop = M->hop, D = M->arch.dim;
+    const int ctl = P->ctl;
+    const long nc = P->n_codes, n0 = P->n_out, n1 = P->n_aux;      // what the builder said a call writes
     P->step({ctl}, [=](const RunCtx& c) {
-        int64_t* codes = nullptr;
-        long nc = 0, n0 = 0, n1 = 0;
-        float* f1 = c.aux;
-        if (kind == WT_PLAN_ENCODE) { codes = c.codes; nc = B * L; n0 = B * 512 * L; n1 = n0; }
-        else if (kind == WT_PLAN_DECODE) { n0 = B * wave_samples(M, L); n1 = B * L * D; }
-        else if (kind == WT_PLAN_UNIT_LSTM) { n0 = B * L * 512; f1 = nullptr; }
-        else if (kind == WT_PLAN_HEAD) { n0 = B * wave_samples(M, L); f1 = nullptr; }
-        else { n0 = B * L * hop; f1 = nullptr; }
-        return launch_plan_guard(reinterpret_cast<const unsigned*>(P->ptr(c, ctl)), CTL_WORDS, CTL_SITE0, P->status_dev, M->status_dev, codes,
-                                 nc, c.out_f, n0, f1, n1, nullptr, 0, c.stream);
+        return launch_plan_guard(reinterpret_cast<const unsigned*>(P->ptr(c, ctl)), CTL_WORDS, CTL_SITE0, P->status_dev, M->status_dev,
+                                 nc ? c.codes : nullptr, nc, c.out_f, n0, n1 ? c.aux : nullptr, n1, nullptr, 0, c.stream);
     }, 1, "guard");
 }
 
@@ -742,16 +703,13 @@ int build_unit_lstm(wt_plan* P) {
     const bool s32 = plan_s32(P) && M->enc_lstm.Wih0.s32.p;
     const int x = P->buf("lstm.in", (size_t)B * L * H);
     const int xs = s32 ? P->buf("lstm.in.s32", (size_t)B * L * H, BUF_S32) : -1;
+    P->n_out = (long)B * L * 512;
     P->step({x, xs}, [=](const RunCtx& c) {
-        WT_HIP_CHECK(hipMemcpyAsync(P->ptr(c, x), c.in_f, (size_t)B * L * H * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-        if (s32) return launch_split_s32(c.in_f, P->ptr(c, xs), (long)B * L * H, c.stream);
-        return 0;
+        if (int rc = copy_f32(P->ptr(c, x), c.in_f, (size_t)B * L * H, c.stream)) return rc;
+        return s32 ? launch_split_s32(c.in_f, P->ptr(c, xs), (long)B * L * H, c.stream) : 0;
     }, 2, "lstm.in");
     const int y = plan_lstm(P, M->enc_lstm, B, L, H, x, "lstm.out", false, xs, false);
-    P->step({y}, [=](const RunCtx& c) {
-        WT_HIP_CHECK(hipMemcpyAsync(c.out_f, P->ptr(c, y), (size_t)B * L * H * sizeof(float), hipMemcpyDeviceToDevice, c.stream));
-        return 0;
-    }, 1, "lstm.copy");
+    copy_step(P, y, CALLER, (size_t)B * L * H, "lstm.copy");
     return 0;
 }
 

@@ -1,0 +1,365 @@
+// Entry points that launch kernels outside a plan: wt_codes_to_features, the single-stage calls and the probes through
+// which the tests reach every GEMM form (wt_gemm_probe) and every non-GEMM kernel (wt_op_probe) on its own.
+#include "model.h"
+
+using namespace wt;
+
+extern "C" {
+
+int wt_codes_to_features(const wt_model* m, const int64_t* codes, int32_t K, int32_t B, int64_t L, float* features,
+                         void* stream) {
+    if (!m || !codes || !features) { set_error("wt_codes_to_features: null argument"); return WT_ERR_INVALID; }
+    if (K < 1 || K > m->arch.num_quantizers) { set_error("wt_codes_to_features: K exceeds the number of codebooks"); return WT_ERR_INVALID; }
+    DeviceGuard dg(m->device);
+    if (!dg.ok) { set_error("hipSetDevice failed"); return WT_ERR_HIP; }
+    return launch_codes_to_features(codes, m->embed.w, K, m->arch.vq_bins, B, L, 512, features, static_cast<hipStream_t>(stream),
+                                    m->bad_codes_dev);
+}
+
+int wt_sconv1d(const float* x, const float* w, const float* bias, float* y, int32_t B, int64_t T, int32_t Cin,
+               int32_t Cout, int32_t k, int32_t stride, int32_t dilation, int32_t elu_input, void* stream) {
+    ConvW cw; cw.w = const_cast<float*>(w); cw.b = const_cast<float*>(bias); cw.cout = Cout; cw.cin = Cin; cw.k = k;
+    GemmArgs a = sconv_args(cw, B, T, stride, dilation);
+    a.A = x; a.C = y;
+    return launch_gemm(a, elu_input ? PRO_ELU : PRO_NONE, EPI_BIAS, static_cast<hipStream_t>(stream));
+}
+
+// Both operands of a single-stage S32 call are split here (the plans' producers write S32 directly), each with a
+// per-tensor power-of-two scale chosen on the device; `tail` = 256 spare bytes after the two S32 arrays
+static int split_pair(const float* w, long nw, const float* x, long nx, char* ws_w, char* ws_x, char* tail, GemmArgs& a,
+                      hipStream_t s) {
+    unsigned* bits = reinterpret_cast<unsigned*>(tail);
+    float* sc = reinterpret_cast<float*>(tail + 16);              // {scale_w, scale_x, 1 / (scale_w * scale_x)}
+    if (int rc = launch_pow2_scales(w, nw, x, nx, bits, sc, s)) return rc;
+    if (int rc = launch_split_s32(w, ws_w, nw, s, sc)) return rc;
+    if (int rc = launch_split_s32(x, ws_x, nx, s, sc + 1)) return rc;
+    a.W_hi = ws_w;
+    a.A = reinterpret_cast<const float*>(ws_x);
+    a.acc_scale_dev = sc + 2;
+    return 0;
+}
+
+int wt_linear(const float* x, const float* w, const float* bias, float* y, int64_t M, int32_t N, int32_t K,
+              int32_t f16x3, void* workspace, void* stream) {
+    if (!x || !w || !y) { set_error("wt_linear: null argument"); return WT_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GemmArgs a = linear_args(w, bias, M, N, K);
+    a.A = x; a.C = y;
+    if (!f16x3) return launch_gemm(a, PRO_NONE, EPI_BIAS, s);
+    if (!workspace) { set_error("wt_linear: the f16x3 modes need a workspace"); return WT_ERR_INVALID; }
+    char* hi = static_cast<char*>(workspace);
+    if (f16x3 == 1) { set_error("wt_linear: mode 1 (the in-loop split kernel of round 1) was removed; use 2, 3 or 4"); return WT_ERR_INVALID; }
+    char* xs = hi + (size_t)N * K * 4;
+    if (int rc = split_pair(w, (long)N * K, x, (long)M * K, hi, xs, xs + (size_t)M * K * 4, a, s)) return rc;
+    // timing-experiment builds (WT_GEMM16S_DBG: tools/gemm16s_bench.py) leave their clock stamps behind the scales
+    a.dbg_stamps = reinterpret_cast<unsigned long long*>(xs + (size_t)M * K * 4 + 256);
+    if (f16x3 == 4) return launch_gemm16s(a, EPI_BIAS_GELU, OUT_S32, s);      // ConvNeXt pwconv1: exact-erf GELU epilogue, S32 out
+    return launch_gemm16s(a, EPI_BIAS, f16x3 == 3 ? 1 : 0, s);
+}
+
+int wt_conv1d_s32(const float* x, const float* w, const float* bias, float* y, int32_t B, int64_t T, int32_t Cin,
+                  int32_t Cout, int32_t k, int32_t stride, int32_t zero_same, void* workspace, void* stream) {
+    if (!x || !w || !y || !workspace) { set_error("wt_conv1d_s32: null argument"); return WT_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    ConvW cw; cw.w = const_cast<float*>(w); cw.b = const_cast<float*>(bias); cw.cout = Cout; cw.cin = Cin; cw.k = k;
+    GemmArgs a = zero_same ? zconv_args(cw, B, (int)T) : sconv_args(cw, B, T, stride, 1);
+    char* ws = static_cast<char*>(workspace);
+    char* xs = ws + (size_t)Cout * k * Cin * 4;
+    if (int rc = split_pair(w, (long)Cout * k * Cin, x, (long)B * T * Cin, ws, xs, xs + (size_t)B * T * Cin * 4, a, s)) return rc;
+    a.C = y;
+    return launch_gemm16s(a, EPI_BIAS, 0, s);
+}
+
+static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+// wt_gemm_probe: the S32 copies of A, A2 and B in the workspace (same element offsets as the fp32 arrays), then the scale
+struct ProbeLayout { long nA = 0, nA2 = 0, nB = 0; size_t oA2 = 0, oB = 0, oScale = 0, total = 0; };
+static ProbeLayout probe_layout(const wt_gemm_desc& d) {
+    ProbeLayout L;
+    const long clips = d.M / d.T_out;
+    const long a_cols = d.A2 ? d.K1 : d.Cin;
+    L.nA = (d.nz - 1) * d.zA + (clips - 1) * d.a_bstride + (long)(d.T_in - 1) * d.a_rstride + a_cols;
+    if (d.A2) L.nA2 = (clips - 1) * d.a2_bstride + (long)(d.T_in - 1) * d.a2_rstride + (d.K - d.K1);
+    L.nB = (d.nz - 1) * d.zW + (long)(d.N - 1) * d.w_rstride + d.K;
+    L.oA2 = al256((size_t)L.nA * 4);
+    L.oB = L.oA2 + al256((size_t)L.nA2 * 4);
+    L.oScale = L.oB + al256((size_t)L.nB * 4);
+    L.total = L.oScale + 256;
+    return L;
+}
+// the descriptor as the launchers' arguments; every check that needs no HIP call (the launchers' own included)
+static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
+    if (!d || d->size != (int32_t)sizeof(wt_gemm_desc)) { set_error("wt_gemm_probe: descriptor missing or of another size"); return WT_ERR_INVALID; }
+    if (d->engine != 0 && d->engine != 1) { set_error("wt_gemm_probe: engine is 0 (gemm16s) or 1 (gemm)"); return WT_ERR_INVALID; }
+    if (!d->A || !d->B || !d->C) { set_error("wt_gemm_probe: A, B and C are required"); return WT_ERR_INVALID; }
+    if (d->epi == EPI_ARGMAX) { set_error("wt_gemm_probe: the argmax epilogue is reached through wt_vq_nearest"); return WT_ERR_INVALID; }
+    if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->T_out <= 0 || d->T_in <= 0 || d->M % d->T_out || d->nz < 1 || d->taps < 1 ||
+        d->stride < 1 || d->dil < 1 || d->pad_left < 0 || (d->pad_mode != PAD_ZERO && d->pad_mode != PAD_REFLECT) ||
+        d->a_bstride < 0 || d->a_rstride < 0 || d->a2_bstride < 0 || d->a2_rstride < 0 || d->w_rstride < d->K ||
+        d->c_rstride < d->N || d->r_rstride < 0 || d->zA < 0 || d->zW < 0 || d->zC < 0 || (d->nz > 1 && d->zC <= 0)) {
+        set_error("wt_gemm_probe: bad extents or strides"); return WT_ERR_INVALID;
+    }
+    if (d->engine == 1 && (d->out != OUT_F32 || d->A2 || d->tap_pair)) {
+        set_error("wt_gemm_probe: gemm.hip writes fp32 and has no second K source or tap pairing"); return WT_ERR_INVALID;
+    }
+    if (d->engine == 0 && d->pro != PRO_NONE) { set_error("wt_gemm_probe: gemm16s has no operand prologue"); return WT_ERR_INVALID; }
+    if (d->tap_pair && (d->taps != 2 * d->stride || d->dil != 1)) { set_error("wt_gemm_probe: tap pairing needs k = 2 * stride, dilation 1"); return WT_ERR_INVALID; }
+    if (d->engine == 0 && (!ws || (reinterpret_cast<uintptr_t>(ws) & 255))) { set_error("wt_gemm_probe: gemm16s needs a 256-byte aligned workspace"); return WT_ERR_INVALID; }
+    a = GemmArgs{};
+    a.a_bstride = d->a_bstride; a.a_rstride = d->a_rstride; a.T_in = d->T_in; a.T_out = d->T_out; a.Cin = d->Cin; a.taps = d->taps;
+    a.stride = d->stride; a.dil = d->dil; a.pad_left = d->pad_left; a.pad_mode = d->pad_mode; a.Tp = d->Tp;
+    a.a2_bstride = d->a2_bstride; a.a2_rstride = d->a2_rstride; a.K1 = d->K1;
+    a.w_rstride = d->w_rstride; a.bias = d->bias; a.M = d->M; a.N = d->N; a.K = d->K;
+    a.C = d->C; a.c_rstride = d->c_rstride; a.C2 = d->C2; a.R = d->R; a.r_rstride = d->r_rstride; a.gamma = d->gamma;
+    a.alpha = d->alpha; a.nz = d->nz; a.zA = d->zA; a.zW = d->zW; a.zC = d->zC; a.head_kb = d->head_kb; a.tap_pair = d->tap_pair ? 1 : 0;
+    if (d->engine == 1) {
+        a.A = d->A; a.W = d->B;
+        return check_gemm(a, d->pro, d->epi) ? WT_ERR_INVALID : WT_OK;
+    }
+    const ProbeLayout L = probe_layout(*d);
+    a.A = reinterpret_cast<const float*>(ws);
+    a.A2 = d->A2 ? reinterpret_cast<const float*>(ws + L.oA2) : nullptr;
+    a.W = d->B; a.W_hi = ws + L.oB;
+    a.status = reinterpret_cast<unsigned*>(d->status);
+    return check_gemm16s(a, d->epi, d->out) ? WT_ERR_INVALID : WT_OK;
+}
+
+size_t wt_gemm_probe_workspace_bytes(const wt_gemm_desc* d) {
+    if (!d || d->size != (int32_t)sizeof(wt_gemm_desc) || d->engine != 0 || d->M <= 0 || d->T_out <= 0 || d->nz < 1) return 0;
+    return probe_layout(*d).total;
+}
+
+int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, void* stream) {
+    char* ws = static_cast<char*>(workspace);
+    GemmArgs a;
+    if (int rc = probe_args(d, ws, a)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LaunchForm lf;
+    a.form = &lf;
+    if (d->engine == 1) {
+        if (int rc = launch_gemm(a, d->pro, d->epi, s)) return rc;
+    } else {
+        const ProbeLayout L = probe_layout(*d);
+        float* scale_dev = reinterpret_cast<float*>(ws + L.oScale);
+        float scale = 1.f;
+        if (!d->b_is_act) {      // a weight: the plans' per-tensor power of two (weights.cpp add_s32), chosen over its logical rows
+            std::vector<float> h((size_t)L.nB);
+            WT_HIP_CHECK(hipMemcpyAsync(h.data(), d->B, (size_t)L.nB * 4, hipMemcpyDeviceToHost, s));
+            WT_HIP_CHECK(hipStreamSynchronize(s));
+            float amax = 0.f;
+            for (long z = 0; z < d->nz; ++z)
+                for (long n = 0; n < d->N; ++n)
+                    for (long k = 0; k < d->K; ++k) {
+                        const float v = std::fabs(h[(size_t)(z * d->zW + n * d->w_rstride + k)]);
+                        if (!(v <= 3.0e38f)) { set_error("wt_gemm_probe: a non-finite weight has no S32 copy"); return WT_ERR_INVALID; }
+                        amax = std::max(amax, v);
+                    }
+            scale = s32_weight_scale(amax);
+            uint32_t bits;
+            memcpy(&bits, &scale, 4);
+            if (int rc = launch_fill_u32(scale_dev, bits, 16, s)) return rc;
+            a.acc_scale = 1.f / scale;
+        }
+        if (int rc = launch_split_s32(d->B, ws + L.oB, L.nB, s, scale != 1.f ? scale_dev : nullptr)) return rc;
+        if (int rc = launch_split_s32(d->A, ws, L.nA, s)) return rc;
+        if (d->A2) if (int rc = launch_split_s32(d->A2, ws + L.oA2, L.nA2, s)) return rc;
+        if (int rc = launch_gemm16s(a, d->epi, d->out, s)) return rc;
+    }
+    if (form) *form = wt_launch_form{lf.BM, lf.BN, lf.waves_m, lf.waves_n, lf.stages, lf.ks, lf.prod, lf.staged, lf.bias_cache, lf.G, lf.tiles};
+    return WT_OK;
+}
+
+// wt_op_probe: every check that needs no HIP call and that the launchers do not make themselves (they trust the plans)
+static int op_probe_check(const wt_op_desc* d) {
+    auto bad = [](const char* m) { set_error(std::string("wt_op_probe: ") + m); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_op_desc)) return bad("descriptor missing or of another size");
+    if (d->op < WT_OP_GN_APPLY || d->op > WT_OP_S32_AMAX) return bad("unknown op");
+    auto al16 = [](const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); };
+    const void* ptrs[] = {d->p0, d->p1, d->p2, d->p3, d->p4, d->p5, d->y, d->y2, d->y3};
+    for (const void* p : ptrs) if (!al16(p)) return bad("arrays must be 16-byte aligned");
+    if (!d->x || (reinterpret_cast<uintptr_t>(d->x) & (d->op == WT_OP_SOFTMAX ? 3 : 15))) return bad("x missing or misaligned");
+    if (reinterpret_cast<uintptr_t>(d->status) & 3) return bad("status misaligned");
+    const bool shaped = d->op != WT_OP_SOFTMAX && d->op != WT_OP_ROW_SUMSQ && d->op != WT_OP_S32_AMAX;
+    if (shaped && (d->B <= 0 || d->L <= 0)) return bad("extents must be positive");
+    if (shaped && d->op != WT_OP_CONV_FIRST && d->op != WT_OP_ISTFT_OLA && (d->C <= 0 || (long)d->L * d->C >= (long)INT_MAX)) return bad("extents must be positive (and L * C < 2^31)");
+    switch (d->op) {
+    case WT_OP_GN_APPLY: case WT_OP_GN_STATS:
+        if (!d->p0 || !d->p1 || !d->y2 || !d->y3 || (d->op == WT_OP_GN_APPLY && !d->y)) return bad("null argument");
+        if (d->groups <= 0 || d->C % d->groups || d->C / d->groups > 256 || d->B > 65535) return bad("GroupNorm needs C % groups == 0, at most 256 channels per group, B <= 65535");
+        break;
+    case WT_OP_ROWNORM:
+        if (!d->y || !d->p4 || !d->p5) return bad("null argument");
+        if (d->mode < RN_DWCONV || d->mode > RN_AFFINE_IN) return bad("rownorm mode is 0, 1 or 2");
+        if (d->mode == RN_DWCONV && (!d->p0 || !d->p1)) return bad("null argument");
+        if (d->mode == RN_AFFINE_IN && (!d->p2 || !d->p3)) return bad("null argument");
+        break;
+    case WT_OP_SOFTMAX:
+        if (d->n <= 0 || d->n > INT_MAX || d->L <= 0 || d->ld < d->L) return bad("softmax needs rows > 0 and 0 < L <= ld");
+        break;
+    case WT_OP_ISTFT_OLA:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->n_fft <= 0 || d->hop <= 0 || d->n_fft % 4 || d->n_fft % d->hop || (d->n_fft - d->hop) % 2 || d->Kq < d->n_fft / 4 + 1)
+            return bad("the ISTFT tail needs n_fft % 4 == 0, n_fft % hop == 0 and Kq > n_fft / 4");
+        break;
+    case WT_OP_CONV_FIRST:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->k <= 0 || d->Cout <= 0 || d->Cout % 4) return bad("conv_first needs k > 0 and Cout % 4 == 0");
+        break;
+    case WT_OP_CONV_LAST:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->k <= 0) return bad("conv_last needs k > 0");
+        break;
+    case WT_OP_TRANSPOSE:
+        if (!d->y) return bad("null argument");
+        if (d->B > 65535 || (d->L + 31) / 32 > 65535) return bad("transpose: too many tiles for one launch");
+        break;
+    case WT_OP_CONVTR:
+        if (!d->p0 || !d->p1 || !d->y) return bad("null argument");
+        if (d->stride <= 0 || d->k < d->stride || d->Cout <= 0 || d->Cout % 4) return bad("convtr needs k >= stride > 0 and Cout % 4 == 0");
+        break;
+    case WT_OP_ROW_SUMSQ:
+        if (!d->y) return bad("null argument");
+        if (d->n <= 0 || d->C <= 0 || d->C % 4) return bad("row_sumsq needs rows > 0 and C % 4 == 0");
+        break;
+    case WT_OP_S32_AMAX:
+        if (!d->y) return bad("null argument");
+        if (d->n <= 0 || d->n % 32) return bad("s32_amax needs whole S32 groups of 32 values");
+        break;
+    }
+    return WT_OK;
+}
+
+int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream) {
+    if (int rc = op_probe_check(d)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto F = [](const void* p) { return static_cast<const float*>(p); };
+    auto W = [](void* p) { return static_cast<float*>(p); };
+    OpForm lf;
+    const LaunchCtx saved = g_launch;
+    g_launch.status = reinterpret_cast<unsigned*>(d->status);
+    g_launch.form = &lf;
+    int rc = 0;
+    switch (d->op) {
+    case WT_OP_GN_APPLY:
+        rc = launch_gn_apply(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), W(d->y), d->flag ? 1 : 0, d->B, d->L, d->C, d->groups, d->eps, s,
+                             d->out_s32 ? 1 : 0, const_cast<float*>(F(d->p2)));
+        break;
+    case WT_OP_GN_STATS:
+        rc = launch_gn_stats(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), d->B, d->L, d->C, d->groups, d->eps, s, const_cast<float*>(F(d->p2)));
+        break;
+    case WT_OP_ROWNORM:
+        rc = launch_rownorm(d->mode, F(d->x), W(d->y), d->B, d->L, d->C, F(d->p0), F(d->p1), F(d->p2), F(d->p3), F(d->p4), F(d->p5), d->eps, s,
+                            d->out_s32 ? 1 : 0);
+        break;
+    case WT_OP_SOFTMAX:
+        rc = launch_softmax(const_cast<float*>(F(d->x)), (int)d->n, d->L, d->ld, s, W(d->y));
+        break;
+    case WT_OP_ISTFT_OLA:
+        rc = launch_istft_ola(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->n_fft, d->hop, d->Kq, d->flag ? 1 : 0, s);
+        break;
+    case WT_OP_CONV_FIRST:
+        rc = launch_conv_first(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->k, d->Cout, s);
+        break;
+    case WT_OP_CONV_LAST:
+        rc = launch_conv_last(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->C, d->k, d->flag ? 1 : 0, s);
+        break;
+    case WT_OP_TRANSPOSE:
+        rc = launch_transpose(F(d->x), W(d->y), d->B, d->L, d->C, s, d->out_s32 ? 1 : 0);
+        break;
+    case WT_OP_CONVTR:
+        rc = launch_convtr(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->C, d->Cout, d->k, d->stride, d->flag ? 1 : 0, s);
+        break;
+    case WT_OP_ROW_SUMSQ:
+        rc = launch_row_sumsq(F(d->x), W(d->y), d->n, d->C, s);
+        break;
+    case WT_OP_S32_AMAX:
+        rc = launch_s32_amax(d->x, d->n, static_cast<unsigned*>(d->y), s);
+        break;
+    }
+    g_launch = saved;
+    if (rc) return rc;
+    if (form) *form = wt_op_form{lf.kernel, lf.variant, lf.variant2, (int32_t)lf.grid[0], (int32_t)lf.grid[1], (int32_t)lf.grid[2], (int32_t)lf.block, (int32_t)lf.lds};
+    return WT_OK;
+}
+
+size_t wt_vq_workspace_bytes(int64_t N, int32_t D, int32_t bins) {
+    const size_t np = std::max(gemm_vq_parts(bins), gemm16s_vq_parts(bins));
+    return al256((size_t)N * D * 4) + al256((size_t)bins * D * 4) + al256((size_t)N * sizeof(float)) +
+           2 * al256((size_t)N * np * sizeof(float)) + al256((size_t)bins * sizeof(float)) + 512;
+}
+
+// the ee[] table here is rebuilt per call on the device by row_sumsq (same kernel as |x|^2)
+static int vq_nearest(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
+                      void* workspace, void* stream, bool s32) {
+    if (!x || !embed || !codes_out || !workspace) { set_error("wt_vq_nearest: null argument"); return WT_ERR_INVALID; }
+    if (s32 && (D % 32)) { set_error("wt_vq_nearest: the split-f16 kernel needs D % 32 == 0"); return WT_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int np = s32 ? gemm16s_vq_parts(bins) : gemm_vq_parts(bins);
+    char* ws = static_cast<char*>(workspace);
+    char* xs = ws; ws += al256((size_t)N * D * 4);
+    char* es = ws; ws += al256((size_t)bins * D * 4);
+    float* xx = reinterpret_cast<float*>(ws); ws += al256((size_t)N * sizeof(float));
+    float* pv = reinterpret_cast<float*>(ws); ws += al256((size_t)N * np * sizeof(float));
+    int* pi = reinterpret_cast<int*>(ws); ws += al256((size_t)N * np * sizeof(float));
+    float* ee = reinterpret_cast<float*>(ws); ws += al256((size_t)bins * sizeof(float));
+    if (int rc = launch_row_sumsq(x, xx, N, D, s)) return rc;
+    if (int rc = launch_row_sumsq(embed, ee, bins, D, s)) return rc;
+    GemmArgs a = linear_args(embed, nullptr, N, bins, D);
+    a.A = x; a.vq_xx = xx; a.vq_ee = ee; a.vq_pval = pv; a.vq_pidx = pi; a.vq_nparts = np;
+    if (s32) {
+        // what the encoder plan launches: distances on gemm16s.hip, per-slab argmax in its epilogue
+        if (int rc = split_pair(embed, (long)bins * D, x, (long)N * D, es, xs, ws, a, s)) return rc;
+        if (int rc = launch_gemm16s(a, EPI_ARGMAX, OUT_F32, s)) return rc;
+    } else {
+        if (int rc = launch_gemm(a, PRO_NONE, EPI_ARGMAX, s)) return rc;
+    }
+    for (int64_t r0 = 0; r0 < N; r0 += 8192) {
+        const int n = (int)std::min<int64_t>(8192, N - r0);
+        if (int rc = launch_vq_finalize(pv + r0 * np, pi + r0 * np, np, embed, codes_out + r0, nullptr, 1, n, D, bins, s)) return rc;
+    }
+    return WT_OK;
+}
+int wt_vq_nearest(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
+                  void* workspace, void* stream) {
+    return vq_nearest(x, embed, N, D, bins, codes_out, workspace, stream, true);
+}
+int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
+                      void* workspace, void* stream) {
+    return vq_nearest(x, embed, N, D, bins, codes_out, workspace, stream, false);
+}
+
+int wt_resblock(const float* x, const float* wav, const float* e0_w, const float* e0_b, const float* w3, const float* b3,
+                const float* w1, const float* b1, const float* ws, const float* bs, float* y, int32_t B, int64_t T,
+                int32_t C, int32_t elu_out, int32_t out_s32, int32_t fp32_chain, void* stream) {
+    if ((!x && !wav) || !w3 || !b3 || !w1 || !b1 || !ws || !bs || !y) { set_error("wt_resblock: null argument"); return WT_ERR_INVALID; }
+    if (wav && (!e0_w || !e0_b)) { set_error("wt_resblock: the folded first conv needs its weights"); return WT_ERR_INVALID; }
+    if (B < 1 || T < 1 || (long)B * T >= (long)INT_MAX) { set_error("wt_resblock: bad shape"); return WT_ERR_INVALID; }
+    if (fp32_chain && out_s32) { set_error("wt_resblock: the fp32 kernel writes fp32"); return WT_ERR_INVALID; }
+    ResblockArgs a{};
+    a.x = wav ? nullptr : x; a.wav = wav; a.e0_w = e0_w; a.e0_b = e0_b;
+    a.W3 = w3; a.b3 = b3; a.W1 = w1; a.b1 = b1; a.Ws = ws; a.bs = bs;
+    a.y = y; a.B = B; a.T = (int)T; a.C = C; a.elu_out = elu_out ? 1 : 0; a.out_s32 = out_s32 ? 1 : 0;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return fp32_chain ? launch_resblock(a, s) : launch_resblock16(a, s);
+}
+
+// The stage-1 kernel of the shipped encode plan: first conv + SEANetResnetBlock + ELU + the stage's down conv in one launch
+// (resblock16.hip, DOWN); wd [64][2r][32], y_down [B][ceil(T / r)][64] fp32.
+int wt_resblock_down(const float* wav, const float* e0_w, const float* e0_b, const float* w3, const float* b3, const float* w1,
+                     const float* b1, const float* ws, const float* bs, const float* wd, const float* bd, float* y_down,
+                     int32_t B, int64_t T, int32_t r, void* stream) {
+    if (!wav || !e0_w || !e0_b || !w3 || !b3 || !w1 || !b1 || !ws || !bs || !wd || !bd || !y_down) {
+        set_error("wt_resblock_down: null argument"); return WT_ERR_INVALID;
+    }
+    if (B < 1 || T < 1 || (long)B * T >= (long)INT_MAX) { set_error("wt_resblock_down: bad shape"); return WT_ERR_INVALID; }
+    if (!resblock16_down_fusable(32, T, r, 2 * r)) {
+        set_error("wt_resblock_down: needs stride 2 or 4 and T >= 1024"); return WT_ERR_INVALID;
+    }
+    ResblockArgs a{};
+    a.wav = wav; a.e0_w = e0_w; a.e0_b = e0_b; a.W3 = w3; a.b3 = b3; a.W1 = w1; a.b1 = b1; a.Ws = ws; a.bs = bs;
+    a.Wd = wd; a.bd = bd; a.y_down = y_down; a.R = r; a.B = B; a.T = (int)T; a.C = 32;
+    return launch_resblock16_down(a, static_cast<hipStream_t>(stream));
+}
+
+
+}  // extern "C"

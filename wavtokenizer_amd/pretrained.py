@@ -227,7 +227,7 @@ class _Engine:
     def _key(kind: int, B: int, length: int, flags: int, device, sites: int = 0) -> tuple:
         """A plan owns a workspace, so it serves ONE stream: calls made under another current stream than the default one
         get plans (and staging buffers) of their own, keyed (..., stream handle).  Two streams can then run the same model
-        side by side (sharding.StepRunner(lanes=2)); the library orders their persistent LSTM launches itself (capi.cpp).
+        side by side (sharding.StepRunner(lanes=2)); the library orders their persistent LSTM launches itself (run.cpp).
         Key: (kind, B, length, flags) on the default stream, + (stream,) on another one, + (stream, fp32 site mask) for a
         plan with range sites on fp32 operands (stream 0 = the default stream)."""
         sp = torch.cuda.current_stream(device).cuda_stream if device is not None else 0

@@ -133,7 +133,7 @@ class StepRunner:
         # lanes > 1 (only without the exchange): step i runs on HIP stream i % lanes, so step i+1's encode_infer runs beside
         # step i's decode and fills the launch gaps and last-round tails of its kernels.  The model keeps a plan + workspace
         # per stream (pretrained._Engine._key) and the library chains the persistent LSTM launches of different streams
-        # (capi.cpp, LstmChain): at most one of them is on the GPU at a time.  Same kernels, same results.
+        # (run.cpp, LstmChain): at most one of them is on the GPU at a time.  Same kernels, same results.
         if lanes > 1 and self.gather:
             raise ValueError("lanes > 1 is the single-rank pipeline; the sharded exchange keeps one lane (DESIGN section 6)")
         self.lanes = int(lanes)

@@ -54,7 +54,8 @@ typedef enum {
 /* Device-side failure bits of a call (wt_plan_status). */
 enum wt_status_bits {
     WT_STATUS_BIT_LSTM = 1,   /* persistent LSTM: a step barrier timed out */
-    WT_STATUS_BIT_RANGE = 2   /* an S32 (split-f16) producer met |v| >= 65504 */
+    WT_STATUS_BIT_RANGE = 2,  /* an S32 (split-f16) producer met |v| >= 65504 */
+    WT_STATUS_BIT_LENGTH = 4  /* wt_decode_mixed: a clip length outside [1, Lpad] (the next call returns WT_ERR_INVALID once) */
 };
 
 /* Architecture: the YAML keys decoder/pretrained.py:81-92 (from_hparams0802) reads. */
@@ -89,7 +90,8 @@ typedef enum {
     WT_PLAN_DECODE = 1,          /* features (B,512,L) -> audio (B, L*hop)                     */
     WT_PLAN_SEANET_DECODER = 2,  /* features (B,512,L) -> audio (B,1,L*hop): encodec.decoder   */
     WT_PLAN_HEAD = 3,            /* backbone output (B,L,dim) -> audio (B, L*hop): model.head   */
-    WT_PLAN_UNIT_LSTM = 4        /* unit tests: x [B][L][512] -> SLSTM(x) [B][L][512], time-major (wt_unit_run) */
+    WT_PLAN_UNIT_LSTM = 4,       /* unit tests: x [B][L][512] -> SLSTM(x) [B][L][512], time-major (wt_unit_run) */
+    WT_PLAN_DECODE_MIXED = 5     /* features (B,512,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_mixed; `len` = Lpad */
 } wt_plan_kind;
 
 enum {
@@ -253,6 +255,19 @@ int wt_codes_to_features(const wt_model* m, const int64_t* codes, int32_t K, int
 int wt_decode(const wt_plan* p, const float* features, int32_t bandwidth_id, float* wav_out,
               float* backbone_out, void* workspace, void* stream);
 
+/* A batch of clips of different lengths on a WT_PLAN_DECODE_MIXED plan (B, Lpad): clip b is lengths[b] frames long and gets
+ * exactly the waveform a WT_PLAN_DECODE plan of its own length computes, whatever the other clips, the padded length and the
+ * contents of `features` past its frames (the lengths are read on the device, so a recorded graph replays for any lengths).
+ *   features [B][512][Lpad] fp32 (device): frames past a clip's length are read and dropped
+ *   lengths  [B] int32 (device), each in [1, Lpad]
+ *   wav_out  [B][Lpad*hop] ("center": [B][(Lpad-1)*hop]): clip b's first lengths[b]*hop ("center": (lengths[b]-1)*hop) samples,
+ *            zeros behind them.  A length outside the range poisons the whole call: wav_out is NaN and WT_STATUS_BIT_LENGTH is
+ *            left in the plan's and the model's status words.
+ * The plan runs the shipped split-f16 route only: its creation fails with WT_PLAN_FLAG_UNFUSED, FP32_GEMM, KEEP_STAGES or
+ * RANGE_REPORT and with any fp32 range site.  wt_decode refuses a mixed-length plan, and wt_decode_mixed every other plan. */
+int wt_decode_mixed(const wt_plan* p, const float* features, const int32_t* lengths, int32_t bandwidth_id, float* wav_out,
+                    void* workspace, void* stream);
+
 /* Replaces: ISTFTHead.forward (decoder/heads.py:42-67) + ISTFT.forward (decoder/spectral_ops.py:33-75) on its own,
  * reached by callers as model.head(x).  x [B][L][dim] fp32 (the backbone output), wav_out [B][L*hop] ("center":
  * [B][(L-1)*hop]). */
@@ -357,6 +372,10 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
  *   CONVTR     x [B][L][C], p0 w [k][C][Cout], p1 bias [Cout] -> y [B][L * stride][Cout]; flag = ELU on the input
  *   ROW_SUMSQ  x [n][C] -> y [n]
  *   S32_AMAX   x S32 array of n values -> y: one uint32 word, atomic max of the bit pattern of max |value|
+ * lengths (optional; GN_APPLY, GN_STATS, ROWNORM mode 0, SOFTMAX, ISTFT_OLA, TRANSPOSE): device int32 [B] (SOFTMAX: n / L clips of
+ * L query rows each; TRANSPOSE: of the C frames).  The op then runs its length-aware launch (the kernels of a WT_PLAN_DECODE_MIXED
+ * plan): the extents are the padded ones, clip b's reductions run over its own lengths[b] rows in the order of a call of that
+ * length, and its output rows (ISTFT_OLA: samples) past them are zeros.
  * status: optional device word that the S32 producers OR WT_STATUS_BIT_RANGE into (the launch context's status word is
  * set for the call and restored).  The descriptor is checked before any HIP call: whatever the launcher refuses returns
  * WT_ERR_INVALID with its message and touches no memory.  form (optional): the launch the launcher chose. */
@@ -365,7 +384,10 @@ enum { WT_OP_GN_APPLY = 0, WT_OP_GN_STATS = 1, WT_OP_ROWNORM = 2, WT_OP_SOFTMAX 
 /* wt_op_form.kernel */
 enum { WT_OPK_GN_TILE = 1, WT_OPK_GN_CHUNK = 2, WT_OPK_GN_STATS = 3, WT_OPK_ROWNORM = 4, WT_OPK_DWCONV_LN = 5,
        WT_OPK_SOFTMAX_REG = 6, WT_OPK_SOFTMAX_RMW = 7, WT_OPK_ISTFT_OLA = 8, WT_OPK_CONV_FIRST = 9, WT_OPK_CONV_LAST32 = 10,
-       WT_OPK_CONV_LAST = 11, WT_OPK_TRANSPOSE = 12, WT_OPK_CONVTR = 13, WT_OPK_ROW_SUMSQ = 14, WT_OPK_S32_AMAX = 15 };
+       WT_OPK_CONV_LAST = 11, WT_OPK_TRANSPOSE = 12, WT_OPK_CONVTR = 13, WT_OPK_ROW_SUMSQ = 14, WT_OPK_S32_AMAX = 15,
+       /* the length-aware launches (wt_op_desc.lengths) */
+       WT_OPK_TRANSPOSE_MIXED = 16, WT_OPK_GN_MIXED = 17, WT_OPK_DWCONV_LN_MIXED = 18, WT_OPK_SOFTMAX_REG_MIXED = 19,
+       WT_OPK_SOFTMAX_RMW_MIXED = 20, WT_OPK_ISTFT_OLA_MIXED = 21 };
 typedef struct {
     int32_t size;                   /* sizeof(wt_op_desc) */
     int32_t op;
@@ -378,11 +400,13 @@ typedef struct {
     const void *p0, *p1, *p2, *p3, *p4, *p5;
     void *y, *y2, *y3;
     uint32_t* status;
+    const int32_t* lengths;         /* optional, last: `size` may also be the struct's size without it (then NULL) */
 } wt_op_desc;
 typedef struct {
     int32_t kernel;                 /* WT_OPK_* */
-    int32_t variant;                /* gn_*: APPLY / SWISH template value; rownorm, dwconv_ln: NV; softmax_reg: NV4 */
-    int32_t variant2;               /* dwconv_ln: R; rownorm: MODE; gn_tile: waves per group */
+    int32_t variant;                /* gn_*: APPLY / SWISH template value (gn_mixed: APPLY); rownorm, dwconv_ln: NV; softmax_reg: NV4 */
+    int32_t variant2;               /* dwconv_ln: R; rownorm: MODE; gn_tile: waves per group; gn_mixed: forms launched (bit 0 slab /
+                                       stats kernel, bit 1 chunked pair) */
     int32_t grid_x, grid_y, grid_z, block, lds;     /* gn_chunk: the apply launch */
 } wt_op_form;
 int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream);

@@ -6,7 +6,12 @@ WavTokenizer.encode_infer_many, encode only.  python3 tools/mixed_length_bench.p
 One seeded set of file lengths.  Each method runs on a fresh model twice: "cold" is the first pass over the dataset (every plan,
 graph and workspace is created on the way, as a one-off tokenising job pays), "warm" the second pass over the same files.
 Reported per method and pass: files/s, audio-s/s, plans created; for encode_infer_many also the padding overhead of its calls
-(padded samples / real samples - 1).  Both methods are checked to return the same codes.  Prints one JSON line at the end."""
+(padded samples / real samples - 1).  Both methods are checked to return the same codes.  Prints one JSON line at the end.
+
+--decode [--files 64 --min-s 1 --max-s 10 --rounds 5]: the way back.  Features of random codes for the same kind of length set;
+the loop of one decode call per clip (what a caller without decode_many writes) against WavTokenizer.decode_many, on one model
+with every plan warm: the two methods alternate `rounds` times in the same process, and the medians, the spread (min .. max) of
+each and the ratio of the medians are reported.  Both methods are checked to return the same waveforms."""
 import argparse
 import json
 import os
@@ -52,6 +57,44 @@ def run(method, m, wavs):
     return time.perf_counter() - t0, out
 
 
+def main_decode(a):
+    from wavtokenizer_amd.mixed_length import group_frames
+    arch = NAMED_ARCHS[a.arch]
+    rng = np.random.default_rng(a.seed)
+    frames = [arch.frames(int(x)) for x in rng.integers(int(a.min_s * SR), int(a.max_s * SR) + 1, size=a.files)]
+    m, created = fresh_model(arch, synth.make_state_dict(arch, seed=0))
+    feats = [m.codes_to_features(torch.from_numpy(rng.integers(0, arch.vq_bins, size=(1, 1, L))).cuda())[0].contiguous() for L in frames]
+    bw = torch.tensor([0])
+    groups = group_frames(frames)
+    methods = {"loop": lambda: [m.decode(f[None], bandwidth_id=bw) for f in feats],
+               "many": lambda: m.decode_many(feats, bandwidth_id=bw)}
+    outs, times = {}, {"loop": [], "many": []}
+    for name, fn in methods.items():          # every plan (and graph) is created and recorded before anything is timed
+        for _ in range(3):
+            outs[name] = fn()
+        torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for name, fn in methods.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    m.check_status()
+    same = all(x.shape == y.shape and torch.equal(x, y) for x, y in zip(outs["loop"], outs["many"]))
+    res = {"mode": "decode", "arch": a.arch, "clips": a.files, "frames_total": sum(frames), "rounds": a.rounds,
+           "many_calls": len(groups), "many_padding_overhead": round(sum(L_pad * len(idx) for L_pad, idx in groups) / sum(frames) - 1, 4),
+           "plans_created": created[0], "identical_outputs": same}
+    for name, t in times.items():
+        res[f"{name}_ms"] = [round(x, 3) for x in t]
+        res[f"{name}_median_ms"] = round(float(np.median(t)), 3)
+        res[f"{name}_spread_ms"] = round(max(t) - min(t), 3)
+        print(f"{name:4s}: median {np.median(t):8.3f} ms  min {min(t):8.3f}  max {max(t):8.3f}  ({a.files} clips, {sum(frames)} frames)", flush=True)
+    res["speedup"] = round(res["loop_median_ms"] / res["many_median_ms"], 2)
+    print(json.dumps(res), flush=True)
+    return 0 if same else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--arch", default="hop600", choices=sorted(NAMED_ARCHS))
@@ -59,7 +102,11 @@ def main():
     ap.add_argument("--min-s", type=float, default=0.5)
     ap.add_argument("--max-s", type=float, default=20.0)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--decode", action="store_true", help="time decode_many against the loop of one decode call per clip")
+    ap.add_argument("--rounds", type=int, default=5, help="--decode: alternations of the two methods")
     a = ap.parse_args()
+    if a.decode:
+        return main_decode(a)
     arch = NAMED_ARCHS[a.arch]
     rng = np.random.default_rng(a.seed)
     lengths = [int(x) for x in rng.integers(int(a.min_s * SR), int(a.max_s * SR) + 1, size=a.files)]

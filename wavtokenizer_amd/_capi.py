@@ -23,10 +23,11 @@ EXPORTS = [
     "wt_decode", "wt_seanet_decode", "wt_head", "wt_unit_run", "wt_sconv1d", "wt_linear", "wt_conv1d_s32", "wt_vq_workspace_bytes",
     "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down", "wt_gemm_probe_workspace_bytes", "wt_gemm_probe", "wt_op_probe",
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
-    "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry",
+    "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
+WT_PLAN_DECODE_MIXED = 5
 WT_PLAN_FLAG_KEEP_STAGES = 1
 WT_PLAN_FLAG_FP32_GEMM = 2
 WT_PLAN_FLAG_STEP_LSTM = 4
@@ -38,7 +39,7 @@ WT_SITE_ENCODER, WT_SITE_BB_EMBED, WT_SITE_RES0, WT_SITE_RES1, WT_SITE_ATTN, WT_
 WT_SITE_CNX0, WT_SITE_HEAD, WT_SITE_SEANET_DECODER = 7, 40, 41
 WT_ERR_INVALID = -1
 WT_ERR_RANGE, WT_ERR_LSTM_SYNC, WT_ERR_INDEX = -6, -7, -8
-WT_STATUS_BIT_LSTM, WT_STATUS_BIT_RANGE = 1, 2
+WT_STATUS_BIT_LSTM, WT_STATUS_BIT_RANGE, WT_STATUS_BIT_LENGTH = 1, 2, 4
 BUF_S32, BUF_ELU = 1, 2
 
 
@@ -73,7 +74,8 @@ WT_OP_GN_APPLY, WT_OP_GN_STATS, WT_OP_ROWNORM, WT_OP_SOFTMAX, WT_OP_ISTFT_OLA, W
 WT_OP_CONV_LAST, WT_OP_TRANSPOSE, WT_OP_CONVTR, WT_OP_ROW_SUMSQ, WT_OP_S32_AMAX = 6, 7, 8, 9, 10
 WT_OPK_NAMES = {1: "gn_tile", 2: "gn_chunk", 3: "gn_stats", 4: "rownorm", 5: "dwconv_ln", 6: "softmax_reg", 7: "softmax_rmw",
                 8: "istft_ola", 9: "conv_first", 10: "conv_last32", 11: "conv_last", 12: "transpose", 13: "convtr",
-                14: "row_sumsq", 15: "s32_amax"}
+                14: "row_sumsq", 15: "s32_amax", 16: "transpose_mixed", 17: "gn_mixed", 18: "dwconv_ln_mixed",
+                19: "softmax_reg_mixed", 20: "softmax_rmw_mixed", 21: "istft_ola_mixed"}
 
 
 class WtOpDesc(ctypes.Structure):
@@ -81,7 +83,7 @@ class WtOpDesc(ctypes.Structure):
     _fields_ = ([(n, c_int32) for n in ("size", "op", "B", "L", "C", "groups", "mode", "flag", "out_s32", "ld", "k", "stride",
                                         "Cout", "n_fft", "hop", "Kq")]
                 + [("eps", c_float), ("n", c_int64)]
-                + [(n, c_void_p) for n in ("x", "p0", "p1", "p2", "p3", "p4", "p5", "y", "y2", "y3", "status")])
+                + [(n, c_void_p) for n in ("x", "p0", "p1", "p2", "p3", "p4", "p5", "y", "y2", "y3", "status", "lengths")])
 
 
 class WtOpForm(ctypes.Structure):
@@ -159,6 +161,7 @@ def _load() -> ctypes.CDLL:
     lib.wt_plan_read_timing.argtypes = [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]
     lib.wt_encode.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.wt_encode_mixed.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.wt_decode_mixed.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
     lib.wt_plan_min_clip_length.argtypes = [c_void_p]
     lib.wt_plan_min_clip_length.restype = c_int64
     lib.wt_sconv_geometry.argtypes = [c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]

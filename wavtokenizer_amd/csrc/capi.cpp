@@ -189,6 +189,7 @@ static const PlanKind kPlanKinds[] = {
     {WT_PLAN_ENCODE, build_encode, SITE_ENC, false, true},  {WT_PLAN_DECODE, build_decode, -1, true, false},
     {WT_PLAN_SEANET_DECODER, build_seanet_decoder, SITE_SEADEC, false, false},  {WT_PLAN_HEAD, build_head, SITE_HEAD, true, false},
     {WT_PLAN_UNIT_LSTM, build_unit_lstm, SITE_ENC, false, false},
+    {WT_PLAN_DECODE_MIXED, build_decode, -1, true, false},      // build_decode with the clip lengths threaded to its steps
 };
 
 int wt_plan_create_ex(const wt_model* m, int32_t kind, int32_t B, int64_t len, int32_t flags, uint64_t fp32_sites, wt_plan** out) {

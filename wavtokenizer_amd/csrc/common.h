@@ -43,7 +43,8 @@ struct PerDeviceOnce {
 // it is non-zero and copies it to a host-visible word, so a failed call can never hand out plausible-looking data.
 //   WT_STATUS_LSTM  : a step barrier of the persistent LSTM timed out (lost co-residency)
 //   WT_STATUS_RANGE : an S32 producer met |v| >= 65504: the f16 hi half of the split representation would be inf
-enum : unsigned { WT_STATUS_LSTM = 1u, WT_STATUS_RANGE = 2u };
+//   WT_STATUS_LENGTH: a mixed-length decode call was given a clip length outside [1, padded length]
+enum : unsigned { WT_STATUS_LSTM = 1u, WT_STATUS_RANGE = 2u, WT_STATUS_LENGTH = 4u };
 // The launch functions below take the status pointer from this per-thread context, which run_plan sets for the
 // duration of a call (nullptr outside a plan: the single-stage entry points have no status word)
 // stamp_start / stamp_end: when set (wt_plan_set_timing("@name")), the next gemm16s launch records its own duration on the
@@ -52,12 +53,14 @@ enum : unsigned { WT_STATUS_LSTM = 1u, WT_STATUS_RANGE = 2u };
 // form: when set (wt_op_probe), a non-GEMM launcher records the launch it chose (plans leave it null)
 enum OpKernel : int {
     OPK_NONE = 0, OPK_GN_TILE, OPK_GN_CHUNK, OPK_GN_STATS, OPK_ROWNORM, OPK_DWCONV_LN, OPK_SOFTMAX_REG, OPK_SOFTMAX_RMW,
-    OPK_ISTFT_OLA, OPK_CONV_FIRST, OPK_CONV_LAST32, OPK_CONV_LAST, OPK_TRANSPOSE, OPK_CONVTR, OPK_ROW_SUMSQ, OPK_S32_AMAX
+    OPK_ISTFT_OLA, OPK_CONV_FIRST, OPK_CONV_LAST32, OPK_CONV_LAST, OPK_TRANSPOSE, OPK_CONVTR, OPK_ROW_SUMSQ, OPK_S32_AMAX,
+    // the length-aware launches of a WT_PLAN_DECODE_MIXED plan (ops_kernel.inc, OPS_MIX 1)
+    OPK_TRANSPOSE_MIXED, OPK_GN_MIXED, OPK_DWCONV_LN_MIXED, OPK_SOFTMAX_REG_MIXED, OPK_SOFTMAX_RMW_MIXED, OPK_ISTFT_OLA_MIXED
 };
 struct OpForm {
     int kernel = OPK_NONE;       // OpKernel
-    int variant = 0;             // gn_*: the APPLY / SWISH template value; rownorm, dwconv_ln: NV; softmax_reg: NV4; else 0
-    int variant2 = 0;            // dwconv_ln: R; rownorm: MODE; gn_tile: waves per group; else 0
+    int variant = 0;             // gn_*: the APPLY / SWISH template value (gn_mixed: APPLY); rownorm, dwconv_ln: NV; softmax_reg: NV4; else 0
+    int variant2 = 0;            // dwconv_ln: R; rownorm: MODE; gn_tile: waves per group; gn_mixed: forms launched (1 slab / stats, 2 chunked); else 0
     unsigned grid[3] = {0, 0, 0};
     unsigned block = 0;
     unsigned lds = 0;            // dynamic LDS bytes
@@ -290,20 +293,24 @@ int launch_conv_first(const float* wav, const float* w /*[7][Cout]*/, const floa
                       int k, int Cout, hipStream_t s);
 int launch_conv_last(const float* x /*[B][T][Cin]*/, const float* w /*[k][Cin]*/, const float* bias, float* y /*[B][T]*/,
                      int B, long T, int Cin, int k, int elu_in, hipStream_t s);
-int launch_transpose(const float* in, float* out, int B, int R, int C, hipStream_t s, int out_s32 = 0);  // [B][R][C] -> [B][C][R]
+// `lens` (every launcher below that takes it; device int32 [B]): the length-aware launch of a WT_PLAN_DECODE_MIXED plan.  The
+// extents are then the padded ones, clip b's own length is lens[b] (clamped to them), a clip's reductions run over its own rows in
+// the order of a call of its own, and its output rows past them are zeros
+int launch_transpose(const float* in, float* out, int B, int R, int C, hipStream_t s, int out_s32 = 0, const int* lens = nullptr);  // [B][R][C] -> [B][C][R]
 // `part`: gn_part_floats() floats of scratch for sequences too long for the one-slab kernel (chunk statistics)
 size_t gn_part_floats(int B, int L, int groups);
 int launch_gn_stats(const float* x, const float* gamma, const float* beta, float* scale, float* shift, int B, int L,
-                    int C, int groups, float eps, hipStream_t s, float* part = nullptr);
+                    int C, int groups, float eps, hipStream_t s, float* part = nullptr, const int* lens = nullptr);
 int launch_gn_apply(const float* x, const float* gamma, const float* beta, float* scale, float* shift, float* y,
-                    int swish, int B, int L, int C, int groups, float eps, hipStream_t s, int out_s32 = 0, float* part = nullptr);
+                    int swish, int B, int L, int C, int groups, float eps, hipStream_t s, int out_s32 = 0, float* part = nullptr,
+                    const int* lens = nullptr);
 enum RowNormMode : int { RN_DWCONV = 0, RN_PLAIN = 1, RN_AFFINE_IN = 2 };
 int launch_rownorm(int mode, const float* x, float* y, int B, int L, int C, const float* dw_w /*[7][C]*/,
                    const float* dw_b, const float* in_scale, const float* in_shift, const float* out_scale,
-                   const float* out_shift, float eps, hipStream_t s, int out_s32 = 0);
+                   const float* out_shift, float eps, hipStream_t s, int out_s32 = 0, const int* lens = nullptr);   // lens: RN_DWCONV only
 int launch_istft_ola(const float* parts, const float* win, const float* wsq, float* out, int B, int L, int n_fft, int hop,
-                     int Kq, int center, hipStream_t s);
-int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s32 = nullptr);
+                     int Kq, int center, hipStream_t s, const int* lens = nullptr);
+int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s32 = nullptr, const int* lens = nullptr);   // lens: L rows per clip
 int launch_row_sumsq(const float* x, float* out, long rows, int D, hipStream_t s);
 int launch_vq_finalize(const float* pval, const int* pidx, int nparts, const float* embed, int64_t* codes,
                        float* feat_ncl, int B, int L, int D, int bins, hipStream_t s);
@@ -396,6 +403,9 @@ int launch_mixed_geometry(const int* lengths, int* geom, int B, long Tpad, int t
                           int kf, hipStream_t s);
 int launch_mixed_pad(const int* geom, int l_word, int64_t* codes, float* feat_ncl, float* emb_ncl, int B, int L, int D,
                      hipStream_t s);
+// mixed-length decode plans: a length outside [1, Lpad] sets WT_STATUS_LENGTH in the call's status word (the guard step then
+// poisons the call's output); the kernels themselves clamp every length to [0, Lpad]
+int launch_mixed_check_lengths(const int* lengths, int B, int Lpad, unsigned* status, hipStream_t s);
 int launch_convtr(const float* x, const float* w /*[k][Cin][Cout]*/, const float* bias, float* y, int B, int Tin,
                   int Cin, int Cout, int k, int stride, int elu_in, hipStream_t s);
 

@@ -77,4 +77,18 @@ int launch_mixed_pad(const int* geom, int l_word, int64_t* codes, float* feat_nc
     return 0;
 }
 
+__global__ __launch_bounds__(64) void mixed_check_lengths_kernel(const int* __restrict__ lengths, int B, int Lpad, unsigned* status) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int l = lengths[b];
+    if (l < 1 || l > Lpad) __hip_atomic_fetch_or(status, (unsigned)WT_STATUS_LENGTH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int launch_mixed_check_lengths(const int* lengths, int B, int Lpad, unsigned* status, hipStream_t s) {
+    if (!lengths || !status) { set_error("mixed-length decode: no clip lengths"); return -1; }
+    hipLaunchKernelGGL(mixed_check_lengths_kernel, dim3((B + 63) / 64), dim3(64), 0, s, lengths, B, Lpad, status);
+    WT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 }  // namespace wt

@@ -157,7 +157,7 @@ struct RunCtx {
     int64_t* codes;
     float* aux;              // emb_out (encode) / backbone_out (decode)
     int bw_id;
-    const int* lengths = nullptr;    // mixed-length encode: the clip lengths (device int32 [B])
+    const int* lengths = nullptr;    // mixed-length encode / decode: the clip lengths in samples / frames (device int32 [B])
 };
 // Range sites (wt_plan_create_ex, wt_plan_range_sites): the units in which a plan can leave the split-f16 (S32) form.  Every
 // S32 tensor is produced and consumed inside ONE site, so a site can run on fp32 operands (gemm.hip) on its own while the

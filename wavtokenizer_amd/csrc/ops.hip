@@ -198,107 +198,64 @@ int launch_conv_last(const float* x, const float* w, const float* bias, float* y
     return 0;
 }
 
-// ------------------------------------------------------------------------------------ transpose
-// [B][R][C] -> [B][C][R] through a padded 32x32 LDS tile (coalesced on both sides).
-__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ in, float* __restrict__ out, int R,
-                                                        int C, int s32, unsigned* status) {
-    __shared__ float tile[32][33];
-    float amax = 0.f;
-    const long boff = (long)blockIdx.z * R * C;
-    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int i = ty; i < 32; i += 8) {
-        const int r = r0 + i, c = c0 + tx;
-        if (r < R && c < C) tile[i][tx] = in[boff + (long)r * C + c];
-    }
-    __syncthreads();
-    for (int i = ty; i < 32; i += 8) {
-        const int c = c0 + i, r = r0 + tx;
-        if (r < R && c < C) {
-            if (s32) store_s32_1(out + boff + (long)c * R, r, tile[tx][i], amax);
-            else out[boff + (long)c * R + r] = tile[tx][i];
-        }
-    }
-    range_report(status, amax);
+// The kernels a decode plan runs per clip length live in ops_kernel.inc, compiled twice: as they are (x_kernel: the plans of one
+// length) and as the length-aware twins of a WT_PLAN_DECODE_MIXED plan (x_mixed_kernel: `lens`, device int32 [B])
+static constexpr int GN_CH = 128;      // rows per chunk of the chunked GroupNorm
+// a clip's own length, clamped to the padded extent before it indexes anything (an invalid length is reported by the plan's
+// first step; here it must only stay inside the buffers)
+__device__ __forceinline__ int mix_len(const int* __restrict__ lens, int b, int Lpad) {
+    const int l = lens[b];
+    return l < 0 ? 0 : (l > Lpad ? Lpad : l);
 }
+#define OPS_MIX 0
+#define OPS_K(base) base##_kernel
+#define OPS_L L
+#include "ops_kernel.inc"
+#undef OPS_MIX
+#undef OPS_K
+#undef OPS_L
+#define OPS_MIX 1
+#define OPS_K(base) base##_mixed_kernel
+#define OPS_L Lpad
+#include "ops_kernel.inc"
+#undef OPS_MIX
+#undef OPS_K
+#undef OPS_L
 
-int launch_transpose(const float* in, float* out, int B, int R, int C, hipStream_t s, int out_s32) {
+// ------------------------------------------------------------------------------------ transpose
+int launch_transpose(const float* in, float* out, int B, int R, int C, hipStream_t s, int out_s32, const int* lens) {
     if (out_s32 && (R % 32)) { set_error("transpose: an S32 output needs rows in multiples of 32 elements"); return -1; }
     dim3 grid((C + 31) / 32, (R + 31) / 32, B);
+    if (lens) {      // clip b holds lens[b] of the C frames; the output rows past them are zeros
+        note_form(OPK_TRANSPOSE_MIXED, 0, 0, grid, 256);
+        hipLaunchKernelGGL(transpose_mixed_kernel, grid, dim3(256), 0, s, in, out, R, C, out_s32, g_launch.status, lens);
+        WT_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     note_form(OPK_TRANSPOSE, 0, 0, grid, 256);
     hipLaunchKernelGGL(transpose_kernel, grid, dim3(256), 0, s, in, out, R, C, out_s32, g_launch.status);
     WT_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-// ---------------------------------------------------------------------------- GroupNorm statistics
-// decoder/models.py:15-16 Normalize = GroupNorm(32, C, eps=1e-6, affine): per (clip, group) mean and
-// biased variance over L x C/32 values, emitted as the per-(clip, channel) scale/shift
-//   y = x * (rstd*gamma[c]) + (beta[c] - mean*rstd*gamma[c])
-// (consumed by the row-norm pass for pos_net[5]); APPLY > 0 also writes the normalised (and
-// swish-activated) tensor once, which the following conv reads as a plain operand.
-template <int APPLY>   // 0: scale/shift only; 1: y = x*scale + shift; 2: y = swish(x*scale + shift)
-__global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, float* __restrict__ scale,
-                                                       float* __restrict__ shift, float* __restrict__ y, int L, int C,
-                                                       int cg, float eps, int s32, unsigned* status) {
-    __shared__ float red[4];
-    float amax = 0.f;
-    __shared__ float s_mean, s_rstd;
-    const int g = blockIdx.x, b = blockIdx.y;
-    const float* xb = x + (long)b * L * C + g * cg;
-    const int n = L * cg;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    float sum = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int t = i / cg, j = i - t * cg;
-        sum += xb[(long)t * C + j];
-    }
-    sum = wave_sum(sum);
-    if (lane == 0) red[wv] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) s_mean = (red[0] + red[1] + red[2] + red[3]) / (float)n;
-    __syncthreads();
-    const float mean = s_mean;
-    float sq = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int t = i / cg, j = i - t * cg;
-        const float d = xb[(long)t * C + j] - mean;
-        sq += d * d;
-    }
-    sq = wave_sum(sq);
-    __syncthreads();
-    if (lane == 0) red[wv] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) s_rstd = 1.f / sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)n + eps);
-    __syncthreads();
-    if (threadIdx.x < cg) {
-        const int c = g * cg + threadIdx.x;
-        const float sc = s_rstd * gamma[c];
-        scale[(long)b * C + c] = sc;
-        shift[(long)b * C + c] = beta[c] - mean * sc;
-    }
-    if (APPLY) {
-        float* yb = y + (long)b * L * C + g * cg;
-        const float rstd = s_rstd;
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const int t = i / cg, j = i - t * cg;
-            const float sc = rstd * gamma[g * cg + j];
-            float v = xb[(long)t * C + j] * sc + (beta[g * cg + j] - mean * sc);
-            if (APPLY == 2) v = v / (1.f + expf(-v));
-            if (s32) store_s32_1(y + ((long)b * L + t) * C, g * cg + j, v, amax);
-            else yb[(long)t * C + j] = v;
-        }
-        range_report(status, amax);
-    }
-}
-
+// ---------------------------------------------------------------------------------- GroupNorm
 static int launch_gn_chunked(const float*, const float*, const float*, float*, float*, float*, int, int, int, int, int, int, float,
-                             hipStream_t, int, float*);
+                             hipStream_t, int, float*, const int* lens = nullptr, int lmin = 0);
 static int gn_slab_groups(int C, int groups);
 int launch_gn_stats(const float* x, const float* gamma, const float* beta, float* scale, float* shift, int B, int L,
-                    int C, int groups, float eps, hipStream_t s, float* part) {
+                    int C, int groups, float eps, hipStream_t s, float* part, const int* lens) {
     const int GBs = gn_slab_groups(C, groups), cgs = C / groups;
+    if (lens) {
+        // The form is a clip's own choice: gn_stats_kernel<0> up to 256 frames, the chunked pair above (the rule below, per clip).
+        // Both launches are issued when the padded length allows both; each serves its clips and leaves at once for the others
+        const bool chunk_ok = part && GBs && (cgs % 4 == 0) && (C % 4 == 0) && GBs <= 8;
+        note_form(OPK_GN_MIXED, 0, chunk_ok && L > 256 ? 3 : 1, dim3(groups, B), 256);
+        hipLaunchKernelGGL(gn_stats_mixed_kernel<0>, dim3(groups, B), dim3(256), 0, s, x, gamma, beta, scale, shift,
+                           (float*)nullptr, L, C, C / groups, eps, 0, (unsigned*)nullptr, lens, chunk_ok ? 256 : INT_MAX);
+        WT_HIP_CHECK(hipGetLastError());
+        if (chunk_ok && L > 256) return launch_gn_chunked(x, gamma, beta, scale, shift, nullptr, 0, B, L, C, groups, GBs, eps, s, 0, part, lens, 256);
+        return 0;
+    }
     if (part && L > 256 && GBs && (cgs % 4 == 0) && (C % 4 == 0) && GBs <= 8)
         return launch_gn_chunked(x, gamma, beta, scale, shift, nullptr, 0, B, L, C, groups, GBs, eps, s, 0, part);
     note_form(OPK_GN_STATS, 0, 0, dim3(groups, B), 256);
@@ -308,218 +265,25 @@ int launch_gn_stats(const float* x, const float* gamma, const float* beta, float
     return 0;
 }
 
-// GroupNorm apply for short sequences: a block owns GB groups (a 384-byte channel slab for C/32 = 24, GB = 4) of one
-// clip, pulls the L x (GB*cg) slab into LDS with full-line loads, takes mean and variance from LDS (two-pass, one
-// wave per group), and writes the normalised (swish-activated) slab back once, fp32 or S32: one global read and one
-// write per element where gn_stats_kernel makes three strided read passes.
-template <int SWISH>
-__global__ __launch_bounds__(512) void gn_tile_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                                      const float* __restrict__ beta, float* __restrict__ scale,
-                                                      float* __restrict__ shift, float* __restrict__ y, int L, int C,
-                                                      int cg, int GB, float eps, int s32, unsigned* status) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];      // [L][W], W = GB * cg
-    float amax = 0.f;
-    __shared__ float s_sc[128], s_sh[128], s_red[8];
-    const int NT = blockDim.x;                             // 256, or 512 for slabs so large that one workgroup fills the CU
-    const int W = GB * cg, W4 = W / 4;
-    const int c0 = blockIdx.x * W, b = blockIdx.y;
-    const float* xb = x + (long)b * L * C + c0;
-    // (row, float4) of element e = threadIdx.x + NT k, advanced without divisions
-    const int dt = NT / W4, dq = NT - dt * W4;
-    {
-        int t = threadIdx.x / W4, q = threadIdx.x - t * W4;
-        for (; t < L; t += dt, q += dq) {
-            if (q >= W4) { q -= W4; ++t; if (t >= L) break; }
-            *reinterpret_cast<f32x4*>(tile + t * W + q * 4) = *reinterpret_cast<const f32x4*>(xb + (long)t * C + q * 4);
-        }
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = NT >> 6;
-    if (nw == 2 * GB) {
-        // two waves per group, each over half of the rows; the halves meet in LDS in a fixed order
-        const int gl = wv >> 1, part = wv & 1;
-        const int r0 = part ? L / 2 : 0, r1 = part ? L : L / 2;
-        const int n = L * cg;
-        const float* col = tile + gl * cg;
-        // a lane reads 4 channels of one row per step: 64 / (cg / 4) rows per wave instruction
-        const int cg4 = cg >> 2, rp = 64 / cg4, lr = lane / cg4, lq = lane - lr * cg4;
-        float sum = 0.f;
-        if (lr < rp)
-            for (int t = r0 + lr; t < r1; t += rp) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(col + t * W + lq * 4);
-                sum += (v.x + v.y) + (v.z + v.w);
-            }
-        sum = wave_sum(sum);
-        if (lane == 0) s_red[wv] = sum;
-        __syncthreads();
-        const float mean = (s_red[2 * gl] + s_red[2 * gl + 1]) / (float)n;
-        __syncthreads();
-        float sq = 0.f;
-        if (lr < rp)
-            for (int t = r0 + lr; t < r1; t += rp) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(col + t * W + lq * 4);
-                const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-                sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-            }
-        sq = wave_sum(sq);
-        if (lane == 0) s_red[wv] = sq;
-        __syncthreads();
-        const float rstd = 1.f / sqrtf((s_red[2 * gl] + s_red[2 * gl + 1]) / (float)n + eps);
-        if (part == 0 && lane < cg) {
-            const int c = c0 + gl * cg + lane;
-            const float sc = rstd * gamma[c], sh = beta[c] - mean * sc;
-            s_sc[gl * cg + lane] = sc; s_sh[gl * cg + lane] = sh;
-            scale[(long)b * C + c] = sc; shift[(long)b * C + c] = sh;
-        }
-    } else
-    for (int gl = wv; gl < GB; gl += nw) {                 // one wave per group
-        const int n = L * cg;
-        const float* col = tile + gl * cg;
-        const int cg4 = cg >> 2, rp = 64 / cg4, lr = lane / cg4, lq = lane - lr * cg4;
-        float sum = 0.f;
-        if (lr < rp)
-            for (int t = lr; t < L; t += rp) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(col + t * W + lq * 4);
-                sum += (v.x + v.y) + (v.z + v.w);
-            }
-        const float mean = wave_sum(sum) / (float)n;
-        float sq = 0.f;
-        if (lr < rp)
-            for (int t = lr; t < L; t += rp) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(col + t * W + lq * 4);
-                const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-                sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-            }
-        const float rstd = 1.f / sqrtf(wave_sum(sq) / (float)n + eps);
-        if (lane < cg) {
-            const int c = c0 + gl * cg + lane;
-            const float sc = rstd * gamma[c], sh = beta[c] - mean * sc;
-            s_sc[gl * cg + lane] = sc; s_sh[gl * cg + lane] = sh;
-            scale[(long)b * C + c] = sc; shift[(long)b * C + c] = sh;
-        }
-    }
-    __syncthreads();
-    float* yb = y + (long)b * L * C;
-    {
-        int t = threadIdx.x / W4, q = threadIdx.x - t * W4;
-        for (; t < L; t += dt, q += dq) {
-            if (q >= W4) { q -= W4; ++t; if (t >= L) break; }
-            const f32x4 v = *reinterpret_cast<const f32x4*>(tile + t * W + q * 4);
-            const f32x4 sc = *reinterpret_cast<const f32x4*>(s_sc + q * 4), sh = *reinterpret_cast<const f32x4*>(s_sh + q * 4);
-            f32x4 o = v * sc + sh;
-            if (SWISH) {     // x * sigmoid(x) on the hardware exp / rcp (relative error ~1e-7)
-                o.x *= __builtin_amdgcn_rcpf(1.f + __expf(-o.x)); o.y *= __builtin_amdgcn_rcpf(1.f + __expf(-o.y));
-                o.z *= __builtin_amdgcn_rcpf(1.f + __expf(-o.z)); o.w *= __builtin_amdgcn_rcpf(1.f + __expf(-o.w));
-            }
-            if (s32) store_s32_4(yb + (long)t * C, c0 + q * 4, o, amax);
-            else *reinterpret_cast<f32x4*>(yb + (long)t * C + c0 + q * 4) = o;
-        }
-    }
-    range_report(status, amax);
-}
-
-// GroupNorm for sequences too long for one LDS slab (30 s clips: L = 1200): the L x 96-channel slab is cut into chunks of
-// GN_CH rows.  Pass 1: every (slab, chunk) workgroup pulls its chunk into LDS and leaves, per group, the chunk mean and
-// the sum of squared deviations about it.  Pass 2: every workgroup merges the chunk statistics of its groups in chunk
-// order (Chan's pairwise update: deterministic, no atomics) and normalises its own chunk straight from global memory.
-// Two coalesced reads and one write per element where gn_stats_kernel makes three strided reads.
-static constexpr int GN_CH = 128;
-__global__ __launch_bounds__(256) void gn_chunk_stats_kernel(const float* __restrict__ x, float* __restrict__ part, int L,
-                                                             int C, int cg, int GB, int groups, int nch) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];      // [rows][W]
-    const int W = GB * cg, W4 = W / 4;
-    const int c0 = blockIdx.x * W, k = blockIdx.y, b = blockIdx.z;
-    const int t0 = k * GN_CH, rows = L - t0 < GN_CH ? L - t0 : GN_CH;
-    const float* xb = x + ((long)b * L + t0) * C + c0;
-    for (int e = threadIdx.x; e < rows * W4; e += 256) {
-        const int t = e / W4, q = e - t * W4;
-        *reinterpret_cast<f32x4*>(tile + t * W + q * 4) = *reinterpret_cast<const f32x4*>(xb + (long)t * C + q * 4);
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int gl = wv; gl < GB; gl += 4) {
-        const float* col = tile + gl * cg;
-        const int cg4 = cg >> 2, rp = 64 / cg4, lr = lane / cg4, lq = lane - lr * cg4;
-        float sum = 0.f;
-        if (lr < rp)
-            for (int t = lr; t < rows; t += rp) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(col + t * W + lq * 4);
-                sum += (v.x + v.y) + (v.z + v.w);
-            }
-        const float mean = wave_sum(sum) / (float)(rows * cg);
-        float sq = 0.f;
-        if (lr < rp)
-            for (int t = lr; t < rows; t += rp) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(col + t * W + lq * 4);
-                const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-                sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-            }
-        sq = wave_sum(sq);
-        if (lane == 0) {
-            float* o = part + (((long)b * groups + blockIdx.x * GB + gl) * nch + k) * 2;
-            o[0] = mean; o[1] = sq;
-        }
-    }
-}
-
-template <int APPLY>   // 0: scale/shift only; 1: y = x*scale + shift; 2: y = swish(x*scale + shift)
-__global__ __launch_bounds__(256) void gn_chunk_apply_kernel(const float* __restrict__ x, const float* __restrict__ part,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             float* __restrict__ scale, float* __restrict__ shift,
-                                                             float* __restrict__ y, int L, int C, int cg, int GB, int groups,
-                                                             int nch, float eps, int s32, unsigned* status) {
-    __shared__ float s_mean[8], s_rstd[8], s_sc[128], s_sh[128];
-    float amax = 0.f;
-    const int W = GB * cg, W4 = W / 4;
-    const int c0 = blockIdx.x * W, k = blockIdx.y, b = blockIdx.z;
-    if (threadIdx.x < GB) {
-        const float* pp = part + ((long)b * groups + blockIdx.x * GB + threadIdx.x) * nch * 2;
-        float n = 0.f, mean = 0.f, m2 = 0.f;
-        for (int q = 0; q < nch; ++q) {
-            const int rows = L - q * GN_CH < GN_CH ? L - q * GN_CH : GN_CH;
-            const float nq = (float)(rows * cg), d = pp[2 * q] - mean, tot = n + nq;
-            mean += d * (nq / tot);
-            m2 += pp[2 * q + 1] + d * d * (n * nq / tot);
-            n = tot;
-        }
-        s_mean[threadIdx.x] = mean;
-        s_rstd[threadIdx.x] = 1.f / sqrtf(m2 / n + eps);
-    }
-    __syncthreads();
-    if (threadIdx.x < W) {
-        const int c = c0 + threadIdx.x, gl = threadIdx.x / cg;
-        const float sc = s_rstd[gl] * gamma[c], sh = beta[c] - s_mean[gl] * sc;
-        s_sc[threadIdx.x] = sc; s_sh[threadIdx.x] = sh;
-        if (k == 0) { scale[(long)b * C + c] = sc; shift[(long)b * C + c] = sh; }
-    }
-    if (APPLY == 0) return;
-    __syncthreads();
-    const int t0 = k * GN_CH, rows = L - t0 < GN_CH ? L - t0 : GN_CH;
-    const float* xb = x + ((long)b * L + t0) * C + c0;
-    float* yb = y + ((long)b * L + t0) * C;
-    for (int e = threadIdx.x; e < rows * W4; e += 256) {
-        const int t = e / W4, q = e - t * W4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)t * C + q * 4);
-        const f32x4 sc = *reinterpret_cast<const f32x4*>(s_sc + q * 4), sh = *reinterpret_cast<const f32x4*>(s_sh + q * 4);
-        f32x4 o = v * sc + sh;
-        if (APPLY == 2) {
-            o.x *= __builtin_amdgcn_rcpf(1.f + __expf(-o.x)); o.y *= __builtin_amdgcn_rcpf(1.f + __expf(-o.y));
-            o.z *= __builtin_amdgcn_rcpf(1.f + __expf(-o.z)); o.w *= __builtin_amdgcn_rcpf(1.f + __expf(-o.w));
-        }
-        if (s32) store_s32_4(yb + (long)t * C, c0 + q * 4, o, amax);
-        else *reinterpret_cast<f32x4*>(yb + (long)t * C + c0 + q * 4) = o;
-    }
-    range_report(status, amax);
-}
-
 size_t gn_part_floats(int B, int L, int groups) { return (size_t)B * groups * ((L + GN_CH - 1) / GN_CH) * 2; }
 
 // the chunked pair of launches; mode as gn_chunk_apply_kernel's APPLY
 static int launch_gn_chunked(const float* x, const float* gamma, const float* beta, float* scale, float* shift, float* y,
                              int mode, int B, int L, int C, int groups, int GB, float eps, hipStream_t s, int out_s32,
-                             float* part) {
+                             float* part, const int* lens, int lmin) {
     const int cg = C / groups, nch = (L + GN_CH - 1) / GN_CH;
     const size_t smem = (size_t)GN_CH * GB * cg * sizeof(float);
+    if (lens) {      // the clips longer than lmin frames, each over its own chunks (the caller reports the form)
+        static PerDeviceOnce attr_mixed;
+        if (int rc = attr_mixed.run([&]() -> int { WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_chunk_stats_mixed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); return 0; })) return rc;
+        hipLaunchKernelGGL(gn_chunk_stats_mixed_kernel, dim3(groups / GB, nch, B), dim3(256), smem, s, x, part, L, C, cg, GB, groups, nch, lens, lmin);
+        const dim3 grid(groups / GB, mode ? nch : 1, B);
+        if (mode == 0) hipLaunchKernelGGL(gn_chunk_apply_mixed_kernel<0>, grid, dim3(256), 0, s, x, part, gamma, beta, scale, shift, y, L, C, cg, GB, groups, nch, eps, out_s32, g_launch.status, lens, lmin);
+        else if (mode == 1) hipLaunchKernelGGL(gn_chunk_apply_mixed_kernel<1>, grid, dim3(256), 0, s, x, part, gamma, beta, scale, shift, y, L, C, cg, GB, groups, nch, eps, out_s32, g_launch.status, lens, lmin);
+        else hipLaunchKernelGGL(gn_chunk_apply_mixed_kernel<2>, grid, dim3(256), 0, s, x, part, gamma, beta, scale, shift, y, L, C, cg, GB, groups, nch, eps, out_s32, g_launch.status, lens, lmin);
+        WT_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     static PerDeviceOnce attr_once;
     if (int rc = attr_once.run([&]() -> int { WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_chunk_stats_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); return 0; })) return rc;
     hipLaunchKernelGGL(gn_chunk_stats_kernel, dim3(groups / GB, nch, B), dim3(256), smem, s, x, part, L, C, cg, GB, groups, nch);
@@ -539,13 +303,36 @@ static int gn_slab_groups(int C, int groups) {      // groups per slab: a multip
 }
 
 int launch_gn_apply(const float* x, const float* gamma, const float* beta, float* scale, float* shift, float* y,
-                    int swish, int B, int L, int C, int groups, float eps, hipStream_t s, int out_s32, float* part) {
+                    int swish, int B, int L, int C, int groups, float eps, hipStream_t s, int out_s32, float* part, const int* lens) {
     if (out_s32 && (C % 32)) { set_error("gn_apply: an S32 output needs C % 32 == 0"); return -1; }
     const int cg = C / groups;
     // slab kernel: GB groups = a multiple of 32 channels (whole S32 groups, 16-byte rows), slab within the LDS budget
     int GB = 0;
     for (int g = 1; g <= groups; ++g)
         if (groups % g == 0 && (g * cg) % 32 == 0 && g * cg <= 128) { GB = g; break; }
+    if (lens) {
+        // The form is a clip's own choice (the rules below, per clip): the LDS slab while the clip's own rows fit 96 KB, the
+        // chunked pair above.  The slab launch is sized by the shorter of the padded length and the slab limit and also zeroes
+        // its clips' pad rows; the chunked launches are issued only when the padded length can hold a clip that needs them
+        if (!GB || (cg % 4) || (C % 4) || GB > 8) { set_error("gn_apply: no length-aware form for this channel layout"); return -1; }
+        const int lmax = (int)((96 * 1024) / ((size_t)GB * cg * 4));        // rows of the largest slab
+        if (L > lmax && !part) { set_error("gn_apply: the length-aware launch needs the chunk scratch beyond the slab limit"); return -1; }
+        const size_t smem = (size_t)(L < lmax ? L : lmax) * GB * cg * sizeof(float);
+        static PerDeviceOnce attr_mixed;
+        if (int rc = attr_mixed.run([&]() -> int {
+            WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_tile_mixed_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+            WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gn_tile_mixed_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+            return 0;
+        })) return rc;
+        dim3 grid(groups / GB, B);
+        const int nt = GB == 4 ? 512 : 256;
+        note_form(OPK_GN_MIXED, swish ? 2 : 1, L > lmax ? 3 : 1, grid, nt, smem);      // variant2: bit 0 slab launch, bit 1 chunked launches
+        if (swish) hipLaunchKernelGGL(gn_tile_mixed_kernel<1>, grid, dim3(nt), smem, s, x, gamma, beta, scale, shift, y, L, C, cg, GB, eps, out_s32, g_launch.status, lens, lmax);
+        else hipLaunchKernelGGL(gn_tile_mixed_kernel<0>, grid, dim3(nt), smem, s, x, gamma, beta, scale, shift, y, L, C, cg, GB, eps, out_s32, g_launch.status, lens, lmax);
+        WT_HIP_CHECK(hipGetLastError());
+        if (L > lmax) return launch_gn_chunked(x, gamma, beta, scale, shift, y, swish ? 2 : 1, B, L, C, groups, GB, eps, s, out_s32, part, lens, lmax);
+        return 0;
+    }
     if (GB && (cg % 4 == 0) && (size_t)L * GB * cg * 4 <= 96 * 1024 && (C % 4 == 0)) {
         const size_t smem = (size_t)L * GB * cg * sizeof(float);
         static PerDeviceOnce attr_once;
@@ -647,81 +434,28 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ 
     range_report(status, amax);
 }
 
-// RN_DWCONV with each wave producing R consecutive frames of one clip: the R + 6 input rows and the 7 tap rows are
-// loaded once per 256-channel slice instead of once per output frame (7 row loads + 7 tap loads per frame before).
-// Same accumulation order per output as rownorm_kernel, so the results are identical.
-template <int NV, int R>
-__global__ __launch_bounds__(256) void dwconv_ln_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int L,
-                                                        const float* __restrict__ dw_w, const float* __restrict__ dw_b,
-                                                        const float* __restrict__ out_scale,
-                                                        const float* __restrict__ out_shift, float eps, int s32, unsigned* status) {
-    constexpr int C = NV * 256;
-    const int lane = threadIdx.x & 63;
-    float amax = 0.f;
-    const int per_clip = (L + R - 1) / R;
-    const long wq = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wq >= (long)B * per_clip) return;
-    const int b = (int)(wq / per_clip);
-    const int t0 = (int)(wq - (long)b * per_clip) * R;
-    const float* xb = x + (long)b * L * C;
-    f32x4 v[R][NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        f32x4 xr[R + 6], w[7];
-#pragma unroll
-        for (int k = 0; k < R + 6; ++k) {
-            const int tt = t0 + k - 3;
-            xr[k] = (tt >= 0 && tt < L) ? *reinterpret_cast<const f32x4*>(xb + (long)tt * C + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < 7; ++j) w[j] = *reinterpret_cast<const f32x4*>(dw_w + j * C + c);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(dw_b + c);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            f32x4 acc = bias;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) {
-                const int tt = t0 + r + j - 3;
-                if (tt >= 0 && tt < L) acc += xr[r + j] * w[j];
-            }
-            v[r][i] = acc;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (t0 + r >= L) break;
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) sum += (v[r][i].x + v[r][i].y) + (v[r][i].z + v[r][i].w);
-        const float mean = wave_sum(sum) * (1.f / C);
-        float sq = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const f32x4 d = v[r][i] - mean;
-            sq += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-        }
-        const float rstd = 1.f / sqrtf(wave_sum(sq) * (1.f / C) + eps);
-        float* yrow = y + ((long)b * L + t0 + r) * C;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            const f32x4 os = *reinterpret_cast<const f32x4*>(out_scale + c);
-            const f32x4 oh = *reinterpret_cast<const f32x4*>(out_shift + c);
-            const f32x4 o = ((v[r][i] - mean) * rstd) * os + oh;
-            if (s32) store_s32_4(yrow, c, o, amax);
-            else *reinterpret_cast<f32x4*>(yrow + c) = o;
-        }
-    }
-    range_report(status, amax);
-}
-
 template <int NV>
 static int launch_rownorm_nv(int mode, const float* x, float* y, long M, int L, const float* dw_w, const float* dw_b,
                              const float* is, const float* ih, const float* os, const float* oh, float eps,
-                             hipStream_t s, int s32) {
+                             hipStream_t s, int s32, const int* lens) {
     dim3 grid((unsigned)((M + 3) / 4));
-    if (mode == RN_DWCONV) {
+    if (mode == RN_DWCONV && lens) {
+        // the length-aware twin, in the form the padded extent picks (both forms give an output the same bits)
+        const int B = (int)(M / L);
+        if (M <= 2048) {
+            const long waves = (long)B * L;
+            note_form(OPK_DWCONV_LN_MIXED, NV, 1, dim3((unsigned)((waves + 3) / 4)), 256);
+            hipLaunchKernelGGL((dwconv_ln_mixed_kernel<NV, 1>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, y, B, L, dw_w, dw_b,
+                               os, oh, eps, s32, g_launch.status, lens);
+        } else {
+            constexpr int R = 4;
+            const long waves = (long)B * ((L + R - 1) / R);
+            note_form(OPK_DWCONV_LN_MIXED, NV, R, dim3((unsigned)((waves + 3) / 4)), 256);
+            hipLaunchKernelGGL((dwconv_ln_mixed_kernel<NV, R>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, x, y, B, L, dw_w, dw_b,
+                               os, oh, eps, s32, g_launch.status, lens);
+        }
+    }
+    else if (mode == RN_DWCONV) {
         const int B = (int)(M / L);
         if (M <= 2048) {
             // a few clips: one frame per wave (four frames per wave would be fewer waves than the chip has SIMDs, each walking
@@ -751,95 +485,38 @@ static int launch_rownorm_nv(int mode, const float* x, float* y, long M, int L, 
 
 int launch_rownorm(int mode, const float* x, float* y, int B, int L, int C, const float* dw_w, const float* dw_b,
                    const float* in_scale, const float* in_shift, const float* out_scale, const float* out_shift,
-                   float eps, hipStream_t s, int out_s32) {
+                   float eps, hipStream_t s, int out_s32, const int* lens) {
     const long M = (long)B * L;
     switch (C) {
-        case 256: return launch_rownorm_nv<1>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32);
-        case 512: return launch_rownorm_nv<2>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32);
-        case 768: return launch_rownorm_nv<3>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32);
-        case 1024: return launch_rownorm_nv<4>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32);
+        case 256: return launch_rownorm_nv<1>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32, lens);
+        case 512: return launch_rownorm_nv<2>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32, lens);
+        case 768: return launch_rownorm_nv<3>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32, lens);
+        case 1024: return launch_rownorm_nv<4>(mode, x, y, M, L, dw_w, dw_b, in_scale, in_shift, out_scale, out_shift, eps, s, out_s32, lens);
         default: set_error("rownorm: backbone dim must be 256, 512, 768 or 1024"); return -1;
     }
 }
 
 // -------------------------------------------------------------------------------------- softmax
-// AttnBlock softmax over keys (decoder/models.py:119); one wave per query row; pad columns
-// [L, ld) are zero-filled so the P.V contraction can run over the padded length.
-__global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ S, long rows, int L, int ld, float* __restrict__ P_s32) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    float* row = S + r * ld;
-    float mx = -INFINITY;
-    for (int j = lane; j < L; j += 64) mx = fmaxf(mx, row[j]);
-    mx = wave_max(mx);
-    // a lane owns columns 4 (lane + 64 i) + e, i ascending, like softmax_reg_kernel: the same partial sums in the same order
-    float sum = 0.f;
-    for (int j0 = 4 * lane; j0 < L; j0 += 256)
-        for (int j = j0; j < j0 + 4 && j < L; ++j) {
-            const float e = expf(row[j] - mx);
-            row[j] = e;
-            sum += e;
-        }
-    sum = wave_sum(sum);
-    if (P_s32) {        // probabilities for a split-f16 GEMM: S32 rows in a separate buffer (pad columns zero)
-        float unused = 0.f;                                      // probabilities never leave [0, 1]
-        for (int j0 = 4 * lane; j0 < ld; j0 += 256)
-            for (int j = j0; j < j0 + 4 && j < ld; ++j) store_s32_1(P_s32 + r * ld, j, j < L ? row[j] / sum : 0.f, unused);
-    } else {
-        for (int j0 = 4 * lane; j0 < ld; j0 += 256)
-            for (int j = j0; j < j0 + 4 && j < ld; ++j) row[j] = j < L ? row[j] / sum : 0.f;
-    }
-}
-
-// The same with the row held in registers (NV4 float4 per lane, row pitch <= 256 * NV4): the scores are read ONCE with
-// 16-byte loads and the probabilities written once (S32: 8 + 8 bytes per four values), instead of read / write-back of the
-// exponentials / read / 2-byte stores (30 s clips: 737 MB -> 368 MB per launch).  Same arithmetic per element (max, exp(x - max),
-// sum in the same lane order, division by the sum).
-template <int NV4>
-__global__ __launch_bounds__(256) void softmax_reg_kernel(float* __restrict__ S, long rows, int L, int ld, float* __restrict__ P_s32) {
-    const int lane = threadIdx.x & 63;
-    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= rows) return;
-    const f32x4* row4 = reinterpret_cast<const f32x4*>(S + r * ld);
-    f32x4 v[NV4];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-        const int j = 4 * (lane + 64 * i);
-        v[i] = j < ld ? row4[lane + 64 * i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (j + e >= L) v[i][e] = -INFINITY;
-            mx = fmaxf(mx, v[i][e]);
-        }
-    }
-    mx = wave_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ex = 4 * (lane + 64 * i) + e < L ? expf(v[i][e] - mx) : 0.f;
-            v[i][e] = ex;
-            sum += ex;
-        }
-    sum = wave_sum(sum);
-    float unused = 0.f;                                          // probabilities never leave [0, 1]
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-        const int j = 4 * (lane + 64 * i);
-        if (j >= ld) continue;
-        f32x4 p;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) p[e] = j + e < L ? v[i][e] / sum : 0.f;
-        if (P_s32) store_s32_4(P_s32 + r * ld, j, p, unused);
-        else *reinterpret_cast<f32x4*>(S + r * ld + j) = p;
-    }
-}
-
-int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s32) {
+int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s32, const int* lens) {
     if (P_s32 && (ld % 32)) { set_error("softmax: an S32 output needs a row pitch in multiples of 32"); return -1; }
+    if (lens) {
+        // L query rows per clip (rows = clips * L); a row's keys are masked at its clip's own length.  The form follows the row
+        // pitch as below: every form sums a lane's columns in the same order
+        if (L <= 0 || rows % L) { set_error("softmax: the length-aware launch needs whole clips of L rows"); return -1; }
+        const dim3 grid((rows + 3) / 4), block(256);
+        if (ld % 4 == 0 && ld <= 2048 && !(reinterpret_cast<uintptr_t>(S) & 15)) {
+            note_form(OPK_SOFTMAX_REG_MIXED, ld <= 256 ? 1 : ld <= 512 ? 2 : ld <= 1280 ? 5 : 8, 0, grid, 256);
+            if (ld <= 256) hipLaunchKernelGGL(softmax_reg_mixed_kernel<1>, grid, block, 0, s, S, (long)rows, L, ld, P_s32, lens);
+            else if (ld <= 512) hipLaunchKernelGGL(softmax_reg_mixed_kernel<2>, grid, block, 0, s, S, (long)rows, L, ld, P_s32, lens);
+            else if (ld <= 1280) hipLaunchKernelGGL(softmax_reg_mixed_kernel<5>, grid, block, 0, s, S, (long)rows, L, ld, P_s32, lens);
+            else hipLaunchKernelGGL(softmax_reg_mixed_kernel<8>, grid, block, 0, s, S, (long)rows, L, ld, P_s32, lens);
+        } else {
+            note_form(OPK_SOFTMAX_RMW_MIXED, 0, 0, grid, 256);
+            hipLaunchKernelGGL(softmax_mixed_kernel, grid, block, 0, s, S, (long)rows, L, ld, P_s32, lens);
+        }
+        WT_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     if (ld % 4 == 0 && ld <= 2048 && !(reinterpret_cast<uintptr_t>(S) & 15)) {
         const dim3 grid((rows + 3) / 4), block(256);
         note_form(OPK_SOFTMAX_REG, ld <= 256 ? 1 : ld <= 512 ? 2 : ld <= 1280 ? 5 : 8, 0, grid, 256);
@@ -857,57 +534,21 @@ int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s3
 }
 
 // ------------------------------------------------------------------------------- ISTFT tail
-// ISTFT.forward (decoder/spectral_ops.py:33-75) after the four quarter transforms
-// Ce, Co, Se, So [frame][0..N/4]: rebuild x_t[n] with the two radix-2 butterflies, multiply by the
-// window, overlap-add the n_fft/hop frames that cover an output sample (ascending n, like fold),
-// trim and divide by the window-square envelope.  One thread per output sample.
-// "same" (:46, 56-73): trim (n_fft - hop) / 2 at both ends, L * hop samples.  "center" (:43-45, torch.istft(center=True)):
-// trim n_fft / 2 at both ends, (L - 1) * hop samples; the same overlap-add and the same envelope otherwise.
-__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ parts, const float* __restrict__ win,
-                                                        const float* __restrict__ wsq, float* __restrict__ out,
-                                                        long total, long Mrows, int L, int N, int hop, int Kq, int pad, long Tout) {
-    const int R = N / hop, Q = N / 4, Nh = N / 2;
-    const float* Ce = parts;
-    const float* Co = parts + Mrows * Kq;
-    const float* Se = parts + 2 * Mrows * Kq;
-    const float* So = parts + 3 * Mrows * Kq;
-    // Workgroup i runs on XCD i % 8 and every spectrum value is read by four output samples up to n_fft apart: with the
-    // chunks of 256 samples dealt out round robin each XCD's L2 fetched (nearly) all of `parts` for itself (301 MB of traffic
-    // for 93 MB, profiles/r03_pmc_traffic.json).  XCD x takes the x-th contiguous eighth of the chunks instead
-    const long nchunk = (long)gridDim.x;                     // a multiple of 8 (host), one chunk per workgroup
-    const long chunk = (long)(blockIdx.x & 7) * (nchunk >> 3) + (blockIdx.x >> 3);
-    for (long idx = chunk * blockDim.x + threadIdx.x; idx < total; idx += total) {       // (one pass)
-        const long b = idx / Tout;
-        const long u = idx - b * Tout;
-        const long up = u + pad;
-        const int jp = (int)(up / hop), r = (int)(up - (long)jp * hop);
-        float acc = 0.f, env = 0.f;
-        for (int d = 0; d < R; ++d) {
-            const int t = jp - d;
-            if (t < 0 || t >= L) continue;
-            const int n = r + hop * d;
-            const int m = n <= Nh ? n : N - n;               // x[N-m] = C[m] + S[m]
-            const int mm = m <= Q ? m : Nh - m;              // C[N/2-mm] = Ce - Co, S[N/2-mm] = So - Se
-            const long o = (b * L + t) * Kq + mm;
-            const float ce = Ce[o], co = Co[o], se = Se[o], so = So[o];
-            const float Cv = m <= Q ? ce + co : ce - co;
-            const float Sv = m <= Q ? se + so : so - se;
-            const float x = n <= Nh ? Cv - Sv : Cv + Sv;
-            acc += x * win[n];
-            env += wsq[n];
-        }
-        out[idx] = acc / env;
-    }
-}
-
 int launch_istft_ola(const float* parts, const float* win, const float* wsq, float* out, int B, int L, int n_fft, int hop,
-                     int Kq, int center, hipStream_t s) {
+                     int Kq, int center, hipStream_t s, const int* lens) {
     const int pad = center ? n_fft / 2 : (n_fft - hop) / 2;
     const long Tout = center ? (long)hop * (L - 1) : (long)hop * L;
     const long total = (long)B * Tout;
     if (total <= 0) return 0;
     const long blocks = (((total + 255) / 256) + 7) / 8 * 8;          // one 256-sample chunk per workgroup, a multiple of 8
     if (blocks > 0x7fffffffL) { set_error("istft_ola: too many samples for one launch"); return -1; }
+    if (lens) {      // L = the padded frames: clip b's samples come from its own lens[b] frames, the rest of its row is zeros
+        note_form(OPK_ISTFT_OLA_MIXED, 0, 0, dim3((unsigned)blocks), 256);
+        hipLaunchKernelGGL(istft_ola_mixed_kernel, dim3((unsigned)blocks), dim3(256), 0, s, parts, win, wsq, out, total, (long)B * L, L, n_fft,
+                           hop, Kq, pad, Tout, lens, center);
+        WT_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     note_form(OPK_ISTFT_OLA, 0, 0, dim3((unsigned)blocks), 256);
     hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)blocks), dim3(256), 0, s, parts, win, wsq, out, total, (long)B * L, L, n_fft,
                        hop, Kq, pad, Tout);

@@ -412,7 +412,7 @@ int build_encode(wt_plan* P) {
 // ISTFTHead (heads.py:53-66) on the backbone output xo [M][dim] (S32 when s32): Linear + exp/clip/cos/sin fused ->
 // spectrum rows [re | im]; ISTFT (spectral_ops.py:56-73) as four quarter-size real transforms (one batched GEMM), then
 // the butterflies + window + overlap-add + trim + envelope divide in one pass into the caller's audio buffer
-static void plan_head(wt_plan* P, int xo, bool s32) {
+static void plan_head(wt_plan* P, int xo, bool s32, bool mixed = false) {
     const wt_model* M = P->model;
     const wt_arch& ar = M->arch;
     const int B = P->B, L = (int)P->L, D = ar.dim;
@@ -430,7 +430,8 @@ static void plan_head(wt_plan* P, int xo, bool s32) {
     ai.c_rstride = Kq; ai.zC = (long)Mrows * Kq;
     gemm_step(P, s32, ai, {spec, -1, parts}, PRO_NONE, EPI_BIAS, OUT_F32, "head.istft");
     P->step({parts}, [=](const RunCtx& c) {
-        return launch_istft_ola(P->ptr(c, parts), M->win, M->wsq, c.out_f, B, L, ar.n_fft, hop, Kq, ar.padding_same ? 0 : 1, c.stream);
+        return launch_istft_ola(P->ptr(c, parts), M->win, M->wsq, c.out_f, B, L, ar.n_fft, hop, Kq, ar.padding_same ? 0 : 1, c.stream,
+                                mixed ? c.lengths : nullptr);
     }, 1, "head.ola");
 }
 
@@ -448,8 +449,27 @@ int build_decode(wt_plan* P) {
     auto s32_at = [&](int site) { return s32_plan && !site_fp32(P, site); };
     P->cur_site = SITE_BB_EMBED;
     const bool s32_e = s32_at(SITE_BB_EMBED);
+    // Mixed-length plan (WT_PLAN_DECODE_MIXED): L is the padded length, every clip brings its own (RunCtx::lengths).  The GEMMs run
+    // at (B, L) as they are: they are row-independent, and the steps that reduce over time (GroupNorm, softmax, the dwconv's
+    // taps, the overlap-add) read each clip's length and leave zeros in its rows past it, which stand for the zero padding of
+    // the convs and add exact zeros to the attention output.  Only the shipped split-f16 route takes lengths
+    const bool mixed = P->kind == WT_PLAN_DECODE_MIXED;
+    if (mixed) {
+        const bool ok = s32_plan && !P->fp32_sites && !(P->flags & (WT_PLAN_FLAG_KEEP_STAGES | WT_PLAN_FLAG_RANGE_REPORT)) &&
+                        M->at_Wqk.s32.p && M->at_Wv.s32.p && M->at_Wp.s32.p;
+        if (!ok) {
+            set_error("mixed-length plans run only the shipped split-f16 decoder route: not with WT_PLAN_FLAG_UNFUSED, "
+                      "FP32_GEMM, KEEP_STAGES or RANGE_REPORT, a decoder range site on fp32, or weights without S32 copies");
+            return WT_ERR_INVALID;
+        }
+        const int ctl = P->ctl;
+        P->step({ctl}, [=](const RunCtx& c) {
+            return launch_mixed_check_lengths(c.lengths, B, L, reinterpret_cast<unsigned*>(P->ptr(c, ctl)), c.stream);
+        }, 1, "mix.lengths");
+    }
+    auto lens = [mixed](const RunCtx& c) { return mixed ? c.lengths : nullptr; };
     const int x0 = P->buf("bb.in", (size_t)Mrows * Cin, s32_e ? BUF_S32 : BUF_F32);
-    P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, Cin, L, c.stream, s32_e); });
+    P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, Cin, L, c.stream, s32_e, lens(c)); });
     const int x = P->buf("bb.x", (size_t)Mrows * D);       // residual stream, updated in place
     gemm_step(P, s32_e, zconv_args(M->bb_embed, B, L), {x0, -1, x}, PRO_NONE, EPI_BIAS, OUT_F32);
     const bool keep = P->flags & WT_PLAN_FLAG_KEEP_STAGES;
@@ -470,11 +490,11 @@ int build_decode(wt_plan* P) {
         const bool s32 = s32_at(site);
         P->bufs[h1].fmt = s32 ? BUF_S32 : BUF_F32;         // (h1 is shared by the sites; the range report reads the format per step)
         P->step({x, sc, sh, h1, gp}, [=](const RunCtx& c) {
-            return launch_gn_apply(P->ptr(c, x), r.n1w, r.n1b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
+            return launch_gn_apply(P->ptr(c, x), r.n1w, r.n1b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp), lens(c));
         }, 1, "res.gn1");
         gemm_step(P, s32, zconv_args(r.c1, B, L), {h1, -1, h2}, PRO_NONE, EPI_BIAS, OUT_F32, "res.conv1");
         P->step({h2, sc, sh, h1, gp}, [=](const RunCtx& c) {
-            return launch_gn_apply(P->ptr(c, h2), r.n2w, r.n2b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
+            return launch_gn_apply(P->ptr(c, h2), r.n2w, r.n2b, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 1, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp), lens(c));
         }, 1, "res.gn2");
         GemmArgs a2 = zconv_args(r.c2, B, L);
         a2.r_rstride = D;
@@ -496,7 +516,7 @@ int build_decode(wt_plan* P) {
         const int Ps = s32 ? P->buf("bb.attn.p", (size_t)Mrows * Lp, BUF_S32) : S;    // probabilities
         const int o = P->buf("bb.attn.o", (size_t)Mrows * D, fmt);
         P->step({x, sc, sh, gp, h1}, [=](const RunCtx& c) {
-            return launch_gn_apply(P->ptr(c, x), M->at_nw, M->at_nb, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 0, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp));
+            return launch_gn_apply(P->ptr(c, x), M->at_nw, M->at_nb, P->ptr(c, sc), P->ptr(c, sh), P->ptr(c, h1), 0, B, L, D, 32, 1e-6f, c.stream, s32, P->ptr(c, gp), lens(c));
         }, 1, "attn.gn");
         gemm_step(P, s32, linear_args(M->at_Wqk, M->at_bqk, Mrows, 2 * D, D), {h1, -1, qk}, PRO_NONE, EPI_BIAS, OUT_S32, "attn.qk");
         P->step({h1, vt}, [=](const RunCtx& c) {     // V^T[b] = Wv . hn[b]^T + bv   (D x L, pitch Lp; pad columns stay zero)
@@ -515,7 +535,7 @@ int build_decode(wt_plan* P) {
             a.alpha = (float)std::pow((double)D, -0.5);
             return dense_act(P, s32, a, P->ptr(c, qk) + D, EPI_SCALE, OUT_F32, c.stream);
         }, 1, "attn.s");
-        P->step({S, Ps}, [=](const RunCtx& c) { return launch_softmax(P->ptr(c, S), (int)Mrows, L, Lp, c.stream, s32 ? P->ptr(c, Ps) : nullptr); });
+        P->step({S, Ps}, [=](const RunCtx& c) { return launch_softmax(P->ptr(c, S), (int)Mrows, L, Lp, c.stream, s32 ? P->ptr(c, Ps) : nullptr, lens(c)); });
         P->step({Ps, vt, o}, [=](const RunCtx& c) {  // O[b] = P[b] . V[b]
             GemmArgs a = linear_args(nullptr, nullptr, L, D, Lp);
             a.A = P->ptr(c, Ps); a.zA = (long)L * Lp;
@@ -534,7 +554,7 @@ int build_decode(wt_plan* P) {
     // pos_net[5] GroupNorm + backbone.norm AdaLayerNorm (models.py:213,228), fused into one row pass
     const int xc = P->buf(keep ? "bb.x2" : "bb.norm", (size_t)Mrows * D);
     P->step({x, gp, sc, sh}, [=](const RunCtx& c) {
-        return launch_gn_stats(P->ptr(c, x), M->gn5w, M->gn5b, P->ptr(c, sc), P->ptr(c, sh), B, L, D, 32, 1e-6f, c.stream, P->ptr(c, gp));
+        return launch_gn_stats(P->ptr(c, x), M->gn5w, M->gn5b, P->ptr(c, sc), P->ptr(c, sh), B, L, D, 32, 1e-6f, c.stream, P->ptr(c, gp), lens(c));
     });
     P->step({x, sc, sh, xc}, [=](const RunCtx& c) {
         return launch_rownorm(RN_AFFINE_IN, P->ptr(c, x), P->ptr(c, xc), B, L, D, nullptr, nullptr, P->ptr(c, sc),
@@ -551,7 +571,7 @@ int build_decode(wt_plan* P) {
         P->bufs[nrm].fmt = P->bufs[mid].fmt = s32 ? BUF_S32 : BUF_F32;
         P->step({xc, nrm}, [=](const RunCtx& c) {
             return launch_rownorm(RN_DWCONV, P->ptr(c, xc), P->ptr(c, nrm), B, L, D, cb.dw_w, cb.dw_b, nullptr, nullptr,
-                                  cb.ada_s + (size_t)c.bw_id * D, cb.ada_h + (size_t)c.bw_id * D, 1e-6f, c.stream, s32);
+                                  cb.ada_s + (size_t)c.bw_id * D, cb.ada_h + (size_t)c.bw_id * D, 1e-6f, c.stream, s32, lens(c));
         });
         // GELU output pre-split for pwconv2
         gemm_step(P, s32, linear_args(cb.W1, cb.b1, Mrows, I, D), {nrm, -1, mid}, PRO_NONE, EPI_BIAS_GELU, OUT_S32, "cnx.pwconv1");
@@ -571,7 +591,7 @@ int build_decode(wt_plan* P) {
                                   M->fln_b, 1e-6f, c.stream, 0);
         return c.aux ? copy_f32(c.aux, P->ptr(c, xo), (size_t)Mrows * D, c.stream) : 0;
     });
-    plan_head(P, xo, s32);
+    plan_head(P, xo, s32, mixed);
     return 0;
 }
 

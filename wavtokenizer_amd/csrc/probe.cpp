@@ -172,7 +172,15 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
 // wt_op_probe: every check that needs no HIP call and that the launchers do not make themselves (they trust the plans)
 static int op_probe_check(const wt_op_desc* d) {
     auto bad = [](const char* m) { set_error(std::string("wt_op_probe: ") + m); return (int)WT_ERR_INVALID; };
-    if (!d || d->size != (int32_t)sizeof(wt_op_desc)) return bad("descriptor missing or of another size");
+    if (!d || (d->size != (int32_t)sizeof(wt_op_desc) && d->size != (int32_t)offsetof(wt_op_desc, lengths))) return bad("descriptor missing or of another size");
+    const int32_t* lengths = d->size == (int32_t)sizeof(wt_op_desc) ? d->lengths : nullptr;
+    if (lengths) {
+        if (reinterpret_cast<uintptr_t>(lengths) & 3) return bad("lengths misaligned");
+        const bool aware = d->op == WT_OP_GN_APPLY || d->op == WT_OP_GN_STATS || (d->op == WT_OP_ROWNORM && d->mode == RN_DWCONV) ||
+                           d->op == WT_OP_SOFTMAX || d->op == WT_OP_ISTFT_OLA || d->op == WT_OP_TRANSPOSE;
+        if (!aware) return bad("this op has no length-aware launch");
+        if (d->op == WT_OP_SOFTMAX && (d->L <= 0 || d->n % d->L)) return bad("the length-aware softmax needs whole clips of L rows");
+    }
     if (d->op < WT_OP_GN_APPLY || d->op > WT_OP_S32_AMAX) return bad("unknown op");
     auto al16 = [](const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); };
     const void* ptrs[] = {d->p0, d->p1, d->p2, d->p3, d->p4, d->p5, d->y, d->y2, d->y3};
@@ -235,6 +243,7 @@ int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream) {
     auto F = [](const void* p) { return static_cast<const float*>(p); };
     auto W = [](void* p) { return static_cast<float*>(p); };
     OpForm lf;
+    const int* lens = d->size == (int32_t)sizeof(wt_op_desc) ? d->lengths : nullptr;
     const LaunchCtx saved = g_launch;
     g_launch.status = reinterpret_cast<unsigned*>(d->status);
     g_launch.form = &lf;
@@ -242,20 +251,20 @@ int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream) {
     switch (d->op) {
     case WT_OP_GN_APPLY:
         rc = launch_gn_apply(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), W(d->y), d->flag ? 1 : 0, d->B, d->L, d->C, d->groups, d->eps, s,
-                             d->out_s32 ? 1 : 0, const_cast<float*>(F(d->p2)));
+                             d->out_s32 ? 1 : 0, const_cast<float*>(F(d->p2)), lens);
         break;
     case WT_OP_GN_STATS:
-        rc = launch_gn_stats(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), d->B, d->L, d->C, d->groups, d->eps, s, const_cast<float*>(F(d->p2)));
+        rc = launch_gn_stats(F(d->x), F(d->p0), F(d->p1), W(d->y2), W(d->y3), d->B, d->L, d->C, d->groups, d->eps, s, const_cast<float*>(F(d->p2)), lens);
         break;
     case WT_OP_ROWNORM:
         rc = launch_rownorm(d->mode, F(d->x), W(d->y), d->B, d->L, d->C, F(d->p0), F(d->p1), F(d->p2), F(d->p3), F(d->p4), F(d->p5), d->eps, s,
-                            d->out_s32 ? 1 : 0);
+                            d->out_s32 ? 1 : 0, lens);
         break;
     case WT_OP_SOFTMAX:
-        rc = launch_softmax(const_cast<float*>(F(d->x)), (int)d->n, d->L, d->ld, s, W(d->y));
+        rc = launch_softmax(const_cast<float*>(F(d->x)), (int)d->n, d->L, d->ld, s, W(d->y), lens);
         break;
     case WT_OP_ISTFT_OLA:
-        rc = launch_istft_ola(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->n_fft, d->hop, d->Kq, d->flag ? 1 : 0, s);
+        rc = launch_istft_ola(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->n_fft, d->hop, d->Kq, d->flag ? 1 : 0, s, lens);
         break;
     case WT_OP_CONV_FIRST:
         rc = launch_conv_first(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->k, d->Cout, s);
@@ -264,7 +273,7 @@ int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream) {
         rc = launch_conv_last(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->C, d->k, d->flag ? 1 : 0, s);
         break;
     case WT_OP_TRANSPOSE:
-        rc = launch_transpose(F(d->x), W(d->y), d->B, d->L, d->C, s, d->out_s32 ? 1 : 0);
+        rc = launch_transpose(F(d->x), W(d->y), d->B, d->L, d->C, s, d->out_s32 ? 1 : 0, lens);
         break;
     case WT_OP_CONVTR:
         rc = launch_convtr(F(d->x), F(d->p0), F(d->p1), W(d->y), d->B, d->L, d->C, d->Cout, d->k, d->stride, d->flag ? 1 : 0, s);

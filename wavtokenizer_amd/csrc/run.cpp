@@ -204,6 +204,11 @@ static int run_plan(const wt_plan* p, const RunCtx& c) {
                       "outputs were overwritten (codes = -1, NaN); the model's plans now run the LSTM one launch per step: repeat the call");
             return WT_ERR_LSTM_SYNC;
         }
+        if (bits & WT_STATUS_LENGTH) {
+            set_error("an earlier mixed-length decode call on this model was given a clip length outside [1, padded length]; "
+                      "that call's outputs were overwritten (NaN); repeat the call");
+            return WT_ERR_INVALID;
+        }
         set_error("an earlier call on this model met a value outside the f16 range of the split-f16 (S32) form (|v| >= 65504); "
                   "that call's outputs were overwritten (codes = -1, NaN); re-plan with WT_PLAN_FLAG_FP32_GEMM and repeat the call");
         return WT_ERR_RANGE;
@@ -351,12 +356,24 @@ int wt_encode_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, 
 
 int wt_decode(const wt_plan* p, const float* features, int32_t bandwidth_id, float* wav_out, float* backbone_out,
               void* workspace, void* stream) {
+    if (p && p->kind == WT_PLAN_DECODE_MIXED) { set_error("wt_decode: a mixed-length plan runs through wt_decode_mixed"); return WT_ERR_INVALID; }
     if (int rc = check_kind(p, WT_PLAN_DECODE, -1, "wt_decode: not a decode plan")) return rc;
     if (!features || !wav_out || !workspace) { set_error("wt_decode: null buffer"); return WT_ERR_INVALID; }
     if (bandwidth_id < 0 || bandwidth_id >= p->model->arch.adanorm_num_embeddings) {
         set_error("wt_decode: bandwidth_id out of range"); return WT_ERR_INVALID;
     }
     RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features, wav_out, nullptr, backbone_out, bandwidth_id};
+    return run_plan(p, c);
+}
+
+int wt_decode_mixed(const wt_plan* p, const float* features, const int32_t* lengths, int32_t bandwidth_id, float* wav_out,
+                    void* workspace, void* stream) {
+    if (int rc = check_kind(p, WT_PLAN_DECODE_MIXED, -1, "wt_decode_mixed: not a mixed-length decode plan (WT_PLAN_DECODE_MIXED)")) return rc;
+    if (!features || !lengths || !wav_out || !workspace) { set_error("wt_decode_mixed: null buffer"); return WT_ERR_INVALID; }
+    if (bandwidth_id < 0 || bandwidth_id >= p->model->arch.adanorm_num_embeddings) {
+        set_error("wt_decode_mixed: bandwidth_id out of range"); return WT_ERR_INVALID;
+    }
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features, wav_out, nullptr, nullptr, bandwidth_id, lengths};
     return run_plan(p, c);
 }
 

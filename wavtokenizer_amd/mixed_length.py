@@ -1,5 +1,5 @@
-"""Grouping policy of WavTokenizer.encode_infer_many: which clips share a mixed-length encode call, and how long its padded
-staging tensor is.  Pure functions of the clip lengths (no GPU), so the policy is tested on its own.
+"""Grouping policy of WavTokenizer.encode_infer_many and decode_many: which clips share a mixed-length call, and how long its
+padded staging tensor is.  Pure functions of the clip lengths (no GPU), so the policy is tested on its own.
 
 A mixed-length call returns for every clip the bits a call of its own length returns (the kernels read each clip's length on
 the device), so grouping and bucketing change only the cost: a bucket is a coarse padded length that many calls share, which
@@ -26,14 +26,28 @@ def bucket_length(T: int, hop: int) -> int:
     return -(-T // q) * q
 
 
-def group_clips(lengths: Sequence[int], hop: int, min_clip: int = MIN_CLIP, max_group: int = MAX_GROUP
+MAX_SCORE_CELLS = 32 * 1200 * 1216   # attention score cells (B * L_pad * Lp, held twice as floats) per decode call: the largest
+                                     # attention workspace this project measures (the 32 x 30 s row of bench.py --full)
+
+
+def score_cells(B: int, L_pad: int) -> int:
+    """Cells of the decoder's attention score matrix for B clips of L_pad frames (row pitch: L_pad rounded up to 32)."""
+    return B * L_pad * (-(-L_pad // 32) * 32)
+
+
+def group_clips(lengths: Sequence[int], hop: int, min_clip: int = MIN_CLIP, max_group: int = MAX_GROUP, max_cells: int = 0
                 ) -> Tuple[List[Tuple[int, List[int]]], List[int]]:
     """(groups, solo): groups = [(padded length, clip indices)], solo = indices of the clips shorter than min_clip (they run
     one at a time through encode_infer).  Clips are taken in order of length (ties in input order); a group closes at
     max_group clips or when the next clip's bucket is more than twice the group's first clip (more than half of the call
-    would be padding).  Every clip index appears exactly once."""
+    would be padding).  max_cells > 0 (decode, lengths in frames): a group also closes before the clip with which its score
+    matrix (score_cells at the padded length) would exceed max_cells; a single clip always forms a group.  Every clip index
+    appears exactly once."""
     def padded(T: int) -> int:
         return max(T, min(bucket_length(T, hop), MAX_FRAMES * hop))
+
+    def over_cells(n: int, T: int) -> bool:
+        return max_cells > 0 and score_cells(n, padded(T)) > max_cells
 
     order = sorted(range(len(lengths)), key=lambda i: (int(lengths[i]), i))
     solo = [i for i in order if int(lengths[i]) < min_clip]
@@ -43,10 +57,18 @@ def group_clips(lengths: Sequence[int], hop: int, min_clip: int = MIN_CLIP, max_
         T = int(lengths[i])
         if T < min_clip:
             continue
-        if cur and (len(cur) >= max_group or bucket_length(T, hop) > 2 * int(lengths[cur[0]])):
+        if cur and (len(cur) >= max_group or bucket_length(T, hop) > 2 * int(lengths[cur[0]]) or over_cells(len(cur) + 1, T)):
             groups.append((padded(int(lengths[cur[-1]])), cur))
             cur = []
         cur.append(i)
     if cur:
         groups.append((padded(int(lengths[cur[-1]])), cur))
     return groups, solo
+
+
+def group_frames(frames: Sequence[int], max_group: int = MAX_GROUP) -> List[Tuple[int, List[int]]]:
+    """Grouping of WavTokenizer.decode_many: group_clips in units of frames (hop 1, every clip of one frame or more is taken)
+    with the score-cell cap.  Returns [(padded frames, clip indices)]; every index appears exactly once."""
+    groups, solo = group_clips(frames, 1, min_clip=1, max_group=max_group, max_cells=MAX_SCORE_CELLS)
+    assert not solo
+    return groups

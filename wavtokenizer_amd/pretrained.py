@@ -892,6 +892,81 @@ class WavTokenizer(nn.Module):
         return self._call(lib.wt_decode, _capi.WT_PLAN_DECODE, B, L, flags, dev, (features,),
                           (((B, self._wave_len(L)), torch.float32, True), bb), (bw,))
 
+    def _run_decode_mixed(self, feats: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None):
+        """One mixed-length decode call (WT_PLAN_DECODE_MIXED) on clips (512, L_i) of 1 <= L_i <= L_pad frames: returns the
+        waveforms (B, wave_len(L_pad)), clip j's own samples first and zeros behind them, or None when the current flags or
+        fp32 sites keep the decoder off the route a mixed-length plan takes (_decode_mixed_route_ok; the caller then decodes
+        the clips one at a time).  Any other refusal of the plan raises."""
+        dev = dev if dev is not None else self._ensure_engine()
+        B = len(feats)
+        lengths = [int(f.shape[1]) for f in feats]
+        if min(lengths) < 1 or max(lengths) > L_pad:
+            raise ValueError("every clip needs between 1 and L_pad frames")
+
+        def fill_feats(buf: torch.Tensor):      # (frames past a clip's length are read and dropped by the first kernel)
+            for j, f in enumerate(feats):
+                buf[j, :, :lengths[j]].copy_(f)
+
+        ins = (((B, self._arch.input_channels, L_pad), torch.float32, fill_feats),
+               ((B,), torch.int32, lambda lens: lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)))
+        outs = (((B, self._wave_len(L_pad)), torch.float32, True),)
+
+        def call():
+            # checked on every attempt: a range fallback inside _guarded can put a decoder site on fp32
+            if not self._decode_mixed_route_ok():
+                raise _OffRoute()
+            return self._call(lib.wt_decode_mixed, _capi.WT_PLAN_DECODE_MIXED, B, L_pad, self._graph_flags(B), dev, ins, outs, (bw,))
+
+        try:
+            return self._guarded(dev, call, self._is_strict(B))[0]
+        except _OffRoute:
+            return None
+
+    def _decode_mixed_route_ok(self) -> bool:
+        """Whether the decoder runs the route a mixed-length plan takes (the shipped split-f16 one): no fp32 GEMMs, no unfused
+        debug plan, no debug taps or range report, no decoder range site on fp32, and weights that fit the split-f16 form
+        (the conditions build_decode checks; a plan refused in spite of them is an error, not a fallback)."""
+        off_route = (_capi.WT_PLAN_FLAG_FP32_GEMM | _capi.WT_PLAN_FLAG_UNFUSED | _capi.WT_PLAN_FLAG_KEEP_STAGES |
+                     _capi.WT_PLAN_FLAG_RANGE_REPORT)
+        return (not (self._plan_flags & off_route) and not self._sites(_capi.WT_PLAN_DECODE_MIXED) and
+                bool(lib.wt_model_split_ok(self._engine.model)))
+
+    @torch.inference_mode()
+    def decode_many(self, features: Sequence[torch.Tensor], bandwidth_id=None) -> List[torch.Tensor]:
+        """decode over clips of different lengths (the reference's infer.py loop, one call per file) in a few batched calls:
+        features[i] is (512, L_i) or (1, 512, L_i) with L_i >= 1; returns [(1, wave_len(L_i))] in input order, each the same
+        bits as decode(features[i][None], bandwidth_id=...), whatever the other clips and the grouping.  Clips are sorted by
+        length and grouped (mixed_length.group_frames: at most 64 per call and at most MAX_SCORE_CELLS attention score cells,
+        padded to a coarse bucket so that calls share plans and graphs).  A clip that forms a group alone, and every clip while
+        the decoder runs off its shipped route (set_gemm_precision("f32"), an fp32 decoder site after a range fallback, the
+        unfused debug plans), goes through decode."""
+        from .mixed_length import group_frames
+        dev = self._ensure_engine()
+        bw = self._bandwidth_index(bandwidth_id)
+        feats: List[torch.Tensor] = []
+        for f in features:
+            if isinstance(f, torch.Tensor) and f.dim() == 3 and f.shape[0] == 1:
+                f = f[0]
+            if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] != self._arch.input_channels or f.shape[1] < 1:
+                raise ValueError("decode_many takes a sequence of tensors (512, L) or (1, 512, L) with L >= 1")
+            feats.append(self._as_input(f, dev))
+        out: List[Optional[torch.Tensor]] = [None] * len(feats)
+        solo: List[int] = []
+        min_frames = 1 if self._arch.padding == "same" else 2      # (decode raises for a 'center' clip of one frame)
+        for L_pad, idx in group_frames([int(f.shape[1]) for f in feats]):
+            if len(idx) == 1 or int(feats[idx[0]].shape[1]) < min_frames:
+                solo.extend(idx)
+                continue
+            wav = self._run_decode_mixed([feats[i] for i in idx], L_pad, bw, dev)
+            if wav is None:
+                solo.extend(idx)
+                continue
+            for j, i in enumerate(idx):
+                out[i] = wav[j:j + 1, :self._wave_len(int(feats[i].shape[1]))].clone()
+        for i in sorted(solo):
+            out[i] = self.decode(feats[i][None], bandwidth_id=bw)
+        return out  # type: ignore[return-value]
+
     def _run_head(self, x: torch.Tensor) -> torch.Tensor:
         dev = self._ensure_engine()
         assert x.dim() == 3 and x.shape[2] == self._arch.dim, "expected the backbone output (B, L, dim)"

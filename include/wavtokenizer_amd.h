@@ -328,7 +328,11 @@ int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, 
  * Pro enums (the argmax epilogue is reached through wt_vq_nearest instead).  C (and C2) are written in the format
  * `out` names (S32: 128-byte groups [32 x f16 hi | 32 x f16 lo]).  status: optional device word that the S32
  * producers OR WT_STATUS_BIT_RANGE into.  The whole descriptor is checked before any HIP call: a problem the
- * launchers refuse returns WT_ERR_INVALID and touches no memory.  form (optional): the launch the launcher chose. */
+ * launchers refuse returns WT_ERR_INVALID and touches no memory.  form (optional): the launch the launcher chose.
+ * mix_geom (optional, engine 0): the mixed-length launch of a WT_PLAN_FLAG_MIXED_LENGTH plan.  It points at clip 0's
+ * {T_in, Tp, T_out} triple of this conv in a device geometry table (wt_geometry_probe; clip stride wt_geom_words.words); the
+ * descriptor's extents are then the padded ones, a clip's rows below its T_out gather reflect-about-Tp positions below its
+ * T_in, and its rows past T_out gather nothing.  Every clip's T_in must be at most the descriptor's. */
 typedef struct {
     int32_t size;                   /* sizeof(wt_gemm_desc) */
     int32_t engine, epi, out, pro, b_is_act;
@@ -346,6 +350,7 @@ typedef struct {
     float* C;
     float* C2;
     uint32_t* status;
+    const int32_t* mix_geom;        /* optional, last: `size` may also be the struct's size without it (then NULL) */
 } wt_gemm_desc;
 typedef struct {
     int32_t BM, BN, waves_m, waves_n, stages, ks, prod, staged, bias_cache, G, tiles;   /* G < tiles: persistent grid */
@@ -424,6 +429,51 @@ int wt_resblock(const float* x, const float* wav, const float* e0_w, const float
 int wt_resblock_down(const float* wav, const float* e0_w, const float* e0_b, const float* w3, const float* b3, const float* w1,
                      const float* b1, const float* ws, const float* bs, const float* wd, const float* bd, float* y_down,
                      int32_t B, int64_t T, int32_t r, void* stream);
+
+/* One launch of a fused resblock kernel through the plans' own launchers, with the launch it chose reported: wt_resblock
+ * (r = 0) and wt_resblock_down (r = 2 or 4: wd, bd set, y = y_down, elu_out / out_s32 ignored) behind one descriptor, the
+ * arrays as described there.  status: optional device word that the split-f16 conversions OR WT_STATUS_BIT_RANGE into.
+ * mix_T / mix_Tread (optional, both or none; resblock16.hip only): the mixed-length launch of a WT_PLAN_FLAG_MIXED_LENGTH plan:
+ * clip 0's length word and readable-length word in a device geometry table (wt_geometry_probe; clip stride
+ * wt_geom_words.words).  T is then the padded length (the row stride of x / wav / y, of y_down through ceil(T / r)) and every
+ * clip's own length must lie in [1, T] (r != 0: [1024, T]); rows past a clip's length are neither read nor written.
+ * The descriptor is checked before any HIP call: whatever a launcher refuses returns WT_ERR_INVALID with its message. */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_resblock_desc) */
+    int32_t B, T, C, r;
+    int32_t elu_out, out_s32, fp32_chain;
+    const float *x, *wav, *e0_w, *e0_b, *w3, *b3, *w1, *b1, *ws, *bs, *wd, *bd;
+    float* y;
+    uint32_t* status;
+    const int32_t *mix_T, *mix_Tread;
+} wt_resblock_desc;
+typedef struct {
+    int32_t kernel;                 /* 0 resblock16_kernel, 1 resblock16_mixed_kernel, 2 resblock_kernel (fp32 chain) */
+    int32_t C, fold, down, fpw;     /* the instantiation: channels, first conv folded in, down-conv stride (0: none), frames per wave */
+    int32_t grid, block, lds, tiles;    /* lds: dynamic LDS bytes; grid < tiles: the persistent loop wraps */
+} wt_resblock_form;
+int wt_resblock_probe(const wt_resblock_desc* d, wt_resblock_form* form, void* stream);
+
+/* The geometry step of a WT_PLAN_FLAG_MIXED_LENGTH encode plan on its own: from lengths (device int32 [B]) the table
+ * geom (device int32 [B][words]) of every conv's {T_in, Tp, T_out} along a chain of n_stages encoder stages (k3 conv, 1x1
+ * shortcut, down conv of kernel size kd[s] and stride rd[s]) and the final conv of kernel size kf, as a plan of padded length
+ * Tpad and shortest clip tmin writes it.  A length outside [tmin, Tpad] gives the geometry of tmin with a readable length 0.
+ * wt_geometry_words: the word offsets inside a clip's entry: stage s starts at stage0 + s * stage_words, its three triples at
+ * c3, sc and down from there; `final_conv` is the final conv's triple and L the clip's frame count. */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_geom_desc) */
+    int32_t B, tmin, n_stages;
+    int32_t kd[8], rd[8];           /* n_stages entries are read; 8 as wt_arch.ratios holds, the table itself takes max_stages (6) */
+    int32_t kf;
+    int64_t Tpad;
+    const int32_t* lengths;
+    int32_t* geom;
+} wt_geom_desc;
+typedef struct {
+    int32_t words, valid, T, Tread, stage0, stage_words, c3, sc, down, final_conv, L, max_stages;
+} wt_geom_words;
+int wt_geometry_words(int32_t n_stages, wt_geom_words* out);
+int wt_geometry_probe(const wt_geom_desc* d, void* stream);
 
 /* Runs a WT_PLAN_UNIT_LSTM plan: x, y [B][L][512] fp32 time-major; y = SLSTM(x) (encoder/modules/lstm.py:31-39) with
  * the encoder's LSTM weights of the plan's model. */

@@ -24,6 +24,7 @@ EXPORTS = [
     "wt_vq_nearest", "wt_vq_nearest_f32", "wt_resblock", "wt_resblock_down", "wt_gemm_probe_workspace_bytes", "wt_gemm_probe", "wt_op_probe",
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
+    "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -63,7 +64,7 @@ class WtGemmDesc(ctypes.Structure):
                 + [("alpha", c_float)]
                 + [(n, c_int64) for n in ("a_bstride", "a_rstride", "a2_bstride", "a2_rstride", "w_rstride", "c_rstride",
                                          "r_rstride", "zA", "zW", "zC")]
-                + [(n, c_void_p) for n in ("A", "A2", "B", "bias", "R", "gamma", "C", "C2", "status")])
+                + [(n, c_void_p) for n in ("A", "A2", "B", "bias", "R", "gamma", "C", "C2", "status", "mix_geom")])
 
 
 class WtLaunchForm(ctypes.Structure):
@@ -88,6 +89,28 @@ class WtOpDesc(ctypes.Structure):
 
 class WtOpForm(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("kernel", "variant", "variant2", "grid_x", "grid_y", "grid_z", "block", "lds")]
+
+
+class WtResblockDesc(ctypes.Structure):
+    """wt_resblock_desc: one fused resblock launch through the plans' launchers (wt_resblock_probe)."""
+    _fields_ = ([(n, c_int32) for n in ("size", "B", "T", "C", "r", "elu_out", "out_s32", "fp32_chain")]
+                + [(n, c_void_p) for n in ("x", "wav", "e0_w", "e0_b", "w3", "b3", "w1", "b1", "ws", "bs", "wd", "bd", "y", "status",
+                                          "mix_T", "mix_Tread")])
+
+
+class WtResblockForm(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("kernel", "C", "fold", "down", "fpw", "grid", "block", "lds", "tiles")]
+
+
+class WtGeomDesc(ctypes.Structure):
+    """wt_geom_desc: the geometry step of a mixed-length encode plan on its own (wt_geometry_probe)."""
+    _fields_ = [("size", c_int32), ("B", c_int32), ("tmin", c_int32), ("n_stages", c_int32), ("kd", c_int32 * 8), ("rd", c_int32 * 8),
+                ("kf", c_int32), ("Tpad", c_int64), ("lengths", c_void_p), ("geom", c_void_p)]
+
+
+class WtGeomWords(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("words", "valid", "T", "Tread", "stage0", "stage_words", "c3", "sc", "down", "final_conv",
+                                       "L", "max_stages")]
 
 
 class WavTokError(RuntimeError):
@@ -184,6 +207,9 @@ def _load() -> ctypes.CDLL:
     lib.wt_gemm_probe_workspace_bytes.restype = c_size_t
     lib.wt_gemm_probe.argtypes = [POINTER(WtGemmDesc), POINTER(WtLaunchForm), c_void_p, c_void_p]
     lib.wt_op_probe.argtypes = [POINTER(WtOpDesc), POINTER(WtOpForm), c_void_p]
+    lib.wt_resblock_probe.argtypes = [POINTER(WtResblockDesc), POINTER(WtResblockForm), c_void_p]
+    lib.wt_geometry_words.argtypes = [c_int32, POINTER(WtGeomWords)]
+    lib.wt_geometry_probe.argtypes = [POINTER(WtGeomDesc), c_void_p]
     lib.wt_resampler_create.argtypes = [c_int32, c_int32, c_int32, POINTER(c_void_p)]
     lib.wt_resampler_destroy.argtypes = [c_void_p]
     lib.wt_resampler_destroy.restype = None

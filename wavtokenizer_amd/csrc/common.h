@@ -65,9 +65,17 @@ struct OpForm {
     unsigned block = 0;
     unsigned lds = 0;            // dynamic LDS bytes
 };
+// rb_form: when set (wt_resblock_probe), a resblock launcher records the launch it chose
+struct RbForm {
+    int kernel = -1;             // 0 resblock16_kernel, 1 resblock16_mixed_kernel, 2 resblock_kernel (fp32 chain)
+    int C = 0, fold = 0, down = 0, fpw = 0;      // template values (fp32 chain: fpw = 32, fold = the waveform was given)
+    unsigned grid = 0, block = 0, lds = 0;       // lds: dynamic LDS bytes
+    long tiles = 0;              // grid < tiles: the persistent loop wraps
+};
 struct LaunchCtx {
     unsigned* status = nullptr;
     OpForm* form = nullptr;
+    RbForm* rb_form = nullptr;
     unsigned long long* stamp_start = nullptr;
     unsigned long long* stamp_end = nullptr;
     bool stamp_used = false;

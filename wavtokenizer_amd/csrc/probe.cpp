@@ -1,5 +1,6 @@
 // Entry points that launch kernels outside a plan: wt_codes_to_features, the single-stage calls and the probes through
-// which the tests reach every GEMM form (wt_gemm_probe) and every non-GEMM kernel (wt_op_probe) on its own.
+// which the tests reach every GEMM form (wt_gemm_probe), every non-GEMM kernel (wt_op_probe), the fused resblocks
+// (wt_resblock_probe) and the mixed-length geometry step (wt_geometry_probe) on their own.
 #include "model.h"
 
 using namespace wt;
@@ -87,9 +88,16 @@ static ProbeLayout probe_layout(const wt_gemm_desc& d) {
     L.total = L.oScale + 256;
     return L;
 }
+// mix_geom is the descriptor's last field and optional: `size` may also be the struct's size without it (then NULL)
+static bool gemm_desc_size_ok(const wt_gemm_desc* d) {
+    return d && (d->size == (int32_t)sizeof(wt_gemm_desc) || d->size == (int32_t)offsetof(wt_gemm_desc, mix_geom));
+}
+static const int32_t* gemm_desc_mix(const wt_gemm_desc* d) { return d->size == (int32_t)sizeof(wt_gemm_desc) ? d->mix_geom : nullptr; }
 // the descriptor as the launchers' arguments; every check that needs no HIP call (the launchers' own included)
 static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
-    if (!d || d->size != (int32_t)sizeof(wt_gemm_desc)) { set_error("wt_gemm_probe: descriptor missing or of another size"); return WT_ERR_INVALID; }
+    if (!gemm_desc_size_ok(d)) { set_error("wt_gemm_probe: descriptor missing or of another size"); return WT_ERR_INVALID; }
+    const int32_t* mix = gemm_desc_mix(d);
+    if (mix && (d->engine != 0 || (reinterpret_cast<uintptr_t>(mix) & 3))) { set_error("wt_gemm_probe: mix_geom is a 4-byte aligned device table for gemm16s"); return WT_ERR_INVALID; }
     if (d->engine != 0 && d->engine != 1) { set_error("wt_gemm_probe: engine is 0 (gemm16s) or 1 (gemm)"); return WT_ERR_INVALID; }
     if (!d->A || !d->B || !d->C) { set_error("wt_gemm_probe: A, B and C are required"); return WT_ERR_INVALID; }
     if (d->epi == EPI_ARGMAX) { set_error("wt_gemm_probe: the argmax epilogue is reached through wt_vq_nearest"); return WT_ERR_INVALID; }
@@ -121,11 +129,11 @@ static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
     a.A2 = d->A2 ? reinterpret_cast<const float*>(ws + L.oA2) : nullptr;
     a.W = d->B; a.W_hi = ws + L.oB;
     a.status = reinterpret_cast<unsigned*>(d->status);
-    return check_gemm16s(a, d->epi, d->out) ? WT_ERR_INVALID : WT_OK;
+    return check_gemm16s(a, d->epi, d->out, mix) ? WT_ERR_INVALID : WT_OK;
 }
 
 size_t wt_gemm_probe_workspace_bytes(const wt_gemm_desc* d) {
-    if (!d || d->size != (int32_t)sizeof(wt_gemm_desc) || d->engine != 0 || d->M <= 0 || d->T_out <= 0 || d->nz < 1) return 0;
+    if (!gemm_desc_size_ok(d) || d->engine != 0 || d->M <= 0 || d->T_out <= 0 || d->nz < 1) return 0;
     return probe_layout(*d).total;
 }
 
@@ -163,7 +171,7 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
         if (int rc = launch_split_s32(d->B, ws + L.oB, L.nB, s, scale != 1.f ? scale_dev : nullptr)) return rc;
         if (int rc = launch_split_s32(d->A, ws, L.nA, s)) return rc;
         if (d->A2) if (int rc = launch_split_s32(d->A2, ws + L.oA2, L.nA2, s)) return rc;
-        if (int rc = launch_gemm16s(a, d->epi, d->out, s)) return rc;
+        if (int rc = launch_gemm16s(a, d->epi, d->out, s, gemm_desc_mix(d))) return rc;
     }
     if (form) *form = wt_launch_form{lf.BM, lf.BN, lf.waves_m, lf.waves_n, lf.stages, lf.ks, lf.prod, lf.staged, lf.bias_cache, lf.G, lf.tiles};
     return WT_OK;
@@ -370,5 +378,65 @@ int wt_resblock_down(const float* wav, const float* e0_w, const float* e0_b, con
     return launch_resblock16_down(a, static_cast<hipStream_t>(stream));
 }
 
+// wt_geometry_words: the table layout of common.h (GEOM_*, geom_final, geom_L) for a chain of n_stages encoder stages
+int wt_geometry_words(int32_t n_stages, wt_geom_words* out) {
+    if (!out || n_stages < 1 || n_stages > GEOM_MAX_STAGES) { set_error("wt_geometry_words: 1 to " + std::to_string((int)GEOM_MAX_STAGES) + " encoder stages"); return WT_ERR_INVALID; }
+    *out = wt_geom_words{GEOM_WORDS, GEOM_VALID, GEOM_T, GEOM_TREAD, GEOM_STAGE0, GEOM_STAGE_WORDS, GEOM_C3, GEOM_SC, GEOM_DOWN,
+                         geom_final(n_stages), geom_L(n_stages), GEOM_MAX_STAGES};
+    return WT_OK;
+}
+
+int wt_geometry_probe(const wt_geom_desc* d, void* stream) {
+    static_assert(GEOM_MAX_STAGES <= (int)(sizeof(wt_geom_desc::kd) / sizeof(int32_t)), "wt_geom_desc holds every stage the table can");
+    auto bad = [](const char* m) { set_error(std::string("wt_geometry_probe: ") + m); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_geom_desc)) return bad("descriptor missing or of another size");
+    if (!d->lengths || !d->geom || (reinterpret_cast<uintptr_t>(d->lengths) & 3) || (reinterpret_cast<uintptr_t>(d->geom) & 3)) return bad("lengths and geom are 4-byte aligned device arrays");
+    if (d->B < 1 || d->tmin < 1 || d->Tpad < d->tmin || d->Tpad >= (int64_t)INT_MAX) return bad("needs B >= 1 and 1 <= tmin <= Tpad < 2^31");
+    if (d->n_stages < 1 || d->n_stages > GEOM_MAX_STAGES) return bad(("1 to " + std::to_string((int)GEOM_MAX_STAGES) + " encoder stages").c_str());
+    for (int i = 0; i < d->n_stages; ++i)
+        if (d->rd[i] < 1 || d->kd[i] < d->rd[i]) return bad("a stage's down conv needs kernel size >= stride >= 1");
+    if (d->kf < 1) return bad("the final conv needs a kernel size");
+    if (int rc = launch_mixed_geometry(d->lengths, d->geom, d->B, d->Tpad, d->tmin, d->n_stages, d->kd, d->rd, d->kf,
+                                       static_cast<hipStream_t>(stream))) return rc < -1 ? rc : (int)WT_ERR_INVALID;
+    return WT_OK;
+}
+
+// wt_resblock_probe: every check that needs no HIP call; the launchers' own refusals come back through their return value,
+// which they decide before their first HIP call
+int wt_resblock_probe(const wt_resblock_desc* d, wt_resblock_form* form, void* stream) {
+    auto bad = [](const char* m) { set_error(std::string("wt_resblock_probe: ") + m); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_resblock_desc)) return bad("descriptor missing or of another size");
+    const bool down = d->r != 0;
+    if (!d->w3 || !d->b3 || !d->w1 || !d->b1 || !d->ws || !d->bs || !d->y) return bad("null argument");
+    if (!d->x && !d->wav) return bad("needs x or the waveform");
+    if (d->wav && (!d->e0_w || !d->e0_b)) return bad("the folded first conv needs its weights");
+    if (down && (!d->wav || !d->wd || !d->bd)) return bad("the fused down conv needs the waveform and its weights");
+    if (d->B < 1 || d->T < 1 || (long)d->B * d->T >= (long)INT_MAX) return bad("bad shape");
+    if (d->fp32_chain && (d->out_s32 || down || d->mix_T || d->mix_Tread)) return bad("the fp32 kernel writes fp32, has no down conv and no mixed-length form");
+    if ((d->mix_T != nullptr) != (d->mix_Tread != nullptr)) return bad("a mixed-length launch needs both length words");
+    const void* p4[] = {d->wav, d->e0_w, d->e0_b, d->b3, d->b1, d->bs, d->bd, d->status, d->mix_T, d->mix_Tread};
+    for (const void* p : p4) if (reinterpret_cast<uintptr_t>(p) & 3) return bad("arrays must be 4-byte aligned");
+    const void* p16[] = {d->x, d->w3, d->w1, d->ws, d->wd, d->y};
+    for (const void* p : p16) if (reinterpret_cast<uintptr_t>(p) & 15) return bad("x, y and the conv weights must be 16-byte aligned");
+    ResblockArgs a{};
+    a.x = d->wav ? nullptr : d->x; a.wav = d->wav; a.e0_w = d->e0_w; a.e0_b = d->e0_b;
+    a.W3 = d->w3; a.b3 = d->b3; a.W1 = d->w1; a.b1 = d->b1; a.Ws = d->ws; a.bs = d->bs;
+    a.B = d->B; a.T = d->T; a.C = d->C;
+    if (down) { a.Wd = d->wd; a.bd = d->bd; a.y_down = d->y; a.R = d->r; }
+    else { a.y = d->y; a.elu_out = d->elu_out ? 1 : 0; a.out_s32 = d->out_s32 ? 1 : 0; }
+    ResblockMix mix;
+    mix.T = d->mix_T; mix.Tread = d->mix_Tread;
+    const ResblockMix* mp = d->mix_T ? &mix : nullptr;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RbForm lf;
+    const LaunchCtx saved = g_launch;
+    g_launch.status = reinterpret_cast<unsigned*>(d->status);
+    g_launch.rb_form = &lf;
+    const int rc = d->fp32_chain ? launch_resblock(a, s) : down ? launch_resblock16_down(a, s, mp) : launch_resblock16(a, s, mp);
+    g_launch = saved;
+    if (rc) return rc;
+    if (form) *form = wt_resblock_form{lf.kernel, lf.C, lf.fold, lf.down, lf.fpw, (int32_t)lf.grid, (int32_t)lf.block, (int32_t)lf.lds, (int32_t)lf.tiles};
+    return WT_OK;
+}
 
 }  // extern "C"

@@ -246,6 +246,7 @@ static int launch_rb(const ResblockArgs& a, hipStream_t s) {
     const int per_cu = (int)(160 * 1024 / smem) < 4 ? (int)(160 * 1024 / smem) : 4;
     const long slots = (long)device_cus() * per_cu;
     const long grid = tiles < slots ? tiles : slots;
+    if (RbForm* f = g_launch.rb_form) *f = RbForm{2, C, a.wav ? 1 : 0, 0, 32, (unsigned)grid, (unsigned)(ROWS * 2), (unsigned)smem, tiles};
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(ROWS * 2), smem, s, a);
     WT_HIP_CHECK(hipGetLastError());
     return 0;

@@ -152,6 +152,7 @@ static int launch_rb16(const ResblockArgs& a, hipStream_t s, const ResblockMix* 
     ResblockArgs b = a;
     b.dbg = dbg_req;
     if (!b.status) b.status = g_launch.status;
+    if (RbForm* f = g_launch.rb_form) *f = RbForm{MIX ? 1 : 0, C, FOLD, 0, FPW, (unsigned)grid, (unsigned)(ROWS / FPW * 64), (unsigned)smem, tiles};
     if constexpr (MIX)
         hipLaunchKernelGGL((resblock16_mixed_kernel<C, ROWS, FOLD, false, 0, FPW>), dim3((unsigned)grid), dim3(ROWS / FPW * 64), smem, s, b, *mix);
     else
@@ -192,6 +193,7 @@ static int launch_rb16_down(const ResblockArgs& a, hipStream_t s, const Resblock
     ResblockArgs b = a;
     b.dbg = dbg_req;
     if (!b.status) b.status = g_launch.status;
+    if (RbForm* f = g_launch.rb_form) *f = RbForm{MIX ? 1 : 0, 32, 1, R, 32, (unsigned)grid, 256u, (unsigned)smem, tiles};
     if constexpr (MIX)
         hipLaunchKernelGGL((resblock16_mixed_kernel<32, 128, 1, false, R>), dim3((unsigned)grid), dim3(256), smem, s, b, *mix);
     else

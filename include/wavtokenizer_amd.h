@@ -26,6 +26,8 @@
  *     (wt_plan_status, wt_model_status): a caller that makes a new plan per input length still meets it.
  *   - activations inside the library are time-major [clip][frame][channel] fp32; the API
  *     tensors keep the reference's layouts (wav (B,T); features (B,512,L); codes (K,B,L) int64).
+ *   - a decoder that holds codes calls wt_decode_codes / wt_decode_codes_mixed: the codebook rows are gathered straight into
+ *     the plan's first operand, and no (B,512,L) feature tensor exists (wt_codes_to_features + wt_decode computes the same bits).
  */
 #ifndef WAVTOKENIZER_AMD_H
 #define WAVTOKENIZER_AMD_H
@@ -91,7 +93,10 @@ typedef enum {
     WT_PLAN_SEANET_DECODER = 2,  /* features (B,512,L) -> audio (B,1,L*hop): encodec.decoder   */
     WT_PLAN_HEAD = 3,            /* backbone output (B,L,dim) -> audio (B, L*hop): model.head   */
     WT_PLAN_UNIT_LSTM = 4,       /* unit tests: x [B][L][512] -> SLSTM(x) [B][L][512], time-major (wt_unit_run) */
-    WT_PLAN_DECODE_MIXED = 5     /* features (B,512,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_mixed; `len` = Lpad */
+    WT_PLAN_DECODE_MIXED = 5,    /* features (B,512,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_mixed; `len` = Lpad */
+    WT_PLAN_DECODE_CODES = 6,    /* codes (K,B,L) -> audio (B, L*hop): wt_decode_codes; WT_PLAN_DECODE with its first step (the transpose
+                                    of the features) replaced by the gather of the codebook rows; `len` = L */
+    WT_PLAN_DECODE_CODES_MIXED = 7   /* codes (K,B,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_codes_mixed; `len` = Lpad */
 } wt_plan_kind;
 
 enum {
@@ -164,7 +169,7 @@ int  wt_device_info(int32_t device, int32_t* compute_units, int32_t* is_gfx950, 
 int64_t wt_model_weight_bytes(const wt_model* m);     /* packed fp32 bytes resident in HBM */
 
 /* A plan fixes (kind, B, T or L): kernel launch list + workspace layout.
- * `len` = T (samples) for WT_PLAN_ENCODE, L (frames) for the two decode kinds. */
+ * `len` = T (samples) for WT_PLAN_ENCODE, L (frames) for every other kind. */
 int    wt_plan_create(const wt_model* m, int32_t kind, int32_t B, int64_t len, int32_t flags, wt_plan** out);
 /* ... with a mask of range sites (wt_range_site) that keep fp32 operands and run their GEMMs on the fp32 MFMA chain while
  * every other site stays on the split-f16 kernel: the answer to WT_ERR_RANGE that costs one block, not the model. */
@@ -267,6 +272,28 @@ int wt_decode(const wt_plan* p, const float* features, int32_t bandwidth_id, flo
  * RANGE_REPORT and with any fp32 range site.  wt_decode refuses a mixed-length plan, and wt_decode_mixed every other plan. */
 int wt_decode_mixed(const wt_plan* p, const float* features, const int32_t* lengths, int32_t bandwidth_id, float* wav_out,
                     void* workspace, void* stream);
+
+/* Replaces: WavTokenizer.decode(WavTokenizer.codes_to_features(codes)) (decoder/pretrained.py:192-239) in one call on a
+ * WT_PLAN_DECODE_CODES plan (B, L): the bits of wt_codes_to_features followed by wt_decode, without the (B,512,L) feature tensor
+ * (the plan's first step gathers the codebook rows, summed over the K codebooks in their order, into the operand of
+ * backbone.embed; every later step is the WT_PLAN_DECODE plan's).  The plan takes every flag and range site a WT_PLAN_DECODE
+ * plan takes; its creation fails when input_channels differs from the codebook width.
+ *   codes [K][B][L] int64 (device), 1 <= K <= num_quantizers (an argument of the call, not of the plan: a recorded graph is
+ *   keyed by it); bandwidth_id, wav_out, backbone_out as for wt_decode.
+ * A code outside [0, bins) is never used as an index: the frame's row becomes NaN, so that clip's waveform is NaN (the other
+ * clips and the call's status are not affected), and wt_model_take_bad_codes reports it once the stream work has completed. */
+int wt_decode_codes(const wt_plan* p, const int64_t* codes, int32_t K, int32_t bandwidth_id, float* wav_out,
+                    float* backbone_out, void* workspace, void* stream);
+
+/* The same for clips of different lengths on a WT_PLAN_DECODE_CODES_MIXED plan (B, Lpad): clip b is lengths[b] frames long and
+ * gets exactly the waveform wt_decode_codes computes for it alone, whatever the other clips, the padded length and the contents
+ * of `codes` past its frames (those are never read, range-checked or reported).
+ *   codes [K][B][Lpad] int64 (device); lengths, wav_out and the poisoning of a call with a length outside [1, Lpad] as for
+ *   wt_decode_mixed.
+ * The plan runs the shipped split-f16 route only, like WT_PLAN_DECODE_MIXED (same refusals at creation).  wt_decode_codes refuses
+ * a mixed-length plan, and wt_decode_codes_mixed every other plan. */
+int wt_decode_codes_mixed(const wt_plan* p, const int64_t* codes, int32_t K, const int32_t* lengths, int32_t bandwidth_id,
+                          float* wav_out, void* workspace, void* stream);
 
 /* Replaces: ISTFTHead.forward (decoder/heads.py:42-67) + ISTFT.forward (decoder/spectral_ops.py:33-75) on its own,
  * reached by callers as model.head(x).  x [B][L][dim] fp32 (the backbone output), wav_out [B][L*hop] ("center":
@@ -377,22 +404,30 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
  *   CONVTR     x [B][L][C], p0 w [k][C][Cout], p1 bias [Cout] -> y [B][L * stride][Cout]; flag = ELU on the input
  *   ROW_SUMSQ  x [n][C] -> y [n]
  *   S32_AMAX   x S32 array of n values -> y: one uint32 word, atomic max of the bit pattern of max |value|
- * lengths (optional; GN_APPLY, GN_STATS, ROWNORM mode 0, SOFTMAX, ISTFT_OLA, TRANSPOSE): device int32 [B] (SOFTMAX: n / L clips of
- * L query rows each; TRANSPOSE: of the C frames).  The op then runs its length-aware launch (the kernels of a WT_PLAN_DECODE_MIXED
+ *   CODE_ROWS  x codes int64 [k][B][L], p0 table [k * n][C] (k codebooks of n bins) -> y [B][L][C] (out_s32: S32 rows): row (b, t)
+ *              = sum over the k codebooks of their row codes[.][b][t], in codebook order; a code outside [0, n) gives a NaN
+ *              row and sets y2 (optional: one uint32 word the device can write) to 1; C % 4 == 0, C <= 1024
+ * lengths (optional; GN_APPLY, GN_STATS, ROWNORM mode 0, SOFTMAX, ISTFT_OLA, TRANSPOSE, CODE_ROWS): device int32 [B] (SOFTMAX: n / L
+ * clips of L query rows each; TRANSPOSE: of the C frames; CODE_ROWS: codes past a clip's length are never read).  The op then runs its length-aware launch (the kernels of a WT_PLAN_DECODE_MIXED
  * plan): the extents are the padded ones, clip b's reductions run over its own lengths[b] rows in the order of a call of that
  * length, and its output rows (ISTFT_OLA: samples) past them are zeros.
  * status: optional device word that the S32 producers OR WT_STATUS_BIT_RANGE into (the launch context's status word is
  * set for the call and restored).  The descriptor is checked before any HIP call: whatever the launcher refuses returns
  * WT_ERR_INVALID with its message and touches no memory.  form (optional): the launch the launcher chose. */
 enum { WT_OP_GN_APPLY = 0, WT_OP_GN_STATS = 1, WT_OP_ROWNORM = 2, WT_OP_SOFTMAX = 3, WT_OP_ISTFT_OLA = 4, WT_OP_CONV_FIRST = 5,
-       WT_OP_CONV_LAST = 6, WT_OP_TRANSPOSE = 7, WT_OP_CONVTR = 8, WT_OP_ROW_SUMSQ = 9, WT_OP_S32_AMAX = 10 };
+       WT_OP_CONV_LAST = 6, WT_OP_TRANSPOSE = 7, WT_OP_CONVTR = 8, WT_OP_ROW_SUMSQ = 9, WT_OP_S32_AMAX = 10,
+       /* 11 is not assigned and stays refused as unknown: callers written against the ops above probe it as the first op id
+          the library does not know, with a descriptor that CODE_ROWS would otherwise take */
+       WT_OP_CODE_ROWS = 12 };
 /* wt_op_form.kernel */
 enum { WT_OPK_GN_TILE = 1, WT_OPK_GN_CHUNK = 2, WT_OPK_GN_STATS = 3, WT_OPK_ROWNORM = 4, WT_OPK_DWCONV_LN = 5,
        WT_OPK_SOFTMAX_REG = 6, WT_OPK_SOFTMAX_RMW = 7, WT_OPK_ISTFT_OLA = 8, WT_OPK_CONV_FIRST = 9, WT_OPK_CONV_LAST32 = 10,
        WT_OPK_CONV_LAST = 11, WT_OPK_TRANSPOSE = 12, WT_OPK_CONVTR = 13, WT_OPK_ROW_SUMSQ = 14, WT_OPK_S32_AMAX = 15,
        /* the length-aware launches (wt_op_desc.lengths) */
        WT_OPK_TRANSPOSE_MIXED = 16, WT_OPK_GN_MIXED = 17, WT_OPK_DWCONV_LN_MIXED = 18, WT_OPK_SOFTMAX_REG_MIXED = 19,
-       WT_OPK_SOFTMAX_RMW_MIXED = 20, WT_OPK_ISTFT_OLA_MIXED = 21 };
+       WT_OPK_SOFTMAX_RMW_MIXED = 20, WT_OPK_ISTFT_OLA_MIXED = 21,
+       /* the gather of the decode-from-codes plans and its length-aware twin */
+       WT_OPK_CODE_ROWS = 22, WT_OPK_CODE_ROWS_MIXED = 23 };
 typedef struct {
     int32_t size;                   /* sizeof(wt_op_desc) */
     int32_t op;
@@ -409,7 +444,7 @@ typedef struct {
 } wt_op_desc;
 typedef struct {
     int32_t kernel;                 /* WT_OPK_* */
-    int32_t variant;                /* gn_*: APPLY / SWISH template value (gn_mixed: APPLY); rownorm, dwconv_ln: NV; softmax_reg: NV4 */
+    int32_t variant;                /* gn_*: APPLY / SWISH template value (gn_mixed: APPLY); rownorm, dwconv_ln, code_rows: NV; softmax_reg: NV4 */
     int32_t variant2;               /* dwconv_ln: R; rownorm: MODE; gn_tile: waves per group; gn_mixed: forms launched (bit 0 slab /
                                        stats kernel, bit 1 chunked pair) */
     int32_t grid_x, grid_y, grid_z, block, lds;     /* gn_chunk: the apply launch */
@@ -514,8 +549,8 @@ typedef struct {
 size_t wt_lstm_probe_workspace_bytes(const wt_lstm_desc* d);
 int wt_lstm_probe(const wt_model* m, const wt_lstm_desc* d, wt_lstm_form* form, void* workspace, void* stream);
 
-/* After wt_codes_to_features has completed on its stream: 1 if a call since the last query met a code outside
- * [0, bins) (the frames it touched were written as NaN), else 0; the flag is cleared. */
+/* After wt_codes_to_features, wt_decode_codes or wt_decode_codes_mixed has completed on its stream: 1 if a call since the last
+ * query met a code outside [0, bins) (the frames it touched were written as NaN), else 0; the flag is cleared. */
 int wt_model_take_bad_codes(const wt_model* m);
 
 /* ---- helpers on either side of the hot path ------------------------------------- */

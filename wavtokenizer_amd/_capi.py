@@ -25,10 +25,12 @@ EXPORTS = [
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
     "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe", "wt_lstm_probe_workspace_bytes", "wt_lstm_probe",
+    "wt_decode_codes", "wt_decode_codes_mixed",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
 WT_PLAN_DECODE_MIXED = 5
+WT_PLAN_DECODE_CODES, WT_PLAN_DECODE_CODES_MIXED = 6, 7
 WT_PLAN_FLAG_KEEP_STAGES = 1
 WT_PLAN_FLAG_FP32_GEMM = 2
 WT_PLAN_FLAG_STEP_LSTM = 4
@@ -73,10 +75,12 @@ class WtLaunchForm(ctypes.Structure):
 
 WT_OP_GN_APPLY, WT_OP_GN_STATS, WT_OP_ROWNORM, WT_OP_SOFTMAX, WT_OP_ISTFT_OLA, WT_OP_CONV_FIRST = 0, 1, 2, 3, 4, 5
 WT_OP_CONV_LAST, WT_OP_TRANSPOSE, WT_OP_CONVTR, WT_OP_ROW_SUMSQ, WT_OP_S32_AMAX = 6, 7, 8, 9, 10
+WT_OP_CODE_ROWS = 12             # (11 is unassigned: the library refuses it as unknown)
 WT_OPK_NAMES = {1: "gn_tile", 2: "gn_chunk", 3: "gn_stats", 4: "rownorm", 5: "dwconv_ln", 6: "softmax_reg", 7: "softmax_rmw",
                 8: "istft_ola", 9: "conv_first", 10: "conv_last32", 11: "conv_last", 12: "transpose", 13: "convtr",
                 14: "row_sumsq", 15: "s32_amax", 16: "transpose_mixed", 17: "gn_mixed", 18: "dwconv_ln_mixed",
-                19: "softmax_reg_mixed", 20: "softmax_rmw_mixed", 21: "istft_ola_mixed"}
+                19: "softmax_reg_mixed", 20: "softmax_rmw_mixed", 21: "istft_ola_mixed", 22: "code_rows", 23: "code_rows_mixed"}
+WT_OPK_CODE_ROWS, WT_OPK_CODE_ROWS_MIXED = 22, 23
 
 
 class WtOpDesc(ctypes.Structure):
@@ -198,6 +202,8 @@ def _load() -> ctypes.CDLL:
     lib.wt_encode.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.wt_encode_mixed.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.wt_decode_mixed.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.wt_decode_codes.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.wt_decode_codes_mixed.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
     lib.wt_plan_min_clip_length.argtypes = [c_void_p]
     lib.wt_plan_min_clip_length.restype = c_int64
     lib.wt_sconv_geometry.argtypes = [c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]

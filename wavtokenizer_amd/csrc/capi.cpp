@@ -190,6 +190,8 @@ static const PlanKind kPlanKinds[] = {
     {WT_PLAN_SEANET_DECODER, build_seanet_decoder, SITE_SEADEC, false, false},  {WT_PLAN_HEAD, build_head, SITE_HEAD, true, false},
     {WT_PLAN_UNIT_LSTM, build_unit_lstm, SITE_ENC, false, false},
     {WT_PLAN_DECODE_MIXED, build_decode, -1, true, false},      // build_decode with the clip lengths threaded to its steps
+    // build_decode with its first step replaced: bb.in gathered from the call's codes instead of transposed from its features
+    {WT_PLAN_DECODE_CODES, build_decode, -1, true, false},  {WT_PLAN_DECODE_CODES_MIXED, build_decode, -1, true, false},
 };
 
 int wt_plan_create_ex(const wt_model* m, int32_t kind, int32_t B, int64_t len, int32_t flags, uint64_t fp32_sites, wt_plan** out) {

@@ -55,11 +55,13 @@ enum OpKernel : int {
     OPK_NONE = 0, OPK_GN_TILE, OPK_GN_CHUNK, OPK_GN_STATS, OPK_ROWNORM, OPK_DWCONV_LN, OPK_SOFTMAX_REG, OPK_SOFTMAX_RMW,
     OPK_ISTFT_OLA, OPK_CONV_FIRST, OPK_CONV_LAST32, OPK_CONV_LAST, OPK_TRANSPOSE, OPK_CONVTR, OPK_ROW_SUMSQ, OPK_S32_AMAX,
     // the length-aware launches of a WT_PLAN_DECODE_MIXED plan (ops_kernel.inc, OPS_MIX 1)
-    OPK_TRANSPOSE_MIXED, OPK_GN_MIXED, OPK_DWCONV_LN_MIXED, OPK_SOFTMAX_REG_MIXED, OPK_SOFTMAX_RMW_MIXED, OPK_ISTFT_OLA_MIXED
+    OPK_TRANSPOSE_MIXED, OPK_GN_MIXED, OPK_DWCONV_LN_MIXED, OPK_SOFTMAX_REG_MIXED, OPK_SOFTMAX_RMW_MIXED, OPK_ISTFT_OLA_MIXED,
+    // the first step of the decode-from-codes plans (WT_PLAN_DECODE_CODES / _MIXED) and its length-aware twin
+    OPK_CODE_ROWS, OPK_CODE_ROWS_MIXED
 };
 struct OpForm {
     int kernel = OPK_NONE;       // OpKernel
-    int variant = 0;             // gn_*: the APPLY / SWISH template value (gn_mixed: APPLY); rownorm, dwconv_ln: NV; softmax_reg: NV4; else 0
+    int variant = 0;             // gn_*: the APPLY / SWISH template value (gn_mixed: APPLY); rownorm, dwconv_ln, code_rows: NV; softmax_reg: NV4; else 0
     int variant2 = 0;            // dwconv_ln: R; rownorm: MODE; gn_tile: waves per group; gn_mixed: forms launched (1 slab / stats, 2 chunked); else 0
     unsigned grid[3] = {0, 0, 0};
     unsigned block = 0;
@@ -334,6 +336,13 @@ int launch_vq_finalize(const float* pval, const int* pidx, int nparts, const flo
                        float* feat_ncl, int B, int L, int D, int bins, hipStream_t s);
 int launch_codes_to_features(const int64_t* codes, const float* embed, int K, int bins, int B, long L, int D,
                              float* feat_ncl, hipStream_t s, unsigned* bad = nullptr);
+// Codes [K][B][L] int64 -> y [B][L][C], one row per frame: the sum over k of table[(k * bins + code_k) * C ...] in the order and
+// rounding of codes_to_features_kernel, fp32 or S32 rows: what transpose(codes_to_features(codes)) leaves in a decode plan's
+// first buffer, without the (B, C, L) tensor in between.  A code outside [0, bins) makes its row NaN and sets *bad (optional,
+// host-mapped) to 1; C % 4 == 0, C <= 1024, S32 rows C % 32 == 0.  lens: frames at or past a clip's length are zero rows whose
+// codes are never read
+int launch_code_rows(const int64_t* codes, const float* table, int K, int bins, int B, int L, int C, float* y, hipStream_t s,
+                     int out_s32 = 0, unsigned* bad = nullptr, const int* lens = nullptr);
 // buffer fill as a kernel (hipMemsetAsync nodes misbehave under hipGraph replay: ops.hip); 16-byte aligned pointer and size
 int launch_fill_u32(void* p, unsigned value, size_t n_bytes, hipStream_t s);
 // last step of every plan: on a non-zero status word poison the outputs (codes = -1, floats = NaN) and publish the bits

@@ -158,6 +158,8 @@ struct RunCtx {
     float* aux;              // emb_out (encode) / backbone_out (decode)
     int bw_id;
     const int* lengths = nullptr;    // mixed-length encode / decode: the clip lengths in samples / frames (device int32 [B])
+    const int64_t* in_codes = nullptr;   // decode from codes (WT_PLAN_DECODE_CODES / _MIXED): codes [n_q][B][L] instead of in_f
+    int n_q = 0;                     // ... and the number of codebooks the call sums (an argument of the call, not of the plan)
 };
 // Range sites (wt_plan_create_ex, wt_plan_range_sites): the units in which a plan can leave the split-f16 (S32) form.  Every
 // S32 tensor is produced and consumed inside ONE site, so a site can run on fp32 operands (gemm.hip) on its own while the
@@ -252,8 +254,10 @@ struct wt_plan {
     struct GraphKey {
         const void *ws = nullptr, *in = nullptr, *out = nullptr, *codes = nullptr, *aux = nullptr, *lengths = nullptr;
         int bw = -1;
+        int K = 0;                        // decode from codes: a recording bakes the call's codebook count in
         bool operator==(const GraphKey& o) const {
-            return ws == o.ws && in == o.in && out == o.out && codes == o.codes && aux == o.aux && lengths == o.lengths && bw == o.bw;
+            return ws == o.ws && in == o.in && out == o.out && codes == o.codes && aux == o.aux && lengths == o.lengths && bw == o.bw &&
+                   K == o.K;
         }
     };
     mutable GraphKey graph_key, last_key;

@@ -238,6 +238,35 @@ int launch_transpose(const float* in, float* out, int B, int R, int C, hipStream
     return 0;
 }
 
+// ------------------------------------------------------------------------------------ code_rows
+template <int NV>
+static int launch_code_rows_nv(const int64_t* codes, const float* table, int K, int bins, int B, int L, int C, float* y,
+                               hipStream_t s, int out_s32, unsigned* bad, const int* lens) {
+    const dim3 grid((unsigned)(((long)B * L + 3) / 4));     // one wave per frame
+    if (lens) {
+        note_form(OPK_CODE_ROWS_MIXED, NV, 0, grid, 256);
+        hipLaunchKernelGGL(code_rows_mixed_kernel<NV>, grid, dim3(256), 0, s, codes, table, y, K, bins, B, L, C, out_s32, g_launch.status, bad, lens);
+    } else {
+        note_form(OPK_CODE_ROWS, NV, 0, grid, 256);
+        hipLaunchKernelGGL(code_rows_kernel<NV>, grid, dim3(256), 0, s, codes, table, y, K, bins, B, L, C, out_s32, g_launch.status, bad);
+    }
+    WT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+int launch_code_rows(const int64_t* codes, const float* table, int K, int bins, int B, int L, int C, float* y, hipStream_t s,
+                     int out_s32, unsigned* bad, const int* lens) {
+    if (K < 1 || bins < 1) { set_error("code_rows: needs at least one codebook and one bin"); return -1; }
+    if (C < 4 || (C % 4) || C > 1024) { set_error("code_rows: rows of C % 4 == 0 channels, at most 1024"); return -1; }
+    if (out_s32 && (C % 32)) { set_error("code_rows: an S32 output needs C % 32 == 0"); return -1; }
+    if (B < 1 || L < 1 || (long)B * L >= (long)INT_MAX) { set_error("code_rows: too many frames for one launch"); return -1; }
+    switch ((C + 255) / 256) {
+        case 1: return launch_code_rows_nv<1>(codes, table, K, bins, B, L, C, y, s, out_s32, bad, lens);
+        case 2: return launch_code_rows_nv<2>(codes, table, K, bins, B, L, C, y, s, out_s32, bad, lens);
+        case 3: return launch_code_rows_nv<3>(codes, table, K, bins, B, L, C, y, s, out_s32, bad, lens);
+        default: return launch_code_rows_nv<4>(codes, table, K, bins, B, L, C, y, s, out_s32, bad, lens);
+    }
+}
+
 // ---------------------------------------------------------------------------------- GroupNorm
 static int launch_gn_chunked(const float*, const float*, const float*, float*, float*, float*, int, int, int, int, int, int, float,
                              hipStream_t, int, float*, const int* lens = nullptr, int lmin = 0);

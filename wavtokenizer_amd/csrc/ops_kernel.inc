@@ -1,4 +1,4 @@
-// The kernels of ops.hip that a decode plan runs per clip length: transpose, GroupNorm (gn_stats, gn_tile, gn_chunk_stats /
+// The kernels of ops.hip that a decode plan runs per clip length: transpose, code_rows, GroupNorm (gn_stats, gn_tile, gn_chunk_stats /
 // gn_chunk_apply), dwconv_ln, softmax (rmw and reg forms) and istft_ola.  Included twice by ops.hip with OPS_MIX, OPS_K and OPS_L
 // set.  With OPS_MIX 0 (OPS_K(x) = x_kernel, OPS_L = L) the preprocessed text is exactly the kernels of the plans of one length.
 // OPS_MIX 1 (x_mixed_kernel, OPS_L = Lpad) is the length-aware twin of a WT_PLAN_DECODE_MIXED plan: the tensors have Lpad rows per
@@ -37,6 +37,85 @@ __global__ __launch_bounds__(256) void OPS_K(transpose)(const float* __restrict_
             else out[boff + (long)c * R + r] = tile[tx][i];
 #endif
         }
+    }
+    range_report(status, amax);
+}
+
+// ------------------------------------------------------------------------------------ code_rows
+// The first step of a decode-from-codes plan: codes [K][B][L] int64 -> y [B][L][C], row (b, t) = sum over k of
+// table[(k * bins + codes[k][b][t]) * C ...], i.e. what codes_to_features_kernel followed by transpose_kernel leaves in bb.in,
+// without the (B, C, L) fp32 tensor between them (the codebooks are already row-major [bins][C]).  Same rounding as that pair:
+// acc = 0.f, acc += row_k for k = 0 .. K - 1 (plain adds in that order: a -0.0f entry comes out as +0.0f), then the split of
+// every other S32 producer.  One wave per frame, four frames per workgroup; a lane owns 16 bytes of every 1 KB of the row (NV =
+// ceil(C / 256)).  The frame is wave-uniform, so its codes arrive by scalar loads, once per wave; the row loads of KC codebooks
+// are all issued before the first add.  A code outside [0, bins): the table is not read for it, the row becomes NaN and one lane
+// sets the model's bad-index word (a plain store at system scope, like codes_to_features_kernel); NaN does not reach amax
+// (fmaxf), so the call's status stays clean.
+template <int NV>
+__global__ __launch_bounds__(256) void OPS_K(code_rows)(const int64_t* __restrict__ codes, const float* __restrict__ table,
+                                                        float* __restrict__ y, int K, int bins, int B, int OPS_L, int C, int s32,
+                                                        unsigned* status, unsigned* bad
+#if OPS_MIX
+                                                        , const int* __restrict__ lens     // rows t >= lens[clip] are zeros; their codes are never read
+#endif
+                                                        ) {
+    constexpr int KC = NV <= 2 ? 8 : 4;                    // codebooks whose rows are in flight together
+    const int lane = threadIdx.x & 63;
+    const long m = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long frames = (long)B * OPS_L;                   // (below 2^31: the launcher)
+    if (m >= frames) return;
+    float* row = y + m * C;
+    float amax = 0.f;
+    f32x4 acc[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#if OPS_MIX
+    const int b = (int)((unsigned)m / (unsigned)Lpad), t = (int)m - b * Lpad;
+    if (t >= mix_len(lens, b, Lpad)) {                     // a pad row of the clip: zeros, whatever the staging holds there
+#pragma unroll
+        for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            if (c >= C) continue;
+            if (s32) store_s32_4(row, c, acc[i], amax);
+            else *reinterpret_cast<f32x4*>(row + c) = acc[i];
+        }
+        return;
+    }
+#endif
+    const float qnan = __builtin_nanf("");
+    bool any_bad = false;
+    for (int k0 = 0; k0 < K; k0 += KC) {
+        long code[KC];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) code[j] = k0 + j < K ? codes[(k0 + j) * frames + m] : 0;      // [k][b][t]
+        f32x4 v[KC][NV];
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+            if (k0 + j >= K) continue;
+            const bool ok = code[j] >= 0 && code[j] < bins;
+            any_bad |= !ok;
+            const float* src = table + ((long)(k0 + j) * bins + (ok ? code[j] : 0)) * C;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int c = (i * 64 + lane) * 4;
+                v[j][i] = (f32x4){qnan, qnan, qnan, qnan};
+                if (ok && c < C) v[j][i] = *reinterpret_cast<const f32x4*>(src + c);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+            if (k0 + j >= K) continue;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) acc[i] += v[j][i];
+        }
+    }
+    if (any_bad && bad && lane == 0) __hip_atomic_store(bad, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane) * 4;
+        if (c >= C) continue;
+        if (s32) store_s32_4(row, c, acc[i], amax);
+        else *reinterpret_cast<f32x4*>(row + c) = acc[i];
     }
     range_report(status, amax);
 }

@@ -468,7 +468,16 @@ int build_decode(wt_plan* P) {
     // at (B, L) as they are: they are row-independent, and the steps that reduce over time (GroupNorm, softmax, the dwconv's
     // taps, the overlap-add) read each clip's length and leave zeros in its rows past it, which stand for the zero padding of
     // the convs and add exact zeros to the attention output.  Only the shipped split-f16 route takes lengths
-    const bool mixed = P->kind == WT_PLAN_DECODE_MIXED;
+    const bool mixed = P->kind == WT_PLAN_DECODE_MIXED || P->kind == WT_PLAN_DECODE_CODES_MIXED;
+    // Decode from codes (WT_PLAN_DECODE_CODES / _MIXED): the first step gathers the codebook rows of the call's codes into bb.in
+    // (code_rows) instead of transposing the call's features into it; nothing else in the chain changes
+    const bool from_codes = P->kind == WT_PLAN_DECODE_CODES || P->kind == WT_PLAN_DECODE_CODES_MIXED;
+    if (from_codes && Cin != M->embed.cols) {
+        set_error("decode-from-codes plans need input_channels equal to the codebook width"); return WT_ERR_INVALID;
+    }
+    if (from_codes && Mrows >= (long)INT_MAX) {      // (code_rows runs one wave per frame under a 32-bit frame index)
+        set_error("batch too large for one decode-from-codes plan (32-bit frame index)"); return WT_ERR_INVALID;
+    }
     if (mixed) {
         const bool ok = s32_plan && !P->fp32_sites && !(P->flags & (WT_PLAN_FLAG_KEEP_STAGES | WT_PLAN_FLAG_RANGE_REPORT)) &&
                         M->at_Wqk.s32.p && M->at_Wv.s32.p && M->at_Wp.s32.p;
@@ -484,7 +493,13 @@ int build_decode(wt_plan* P) {
     }
     auto lens = [mixed](const RunCtx& c) { return mixed ? c.lengths : nullptr; };
     const int x0 = P->buf("bb.in", (size_t)Mrows * Cin, s32_e ? BUF_S32 : BUF_F32);
-    P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, Cin, L, c.stream, s32_e, lens(c)); });
+    const int bins = ar.vq_bins;
+    if (from_codes)
+        P->step({x0}, [=](const RunCtx& c) {
+            return launch_code_rows(c.in_codes, M->embed.w, c.n_q, bins, B, L, Cin, P->ptr(c, x0), c.stream, s32_e, M->bad_codes_dev, lens(c));
+        }, 1, "code_rows");
+    else
+        P->step({x0}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x0), B, Cin, L, c.stream, s32_e, lens(c)); });
     const int x = P->buf("bb.x", (size_t)Mrows * D);       // residual stream, updated in place
     gemm_step(P, s32_e, zconv_args(M->bb_embed, B, L), {x0, -1, x}, PRO_NONE, EPI_BIAS, OUT_F32);
     const bool keep = P->flags & WT_PLAN_FLAG_KEEP_STAGES;

@@ -185,11 +185,11 @@ static int op_probe_check(const wt_op_desc* d) {
     if (lengths) {
         if (reinterpret_cast<uintptr_t>(lengths) & 3) return bad("lengths misaligned");
         const bool aware = d->op == WT_OP_GN_APPLY || d->op == WT_OP_GN_STATS || (d->op == WT_OP_ROWNORM && d->mode == RN_DWCONV) ||
-                           d->op == WT_OP_SOFTMAX || d->op == WT_OP_ISTFT_OLA || d->op == WT_OP_TRANSPOSE;
+                           d->op == WT_OP_SOFTMAX || d->op == WT_OP_ISTFT_OLA || d->op == WT_OP_TRANSPOSE || d->op == WT_OP_CODE_ROWS;
         if (!aware) return bad("this op has no length-aware launch");
         if (d->op == WT_OP_SOFTMAX && (d->L <= 0 || d->n % d->L)) return bad("the length-aware softmax needs whole clips of L rows");
     }
-    if (d->op < WT_OP_GN_APPLY || d->op > WT_OP_S32_AMAX) return bad("unknown op");
+    if (d->op < WT_OP_GN_APPLY || (d->op > WT_OP_S32_AMAX && d->op != WT_OP_CODE_ROWS)) return bad("unknown op");     // (11 is unassigned)
     auto al16 = [](const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); };
     const void* ptrs[] = {d->p0, d->p1, d->p2, d->p3, d->p4, d->p5, d->y, d->y2, d->y3};
     for (const void* p : ptrs) if (!al16(p)) return bad("arrays must be 16-byte aligned");
@@ -241,6 +241,13 @@ static int op_probe_check(const wt_op_desc* d) {
         if (!d->y) return bad("null argument");
         if (d->n <= 0 || d->n % 32) return bad("s32_amax needs whole S32 groups of 32 values");
         break;
+    case WT_OP_CODE_ROWS:
+        if (!d->p0 || !d->y) return bad("null argument");
+        if (d->k < 1 || d->n < 1 || d->n > INT_MAX) return bad("code_rows needs k >= 1 codebooks of 1 <= n < 2^31 bins");
+        if (d->C % 4 || d->C > 1024) return bad("code_rows needs C % 4 == 0 and C <= 1024");
+        if (d->out_s32 && d->C % 32) return bad("code_rows: an S32 output needs C % 32 == 0");
+        if ((long)d->B * d->L >= (long)INT_MAX) return bad("code_rows: too many frames for one launch");
+        break;
     }
     return WT_OK;
 }
@@ -291,6 +298,10 @@ int wt_op_probe(const wt_op_desc* d, wt_op_form* form, void* stream) {
         break;
     case WT_OP_S32_AMAX:
         rc = launch_s32_amax(d->x, d->n, static_cast<unsigned*>(d->y), s);
+        break;
+    case WT_OP_CODE_ROWS:
+        rc = launch_code_rows(static_cast<const int64_t*>(d->x), F(d->p0), d->k, (int)d->n, d->B, d->L, d->C, W(d->y), s, d->out_s32 ? 1 : 0,
+                              static_cast<unsigned*>(d->y2), lens);
         break;
     }
     g_launch = saved;

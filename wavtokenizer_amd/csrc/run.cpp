@@ -163,7 +163,7 @@ static int issue_steps(const wt_plan* p, const RunCtx& c, StepObserver* obs = nu
 static int run_graph(const wt_plan* p, const RunCtx& c, bool* eager) {
     *eager = true;
     if (!(p->flags & WT_PLAN_FLAG_GRAPH) || !p->timing_filter.empty() || p->graph_failed || p->range_dev) return WT_OK;
-    const wt_plan::GraphKey key{c.ws, c.in_f, c.out_f, c.codes, c.aux, c.lengths, c.bw_id};
+    const wt_plan::GraphKey key{c.ws, c.in_codes ? static_cast<const void*>(c.in_codes) : c.in_f, c.out_f, c.codes, c.aux, c.lengths, c.bw_id, c.n_q};
     if (!(p->graph_exec && key == p->graph_key)) {
         if (!(key == p->last_key)) { p->last_key = key; return WT_OK; }
         if (p->graph_exec) { (void)hipGraphExecDestroy(p->graph_exec); p->graph_exec = nullptr; }
@@ -374,6 +374,38 @@ int wt_decode_mixed(const wt_plan* p, const float* features, const int32_t* leng
         set_error("wt_decode_mixed: bandwidth_id out of range"); return WT_ERR_INVALID;
     }
     RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features, wav_out, nullptr, nullptr, bandwidth_id, lengths};
+    return run_plan(p, c);
+}
+
+// decode from codes: the checks the two entry points share
+static int check_decode_codes(const wt_plan* p, int32_t K, int32_t bandwidth_id, const std::string& who) {
+    if (K < 1 || K > p->model->arch.num_quantizers) {
+        set_error(who + ": K must be between 1 and the number of codebooks"); return WT_ERR_INVALID;
+    }
+    if (bandwidth_id < 0 || bandwidth_id >= p->model->arch.adanorm_num_embeddings) {
+        set_error(who + ": bandwidth_id out of range"); return WT_ERR_INVALID;
+    }
+    return WT_OK;
+}
+
+int wt_decode_codes(const wt_plan* p, const int64_t* codes, int32_t K, int32_t bandwidth_id, float* wav_out, float* backbone_out,
+                    void* workspace, void* stream) {
+    if (p && p->kind == WT_PLAN_DECODE_CODES_MIXED) { set_error("wt_decode_codes: a mixed-length plan runs through wt_decode_codes_mixed"); return WT_ERR_INVALID; }
+    if (int rc = check_kind(p, WT_PLAN_DECODE_CODES, -1, "wt_decode_codes: not a decode-from-codes plan (WT_PLAN_DECODE_CODES)")) return rc;
+    if (!codes || !wav_out || !workspace) { set_error("wt_decode_codes: null buffer"); return WT_ERR_INVALID; }
+    if (int rc = check_decode_codes(p, K, bandwidth_id, "wt_decode_codes")) return rc;
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), nullptr, wav_out, nullptr, backbone_out, bandwidth_id};
+    c.in_codes = codes; c.n_q = K;
+    return run_plan(p, c);
+}
+
+int wt_decode_codes_mixed(const wt_plan* p, const int64_t* codes, int32_t K, const int32_t* lengths, int32_t bandwidth_id,
+                          float* wav_out, void* workspace, void* stream) {
+    if (int rc = check_kind(p, WT_PLAN_DECODE_CODES_MIXED, -1, "wt_decode_codes_mixed: not a mixed-length decode-from-codes plan (WT_PLAN_DECODE_CODES_MIXED)")) return rc;
+    if (!codes || !lengths || !wav_out || !workspace) { set_error("wt_decode_codes_mixed: null buffer"); return WT_ERR_INVALID; }
+    if (int rc = check_decode_codes(p, K, bandwidth_id, "wt_decode_codes_mixed")) return rc;
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), nullptr, wav_out, nullptr, nullptr, bandwidth_id, lengths};
+    c.in_codes = codes; c.n_q = K;
     return run_plan(p, c);
 }
 

@@ -1,4 +1,4 @@
-"""Grouping policy of WavTokenizer.encode_infer_many and decode_many: which clips share a mixed-length call, and how long its
+"""Grouping policy of WavTokenizer.encode_infer_many, decode_many and decode_codes_many: which clips share a mixed-length call, and how long its
 padded staging tensor is.  Pure functions of the clip lengths (no GPU), so the policy is tested on its own.
 
 A mixed-length call returns for every clip the bits a call of its own length returns (the kernels read each clip's length on
@@ -67,7 +67,7 @@ def group_clips(lengths: Sequence[int], hop: int, min_clip: int = MIN_CLIP, max_
 
 
 def group_frames(frames: Sequence[int], max_group: int = MAX_GROUP) -> List[Tuple[int, List[int]]]:
-    """Grouping of WavTokenizer.decode_many: group_clips in units of frames (hop 1, every clip of one frame or more is taken)
+    """Grouping of WavTokenizer.decode_many and decode_codes_many: group_clips in units of frames (hop 1, every clip of one frame or more is taken)
     with the score-cell cap.  Returns [(padded frames, clip indices)]; every index appears exactly once."""
     groups, solo = group_clips(frames, 1, min_clip=1, max_group=max_group, max_cells=MAX_SCORE_CELLS)
     assert not solo

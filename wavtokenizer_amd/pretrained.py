@@ -308,6 +308,10 @@ def _take_status(read, handle) -> int:
     return bits.value
 
 
+def _decode_codes_mixed_entry(plan, codes, lengths, K, bw, wav, ws, stream):
+    """lib.wt_decode_codes_mixed in the argument order of WavTokenizer._call (inputs, scalars, outputs)."""
+    return lib.wt_decode_codes_mixed(plan, codes, K, lengths, bw, wav, ws, stream)
+
 class _OffRoute(Exception):
     """A mixed-length call found the encoder off the route mixed-length plans take (WavTokenizer._mixed_route_ok)."""
 
@@ -655,6 +659,7 @@ class WavTokenizer(nn.Module):
             return m & (1 << _capi.WT_SITE_HEAD)
         if kind == _capi.WT_PLAN_SEANET_DECODER:
             return m & (1 << _capi.WT_SITE_SEANET_DECODER)
+        # the decode kinds (WT_PLAN_DECODE, _MIXED, _CODES, _CODES_MIXED): every decoder site
         return m & ~((1 << _capi.WT_SITE_ENCODER) | (1 << _capi.WT_SITE_SEANET_DECODER))
 
     def range_report(self, audio_input: torch.Tensor, bandwidth_id=None) -> List[Dict[str, Any]]:
@@ -739,11 +744,12 @@ class WavTokenizer(nn.Module):
         return x.to(dtype).contiguous()
 
     # -- kernels ------------------------------------------------------------------------------------
-    def _call(self, entry, kind: int, B: int, length: int, flags: int, dev: torch.device, ins, outs, scalars=()):
+    def _call(self, entry, kind: int, B: int, length: int, flags: int, dev: torch.device, ins, outs, scalars=(), name=None):
         """One call of a C run entry point, entry(plan, inputs..., scalars..., outputs..., workspace, stream), on the plan
         (kind, B, length, flags) with the kind's fp32 sites.  ins: per input the tensor itself, or (shape, dtype, fill) for a
         buffer that fill(buffer) writes.  outs: per output (shape, dtype, wanted), or None for a null pointer; a direct call
-        passes null for an unwanted output too.  Returns (outputs, None where not wanted; plan)."""
+        passes null for an unwanted output too.  name: what a failed call is reported as (default: entry's own name).
+        Returns (outputs, None where not wanted; plan)."""
         plan, ws = self._engine.plan(kind, B, length, flags, dev, self._sites(kind))
         new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
         graph = flags & _capi.WT_PLAN_FLAG_GRAPH
@@ -763,7 +769,7 @@ class WavTokenizer(nn.Module):
         else:
             bufs = [x if isinstance(x, torch.Tensor) else _fill(x, new(*x[:2])) for x in ins]
             obufs = [new(*o[:2]) if o is not None and o[2] else None for o in outs]
-        check(entry(plan, *map(_ptr, bufs), *scalars, *map(_ptr, obufs), _ptr(ws), _stream_ptr(dev)), entry.__name__)
+        check(entry(plan, *map(_ptr, bufs), *scalars, *map(_ptr, obufs), _ptr(ws), _stream_ptr(dev)), name or entry.__name__)
         if graph:
             return tuple(b.clone() if o is not None and o[2] else None for o, b in zip(outs, obufs)), plan
         return tuple(obufs), plan
@@ -965,6 +971,121 @@ class WavTokenizer(nn.Module):
                 out[i] = wav[j:j + 1, :self._wave_len(int(feats[i].shape[1]))].clone()
         for i in sorted(solo):
             out[i] = self.decode(feats[i][None], bandwidth_id=bw)
+        return out  # type: ignore[return-value]
+
+    # -- decode straight from codes (WT_PLAN_DECODE_CODES / _MIXED): the plans gather the codebook rows themselves ------------
+    def _codes_staging(self, K: int, B: int, L: int, flags: int, fill):
+        """The codes input of a decode-from-codes _call.  K is an argument of the call, not of the plan, while a graph plan
+        keeps ONE staging buffer: it is sized for every codebook, [num_quantizers][B][L], and a call fills its first K slabs
+        (they are the call's [K][B][L] array; the recording is keyed by K).  fill(buf[:K]) writes them."""
+        nq = self._arch.num_quantizers if flags & _capi.WT_PLAN_FLAG_GRAPH else K
+        return ((nq, B, L), torch.int64, lambda buf: fill(buf[:K]))
+
+    def _decode_codes(self, codes: torch.Tensor, bw: int, flags: int, dev: torch.device):
+        """The call of decode_codes: ((waveform, None), plan)."""
+        K, B, L = codes.shape
+        graph = flags & _capi.WT_PLAN_FLAG_GRAPH
+        ins = (self._codes_staging(K, B, L, flags, lambda buf: buf.copy_(codes)),) if graph else (codes,)
+        return self._call(lib.wt_decode_codes, _capi.WT_PLAN_DECODE_CODES, B, L, flags, dev, ins,
+                          (((B, self._wave_len(L)), torch.float32, True), None), (K, bw))
+
+    def _codes_checked(self, dev: torch.device):
+        """set_check_codes("sync") after a decode-from-codes call: wait for it and raise for a code outside the codebook."""
+        if self._check_codes == "sync":
+            torch.cuda.current_stream(dev).synchronize()
+            self._poll_bad_codes()
+
+    @torch.inference_mode()
+    def decode_codes(self, codes: torch.Tensor, bandwidth_id=None) -> torch.Tensor:
+        """decode(codes_to_features(codes), bandwidth_id=...) in one call, the same bits, without the (B, 512, L) feature
+        tensor: codes (K, L) or (K, B, L) int64 as codes_to_features takes them -> (B, wave_len(L)).  The plan's first kernel
+        gathers the codebook rows into the operand of backbone.embed.  A code outside the codebook follows set_check_codes
+        like codes_to_features: "sync" raises IndexError for this call, "deferred" on the next call on this model, "off" never;
+        the offending clip's waveform is NaN in every mode."""
+        dev = self._ensure_engine()
+        bw = self._bandwidth_index(bandwidth_id)
+        if codes.dim() == 2:
+            codes = codes.unsqueeze(1)
+        assert codes.dim() == 3, "expected codes (K, L) or (K, B, L)"
+        if not 1 <= codes.shape[0] <= self._arch.num_quantizers:      # (before a graph plan's staging buffer is filled)
+            raise WavTokError("decode_codes: K must be between 1 and the number of codebooks", _capi.WT_ERR_INVALID)
+        codes = self._as_input(codes, dev, torch.int64)
+        B = codes.shape[1]
+        wav = self._guarded(dev, lambda: self._decode_codes(codes, bw, self._graph_flags(B), dev), self._is_strict(B))[0]
+        self._codes_checked(dev)
+        return wav
+
+    @torch.inference_mode()
+    def _run_decode_codes_mixed(self, codes_list: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None):
+        """One mixed-length decode-from-codes call (WT_PLAN_DECODE_CODES_MIXED) on clips (K, L_i) int64 of 1 <= L_i <= L_pad
+        frames, the counterpart of _run_decode_mixed: returns the waveforms (B, wave_len(L_pad)), clip j's own samples first and
+        zeros behind them, or None when the decoder is off the route a mixed-length plan takes (_decode_mixed_route_ok).  What
+        the staging buffer holds past a clip's frames is never read."""
+        dev = dev if dev is not None else self._ensure_engine()
+        B = len(codes_list)
+        K = int(codes_list[0].shape[0])
+        lengths = [int(c.shape[1]) for c in codes_list]
+        if min(lengths) < 1 or max(lengths) > L_pad:
+            raise ValueError("every clip needs between 1 and L_pad frames")
+        codes_list = [self._as_input(c, dev, torch.int64) for c in codes_list]
+
+        def fill_codes(buf: torch.Tensor):
+            for j, c in enumerate(codes_list):
+                buf[:, j, :lengths[j]].copy_(c)
+
+        outs = (((B, self._wave_len(L_pad)), torch.float32, True),)
+
+        def call():
+            # checked on every attempt: a range fallback inside _guarded can put a decoder site on fp32
+            if not self._decode_mixed_route_ok():
+                raise _OffRoute()
+            flags = self._graph_flags(B)
+            ins = (self._codes_staging(K, B, L_pad, flags, fill_codes),
+                   ((B,), torch.int32, lambda lens: lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)))
+            return self._call(_decode_codes_mixed_entry, _capi.WT_PLAN_DECODE_CODES_MIXED, B, L_pad, flags, dev, ins, outs, (K, bw),
+                              name="wt_decode_codes_mixed")
+
+        try:
+            wav = self._guarded(dev, call, self._is_strict(B))[0]
+        except _OffRoute:
+            return None
+        self._codes_checked(dev)
+        return wav
+
+    @torch.inference_mode()
+    def decode_codes_many(self, codes: Sequence[torch.Tensor], bandwidth_id=None) -> List[torch.Tensor]:
+        """decode_codes over clips of different lengths in a few batched calls: codes[i] is (K, L_i) or (K, 1, L_i), an integer
+        tensor, the same K throughout, L_i >= 1; returns [(1, wave_len(L_i))] in input order, each the same bits as
+        decode_codes(codes[i], bandwidth_id=...) and as decode_many of its features.  The grouping is decode_many's
+        (mixed_length.group_frames); a clip that forms a group alone, and every clip while the decoder runs off its shipped
+        route, goes through decode_codes."""
+        from .mixed_length import group_frames
+        bw = self._bandwidth_index(bandwidth_id)
+        clips: List[torch.Tensor] = []
+        for c in codes:
+            if isinstance(c, torch.Tensor) and c.dim() == 3 and c.shape[1] == 1:
+                c = c[:, 0, :]
+            if (not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] < 1 or c.is_floating_point() or c.is_complex()
+                    or c.dtype == torch.bool):
+                raise ValueError("decode_codes_many takes a sequence of integer tensors (K, L) or (K, 1, L) with L >= 1")
+            if not 1 <= c.shape[0] <= self._arch.num_quantizers or c.shape[0] != (clips[0].shape[0] if clips else c.shape[0]):
+                raise ValueError("decode_codes_many: every clip needs the same K, between 1 and the number of codebooks")
+            clips.append(c)
+        out: List[Optional[torch.Tensor]] = [None] * len(clips)
+        solo: List[int] = []
+        min_frames = 1 if self._arch.padding == "same" else 2      # (decode raises for a 'center' clip of one frame)
+        for L_pad, idx in group_frames([int(c.shape[1]) for c in clips]):
+            if len(idx) == 1 or int(clips[idx[0]].shape[1]) < min_frames:
+                solo.extend(idx)
+                continue
+            wav = self._run_decode_codes_mixed([clips[i] for i in idx], L_pad, bw)
+            if wav is None:
+                solo.extend(idx)
+                continue
+            for j, i in enumerate(idx):
+                out[i] = wav[j:j + 1, :self._wave_len(int(clips[i].shape[1]))].clone()
+        for i in sorted(solo):
+            out[i] = self.decode_codes(clips[i], bandwidth_id=bw)
         return out  # type: ignore[return-value]
 
     def _run_head(self, x: torch.Tensor) -> torch.Tensor:

@@ -115,9 +115,16 @@ enum {
     WT_PLAN_FLAG_RANGE_REPORT = 32,/* diagnostic: behind every step, the largest magnitude held by each S32 (split-f16) buffer the
                                       step touches is measured (wt_plan_range_report): the head-room of every dense layer's
                                       operands below the f16 limit 65504.  Costs a pass per buffer; never graph-replayed */
-    WT_PLAN_FLAG_MIXED_LENGTH = 64 /* WT_PLAN_ENCODE: clips of different lengths in one call (wt_encode_mixed); `len` is the padded
+    WT_PLAN_FLAG_MIXED_LENGTH = 64,/* WT_PLAN_ENCODE: clips of different lengths in one call (wt_encode_mixed); `len` is the padded
                                       length.  Only the shipped route takes it: refused together with UNFUSED, FP32_GEMM,
                                       KEEP_STAGES or RANGE_REPORT, with the encoder site on fp32, or for weights without S32 copies */
+    WT_PLAN_FLAG_F16_GEMM = 128    /* the decode kinds (WT_PLAN_DECODE, _MIXED, _CODES, _CODES_MIXED): half-precision inference mode for
+                                      callers that hold codes and want audio.  Every dense layer that runs on split-f16 operands
+                                      multiplies their f16 hi halves alone: one f16 MFMA per product instead of three, fp32
+                                      accumulate, operands rounded to f16 (waveform error near 1e-3 relative instead of 1e-5).
+                                      Buffers, producers and weights are those of the default plan; a range site on fp32 stays
+                                      on the fp32 chain.  Combines with KEEP_STAGES, RANGE_REPORT and GRAPH; refused (WT_ERR_INVALID)
+                                      for every other plan kind and together with FP32_GEMM or UNFUSED */
 };
 
 /* Range sites: the units in which a plan can leave the split-f16 form on its own (wt_plan_create_ex, wt_plan_range_sites).
@@ -351,7 +358,9 @@ int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, 
  * (gemm16s.hip) splits them into the S32 form in the workspace as the plans hold them: a B operand that is a weight
  * (b_is_act = 0) with its per-tensor power-of-two scale and acc_scale, activations (A, A2, a B operand with
  * b_is_act = 1) unscaled (the weight is read back to choose its scale: the call waits for `stream` once); a tap-paired B operand (tap_pair = 1) must already be packed in the paired tap order.
- * engine 1 (gemm.hip) reads the fp32 arrays directly.  epi / out / pro take the values of the library's Epi, Out16s,
+ * engine 1 (gemm.hip) reads the fp32 arrays directly.  engine 2 is engine 0 on the one-product twin of the kernel
+ * (WT_PLAN_FLAG_F16_GEMM: same operand split, workspace, checks and tile form; the decode plans' (epi, out) pairs only, no
+ * mix_geom).  epi / out / pro take the values of the library's Epi, Out16s,
  * Pro enums (the argmax epilogue is reached through wt_vq_nearest instead).  C (and C2) are written in the format
  * `out` names (S32: 128-byte groups [32 x f16 hi | 32 x f16 lo]).  status: optional device word that the S32
  * producers OR WT_STATUS_BIT_RANGE into.  The whole descriptor is checked before any HIP call: a problem the

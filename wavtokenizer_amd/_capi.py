@@ -33,6 +33,7 @@ WT_PLAN_DECODE_MIXED = 5
 WT_PLAN_DECODE_CODES, WT_PLAN_DECODE_CODES_MIXED = 6, 7
 WT_PLAN_FLAG_KEEP_STAGES = 1
 WT_PLAN_FLAG_FP32_GEMM = 2
+WT_PLAN_FLAG_F16_GEMM = 128
 WT_PLAN_FLAG_STEP_LSTM = 4
 WT_PLAN_FLAG_GRAPH = 8
 WT_PLAN_FLAG_UNFUSED = 16

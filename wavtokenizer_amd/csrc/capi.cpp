@@ -201,6 +201,15 @@ int wt_plan_create_ex(const wt_model* m, int32_t kind, int32_t B, int64_t len, i
     if ((flags & WT_PLAN_FLAG_MIXED_LENGTH) && kind != WT_PLAN_ENCODE) {
         set_error("wt_plan_create: WT_PLAN_FLAG_MIXED_LENGTH is an encode-plan flag"); return WT_ERR_INVALID;
     }
+    if (flags & WT_PLAN_FLAG_F16_GEMM) {
+        const bool decode_kind = kind == WT_PLAN_DECODE || kind == WT_PLAN_DECODE_MIXED || kind == WT_PLAN_DECODE_CODES ||
+                                 kind == WT_PLAN_DECODE_CODES_MIXED;
+        if (!decode_kind) { set_error("wt_plan_create: WT_PLAN_FLAG_F16_GEMM is a flag of the decode plan kinds"); return WT_ERR_INVALID; }
+        if (flags & (WT_PLAN_FLAG_FP32_GEMM | WT_PLAN_FLAG_UNFUSED)) {
+            set_error("wt_plan_create: WT_PLAN_FLAG_F16_GEMM does not combine with WT_PLAN_FLAG_FP32_GEMM or WT_PLAN_FLAG_UNFUSED");
+            return WT_ERR_INVALID;
+        }
+    }
     if ((len + (kind == WT_PLAN_ENCODE ? m->hop - 1 : 0)) / (kind == WT_PLAN_ENCODE ? m->hop : 1) > 12000) {
         set_error("clips longer than 12000 frames are not supported by one plan; split the clip"); return WT_ERR_INVALID;
     }

@@ -228,6 +228,11 @@ enum Out16s : int {
     OUT_F32_AND_S32 = 3      // C = fp32 v and C2 = S32(v): a tensor read by fp32 kernels and by a split-f16 GEMM
 };
 enum PadMode : int { PAD_ZERO = 0, PAD_REFLECT = 1 };
+// gemm16s products per operand pair: a launcher argument (GemmArgs is the kernels' argument and does not carry it)
+enum Prec16s : int {
+    GEMM16S_F16X3 = 0,       // hi.hi + (hi.lo + lo.hi) 2^-11: three f16 MFMAs, fp32-equivalent products (the default)
+    GEMM16S_F16 = 1          // hi.hi alone: operands rounded to f16, one MFMA (gemm16h_kernel; the decode plans' pairs only)
+};
 
 // What a GEMM launcher chose for one launch (host only; GemmArgs::form, filled when set: wt_gemm_probe)
 struct LaunchForm {
@@ -297,11 +302,14 @@ int check_gemm(const GemmArgs& a, int pro, int epi);
 // mix_geom (mixed-length plans): clip 0's {T_in, Tp, T_out} triple of this conv in the geometry table (clip stride GEOM_WORDS).  A
 // clip's row t < T_out gathers reflect-about-Tp positions below T_in, its rows past T_out gather nothing (zero operands); the
 // GemmArgs extents are then the padded ones (strides and M).  Reflect-padded convs and the encoder's pairs only
-int check_gemm16s(const GemmArgs& a, int epi, int out, const int* mix_geom = nullptr);
+int check_gemm16s(const GemmArgs& a, int epi, int out, const int* mix_geom = nullptr, int prec = GEMM16S_F16X3);
 int launch_gemm(const GemmArgs& a, int pro, int epi, hipStream_t s);
 // gemm16s.hip: both operands pre-split in the S32 layout (128-byte groups [32 x f16 hi | 32 x f16 lo], same
 // footprint and strides as the fp32 array); a.A / a.W_hi point at S32 data, out_s32 selects an S32 C
-int launch_gemm16s(const GemmArgs& a, int epi, int out, hipStream_t s, const int* mix_geom = nullptr);     // out: Out16s
+// prec (Prec16s): GEMM16S_F16 runs the one-product twin on the tile form the default picks; it exists for the decode plans' pairs
+// and not for mixed-length launches (both refused like any other unsupported pair)
+int launch_gemm16s(const GemmArgs& a, int epi, int out, hipStream_t s, const int* mix_geom = nullptr, int prec = GEMM16S_F16X3);     // out: Out16s
+int launch_gemm16h_tiled(const GemmArgs& a, int epi, int out, hipStream_t s);      // gemm16h.hip: launch_gemm16s's tail for GEMM16S_F16
 int gemm16s_vq_parts(int N);
 int launch_split_s32(const float* x, void* out, long n, hipStream_t s, const float* scale_dev = nullptr);
 int launch_unsplit_s32(const void* s32, float* out, long n, float inv_scale, hipStream_t s);     // fp32 = (hi + lo * 2^-11) * inv_scale

@@ -242,9 +242,13 @@ __device__ __forceinline__ void wait_vm_lgkm() {
 // wave per SIMD a wave pays for its DMA issue (5 pieces per K tile), its LDS reads and its MFMAs one after the other - at
 // B = 1 the sum IS the launch time (ladder in tools/micro/gemm_lab.hip: MFMA 7, LDS reads 4, barriers 3, DMA issue 5, data 8
 // of 35 us) - while two waves per SIMD with the roles split run the DMA side under the MFMA side
+// G16_HI 1: gemm16h_kernel, the one-product twin (hi halves only: WT_PLAN_FLAG_F16_GEMM).  Its instantiations live in a
+// translation unit of their own, gemm16h.hip, which includes this file with WT_GEMM16H_TU set: the kernels, their device
+// helpers and the tile choice below are this text, so the twin picks the tile form the default picks for the same problem
 #define G16_NAME gemm16s_kernel
 #define G16_PARAMS
 #define G16_MIX 0
+#define G16_HI 0
 #include "gemm16s_kernel.inc"
 #undef G16_NAME
 #undef G16_PARAMS
@@ -256,7 +260,18 @@ __device__ __forceinline__ void wait_vm_lgkm() {
 #undef G16_NAME
 #undef G16_PARAMS
 #undef G16_MIX
+#undef G16_HI
+#define G16_NAME gemm16h_kernel
+#define G16_PARAMS
+#define G16_MIX 0
+#define G16_HI 1
+#include "gemm16s_kernel.inc"
+#undef G16_NAME
+#undef G16_PARAMS
+#undef G16_MIX
+#undef G16_HI
 
+#ifndef WT_GEMM16H_TU       // (gemm16h.hip needs the kernels and the tile choice only)
 // fp32 -> S32 (flat: rows are multiples of 32 elements, so the layout is a function of the flat index alone)
 // `scale` (optional, device): the values are multiplied by scale[0], a power of two chosen by pow2_scale_kernel, first
 __global__ __launch_bounds__(256) void split_s32_kernel(const float* __restrict__ x, _Float16* __restrict__ out, long n,
@@ -330,16 +345,19 @@ int launch_pow2_scales(const float* a, long na, const float* b, long nb, unsigne
     return 0;
 }
 
+#endif      // WT_GEMM16H_TU
+
 // ---------------------------------------------------------------------------------- host side
-// the kernel of a tile form: gemm16s_kernel, or with MIX its mixed-length twin
-template <int BM, int BN, int WMs, int WNs, int NSTAGE, int EPI, int OUT, int WPS, int LABDBG, int KS, int PROD, bool MIX>
+// the kernel of a tile form: gemm16s_kernel, with MIX its mixed-length twin, with HI its one-product twin
+template <int BM, int BN, int WMs, int WNs, int NSTAGE, int EPI, int OUT, int WPS, int LABDBG, int KS, int PROD, bool MIX, int HI>
 static constexpr auto gemm16s_kernel_of() {
-    if constexpr (MIX) return gemm16s_mixed_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
+    if constexpr (HI) return gemm16h_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
+    else if constexpr (MIX) return gemm16s_mixed_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
     else return gemm16s_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
 }
 
 template <int BM, int BN, int WMs, int WNs, int NSTAGE, int EPI, int OUT, int WPS = 2, int LABDBG = 0, int KS = 1, int PROD = 0,
-          bool MIX = false>
+          bool MIX = false, int HI = 0>
 static int launch16s_one(const GemmArgs& a, hipStream_t s, const int* mix_geom = nullptr) {
     if (KS == 2 && ((a.K / SBK) % 2 || a.K / SBK < 6)) { set_error("gemm16s: two K tiles per barrier need an even number (>= 6) of K tiles"); return -1; }
     static PerDeviceOnce attr_once;
@@ -351,11 +369,14 @@ static int launch16s_one(const GemmArgs& a, hipStream_t s, const int* mix_geom =
     static_assert(stage_bytes + 2 * BM * sizeof(unsigned) <= smem_cap, "LDS budget");
     if (smem > smem_cap) { set_error("gemm16s: too many taps for this tile's LDS budget"); return -1; }
     using kern_t = void (*)(const GemmArgs);
-    kern_t kern = gemm16s_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
+    static_assert(!(MIX && HI), "the one-product twin has no mixed-length form");
+    kern_t kern;
+    if constexpr (HI) kern = gemm16h_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
+    else kern = gemm16s_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>;
 #ifdef WT_LAB
     // LAB builds only: the timing-experiment builds of the tile the ConvNeXt GEMMs run on (tools/gemm16s_bench.py dbg): the
     // masks of the ablation ladder, each with the clock stamps (+1024), selected by WT_GEMM16S_DBG per launch
-    constexpr bool has_dbg = !MIX && LABDBG == 0 && KS == 1 && BM == 128 && BN == 192 && WMs == 4 && NSTAGE == 3 && ((EPI == EPI_BIAS && OUT == OUT_F32) || (EPI == EPI_BIAS_GELU && OUT == OUT_S32));
+    constexpr bool has_dbg = !MIX && !HI && LABDBG == 0 && KS == 1 && BM == 128 && BN == 192 && WMs == 4 && NSTAGE == 3 && ((EPI == EPI_BIAS && OUT == OUT_F32) || (EPI == EPI_BIAS_GELU && OUT == OUT_S32));
     int dbg_req = 0;
     if (const char* e = lab_env("WT_GEMM16S_DBG")) dbg_req = atoi(e);
     kern_t dbg_kerns[8] = {};
@@ -377,7 +398,7 @@ static int launch16s_one(const GemmArgs& a, hipStream_t s, const int* mix_geom =
     }
 #endif
     if (int rc = attr_once.run([&]() -> int {
-        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16s_kernel_of<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, WPS, LABDBG, KS, PROD, MIX>()),
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm16s_kernel_of<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, WPS, LABDBG, KS, PROD, MIX, HI>()),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
 #ifdef WT_LAB
         for (int i = 0; i < 8; ++i)
@@ -452,7 +473,13 @@ static int tile16s_override() {
     return e ? atoi(e) : -1;
 }
 
-template <int EPI, int OUT>
+// a tile form of launch16s_tiled: the default kernel, or with HI the one-product twin of the same form
+template <int HI, int BM, int BN, int WMs, int WNs, int NSTAGE, int EPI, int OUT, int KS = 1, int PROD = 0>
+static int launch16s_form(const GemmArgs& a, hipStream_t s) {
+    return launch16s_one<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, 2, 0, KS, PROD, false, HI>(a, s);
+}
+
+template <int EPI, int OUT, int HI = 0>
 static int launch16s_tiled(const GemmArgs& a, hipStream_t s) {
     if constexpr (EPI == EPI_HEAD) {
         // wave tile 32 x 64: one whole 32-slot group per row block, staged full-line stores.  (7680 x 2432: 1140 tiles in 5
@@ -461,20 +488,20 @@ static int launch16s_tiled(const GemmArgs& a, hipStream_t s) {
             const bool ks2_env = [] { const char* e = lab_env("WT_GEMM16S_KS"); return !e || e[0] != '1'; }();
             const int nkt = a.K / SBK;
             if (ks2_env && nkt % 2 == 0 && nkt >= 6 && ((a.M + 63) / 64) * ((a.N + 31) / 32) * a.nz <= device_cus())
-                return launch16s_one<64, 32, 2, 1, 6, EPI, OUT, 2, 0, 2, 2>(a, s);
+                return launch16s_form<HI, 64, 32, 2, 1, 6, EPI, OUT, 2, 2>(a, s);
         }
-        return launch16s_one<128, 128, 4, 2, 3, EPI, OUT>(a, s);
+        return launch16s_form<HI, 128, 128, 4, 2, 3, EPI, OUT>(a, s);
     } else if constexpr (EPI == EPI_ARGMAX) {
-        return launch16s_one<128, 192, 4, 2, 3, EPI, OUT>(a, s);      // gemm16s_vq_parts() assumes this tile
+        return launch16s_form<HI, 128, 192, 4, 2, 3, EPI, OUT>(a, s);      // gemm16s_vq_parts() assumes this tile
     } else {
         switch (tile16s_override()) {       // experiment hook (tools/linear_bench.py)
-            case 2: return launch16s_one<128, 192, 4, 2, 3, EPI, OUT>(a, s);
-            case 3: return launch16s_one<128, 128, 4, 2, 3, EPI, OUT>(a, s);
-            case 8: return launch16s_one<128, 32, 4, 1, 3, EPI, OUT>(a, s);
-            case 9: return launch16s_one<128, 64, 4, 1, 3, EPI, OUT>(a, s);
+            case 2: return launch16s_form<HI, 128, 192, 4, 2, 3, EPI, OUT>(a, s);
+            case 3: return launch16s_form<HI, 128, 128, 4, 2, 3, EPI, OUT>(a, s);
+            case 8: return launch16s_form<HI, 128, 32, 4, 1, 3, EPI, OUT>(a, s);
+            case 9: return launch16s_form<HI, 128, 64, 4, 1, 3, EPI, OUT>(a, s);
             default: break;
         }
-        if (a.N <= 64) return launch16s_one<256, 64, 8, 1, 3, EPI, OUT>(a, s);      // narrow outputs (down conv 1)
+        if (a.N <= 64) return launch16s_form<HI, 256, 64, 8, 1, 3, EPI, OUT>(a, s);      // narrow outputs (down conv 1)
         // a handful of clips (M of a few hundred rows): with 128-column tiles fewer than 32 CUs would each walk the whole
         // K loop alone, so the problem is cut into 32-column tiles instead (4x the workgroups, a third of the work per
         // K step).  Every tile shape accumulates K in the same order: results do not depend on the choice
@@ -489,13 +516,13 @@ static int launch16s_tiled(const GemmArgs& a, hipStream_t s) {
         const long cols32 = ((a.N + 31) / 32) * a.nz;
         const long t32 = ((a.M + 127) / 128) * cols32, t64 = ((a.M + 63) / 64) * cols32;
         const int ncu = device_cus();
-        if (ks2 && t64 <= ncu) return launch16s_one<64, 32, 2, 1, 6, EPI, OUT, 2, 0, 2, 2>(a, s);
-        if (ks2 && t32 <= ncu && a.nz == 1) return launch16s_one<128, 32, 4, 1, 6, EPI, OUT, 2, 0, 2, 1>(a, s);     // (batched per-clip
+        if (ks2 && t64 <= ncu) return launch16s_form<HI, 64, 32, 2, 1, 6, EPI, OUT, 2, 2>(a, s);
+        if (ks2 && t32 <= ncu && a.nz == 1) return launch16s_form<HI, 128, 32, 4, 1, 6, EPI, OUT, 2, 1>(a, s);     // (batched per-clip
                                                     // problems - the attention scores at B = 64 - are better off on 128x64: 21 vs 25 us)
-        if (t128 <= 32) return launch16s_one<128, 32, 4, 1, 3, EPI, OUT>(a, s);
+        if (t128 <= 32) return launch16s_form<HI, 128, 32, 4, 1, 3, EPI, OUT>(a, s);
         if (t128 <= 100) {     // up to ~16 clips: 2x the workgroups; with loader waves where six stages fit beside the offset tables
-            if (ks2 && a.nz == 1 && a.taps <= 7 && !a.A2) return launch16s_one<128, 64, 4, 1, 6, EPI, OUT, 2, 0, 2, 1>(a, s);
-            return launch16s_one<128, 64, 4, 1, 3, EPI, OUT>(a, s);
+            if (ks2 && a.nz == 1 && a.taps <= 7 && !a.A2) return launch16s_form<HI, 128, 64, 4, 1, 6, EPI, OUT, 2, 1>(a, s);
+            return launch16s_form<HI, 128, 64, 4, 1, 3, EPI, OUT>(a, s);
         }
         // one 8-wave workgroup per CU (256 slots): 128x192 unless its last round would be mostly idle
         const long tm = (a.M + 127) / 128;
@@ -503,11 +530,18 @@ static int launch16s_tiled(const GemmArgs& a, hipStream_t s) {
             const long t = tm * ((a.N + bn - 1) / bn) * a.nz;
             return std::ceil((double)t / (double)ncu) * bn / eff;
         };
-        if (cost(128, 0.82) < cost(192, 1.0)) return launch16s_one<128, 128, 4, 2, 3, EPI, OUT>(a, s);
-        return launch16s_one<128, 192, 4, 2, 3, EPI, OUT>(a, s);
+        if (cost(128, 0.82) < cost(192, 1.0)) return launch16s_form<HI, 128, 128, 4, 2, 3, EPI, OUT>(a, s);
+        return launch16s_form<HI, 128, 192, 4, 2, 3, EPI, OUT>(a, s);
     }
 }
 
+// The (epilogue, output format) pairs of the one-product twin: what build_decode and plan_head run on S32 operands (no argmax, no
+// encoder-only pair, no mixed-length form)
+#define WT_GEMM16H_PAIRS(X) \
+    X(EPI_BIAS, OUT_F32) X(EPI_BIAS_RES, OUT_F32) X(EPI_BIAS, OUT_S32) X(EPI_BIAS_ROW, OUT_S32) X(EPI_SCALE, OUT_F32) \
+    X(EPI_BIAS_GELU, OUT_S32) X(EPI_BIAS_GAMMA_RES, OUT_F32) X(EPI_HEAD, OUT_S32)
+
+#ifndef WT_GEMM16H_TU
 int gemm16s_vq_parts(int N) { return ((N + 191) / 192) * 2; }      // (column tiles of 192) x (2 wave columns)
 
 // Mixed-length plans (launch_gemm16s's mix_geom): the encoder's convs on three tile forms.  Every form accumulates K in the same order,
@@ -530,11 +564,19 @@ static int launch16s_mixed(const GemmArgs& a, hipStream_t s, const int* mix_geom
 
 // Contract: a.A = S32 activations (same strides as the fp32 array),
 // a.W_hi = S32 weights [N][K]; out_s32 selects an S32 C (c_rstride in fp32 elements either way).
-int check_gemm16s(const GemmArgs& c, int epi, int out, const int* mix_geom) {
+// prec: GEMM16S_F16X3 (three products, the default) or GEMM16S_F16 (the one-product twin, gemm16h.hip)
+int check_gemm16s(const GemmArgs& c, int epi, int out, const int* mix_geom, int prec) {
     bool known = false;
+    if (prec == GEMM16S_F16) {
+#define WT_PAIR16S(E, O) known = known || (epi == E && out == O);
+        WT_GEMM16H_PAIRS(WT_PAIR16S)
+#undef WT_PAIR16S
+        known = known && !mix_geom;
+    } else if (prec == GEMM16S_F16X3) {
 #define WT_PAIR16S(E, O) known = known || (epi == E && out == O);
     WT_GEMM16S_PAIRS(WT_PAIR16S)
 #undef WT_PAIR16S
+    }
     if (!known) { set_error("gemm16s: unsupported epilogue / output-format pair"); return -1; }
     if (mix_geom) {
         bool mixed = false;
@@ -584,8 +626,8 @@ int check_gemm16s(const GemmArgs& c, int epi, int out, const int* mix_geom) {
     return 0;
 }
 
-int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s, const int* mix_geom) {
-    if (int rc = check_gemm16s(a_in, epi, out, mix_geom)) return rc;
+int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s, const int* mix_geom, int prec) {
+    if (int rc = check_gemm16s(a_in, epi, out, mix_geom, prec)) return rc;
     GemmArgs a = a_in;
     // Tile order.  An XCD runs 30 tiles at a time (240 persistent workgroups / 8); a round pulls the A panels of its row tiles
     // and the W panels of its column tiles through that XCD's L2 once.  Wide outputs (ConvNeXt pwconv1: 60 x 12 tiles) walk
@@ -596,6 +638,7 @@ int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s, const 
     if (tiles_n192 >= 12 && tiles_n192 % 6 == 0 && a.nz == 1) { a.group_m = 5; a.group_n = 6; }
     if (const char* e = lab_env("WT_GEMM16S_GM")) { a.group_m = atoi(e) > 0 ? atoi(e) : a.group_m; a.group_n = 0; }      // sweeps (tools/gemm16s_bench.py)
     if (const char* e = lab_env("WT_GEMM16S_GN")) a.group_n = atoi(e);
+    if (prec == GEMM16S_F16) return launch_gemm16h_tiled(a, epi, out, s);      // (same tile order, same tile choice: gemm16h.hip)
     if (mix_geom) {
 #define WT_CASE16S(E, O) if (epi == E && out == O) return launch16s_mixed<E, O>(a, s, mix_geom);
         WT_GEMM16S_MIXED_PAIRS(WT_CASE16S)
@@ -607,6 +650,7 @@ int launch_gemm16s(const GemmArgs& a_in, int epi, int out, hipStream_t s, const 
     set_error("gemm16s: unsupported epilogue / output-format pair");
     return -1;
 }
+#endif      // WT_GEMM16H_TU
 #endif      // WT_GEMM16S_LAB
 
 }  // namespace wt

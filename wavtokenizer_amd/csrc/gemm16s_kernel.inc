@@ -1,7 +1,11 @@
-// gemm16s_kernel (G16_MIX 0) and gemm16s_mixed_kernel (G16_MIX 1): included twice by gemm16s.hip with G16_NAME, G16_PARAMS and
-// G16_MIX set.  With G16_MIX 0 the preprocessed text is exactly the kernel of the plans of one length.  G16_MIX 1 is the
+// gemm16s_kernel (G16_MIX 0), gemm16s_mixed_kernel (G16_MIX 1) and gemm16h_kernel (G16_HI 1): included three times by gemm16s.hip
+// with G16_NAME, G16_PARAMS, G16_MIX and G16_HI set.  With G16_MIX 0 and G16_HI 0 the preprocessed text is exactly the kernel of the
+// plans of one length.  G16_MIX 1 is the
 // mixed-length form (WT_PLAN_FLAG_MIXED_LENGTH): its second argument is clip 0's {T_in, Tp, T_out} triple of this conv in the
 // geometry table (clip stride GEOM_WORDS), which the gather reads per clip; p.T_in / T_out / Tp are then the padded extents.
+// G16_HI 1 is the one-product twin (WT_PLAN_FLAG_F16_GEMM): the hi halves of both operands only, hi.hi into the main
+// accumulator - no correction accumulators, no lo fragment reads, a third of the MFMAs.  The DMA still moves whole 128-byte
+// groups, so the LDS image, the swizzle, the tile walk, the K order and every epilogue are the same text.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NSTAGE, int EPI, int OUT, int DBG = 0, int MF = WT_GEMM16S_MF, int WPS = 2, int KS = 1,
           int PROD = 0>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_NAME(const GemmArgs p G16_PARAMS) {
@@ -244,6 +248,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
     const int r16 = lane & 15, q4 = lane >> 4;
     // 16-row tiles start at multiples of 16 rows, so the swizzle term (row >> 1) & 7 depends on r16 alone
     const int fo16h = r16 * 128 + ((q4 ^ ((r16 >> 1) & 7)) * 16), fo16l = r16 * 128 + (((4 + q4) ^ ((r16 >> 1) & 7)) * 16);
+#if G16_HI
+    (void)fo16l;
+#endif
     const int offA = wm * WM * 128, offB = (BM + wn * WN) * 128;
 
     // Operand order: the weight fragment is the MFMA's A operand and the activation fragment its B operand, so the
@@ -253,21 +260,31 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
     //   MF = 1: row = 16 (s >> 1) + (lane & 15), col = 16 (s & 1) + 4 (lane >> 4)   (the 16x16 tile (s >> 1, s & 1) of the block)
     // The epilogue then moves 16 bytes (fp32) or 8 + 8 bytes (S32) per lane and store, and bias / gamma are per-register vectors.
     constexpr int TM16 = WM / 16, TN16 = WN / 16, TNH = TN16 / 2;
+#if G16_HI
+    f32x16 accm[MF ? 1 : TM][MF ? 1 : TN];
+    f32x4 am[MF ? TM16 : 1][MF ? TN16 : 1];
+    struct Frags { f16x8 ah[TM], bh[TN]; };
+#else
     f32x16 accm[MF ? 1 : TM][MF ? 1 : TN], accc[MF ? 1 : TM][MF ? 1 : TN];
     f32x4 am[MF ? TM16 : 1][MF ? TN16 : 1], ac[MF ? TM16 : 1][MF ? TN16 : 1];
     struct Frags { f16x8 ah[TM], al[TM], bh[TN], bl[TN]; };
+#endif
     auto read_frags = [&](int stage, int s, Frags& F) {
         const char* sA = smem_s + stage * STG + offA;
         const char* sB = smem_s + stage * STG + offB;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             F.ah[i] = *reinterpret_cast<const f16x8*>(sA + i * 32 * 128 + fo[s]);
+#if !G16_HI
             F.al[i] = *reinterpret_cast<const f16x8*>(sA + i * 32 * 128 + fo[2 + s]);
+#endif
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             F.bh[j] = *reinterpret_cast<const f16x8*>(sB + j * 32 * 128 + fo[s]);
+#if !G16_HI
             F.bl[j] = *reinterpret_cast<const f16x8*>(sB + j * 32 * 128 + fo[2 + s]);
+#endif
         }
     };
     auto mfma_block = [&](const Frags& F) {
@@ -276,19 +293,28 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 accm[MF ? 0 : i][MF ? 0 : j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.bh[j], F.ah[i], accm[MF ? 0 : i][MF ? 0 : j], 0, 0, 0);
+#if !G16_HI
                 accc[MF ? 0 : i][MF ? 0 : j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.bl[j], F.ah[i], accc[MF ? 0 : i][MF ? 0 : j], 0, 0, 0);
                 accc[MF ? 0 : i][MF ? 0 : j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.bh[j], F.al[i], accc[MF ? 0 : i][MF ? 0 : j], 0, 0, 0);
+#endif
             }
     };
     // MF = 1: the activation fragments of a step (all TM16 row tiles) and the weight fragments in two halves of TNH column tiles
+#if G16_HI
+    struct FragA { f16x8 h[TM16]; };
+    struct FragB { f16x8 h[TNH]; };
+#else
     struct FragA { f16x8 h[TM16], l[TM16]; };
     struct FragB { f16x8 h[TNH], l[TNH]; };
+#endif
     auto read_a16 = [&](int stage, FragA& F) {
         const char* sA = smem_s + stage * STG + offA;
 #pragma unroll
         for (int i = 0; i < TM16; ++i) {
             F.h[i] = *reinterpret_cast<const f16x8*>(sA + i * 16 * 128 + fo16h);
+#if !G16_HI
             F.l[i] = *reinterpret_cast<const f16x8*>(sA + i * 16 * 128 + fo16l);
+#endif
         }
     };
     auto read_b16 = [&](int stage, int half, FragB& F) {
@@ -296,7 +322,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
 #pragma unroll
         for (int j = 0; j < TNH; ++j) {
             F.h[j] = *reinterpret_cast<const f16x8*>(sB + j * 16 * 128 + fo16h);
+#if !G16_HI
             F.l[j] = *reinterpret_cast<const f16x8*>(sB + j * 16 * 128 + fo16l);
+#endif
         }
     };
     auto mfma16_block = [&](const FragA& A, const FragB& Bf, auto half_c, auto&& between) {
@@ -309,10 +337,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
                 constexpr int jbase = half * TNH;
                 const int j = jbase + jj;
                 f32x4& m = am[MF ? i : 0][MF ? j : 0];
+#if G16_HI
+                m = __builtin_amdgcn_mfma_f32_16x16x32_f16(Bf.h[jj], A.h[i], m, 0, 0, 0);
+#else
                 f32x4& c = ac[MF ? i : 0][MF ? j : 0];
                 m = __builtin_amdgcn_mfma_f32_16x16x32_f16(Bf.h[jj], A.h[i], m, 0, 0, 0);
                 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Bf.l[jj], A.h[i], c, 0, 0, 0);
                 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Bf.h[jj], A.l[i], c, 0, 0, 0);
+#endif
             }
     };
 
@@ -338,7 +370,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
     // operands may carry a per-tensor power-of-two scale (weights at load, the single-stage entry points): the
     // accumulators are brought back by acc_s, exactly (a power of two), before bias and activation
     const float acc_s = p.acc_scale_dev ? *p.acc_scale_dev : p.acc_scale;
+#if !G16_HI
     const float lo_s = acc_s * (1.f / 2048.f);
+#endif
     if ((dbg & 64) && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);     // experiment: static priority for the younger half
     unsigned long long st_c0 = 0, st_r0 = 0;
     if (dbg & 1024) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
@@ -383,14 +417,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
 #pragma unroll
             for (int i = 0; i < TM16; ++i)
 #pragma unroll
+#if G16_HI
+                for (int j = 0; j < TN16; ++j) am[MF ? i : 0][MF ? j : 0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#else
                 for (int j = 0; j < TN16; ++j) { am[MF ? i : 0][MF ? j : 0] = (f32x4){0.f, 0.f, 0.f, 0.f}; ac[MF ? i : 0][MF ? j : 0] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+#endif
         } else {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
+#if G16_HI
+                    for (int r = 0; r < 16; ++r) accm[MF ? 0 : i][MF ? 0 : j][r] = 0.f;
+#else
                     for (int r = 0; r < 16; ++r) { accm[MF ? 0 : i][MF ? 0 : j][r] = 0.f; accc[MF ? 0 : i][MF ? 0 : j][r] = 0.f; }
+#endif
         }
         if constexpr (KS == 2) {
             // K tiles kt, kt + 1 (stages rs, rs + 1) are resident and visible; the next pair is in flight since the previous
@@ -496,14 +538,22 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
 #pragma unroll
                         for (int j = 0; j < TN16; ++j)
 #pragma unroll
+#if G16_HI
+                            for (int r = 0; r < 4; ++r) p.C[(tid * 4 + r) * 2] = am[MF ? i : 0][MF ? j : 0][r];
+#else
                             for (int r = 0; r < 4; ++r) p.C[(tid * 4 + r) * 2] = am[MF ? i : 0][MF ? j : 0][r] + ac[MF ? i : 0][MF ? j : 0][r];
+#endif
                 } else {
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
                         for (int j = 0; j < TN; ++j)
 #pragma unroll
+#if G16_HI
+                            for (int r = 0; r < 16; ++r) p.C[(tid * 16 + r) * 2] = accm[MF ? 0 : i][MF ? 0 : j][r];
+#else
                             for (int r = 0; r < 16; ++r) p.C[(tid * 16 + r) * 2] = accm[MF ? 0 : i][MF ? 0 : j][r] + accc[MF ? 0 : i][MF ? 0 : j][r];
+#endif
                 }
             }
             continue;
@@ -518,6 +568,18 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
     auto sub_col = [&](int s) { return MF ? 16 * (s & 1) + 4 * q4 : 8 * s + 4 * (lane >> 5); };
     auto acc4 = [&](int i, int j, int s) {
         f32x4 v;
+#if G16_HI
+        // one product: the main accumulator is the result (on operands whose lo halves are zero these are the bits of the
+        // three-product kernel, whose correction accumulator then holds +0)
+        if (MF) {
+            v = am[MF ? 2 * i + (s >> 1) : 0][MF ? 2 * j + (s & 1) : 0] * acc_s;
+        } else {
+            v.x = accm[MF ? 0 : i][MF ? 0 : j][4 * s + 0] * acc_s;
+            v.y = accm[MF ? 0 : i][MF ? 0 : j][4 * s + 1] * acc_s;
+            v.z = accm[MF ? 0 : i][MF ? 0 : j][4 * s + 2] * acc_s;
+            v.w = accm[MF ? 0 : i][MF ? 0 : j][4 * s + 3] * acc_s;
+        }
+#else
         if (MF) {
             const f32x4 m = am[MF ? 2 * i + (s >> 1) : 0][MF ? 2 * j + (s & 1) : 0], c = ac[MF ? 2 * i + (s >> 1) : 0][MF ? 2 * j + (s & 1) : 0];
             v.x = fmaf(c.x, lo_s, m.x * acc_s);
@@ -530,6 +592,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * (1 + PROD), WPS) void G16_
             v.z = fmaf(accc[MF ? 0 : i][MF ? 0 : j][4 * s + 2], lo_s, accm[MF ? 0 : i][MF ? 0 : j][4 * s + 2] * acc_s);
             v.w = fmaf(accc[MF ? 0 : i][MF ? 0 : j][4 * s + 3], lo_s, accm[MF ? 0 : i][MF ? 0 : j][4 * s + 3] * acc_s);
         }
+#endif
         return v;
     };
 

@@ -32,22 +32,26 @@ static void set_s32(GemmArgs& a, const S32Copy& c) {
 
 // Both operands pre-split (S32): the activations were written in S32 by their producer, the weight has an S32 copy
 // (mix: a mixed-length plan's geometry triple of this conv, launch_gemm16s)
-static int gemm_s32(const GemmArgs& a, int epi, int out, hipStream_t s, const int* mix = nullptr) {
+// (prec: Prec16s, plan_prec below)
+static int gemm_s32(const GemmArgs& a, int epi, int out, hipStream_t s, const int* mix = nullptr, int prec = GEMM16S_F16X3) {
     if (!a.W_hi) { set_error("internal: no S32 copy of this weight"); return WT_ERR_INVALID; }
-    return launch_gemm16s(a, epi, out, s, mix);
+    return launch_gemm16s(a, epi, out, s, mix, prec);
 }
+// WT_PLAN_FLAG_F16_GEMM (the decode kinds only: wt_plan_create_ex): every GEMM that runs on S32 operands multiplies their hi
+// halves alone.  Producers, buffers and weights are what they are without the flag; a site on fp32 operands stays on gemm.hip
+static int plan_prec(const wt_plan* P) { return (P->flags & WT_PLAN_FLAG_F16_GEMM) ? GEMM16S_F16 : GEMM16S_F16X3; }
 
 // One GEMM step of a layer that runs on either operand form: S32 on gemm16s.hip (`out`: Out16s) or fp32 on gemm.hip
 // (`pro`: its operand prologue)
 static int dense(const wt_plan* P, bool s32, const GemmArgs& a, int pro, int epi, int out, hipStream_t s, const int* mix = nullptr) {
     if (mix && !s32) { set_error("internal: a mixed-length conv off the S32 route"); return WT_ERR_INVALID; }
-    return s32 ? gemm_s32(a, epi, out, s, mix) : gemm_auto(P, a, pro, epi, s);
+    return s32 ? gemm_s32(a, epi, out, s, mix, plan_prec(P)) : gemm_auto(P, a, pro, epi, s);
 }
 
 // Activation x activation (attention S and O): the B operand is a plan buffer, S32 in W_hi on gemm16s.hip, fp32 in W on
 // gemm.hip
 static int dense_act(const wt_plan* P, bool s32, GemmArgs a, const float* b_op, int epi, int out, hipStream_t s) {
-    if (s32) { a.W_hi = b_op; return launch_gemm16s(a, epi, out, s); }
+    if (s32) { a.W_hi = b_op; return launch_gemm16s(a, epi, out, s, nullptr, plan_prec(P)); }
     a.W = b_op;
     return gemm_auto(P, a, PRO_NONE, epi, s);
 }

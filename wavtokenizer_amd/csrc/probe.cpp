@@ -97,8 +97,9 @@ static const int32_t* gemm_desc_mix(const wt_gemm_desc* d) { return d->size == (
 static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
     if (!gemm_desc_size_ok(d)) { set_error("wt_gemm_probe: descriptor missing or of another size"); return WT_ERR_INVALID; }
     const int32_t* mix = gemm_desc_mix(d);
-    if (mix && (d->engine != 0 || (reinterpret_cast<uintptr_t>(mix) & 3))) { set_error("wt_gemm_probe: mix_geom is a 4-byte aligned device table for gemm16s"); return WT_ERR_INVALID; }
-    if (d->engine != 0 && d->engine != 1) { set_error("wt_gemm_probe: engine is 0 (gemm16s) or 1 (gemm)"); return WT_ERR_INVALID; }
+    const bool e16 = d && (d->engine == 0 || d->engine == 2);       // gemm16s.hip: three products, or (2) the one-product twin
+    if (mix && (!e16 || (reinterpret_cast<uintptr_t>(mix) & 3))) { set_error("wt_gemm_probe: mix_geom is a 4-byte aligned device table for gemm16s"); return WT_ERR_INVALID; }
+    if (d->engine < 0 || d->engine > 2) { set_error("wt_gemm_probe: engine is 0 (gemm16s), 1 (gemm) or 2 (gemm16s, one product)"); return WT_ERR_INVALID; }
     if (!d->A || !d->B || !d->C) { set_error("wt_gemm_probe: A, B and C are required"); return WT_ERR_INVALID; }
     if (d->epi == EPI_ARGMAX) { set_error("wt_gemm_probe: the argmax epilogue is reached through wt_vq_nearest"); return WT_ERR_INVALID; }
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->T_out <= 0 || d->T_in <= 0 || d->M % d->T_out || d->nz < 1 || d->taps < 1 ||
@@ -110,9 +111,9 @@ static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
     if (d->engine == 1 && (d->out != OUT_F32 || d->A2 || d->tap_pair)) {
         set_error("wt_gemm_probe: gemm.hip writes fp32 and has no second K source or tap pairing"); return WT_ERR_INVALID;
     }
-    if (d->engine == 0 && d->pro != PRO_NONE) { set_error("wt_gemm_probe: gemm16s has no operand prologue"); return WT_ERR_INVALID; }
+    if (e16 && d->pro != PRO_NONE) { set_error("wt_gemm_probe: gemm16s has no operand prologue"); return WT_ERR_INVALID; }
     if (d->tap_pair && (d->taps != 2 * d->stride || d->dil != 1)) { set_error("wt_gemm_probe: tap pairing needs k = 2 * stride, dilation 1"); return WT_ERR_INVALID; }
-    if (d->engine == 0 && (!ws || (reinterpret_cast<uintptr_t>(ws) & 255))) { set_error("wt_gemm_probe: gemm16s needs a 256-byte aligned workspace"); return WT_ERR_INVALID; }
+    if (e16 && (!ws || (reinterpret_cast<uintptr_t>(ws) & 255))) { set_error("wt_gemm_probe: gemm16s needs a 256-byte aligned workspace"); return WT_ERR_INVALID; }
     a = GemmArgs{};
     a.a_bstride = d->a_bstride; a.a_rstride = d->a_rstride; a.T_in = d->T_in; a.T_out = d->T_out; a.Cin = d->Cin; a.taps = d->taps;
     a.stride = d->stride; a.dil = d->dil; a.pad_left = d->pad_left; a.pad_mode = d->pad_mode; a.Tp = d->Tp;
@@ -129,11 +130,11 @@ static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
     a.A2 = d->A2 ? reinterpret_cast<const float*>(ws + L.oA2) : nullptr;
     a.W = d->B; a.W_hi = ws + L.oB;
     a.status = reinterpret_cast<unsigned*>(d->status);
-    return check_gemm16s(a, d->epi, d->out, mix) ? WT_ERR_INVALID : WT_OK;
+    return check_gemm16s(a, d->epi, d->out, mix, d->engine == 2 ? GEMM16S_F16 : GEMM16S_F16X3) ? WT_ERR_INVALID : WT_OK;
 }
 
 size_t wt_gemm_probe_workspace_bytes(const wt_gemm_desc* d) {
-    if (!gemm_desc_size_ok(d) || d->engine != 0 || d->M <= 0 || d->T_out <= 0 || d->nz < 1) return 0;
+    if (!gemm_desc_size_ok(d) || (d->engine != 0 && d->engine != 2) || d->M <= 0 || d->T_out <= 0 || d->nz < 1) return 0;
     return probe_layout(*d).total;
 }
 
@@ -171,7 +172,7 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
         if (int rc = launch_split_s32(d->B, ws + L.oB, L.nB, s, scale != 1.f ? scale_dev : nullptr)) return rc;
         if (int rc = launch_split_s32(d->A, ws, L.nA, s)) return rc;
         if (d->A2) if (int rc = launch_split_s32(d->A2, ws + L.oA2, L.nA2, s)) return rc;
-        if (int rc = launch_gemm16s(a, d->epi, d->out, s, gemm_desc_mix(d))) return rc;
+        if (int rc = launch_gemm16s(a, d->epi, d->out, s, gemm_desc_mix(d), d->engine == 2 ? GEMM16S_F16 : GEMM16S_F16X3)) return rc;
     }
     if (form) *form = wt_launch_form{lf.BM, lf.BN, lf.waves_m, lf.waves_n, lf.stages, lf.ks, lf.prod, lf.staged, lf.bias_cache, lf.G, lf.tiles};
     return WT_OK;

@@ -330,6 +330,7 @@ class WavTokenizer(nn.Module):
         self._engine = _Engine()
         self._dirty = True
         self._plan_flags = 0
+        self._f16_gemm = False               # set_gemm_precision("f16"): the decode plan kinds alone get WT_PLAN_FLAG_F16_GEMM (_decode_flags)
         self._fp32_sites = 0                 # range sites (_capi.WT_SITE_*) that have left the split-f16 form after an overflow
         # strict status: None (default) = automatic: calls of up to _graph_max_clips clips (graph-replayed, bound by the host
         # anyway: the reference's own file-by-file usage) synchronise, check and REPEAT a failed call on the fallback path, so
@@ -587,15 +588,29 @@ class WavTokenizer(nn.Module):
             self._fp32_sites |= 1 << site
             return "range site %d (%s) now keeps fp32 operands" % (site, site_name(site))
         self._plan_flags |= _capi.WT_PLAN_FLAG_FP32_GEMM
+        self._f16_gemm = False
         return "no site attribution left: the whole model now runs fp32 GEMMs"
 
     def set_gemm_precision(self, mode: str):
         """"f16x3" (default): dense layers on the fp32-equivalent split-f16 MFMA kernel; "f32": the plain
-        fp32 MFMA chain everywhere.  Both accumulate in fp32; measured error vs float64 is lower for f16x3."""
-        if mode not in ("f16x3", "f32"):
-            raise ValueError("mode must be 'f16x3' or 'f32'")
+        fp32 MFMA chain everywhere.  Both accumulate in fp32; measured error vs float64 is lower for f16x3.
+        "f16": half-precision inference for the decoder, for callers that hold codes and want audio: decode, decode_many,
+        decode_codes, decode_codes_many, model(wav) and model.backbone(...) multiply the f16 hi halves of the split-f16 operands
+        alone (one MFMA per product instead of three, fp32 accumulate; waveform error near 1e-3 relative instead of 1e-5).
+        The encoder, the VQ and the codes, codes_to_features, model.head(...), the SEANet callables and range_report stay on
+        f16x3 whatever the mode."""
+        if mode not in ("f16x3", "f32", "f16"):
+            raise ValueError("mode must be 'f16x3', 'f32' or 'f16'")
         self._plan_flags = (self._plan_flags | _capi.WT_PLAN_FLAG_FP32_GEMM) if mode == "f32" else \
             (self._plan_flags & ~_capi.WT_PLAN_FLAG_FP32_GEMM)
+        self._f16_gemm = mode == "f16"
+
+    def _decode_flags(self, flags: int) -> int:
+        """The flags of a decode-kind plan (WT_PLAN_DECODE, _MIXED, _CODES, _CODES_MIXED): `flags` plus the one-product GEMM mode
+        where it is set and the plan runs split-f16 operands at all (the library refuses it beside FP32_GEMM or UNFUSED)."""
+        if self._f16_gemm and not (flags & (_capi.WT_PLAN_FLAG_FP32_GEMM | _capi.WT_PLAN_FLAG_UNFUSED)):
+            return flags | _capi.WT_PLAN_FLAG_F16_GEMM
+        return flags
 
     def set_check_codes(self, mode: str):
         """How codes_to_features reports an index outside the codebook: "sync" (default: synchronise and raise for the
@@ -887,7 +902,7 @@ class WavTokenizer(nn.Module):
         features = self._as_input(features, dev)
         B = features.shape[0]
         # a call that wants the backbone output is never graph-replayed
-        return self._guarded(dev, lambda: self._decode(features, bw, self._plan_flags if want_backbone else self._graph_flags(B),
+        return self._guarded(dev, lambda: self._decode(features, bw, self._decode_flags(self._plan_flags if want_backbone else self._graph_flags(B)),
                                                        dev, want_backbone), self._is_strict(B))
 
     def _decode(self, features: torch.Tensor, bw: int, flags: int, dev: torch.device, want_backbone: bool):
@@ -921,7 +936,7 @@ class WavTokenizer(nn.Module):
             # checked on every attempt: a range fallback inside _guarded can put a decoder site on fp32
             if not self._decode_mixed_route_ok():
                 raise _OffRoute()
-            return self._call(lib.wt_decode_mixed, _capi.WT_PLAN_DECODE_MIXED, B, L_pad, self._graph_flags(B), dev, ins, outs, (bw,))
+            return self._call(lib.wt_decode_mixed, _capi.WT_PLAN_DECODE_MIXED, B, L_pad, self._decode_flags(self._graph_flags(B)), dev, ins, outs, (bw,))
 
         try:
             return self._guarded(dev, call, self._is_strict(B))[0]
@@ -931,7 +946,8 @@ class WavTokenizer(nn.Module):
     def _decode_mixed_route_ok(self) -> bool:
         """Whether the decoder runs the route a mixed-length plan takes (the shipped split-f16 one): no fp32 GEMMs, no unfused
         debug plan, no debug taps or range report, no decoder range site on fp32, and weights that fit the split-f16 form
-        (the conditions build_decode checks; a plan refused in spite of them is an error, not a fallback)."""
+        (the conditions build_decode checks; a plan refused in spite of them is an error, not a fallback).  The one-product mode
+        (set_gemm_precision("f16")) is on the route: the mixed plans launch the same GEMMs."""
         off_route = (_capi.WT_PLAN_FLAG_FP32_GEMM | _capi.WT_PLAN_FLAG_UNFUSED | _capi.WT_PLAN_FLAG_KEEP_STAGES |
                      _capi.WT_PLAN_FLAG_RANGE_REPORT)
         return (not (self._plan_flags & off_route) and not self._sites(_capi.WT_PLAN_DECODE_MIXED) and
@@ -1011,7 +1027,7 @@ class WavTokenizer(nn.Module):
             raise WavTokError("decode_codes: K must be between 1 and the number of codebooks", _capi.WT_ERR_INVALID)
         codes = self._as_input(codes, dev, torch.int64)
         B = codes.shape[1]
-        wav = self._guarded(dev, lambda: self._decode_codes(codes, bw, self._graph_flags(B), dev), self._is_strict(B))[0]
+        wav = self._guarded(dev, lambda: self._decode_codes(codes, bw, self._decode_flags(self._graph_flags(B)), dev), self._is_strict(B))[0]
         self._codes_checked(dev)
         return wav
 
@@ -1039,7 +1055,7 @@ class WavTokenizer(nn.Module):
             # checked on every attempt: a range fallback inside _guarded can put a decoder site on fp32
             if not self._decode_mixed_route_ok():
                 raise _OffRoute()
-            flags = self._graph_flags(B)
+            flags = self._decode_flags(self._graph_flags(B))
             ins = (self._codes_staging(K, B, L_pad, flags, fill_codes),
                    ((B,), torch.int32, lambda lens: lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)))
             return self._call(_decode_codes_mixed_entry, _capi.WT_PLAN_DECODE_CODES_MIXED, B, L_pad, flags, dev, ins, outs, (K, bw),
@@ -1118,7 +1134,8 @@ class WavTokenizer(nn.Module):
         """A named stage buffer of the cached plan (after a KEEP_STAGES run), decoded to fp32: returns (flat tensor,
         format bits); format & BUF_ELU says the buffer holds elu() of the reference's tensor.  S32 buffers are decoded
         (rows x cols with cols = numel / rows: pass `rows` for them)."""
-        plan, ws = self._engine.plans[(kind, B, length, self._plan_flags)]
+        decode_kinds = (_capi.WT_PLAN_DECODE, _capi.WT_PLAN_DECODE_MIXED, _capi.WT_PLAN_DECODE_CODES, _capi.WT_PLAN_DECODE_CODES_MIXED)
+        plan, ws = self._engine.plans[(kind, B, length, self._decode_flags(self._plan_flags) if kind in decode_kinds else self._plan_flags)]
         off, n, fmt = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int32()
         check(lib.wt_plan_buffer_info(plan, name.encode(), ctypes.byref(off), ctypes.byref(n), ctypes.byref(fmt)),
               "wt_plan_buffer_info")

@@ -230,7 +230,8 @@ int wt_plan_read_timing(const wt_plan* p, double* total_ms, int64_t* launches, i
  * EncodecFeatures.infer (decoder/feature_extractors.py:131-142): SEANetEncoder
  * (encoder/modules/seanet.py:143) + ResidualVectorQuantizer.infer (encoder/quantization/vq.py:115-140).
  *   wav      [B][T] fp32 (device)
- *   features [B][512][L] fp32 (device, out) — quantized embedding
+ *   features [B][512][L] fp32 (device, out) — quantized embedding; may be NULL (a caller that wants the codes alone: the
+ *            gather of the codebook rows and the transposed write are then skipped)
  *   codes    [1][B][L] int64 (device, out)
  *   emb_out  optional [B][512][L] fp32: encoder output before quantisation (may be NULL) */
 int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* codes, float* emb_out,
@@ -243,7 +244,8 @@ int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* code
  *   lengths  [B] int32 (device), each in [wt_plan_min_clip_length(p), Tpad]
  *   features [B][512][Lpad], codes [1][B][Lpad], emb_out (optional) [B][512][Lpad]: past a clip's L = ceil(length / hop) the
  *            codes are -1 and the features (and emb_out) 0.  A clip whose length is outside the range gets -1 codes and NaN
- *            features over its whole row; the other clips and the call's status are not affected.
+ *            features over its whole row; the other clips and the call's status are not affected.  features may be NULL as in
+ *            wt_encode (codes alone).
  * wt_encode refuses a mixed-length plan, and wt_encode_mixed every other plan. */
 int wt_encode_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, float* features, int64_t* codes, float* emb_out,
                     void* workspace, void* stream);
@@ -573,6 +575,40 @@ int     wt_resampler_create(int32_t orig_sr, int32_t new_sr, int32_t device, wt_
 void    wt_resampler_destroy(wt_resampler* r);
 int64_t wt_resampler_out_length(const wt_resampler* r, int64_t T);
 int     wt_convert_audio(const wt_resampler* r, const float* wav, int32_t B, int32_t C, int64_t T, float* out, void* stream);
+
+/* Ragged ingest: the way into wt_encode / wt_encode_mixed for a caller that holds raw PCM.  One launch converts B clips of any
+ * rate, channel count (1 or 2), layout and sample type (fp32, or int16 scaled by 1 / 32768) into the rows of the fp32 tensor
+ * out [B][T_pad], the `wav` operand of wt_encode / wt_encode_mixed: row b holds in its first n_out columns the bits
+ * wt_convert_audio gives for clip b alone as planar fp32; columns from n_out on are not written, and nothing outside a clip's
+ * n_in samples per channel is read.  Sample (c, t) of a clip is src[c * ch_stride + t * sample_stride] (strides in elements, not
+ * negative): planar (C, T) and interleaved (T, C) are both a descriptor.  clips is a HOST array; src and out are device
+ * pointers.  The library uploads the descriptors into workspace (device, wt_ingest_workspace_bytes(B) bytes, 8-byte aligned; its
+ * content must stay untouched until the launch has run) on `stream`.  Every descriptor is checked before any device call: a null
+ * source or resampler, a sample type other than the two, channels other than 1 or 2, n_in < 1, n_out other than
+ * wt_resampler_out_length(resampler, n_in), n_out > T_pad, a source pointer not aligned to its sample type, or a resampler of
+ * another device than clip 0's returns WT_ERR_INVALID with a message and touches no memory.
+ * wt_ingest is a host-side call around its launch: it waits for an event, may allocate pinned memory and enqueues a copy, so it
+ * must NOT be called on a stream that is being captured into a graph (call it before the replay, on the replay's stream).
+ * Calls on one device are serialised by a lock for the time of the upload.  The two pinned descriptor blocks and their events
+ * per device live until the process ends. */
+typedef enum { WT_INGEST_F32 = 0, WT_INGEST_I16 = 1 } wt_ingest_dtype;
+typedef struct {
+    const void* src;                  /* device */
+    int32_t dtype;                    /* wt_ingest_dtype */
+    int32_t channels;                 /* 1 or 2 */
+    int64_t n_in;                     /* samples per channel */
+    int64_t ch_stride, sample_stride; /* elements */
+    const wt_resampler* resampler;    /* the clip's rate pair (equal rates: the K = 1 copy) */
+    int64_t n_out;                    /* wt_resampler_out_length(resampler, n_in) */
+} wt_ingest_clip;
+size_t wt_ingest_workspace_bytes(int32_t B);
+int    wt_ingest(const wt_ingest_clip* clips, int32_t B, int64_t T_pad, float* out, void* workspace, void* stream);
+
+/* Ragged codes out: spans is a device array [B][2] int64 = {L_b, offset_b}; the first L_b codes of row b of codes [1][B][L_pad]
+ * (what wt_encode / wt_encode_mixed write) go to out[offset_b + t], out a flat int64 tensor of out_numel elements (device).  A
+ * span with L_b outside [0, L_pad] or that does not fit out is skipped whole. */
+int wt_codes_unpack(const int64_t* codes, int32_t B, int64_t L_pad, const int64_t* spans, int64_t* out, int64_t out_numel,
+                    void* stream);
 
 /* Replaces: save_audio's clamp / rescale (encoder/utils.py:95-103) + the PCM_S 16 conversion of torchaudio.save
  * (infer.py:70): rescale = 0: clamp to [-limit, limit]; 1: scale by min(limit / max|x|, 1) (workspace: 4 bytes);

@@ -25,7 +25,7 @@ EXPORTS = [
     "wt_resampler_create", "wt_resampler_destroy", "wt_resampler_out_length", "wt_convert_audio", "wt_pcm16",
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
     "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe", "wt_lstm_probe_workspace_bytes", "wt_lstm_probe",
-    "wt_decode_codes", "wt_decode_codes_mixed",
+    "wt_decode_codes", "wt_decode_codes_mixed", "wt_ingest_workspace_bytes", "wt_ingest", "wt_codes_unpack",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -129,6 +129,15 @@ class WtGeomDesc(ctypes.Structure):
 class WtGeomWords(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("words", "valid", "T", "Tread", "stage0", "stage_words", "c3", "sc", "down", "final_conv",
                                        "L", "max_stages")]
+
+
+WT_INGEST_F32, WT_INGEST_I16 = 0, 1
+
+
+class WtIngestClip(ctypes.Structure):
+    """wt_ingest_clip: one clip of a ragged ingest launch (wt_ingest)."""
+    _fields_ = [("src", c_void_p), ("dtype", c_int32), ("channels", c_int32), ("n_in", c_int64), ("ch_stride", c_int64),
+                ("sample_stride", c_int64), ("resampler", c_void_p), ("n_out", c_int64)]
 
 
 class WavTokError(RuntimeError):
@@ -241,6 +250,10 @@ def _load() -> ctypes.CDLL:
     lib.wt_convert_audio.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p]
     lib.wt_pcm16.argtypes = [c_void_p, c_int64, ctypes.c_float, c_int32, c_void_p, c_void_p, c_void_p]
     lib.wt_linear_overlap_add.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]
+    lib.wt_ingest_workspace_bytes.argtypes = [c_int32]
+    lib.wt_ingest_workspace_bytes.restype = c_size_t
+    lib.wt_ingest.argtypes = [POINTER(WtIngestClip), c_int32, c_int64, c_void_p, c_void_p, c_void_p]
+    lib.wt_codes_unpack.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
     return lib
 
 

@@ -7,6 +7,7 @@
 
 All take and return torch tensors on the GPU; there is no CPU fallback."""
 import ctypes
+import functools
 from typing import Dict, List, Sequence, Tuple
 
 import torch
@@ -29,6 +30,44 @@ def _need_gpu(t: torch.Tensor):
         raise RuntimeError("wavtokenizer_amd.audio runs on the GPU only (move the tensor with .to('cuda'))")
 
 
+@functools.lru_cache(maxsize=None)
+def resampler_geometry(sr: int, target_sr: int) -> Tuple[int, int, int, int]:
+    """(orig, new, width, K) of the rate pair as wt_resampler_create derives them, on the host: the gcd-reduced rates, the half
+    width and the taps per phase.  Raises ValueError for a pair the library refuses (a rate below 1, a ratio beyond the LDS
+    window of the kernels), so that a caller can refuse its arguments before any GPU work.  The host twin of the rule in
+    csrc/audio.hip (wt_resampler_create: width, K, the 15 000-float limit; wt_ingest: the 64 KiB of dynamic LDS): change them
+    together (tests/test_encode_codes_host.py compares the two through wt_resampler_out_length and pinned pairs)."""
+    import math
+    sr, target_sr = int(sr), int(target_sr)
+    if sr < 1 or target_sr < 1:
+        raise ValueError("sample rates must be positive")
+    g = math.gcd(sr, target_sr)
+    orig, new = sr // g, target_sr // g
+    if orig == new:
+        return orig, new, 0, 1
+    width = int(math.ceil(6 * orig / (min(orig, new) * 0.99)))
+    K = 2 * width + orig
+    if 256.0 * orig / new + K > 15000 or ((256 // new + 2) * orig + K) * 4 > 64 * 1024:
+        raise ValueError(f"resampling {sr} -> {target_sr}: rate ratio too large for the LDS window")
+    return orig, new, width, K
+
+
+def resampled_length(sr: int, target_sr: int, length: int) -> int:
+    """wt_resampler_out_length on the host: ceil(new * length / orig)."""
+    orig, new, _w, _k = resampler_geometry(sr, target_sr)
+    return -(-new * int(length) // orig)
+
+
+def resampler(sr: int, target_sr: int, device_index: int) -> ctypes.c_void_p:
+    """The wt_resampler of a rate pair on a device, created once per process."""
+    key = (int(sr), int(target_sr), int(device_index))
+    if key not in _resamplers:
+        r = ctypes.c_void_p()
+        check(lib.wt_resampler_create(int(sr), int(target_sr), int(device_index), ctypes.byref(r)), "wt_resampler_create")
+        _resamplers[key] = r
+    return _resamplers[key]
+
+
 def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: int = 1) -> torch.Tensor:
     assert wav.dim() >= 2, "Audio tensor must have at least 2 dimensions"
     assert wav.shape[-2] in [1, 2], "Audio must be mono or stereo."
@@ -38,12 +77,7 @@ def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: i
     *shape, channels, length = wav.shape
     dev = wav.device
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    key = (int(sr), int(target_sr), idx)
-    if key not in _resamplers:
-        r = ctypes.c_void_p()
-        check(lib.wt_resampler_create(int(sr), int(target_sr), idx, ctypes.byref(r)), "wt_resampler_create")
-        _resamplers[key] = r
-    r = _resamplers[key]
+    r = resampler(sr, target_sr, idx)
     B = 1
     for s in shape:
         B *= int(s)

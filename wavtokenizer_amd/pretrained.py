@@ -312,6 +312,16 @@ def _decode_codes_mixed_entry(plan, codes, lengths, K, bw, wav, ws, stream):
     """lib.wt_decode_codes_mixed in the argument order of WavTokenizer._call (inputs, scalars, outputs)."""
     return lib.wt_decode_codes_mixed(plan, codes, K, lengths, bw, wav, ws, stream)
 
+
+class _ClipSpec:
+    """One clip of WavTokenizer.encode_codes_many: the tensor as given, its channels, samples per channel, layout, rate and
+    resampled length."""
+    __slots__ = ("clip", "channels", "n_in", "channels_last", "rate", "n_out")
+
+    def __init__(self, clip: torch.Tensor, channels: int, n_in: int, channels_last: bool, rate: int, n_out: int):
+        self.clip, self.channels, self.n_in, self.channels_last, self.rate, self.n_out = clip, channels, n_in, channels_last, rate, n_out
+
+
 class _OffRoute(Exception):
     """A mixed-length call found the encoder off the route mixed-length plans take (WavTokenizer._mixed_route_ok)."""
 
@@ -352,6 +362,11 @@ class WavTokenizer(nn.Module):
         # batches up to this many clips are replayed as one hipGraph per (shape) plan: they are bound by the host's
         # launch rate (about 100 launches per call), not by the GPU; 0 turns graphs off
         self._graph_max_clips = int(os.environ.get("WAVTOK_GRAPH_MAX_CLIPS", "16"))
+        # encode_codes_many: two pinned host buffers that take turns carrying a group's CPU clips (and its lengths and code
+        # offsets) to the GPU in one copy; the event behind a buffer's last upload guards it against reuse
+        self._pin_bufs: List[Optional[torch.Tensor]] = [None, None]
+        self._pin_events: List[Any] = [None, None]
+        self._pin_next = 0
         for m in (feature_extractor, backbone, head):
             m._bind(self)
 
@@ -789,12 +804,15 @@ class WavTokenizer(nn.Module):
             return tuple(b.clone() if o is not None and o[2] else None for o, b in zip(outs, obufs)), plan
         return tuple(obufs), plan
 
-    def _encode(self, audio: torch.Tensor, flags: int, dev: torch.device, want_emb: bool):
-        """The encode call of _run_encode and range_report: ((features, codes, emb), plan)."""
+    def _encode(self, audio: torch.Tensor, flags: int, dev: torch.device, want_emb: bool, want_feats: bool = True):
+        """The encode call of _run_encode, encode_codes and range_report: ((features, codes, emb), plan).  Without want_feats a
+        direct call passes a null features pointer (the library then skips the gather); a graph plan keeps passing its staging
+        buffer, so encode_infer and encode_codes share one recording."""
         B, T = audio.shape
         L = self._arch.frames(T)
         return self._call(lib.wt_encode, _capi.WT_PLAN_ENCODE, B, T, flags, dev, (audio,),
-                          (((B, 512, L), torch.float32, True), ((1, B, L), torch.int64, True), ((B, 512, L), torch.float32, want_emb)))
+                          (((B, 512, L), torch.float32, want_feats), ((1, B, L), torch.int64, True), ((B, 512, L), torch.float32, want_emb)),
+                          name="wt_encode")
 
     def _run_encode(self, audio: torch.Tensor, want_emb: bool = True):
         dev = self._ensure_engine()
@@ -872,6 +890,196 @@ class WavTokenizer(nn.Module):
         for i in sorted(solo):
             out[i] = self.encode_infer(wavs[i][None], bandwidth_id=bandwidth_id)
         return out  # type: ignore[return-value]
+
+    # -- tokenise straight from PCM: ragged ingest -> encode without a feature tensor -> ragged codes out ----------------------
+    @torch.inference_mode()
+    def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None) -> torch.Tensor:
+        """encode_infer(audio_input, bandwidth_id=...)[1], the same bits, for a caller that wants the codes alone: (B, T) fp32 at
+        the codec rate -> (1, B, L) int64.  A call that is not graph-replayed passes no feature buffer to the library (nothing
+        gathers or writes the (B, 512, L) tensor); a graph-replayed one shares encode_infer's recording and staging buffers.
+        Status, fallbacks and graphs behave as in encode_infer."""
+        if bandwidth_id is not None:
+            _ = self.feature_extractor.bandwidths[self._bandwidth_index(bandwidth_id)]
+        dev = self._ensure_engine()
+        assert audio_input.dim() == 2, "expected audio of shape (B, T)"
+        audio = self._as_input(audio_input, dev)
+        B = audio.shape[0]
+        return self._guarded(dev, lambda: self._encode(audio, self._graph_flags(B), dev, want_emb=False, want_feats=False),
+                             self._is_strict(B))[1]
+
+    def _pinned(self, nbytes: int) -> Tuple[int, torch.Tensor]:
+        """(slot, pinned uint8 buffer of at least nbytes): the two buffers take turns; a buffer whose last upload may still be
+        running is waited for first."""
+        k = self._pin_next
+        self._pin_next ^= 1
+        if self._pin_events[k] is not None:
+            self._pin_events[k].synchronize()
+        buf = self._pin_bufs[k]
+        if buf is None or buf.numel() < nbytes:
+            buf = self._pin_bufs[k] = torch.empty(max(nbytes + nbytes // 4, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        return k, buf
+
+    def _ingest_stage(self, specs: Sequence["_ClipSpec"], offsets: Sequence[int], dev: torch.device):
+        """Brings a group of clips within reach of one wt_ingest: the CPU clips, the resampled lengths (int32) and the code spans
+        (int64 {frames, offset}) are packed into one pinned buffer and uploaded with ONE copy; clips on the GPU stay where they
+        are.  Returns (descriptors, device workspace of wt_ingest, lengths on the GPU, spans on the GPU, what must stay alive)."""
+        from . import audio
+        B = len(specs)
+        up = lambda n, a: -(-n // a) * a
+        nbytes = lambda c: c.numel() * c.element_size()
+        o_spans = up(4 * B, 8)
+        pos = up(o_spans + 16 * B, 16)
+        where = [-1] * B
+        packed = []
+        for j, sp in enumerate(specs):
+            c = sp.clip
+            if c.device.type != "cpu":
+                if c.device != dev:
+                    raise RuntimeError(f"a clip is on {c.device} but the model is on {dev}")
+                continue
+            packed.append(j)
+            where[j] = pos
+            pos = up(pos + nbytes(c), 16)
+        slot, pin = self._pinned(pos)
+        pin[:4 * B].view(torch.int32).copy_(torch.tensor([sp.n_out for sp in specs], dtype=torch.int32))
+        spans = [v for sp, off in zip(specs, offsets) for v in (self._arch.frames(sp.n_out), int(off))]
+        pin[o_spans:o_spans + 16 * B].view(torch.int64).copy_(torch.tensor(spans, dtype=torch.int64))
+        for j in packed:
+            c = specs[j].clip
+            pin[where[j]:where[j] + nbytes(c)].view(c.dtype).view(c.shape).copy_(c)
+        blob = torch.empty(pos, dtype=torch.uint8, device=dev)
+        blob.copy_(pin[:pos], non_blocking=True)
+        ev = self._pin_events[slot] = self._pin_events[slot] or torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        descs = (_capi.WtIngestClip * B)()
+        blob_ptr = blob.data_ptr()
+        handles: Dict[int, ctypes.c_void_p] = {}
+        codec_rate = self.codec_rate
+        for d, sp, o in zip(descs, specs, where):
+            if o >= 0:           # packed contiguously in the clip's own shape
+                st = (1,) if sp.clip.dim() == 1 else (int(sp.clip.shape[1]), 1)
+                d.src = blob_ptr + o
+            else:
+                st = sp.clip.stride()
+                d.src = sp.clip.data_ptr()
+            d.dtype = _capi.WT_INGEST_I16 if sp.clip.dtype == torch.int16 else _capi.WT_INGEST_F32
+            d.channels, d.n_in, d.n_out = sp.channels, sp.n_in, sp.n_out
+            if sp.clip.dim() == 1:
+                d.ch_stride, d.sample_stride = 0, st[0]
+            else:
+                d.ch_stride, d.sample_stride = (st[1], st[0]) if sp.channels_last else (st[0], st[1])
+            if sp.rate not in handles:
+                handles[sp.rate] = audio.resampler(sp.rate, codec_rate, dev.index)
+            d.resampler = handles[sp.rate]
+        ws = torch.empty(max(int(lib.wt_ingest_workspace_bytes(B)), 8), dtype=torch.uint8, device=dev)
+        return descs, ws, blob[:4 * B].view(torch.int32), blob[o_spans:o_spans + 16 * B].view(torch.int64), (blob, [sp.clip for sp in specs])
+
+    @property
+    def codec_rate(self) -> int:
+        return int(self.feature_extractor.encodec.sample_rate)
+
+    def _run_encode_codes_mixed(self, specs: Sequence["_ClipSpec"], T_pad: int, flat: torch.Tensor, offsets: Sequence[int]):
+        """One group of encode_codes_many: one upload, one wt_ingest into the plan's staging tensor, one wt_encode_mixed (no
+        feature buffer unless the plan is graph-replayed), one wt_codes_unpack into flat at the clips' offsets.  Returns True, or
+        None when the encoder is off the route a mixed-length plan takes (_mixed_route_ok)."""
+        dev = self._ensure_engine()
+        if not self._mixed_route_ok():          # (before anything is uploaded; checked again on every attempt below)
+            return None
+        B = len(specs)
+        L = self._arch.frames(T_pad)
+        descs, ws, lengths, spans, _alive = self._ingest_stage(specs, offsets, dev)
+
+        def fill_wav(buf: torch.Tensor):        # (columns past a clip's length are never read)
+            check(lib.wt_ingest(descs, B, T_pad, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
+
+        ins = (((B, T_pad), torch.float32, fill_wav), ((B,), torch.int32, lambda lens: lens.copy_(lengths)))
+        # a graph plan passes its staging feature buffer like encode_infer_many (the recording is keyed by the pointers, so the two
+        # alternate on one recording); a direct call passes none
+        outs = (((B, 512, L), torch.float32, False), ((1, B, L), torch.int64, True), None)
+
+        def call():
+            if not self._mixed_route_ok():
+                raise _OffRoute()
+            return self._call(lib.wt_encode_mixed, _capi.WT_PLAN_ENCODE, B, T_pad,
+                              self._graph_flags(B) | _capi.WT_PLAN_FLAG_MIXED_LENGTH, dev, ins, outs, name="wt_encode_mixed")
+
+        try:
+            codes = self._guarded(dev, call, self._is_strict(B))[1]
+        except _OffRoute:
+            return None
+        check(lib.wt_codes_unpack(_ptr(codes), B, L, _ptr(spans), _ptr(flat), flat.numel(), _stream_ptr(dev)), "wt_codes_unpack")
+        return True
+
+    def _encode_codes_solo(self, specs: Sequence["_ClipSpec"], flat: torch.Tensor, offsets: Sequence[int]):
+        """Clips that run one at a time (shorter than a mixed-length plan takes, or the encoder off its shipped route): ingested
+        together like a group, at most MAX_GROUP per launch, then encode_codes per clip."""
+        from .mixed_length import MAX_GROUP
+        dev = self._ensure_engine()
+        for c0 in range(0, len(specs), MAX_GROUP):
+            part, offs = specs[c0:c0 + MAX_GROUP], offsets[c0:c0 + MAX_GROUP]
+            T_pad = max(sp.n_out for sp in part)
+            descs, ws, _lengths, _spans, _alive = self._ingest_stage(part, offs, dev)
+            wav = torch.empty((len(part), T_pad), dtype=torch.float32, device=dev)
+            check(lib.wt_ingest(descs, len(part), T_pad, _ptr(wav), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
+            for j, (sp, off) in enumerate(zip(part, offs)):
+                codes = self.encode_codes(wav[j:j + 1, :sp.n_out])
+                flat[off:off + codes.shape[-1]].copy_(codes.view(-1))
+
+    @torch.inference_mode()
+    def encode_codes_many(self, clips: Sequence[torch.Tensor], sample_rates=None, channels_last: bool = False, packed: bool = False,
+                          bandwidth_id=None):
+        """Tokenise a set of clips straight from PCM.  clips[i] is (T,), (C, T) or, with channels_last, (T, C), C in {1, 2}, fp32
+        or int16 (scaled by 1 / 32768), on the CPU or on the model's device; sample_rates is one rate or one per clip (default:
+        the codec rate).  Returns [codes (1, 1, L_i)] in input order, views into one flat int64 tensor, L_i =
+        arch.frames(ceil(24000 * T_i / rate_i)); packed=True returns (that flat tensor [sum L_i], offsets [n + 1] on the CPU).
+        Clip i's codes are the bits of encode_infer(audio.convert_audio(clip i as planar fp32, rate_i, 24000, 1)[0], ...)[1].
+        Per group of encode_infer_many's grouping (on the resampled lengths): one upload of the group's CPU clips, one ragged
+        ingest launch, one mixed-length encode without a feature tensor, one launch that hands out the codes.  Clips under the
+        mixed-length plans' minimum, and every clip while the encoder is off its shipped route, are ingested the same way and
+        encoded one at a time.  Argument errors raise ValueError before any GPU work."""
+        from . import audio
+        from .mixed_length import group_clips
+        if bandwidth_id is not None:
+            _ = self.feature_extractor.bandwidths[self._bandwidth_index(bandwidth_id)]
+        clips = list(clips)
+        codec_rate = self.codec_rate
+        if sample_rates is None:
+            rates = [codec_rate] * len(clips)
+        elif isinstance(sample_rates, (int, np.integer)):
+            rates = [int(sample_rates)] * len(clips)
+        else:
+            rates = [int(r) for r in sample_rates]
+            if len(rates) != len(clips):
+                raise ValueError("encode_codes_many: one sample rate, or one per clip")
+        specs: List[_ClipSpec] = []
+        for c, sr in zip(clips, rates):
+            if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2):
+                raise ValueError("encode_codes_many takes tensors (T,), (C, T) or, with channels_last, (T, C)")
+            if c.dtype not in (torch.float32, torch.int16):
+                raise ValueError("encode_codes_many takes fp32 or int16 clips")
+            ch = 1 if c.dim() == 1 else int(c.shape[1 if channels_last else 0])
+            n_in = int(c.shape[0]) if c.dim() == 1 or channels_last else int(c.shape[1])
+            if ch not in (1, 2):
+                raise ValueError("encode_codes_many: audio must be mono or stereo")
+            if n_in < 1:
+                raise ValueError("encode_codes_many: empty clip")
+            specs.append(_ClipSpec(c, ch, n_in, bool(channels_last and c.dim() == 2), sr,
+                                   audio.resampled_length(sr, codec_rate, n_in)))       # (ValueError for a refused ratio)
+        offsets = [0]
+        frames = self._arch.frames
+        for sp in specs:
+            offsets.append(offsets[-1] + frames(sp.n_out))
+        flat = torch.empty(offsets[-1], dtype=torch.int64, device=self._device())
+        groups, solo = group_clips([sp.n_out for sp in specs], self._arch.hop)
+        for T_pad, idx in groups:
+            if self._run_encode_codes_mixed([specs[i] for i in idx], T_pad, flat, [offsets[i] for i in idx]) is None:
+                solo.extend(idx)
+        if solo:
+            solo = sorted(solo)
+            self._encode_codes_solo([specs[i] for i in solo], flat, [offsets[i] for i in solo])
+        if packed:
+            return flat, torch.tensor(offsets, dtype=torch.int64)
+        return [flat[offsets[i]:offsets[i + 1]].view(1, 1, -1) for i in range(len(specs))]
 
     def _bandwidth_index(self, bandwidth_id) -> int:
         if bandwidth_id is None:

@@ -615,6 +615,46 @@ int wt_codes_unpack(const int64_t* codes, int32_t B, int64_t L_pad, const int64_
  * then round-half-even(x * 32768) clipped to int16 (the backend's rounding rule is not pinned by the reference). */
 int wt_pcm16(const float* x, int64_t n, float limit, int32_t rescale, int16_t* out, void* workspace, void* stream);
 
+/* Ragged emit, the mirror of wt_ingest: the way out of wt_decode_codes / wt_decode_codes_mixed / wt_decode / wt_decode_mixed for
+ * a caller that wants sound files.  One launch converts B rows of fp32 mono audio at the codec rate (rows of those calls'
+ * wav_out) each to its own rate, channel count, layout and sample type at its own destination: sample (c, n) of clip b goes to
+ * dst[c * ch_stride + n * sample_stride] (strides in elements, not negative), so planar, interleaved and strided destinations
+ * are all a descriptor.
+ *   WT_EMIT_F32: sample n is the bits wt_convert_audio gives for that clip alone (B = 1, C = 1, T = n_in): the same window, the
+ *     same ascending fmaf chain over the same fp32 table, zeros outside [0, n_in).
+ *   WT_EMIT_I16: the bits of wt_pcm16(that, limit, rescale = 0): clamp to [-limit, limit], round-half-even of x * 32768 clipped
+ *     to int16, in pcm16_kernel's arithmetic (a NaN becomes what it becomes there).  Per-clip rescale needs a reduction over the
+ *     resampled clip and is not offered: take fp32 out and call wt_pcm16.
+ * With channels = 2 both channels receive the same value (convert_audio's expand, encoder/utils.py:85-86).  Nothing past
+ * src[n_in - 1] is read (a decode plan leaves zeros or another clip's pitch there), and nothing outside the clip's
+ * n_out * channels destination elements is written.  An interleaved stereo frame (ch_stride 1, sample_stride 2, frame-aligned
+ * dst) is one store; runs of int16 with sample_stride 1 are stored two samples per 4-byte word wherever a pair shares an aligned
+ * word; an equal-rate clip is copied four samples per thread in 16-byte loads and stores where the alignment allows.  clips is a HOST array; src and dst are device pointers.  The library uploads the descriptors into workspace (device,
+ * wt_emit_workspace_bytes(B) bytes, 8-byte aligned; its content must stay untouched until the launch has run) on `stream`; up to
+ * 64 clips travel in the launch's own argument block instead and leave the workspace untouched (it must be passed all the same).
+ * Every descriptor is checked before any device call: a null src, dst or resampler, a sample type other than the two, channels
+ * other than 1 or 2, n_in < 1, n_out other than wt_resampler_out_length(resampler, n_in), a negative stride, channels = 2 with
+ * ch_stride = 0 and sample_stride < 2 or with sample_stride = 1 and ch_stride < n_out (the channels would overlap), a dst not aligned to its sample type, for WT_EMIT_I16 a
+ * limit outside (0, 1], a resampler of another device than clip 0's, or a window beyond the 64 KiB of dynamic LDS returns
+ * WT_ERR_INVALID with a message and touches no memory.
+ * Like wt_ingest, wt_emit is a host-side call around its launch (it shares wt_ingest's pinned descriptor blocks, their events and
+ * their lock): it waits for an event, may allocate pinned memory and enqueues a copy, so it must NOT be called on a stream that
+ * is being captured into a graph (call it behind the replay, on the replay's stream). */
+typedef enum { WT_EMIT_F32 = 0, WT_EMIT_I16 = 1 } wt_emit_dtype;
+typedef struct {
+    const float* src;                 /* device: the clip's row, n_in valid samples */
+    int64_t n_in;
+    const wt_resampler* resampler;    /* codec rate -> the clip's rate (equal rates: the K = 1 copy) */
+    int64_t n_out;                    /* wt_resampler_out_length(resampler, n_in) */
+    void* dst;                        /* device */
+    int32_t dtype;                    /* wt_emit_dtype */
+    int32_t channels;                 /* 1 or 2: both channels get the same value */
+    int64_t ch_stride, sample_stride; /* elements: sample (c, n) goes to dst[c * ch_stride + n * sample_stride] */
+    float limit;                      /* I16 only: clamp to [-limit, limit] first (save_audio, encoder/utils.py:97-102, rescale = False) */
+} wt_emit_clip;
+size_t wt_emit_workspace_bytes(int32_t B);
+int    wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream);
+
 /* Replaces: _linear_overlap_add (encoder/utils.py:17-56), bit for bit: frames [n_frames][rows][frame_len] (the last
  * one holds last_len valid samples), weight [frame_len] = the reference's triangle 0.5 - |linspace(0,1,len+2)[1:-1] - 0.5|,
  * out [rows][stride * (n_frames - 1) + last_len]. */

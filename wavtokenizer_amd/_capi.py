@@ -26,6 +26,7 @@ EXPORTS = [
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
     "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe", "wt_lstm_probe_workspace_bytes", "wt_lstm_probe",
     "wt_decode_codes", "wt_decode_codes_mixed", "wt_ingest_workspace_bytes", "wt_ingest", "wt_codes_unpack",
+    "wt_emit_workspace_bytes", "wt_emit",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -138,6 +139,15 @@ class WtIngestClip(ctypes.Structure):
     """wt_ingest_clip: one clip of a ragged ingest launch (wt_ingest)."""
     _fields_ = [("src", c_void_p), ("dtype", c_int32), ("channels", c_int32), ("n_in", c_int64), ("ch_stride", c_int64),
                 ("sample_stride", c_int64), ("resampler", c_void_p), ("n_out", c_int64)]
+
+
+WT_EMIT_F32, WT_EMIT_I16 = 0, 1
+
+
+class WtEmitClip(ctypes.Structure):
+    """wt_emit_clip: one clip of a ragged emit launch (wt_emit)."""
+    _fields_ = [("src", c_void_p), ("n_in", c_int64), ("resampler", c_void_p), ("n_out", c_int64), ("dst", c_void_p),
+                ("dtype", c_int32), ("channels", c_int32), ("ch_stride", c_int64), ("sample_stride", c_int64), ("limit", c_float)]
 
 
 class WavTokError(RuntimeError):
@@ -254,6 +264,9 @@ def _load() -> ctypes.CDLL:
     lib.wt_ingest_workspace_bytes.restype = c_size_t
     lib.wt_ingest.argtypes = [POINTER(WtIngestClip), c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     lib.wt_codes_unpack.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.wt_emit_workspace_bytes.argtypes = [c_int32]
+    lib.wt_emit_workspace_bytes.restype = c_size_t
+    lib.wt_emit.argtypes = [POINTER(WtEmitClip), c_int32, c_void_p, c_void_p]
     return lib
 
 

@@ -115,6 +115,212 @@ __global__ __launch_bounds__(256) void ingest_kernel(const IngestClip* __restric
     out[(long)blockIdx.y * T_pad + n] = acc;
 }
 
+// round-half-even of x * 32768 clipped to int16: the PCM_S 16 conversion (what pcm16_kernel stores)
+__device__ __forceinline__ int pcm16_round(float v) {
+    const float r = rintf(v * 32768.f);
+    return (int)fminf(fmaxf(r, -32768.f), 32767.f);
+}
+
+// One clip of a ragged emit launch (device form of wt_emit_clip): the fp32 row at the codec rate, the destination with its
+// element strides, the clip's resampler and both lengths.
+struct EmitClip {
+    const float* src;
+    const float* kern;                          // [nw][K]
+    void* dst;
+    long n_in, n_out;
+    long cstride, sstride;                      // elements between channels / between samples
+    int i16, C;                                 // int16 destination (else fp32); 1 or 2 channels
+    int orig, nw, K, width;
+    float limit;
+};
+
+// A pointer read from a descriptor in memory is a generic one to the compiler (flat loads and stores); the descriptors of a
+// ragged launch hold device pointers by contract (wt_emit), and saying so gives global loads and stores.
+template <class T> using global_ptr = __attribute__((address_space(1))) T*;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int EMIT_COPY_SPAN = 2048;            // samples per block of an equal-rate clip: two rounds of four per thread
+
+// The lanes of a wave hold consecutive int16 samples base[n]: two samples that share an aligned 4-byte word leave as one store
+// of the lane that holds the lower one.  A sample without its partner (the word's other half lies before the clip, behind it or
+// in the next wave) is a 2-byte store.  Every lane of the wave calls this (the shuffle needs them), valid or not.
+__device__ __forceinline__ void store_i16_run(global_ptr<int16_t> base, long n, int q, bool valid, bool next_valid) {
+    const int lane = threadIdx.x & 63;
+    const int qn = __shfl_down(q, 1, 64);
+    if (!valid) return;
+    global_ptr<int16_t> p = base + n;
+    if (((uintptr_t)p & 2) == 0) {
+        if (lane < 63 && next_valid) *(global_ptr<uint32_t>)p = (uint32_t)(uint16_t)q | ((uint32_t)(uint16_t)qn << 16);
+        else *p = (int16_t)q;
+    } else if (lane == 0) {
+        *p = (int16_t)q;                        // (any other lane's sample left with its left neighbour's)
+    }
+}
+
+// An equal-rate clip (K = 1, the table's only tap; n_out = n_in): the window of output n is src[n] alone and the chain one fmaf, so
+// nothing goes through LDS, and a block takes EMIT_COPY_SPAN samples instead of 256: per round a thread loads four consecutive
+// samples (16 bytes where the row is 16-byte aligned) and stores them in the widest form the destination's alignment allows: fp32
+// runs as 16 bytes; int16 runs as 8 bytes, two 4-byte words, or 2 + 4 + 2 bytes on an odd element; interleaved stereo frames as
+// 16 bytes (int16: four frames; fp32: two) or one store per frame.  A tail of fewer than four samples and any other strides get
+// one store per element.  The same values as emit_block's general path, bit for bit.
+__device__ __forceinline__ void emit_copy_block(const EmitClip& d) {
+    const long base = (long)blockIdx.x * EMIT_COPY_SPAN;
+    if (base >= d.n_out) return;
+    const global_ptr<const float> src = (global_ptr<const float>)d.src;
+    const float k0 = ((global_ptr<const float>)d.kern)[0];
+    const bool frames = d.C == 2 && d.cstride == 1 && d.sstride == 2;      // interleaved stereo
+    const bool src16 = (uintptr_t)src % 16 == 0;
+#pragma unroll
+    for (int j = 0; j < EMIT_COPY_SPAN / 1024; ++j) {
+        const long n = base + j * 1024 + 4 * (long)threadIdx.x;
+        if (n >= d.n_out) return;
+        const int m = d.n_out - n < 4 ? (int)(d.n_out - n) : 4;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (m == 4 && src16) {
+            const f32x4 x = *(global_ptr<const f32x4>)(src + n);
+            v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (i < m) v[i] = src[n + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = fmaf(k0, 0.f + v[i], 0.f);      // (resample_mono_kernel's channel sum, then its chain)
+        if (!d.i16) {
+            const global_ptr<float> o = (global_ptr<float>)d.dst;
+            if (frames && (uintptr_t)o % 8 == 0) {
+                const global_ptr<float> p = o + 2 * n;
+                if (m == 4 && (uintptr_t)p % 16 == 0) {
+                    ((global_ptr<f32x4>)p)[0] = f32x4{v[0], v[0], v[1], v[1]};
+                    ((global_ptr<f32x4>)p)[1] = f32x4{v[2], v[2], v[3], v[3]};
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) if (i < m) ((global_ptr<f32x2>)p)[i] = f32x2{v[i], v[i]};
+                }
+            } else if (d.sstride == 1) {
+                for (int c = 0; c < d.C; ++c) {
+                    const global_ptr<float> p = o + c * d.cstride + n;
+                    if (m == 4 && (uintptr_t)p % 16 == 0) {
+                        *(global_ptr<f32x4>)p = f32x4{v[0], v[1], v[2], v[3]};
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) if (i < m) p[i] = v[i];
+                    }
+                }
+            } else {
+                for (int c = 0; c < d.C; ++c)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) if (i < m) o[c * d.cstride + (n + i) * d.sstride] = v[i];
+            }
+            continue;
+        }
+        uint32_t q[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q[i] = (uint32_t)(uint16_t)pcm16_round(fminf(fmaxf(v[i], -d.limit), d.limit));
+        const global_ptr<int16_t> o = (global_ptr<int16_t>)d.dst;
+        if (frames && (uintptr_t)o % 4 == 0) {
+            const global_ptr<uint32_t> p = (global_ptr<uint32_t>)(o + 2 * n);
+            if (m == 4 && (uintptr_t)p % 16 == 0) {
+                *(global_ptr<u32x4>)p = u32x4{q[0] * 0x10001u, q[1] * 0x10001u, q[2] * 0x10001u, q[3] * 0x10001u};
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) if (i < m) p[i] = q[i] * 0x10001u;
+            }
+        } else if (d.sstride == 1) {
+            for (int c = 0; c < d.C; ++c) {
+                const global_ptr<int16_t> p = o + c * d.cstride + n;
+                const int a = (int)(((uintptr_t)p >> 1) & 3);              // the run's first element within its 8-byte word
+                if (m < 4) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) if (i < m) p[i] = (int16_t)q[i];
+                } else if (a == 0) {
+                    *(global_ptr<u32x2>)p = u32x2{q[0] | (q[1] << 16), q[2] | (q[3] << 16)};
+                } else if (a == 2) {
+                    ((global_ptr<uint32_t>)p)[0] = q[0] | (q[1] << 16);
+                    ((global_ptr<uint32_t>)p)[1] = q[2] | (q[3] << 16);
+                } else {
+                    p[0] = (int16_t)q[0];
+                    *(global_ptr<uint32_t>)(p + 1) = q[1] | (q[2] << 16);
+                    p[3] = (int16_t)q[3];
+                }
+            }
+        } else {
+            for (int c = 0; c < d.C; ++c)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) if (i < m) o[c * d.cstride + (n + i) * d.sstride] = (int16_t)q[i];
+        }
+    }
+}
+
+// The mirror of ingest_kernel: grid (ceil(max n_out / 256), B), block (x, b) resamples 256 consecutive outputs of row b (fp32 mono
+// at the codec rate) to the clip's own rate, the same bits as resample_mono_kernel on the row alone with C = 1 (same window, zeros
+// outside [0, n_in), same ascending fmaf chain), and writes them to the clip's destination: fp32 as they are, int16 through
+// pcm16_kernel's clamp and rounding; a stereo clip gets the value in both channels.  Nothing past src[n_in - 1] is read and
+// nothing outside the clip's n_out * C destination elements is written.  The descriptor is uniform over the block, and so is
+// the choice of the store form: one 8- / 4-byte store per interleaved stereo frame, paired int16 stores for runs with sample
+// stride 1 (store_i16_run), one store per element for any other strides.  An equal-rate clip takes emit_copy_block's wider blocks
+// instead (the host sizes the grid for whichever form each clip takes).
+__host__ __device__ inline bool emit_is_copy(int orig, int nw, int K, int width) { return K == 1 && width == 0 && orig == 1 && nw == 1; }
+
+__device__ __forceinline__ void emit_block(const EmitClip& d) {
+    extern __shared__ float win[];
+    if (emit_is_copy(d.orig, d.nw, d.K, d.width)) { emit_copy_block(d); return; }
+    const long n0 = (long)blockIdx.x * 256;
+    if (n0 >= d.n_out) return;
+    const long n = n0 + threadIdx.x;
+    const bool valid = n < d.n_out;
+    const global_ptr<const float> src = (global_ptr<const float>)d.src;
+    const global_ptr<const float> kern = (global_ptr<const float>)d.kern;
+    const long i0 = n0 / d.nw;
+    const long nlast = (n0 + 255 < d.n_out ? n0 + 255 : d.n_out - 1);
+    const long i1 = nlast / d.nw;
+    const long p0 = i0 * d.orig - d.width;                 // input position of win[0]
+    const int Lw = (int)((i1 - i0) * d.orig) + d.K;
+    for (int e = threadIdx.x; e < Lw; e += 256) {
+        const long p = p0 + e;
+        win[e] = (p >= 0 && p < d.n_in) ? 0.f + src[p] : 0.f;        // (resample_mono_kernel's channel sum over one channel)
+    }
+    __syncthreads();
+    float acc = 0.f;
+    if (valid) {
+        const long i = n / d.nw;
+        const int ph = (int)(n - i * d.nw);
+        const global_ptr<const float> kp = kern + (long)ph * d.K;
+        const float* wp = win + (i - i0) * d.orig;
+        for (int k = 0; k < d.K; ++k) acc = fmaf(kp[k], wp[k], acc);
+    }
+    const bool frames = d.C == 2 && d.cstride == 1 && d.sstride == 2;      // interleaved stereo
+    if (!d.i16) {
+        if (!valid) return;
+        const global_ptr<float> o = (global_ptr<float>)d.dst;
+        if (frames && (uintptr_t)o % 8 == 0) {
+            ((global_ptr<f32x2>)o)[n] = f32x2{acc, acc};
+        } else {
+            for (int c = 0; c < d.C; ++c) o[c * d.cstride + n * d.sstride] = acc;
+        }
+        return;
+    }
+    const int q = pcm16_round(fminf(fmaxf(acc, -d.limit), d.limit));
+    const global_ptr<int16_t> o = (global_ptr<int16_t>)d.dst;
+    if (frames && (uintptr_t)o % 4 == 0) {
+        if (valid) ((global_ptr<uint32_t>)o)[n] = (uint32_t)(uint16_t)q * 0x10001u;
+    } else if (d.sstride == 1) {
+        for (int c = 0; c < d.C; ++c) store_i16_run(o + c * d.cstride, n, q, valid, n + 1 < d.n_out);
+    } else if (valid) {
+        for (int c = 0; c < d.C; ++c) o[c * d.cstride + n * d.sstride] = (int16_t)q;
+    }
+}
+
+__global__ __launch_bounds__(256) void emit_kernel(const EmitClip* __restrict__ clips) { emit_block(clips[blockIdx.y]); }
+
+// The same launch with the descriptors in the kernel's argument block: up to EMIT_ARG_CLIPS clips need no upload (a copy on the
+// stream and the wait behind it cost more than a short clip's whole conversion).
+constexpr int EMIT_ARG_CLIPS = 64;
+struct EmitArgs { EmitClip clip[EMIT_ARG_CLIPS]; };
+__global__ __launch_bounds__(256) void emit_args_kernel(const EmitArgs a) { emit_block(a.clip[blockIdx.y]); }
+
 // The ragged way out: spans [B][2] = {L_b, offset_b}; the first L_b codes of row b of codes [B][L_pad] go to out[offset_b + t].
 // A span that does not fit its row or the flat tensor is skipped whole.
 __global__ __launch_bounds__(256) void codes_unpack_kernel(const int64_t* __restrict__ codes, long L_pad, const int64_t* __restrict__ spans,
@@ -138,8 +344,7 @@ __global__ __launch_bounds__(256) void pcm16_kernel(const float* __restrict__ x,
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         float v = x[i];
         v = rescale ? v * scale : fminf(fmaxf(v, -limit), limit);
-        const float r = rintf(v * 32768.f);
-        out[i] = (int16_t)fminf(fmaxf(r, -32768.f), 32767.f);
+        out[i] = (int16_t)pcm16_round(v);
     }
 }
 
@@ -238,7 +443,7 @@ int wt_convert_audio(const wt_resampler* r, const float* wav, int32_t B, int32_t
     return WT_OK;
 }
 
-// The host-side staging of wt_ingest's descriptors: two pinned blocks per device, each guarded by the event recorded behind
+// The host-side staging of wt_ingest's and wt_emit's descriptors: two pinned blocks per device, each guarded by the event recorded behind
 // the copy that last read it, so the upload never waits for the stream and never reads a block that is being rewritten.
 struct IngestStage {
     std::mutex mu;
@@ -248,6 +453,27 @@ struct IngestStage {
     int next = 0;
 };
 static IngestStage g_ingest_stage[64];
+
+// Uploads a launch's device-form descriptors (wt_ingest, wt_emit) into its workspace on s through the device's next pinned block
+// (a block that has to grow is given at least min_bytes).
+static int stage_descriptors(int device, const void* descs, size_t bytes, size_t min_bytes, void* workspace, hipStream_t s) {
+    IngestStage& st = g_ingest_stage[device];
+    std::lock_guard<std::mutex> lock(st.mu);
+    const int k = st.next;
+    st.next ^= 1;
+    if (!st.ev[k]) WT_HIP_CHECK(hipEventCreateWithFlags(&st.ev[k], hipEventDisableTiming));
+    else WT_HIP_CHECK(hipEventSynchronize(st.ev[k]));
+    if (st.cap[k] < bytes) {
+        if (st.host[k]) { (void)hipHostFree(st.host[k]); st.host[k] = nullptr; st.cap[k] = 0; }
+        const size_t cap = std::max(bytes, min_bytes);
+        WT_HIP_CHECK(hipHostMalloc(&st.host[k], cap, hipHostMallocDefault));
+        st.cap[k] = cap;
+    }
+    memcpy(st.host[k], descs, bytes);
+    WT_HIP_CHECK(hipMemcpyAsync(workspace, st.host[k], bytes, hipMemcpyHostToDevice, s));
+    WT_HIP_CHECK(hipEventRecord(st.ev[k], s));
+    return WT_OK;
+}
 
 static size_t resampler_window_bytes(const wt_resampler* r) {
     return (size_t)(256 / r->nw + 2) * r->orig * sizeof(float) + (size_t)r->K * sizeof(float);
@@ -295,26 +521,70 @@ int wt_ingest(const wt_ingest_clip* clips, int32_t B, int64_t T_pad, float* out,
         return 0;
     })) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t bytes = dev.size() * sizeof(IngestClip);
-    {
-        IngestStage& st = g_ingest_stage[device];
-        std::lock_guard<std::mutex> lock(st.mu);
-        const int k = st.next;
-        st.next ^= 1;
-        if (!st.ev[k]) WT_HIP_CHECK(hipEventCreateWithFlags(&st.ev[k], hipEventDisableTiming));
-        else WT_HIP_CHECK(hipEventSynchronize(st.ev[k]));
-        if (st.cap[k] < bytes) {
-            if (st.host[k]) { (void)hipHostFree(st.host[k]); st.host[k] = nullptr; st.cap[k] = 0; }
-            const size_t cap = std::max(bytes, (size_t)64 * sizeof(IngestClip));
-            WT_HIP_CHECK(hipHostMalloc(&st.host[k], cap, hipHostMallocDefault));
-            st.cap[k] = cap;
-        }
-        memcpy(st.host[k], dev.data(), bytes);
-        WT_HIP_CHECK(hipMemcpyAsync(workspace, st.host[k], bytes, hipMemcpyHostToDevice, s));
-        WT_HIP_CHECK(hipEventRecord(st.ev[k], s));
-    }
+    if (int rc = stage_descriptors(device, dev.data(), dev.size() * sizeof(IngestClip), 64 * sizeof(IngestClip), workspace, s)) return rc;
     dim3 grid((unsigned)((max_out + 255) / 256), (unsigned)B);
     hipLaunchKernelGGL(ingest_kernel, grid, dim3(256), smem, s, static_cast<const IngestClip*>(workspace), out, (long)T_pad);
+    WT_HIP_CHECK(hipGetLastError());
+    return WT_OK;
+}
+
+size_t wt_emit_workspace_bytes(int32_t B) { return B > 0 ? (size_t)B * sizeof(EmitClip) : 0; }
+
+int wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream) {
+    if (!clips || !workspace || B < 1 || B > 65535) { set_error("wt_emit: bad argument"); return WT_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error("wt_emit: workspace misaligned"); return WT_ERR_INVALID; }
+    std::vector<EmitClip> dev((size_t)B);
+    size_t smem = 0;
+    int64_t blocks = 0;
+    const int device = clips[0].resampler ? clips[0].resampler->device : 0;
+    for (int b = 0; b < B; ++b) {
+        const wt_emit_clip& c = clips[b];
+        const std::string who = "wt_emit: clip " + std::to_string(b) + ": ";
+        if (!c.src) { set_error(who + "null source"); return WT_ERR_INVALID; }
+        if (!c.dst) { set_error(who + "null destination"); return WT_ERR_INVALID; }
+        if (!c.resampler) { set_error(who + "null resampler"); return WT_ERR_INVALID; }
+        if (c.dtype != WT_EMIT_F32 && c.dtype != WT_EMIT_I16) { set_error(who + "sample type must be fp32 or int16"); return WT_ERR_INVALID; }
+        if (c.channels != 1 && c.channels != 2) { set_error(who + "channels must be 1 or 2"); return WT_ERR_INVALID; }
+        if (c.n_in < 1) { set_error(who + "n_in < 1"); return WT_ERR_INVALID; }
+        if (c.n_out != wt_resampler_out_length(c.resampler, c.n_in)) { set_error(who + "n_out is not wt_resampler_out_length(n_in)"); return WT_ERR_INVALID; }
+        if (c.ch_stride < 0 || c.sample_stride < 0) { set_error(who + "negative stride"); return WT_ERR_INVALID; }
+        if (c.channels == 2 && ((c.ch_stride == 0 && c.sample_stride < 2) || (c.sample_stride == 1 && c.ch_stride < c.n_out))) {
+            set_error(who + "the two channels overlap"); return WT_ERR_INVALID;
+        }
+        if (reinterpret_cast<uintptr_t>(c.src) % sizeof(float)) { set_error(who + "misaligned source pointer"); return WT_ERR_INVALID; }
+        if (reinterpret_cast<uintptr_t>(c.dst) % (c.dtype == WT_EMIT_I16 ? sizeof(int16_t) : sizeof(float))) {
+            set_error(who + "misaligned destination pointer"); return WT_ERR_INVALID;
+        }
+        if (c.dtype == WT_EMIT_I16 && !(c.limit > 0.f && c.limit <= 1.f)) { set_error(who + "limit outside (0, 1]"); return WT_ERR_INVALID; }
+        if (c.resampler->device != device) { set_error(who + "resampler of another device"); return WT_ERR_INVALID; }
+        const size_t w = resampler_window_bytes(c.resampler);
+        if (w > 64 * 1024) { set_error(who + "rate ratio too large for the LDS window"); return WT_ERR_INVALID; }
+        smem = std::max(smem, w);
+        const wt_resampler* r = c.resampler;
+        const int64_t span = emit_is_copy(r->orig, r->nw, r->K, r->width) ? EMIT_COPY_SPAN : 256;     // outputs per block of this clip
+        blocks = std::max(blocks, (c.n_out + span - 1) / span);
+        dev[b] = EmitClip{c.src, c.resampler->kern, c.dst, (long)c.n_in, (long)c.n_out, (long)c.ch_stride, (long)c.sample_stride,
+                          c.dtype == WT_EMIT_I16 ? 1 : 0, c.channels, c.resampler->orig, c.resampler->nw, c.resampler->K,
+                          c.resampler->width, c.dtype == WT_EMIT_I16 ? c.limit : 1.f};
+    }
+    if (device < 0 || device >= 64) { set_error("wt_emit: device index"); return WT_ERR_INVALID; }
+    WT_HIP_CHECK(hipSetDevice(device));
+    static PerDeviceOnce attr_once;
+    if (int rc = attr_once.run([&]() -> int {
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(emit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(emit_args_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        return 0;
+    })) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    dim3 grid((unsigned)blocks, (unsigned)B);
+    if (B <= EMIT_ARG_CLIPS) {
+        EmitArgs args{};
+        memcpy(args.clip, dev.data(), dev.size() * sizeof(EmitClip));      // (blocks read clip[blockIdx.y < B] alone)
+        hipLaunchKernelGGL(emit_args_kernel, grid, dim3(256), smem, s, args);
+    } else {
+        if (int rc = stage_descriptors(device, dev.data(), dev.size() * sizeof(EmitClip), 128 * sizeof(EmitClip), workspace, s)) return rc;
+        hipLaunchKernelGGL(emit_kernel, grid, dim3(256), smem, s, static_cast<const EmitClip*>(workspace));
+    }
     WT_HIP_CHECK(hipGetLastError());
     return WT_OK;
 }

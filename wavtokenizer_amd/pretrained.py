@@ -322,6 +322,15 @@ class _ClipSpec:
         self.clip, self.channels, self.n_in, self.channels_last, self.rate, self.n_out = clip, channels, n_in, channels_last, rate, n_out
 
 
+class _PcmSpec:
+    """One clip of WavTokenizer.decode_pcm_many: its codes (K, L), frames, target rate, samples the decoder returns, samples per
+    channel at the target rate and channels."""
+    __slots__ = ("codes", "frames", "rate", "n_in", "n_out", "channels")
+
+    def __init__(self, codes: Optional[torch.Tensor], frames: int, rate: int, n_in: int, n_out: int, channels: int):
+        self.codes, self.frames, self.rate, self.n_in, self.n_out, self.channels = codes, frames, rate, n_in, n_out, channels
+
+
 class _OffRoute(Exception):
     """A mixed-length call found the encoder off the route mixed-length plans take (WavTokenizer._mixed_route_ok)."""
 
@@ -367,6 +376,7 @@ class WavTokenizer(nn.Module):
         self._pin_bufs: List[Optional[torch.Tensor]] = [None, None]
         self._pin_events: List[Any] = [None, None]
         self._pin_next = 0
+        self._emit_ws: Optional[torch.Tensor] = None      # decode_pcm / decode_pcm_many: the workspace of wt_emit launches of up to 64 clips
         for m in (feature_extractor, backbone, head):
             m._bind(self)
 
@@ -774,11 +784,14 @@ class WavTokenizer(nn.Module):
         return x.to(dtype).contiguous()
 
     # -- kernels ------------------------------------------------------------------------------------
-    def _call(self, entry, kind: int, B: int, length: int, flags: int, dev: torch.device, ins, outs, scalars=(), name=None):
+    def _call(self, entry, kind: int, B: int, length: int, flags: int, dev: torch.device, ins, outs, scalars=(), name=None,
+              borrow: bool = False):
         """One call of a C run entry point, entry(plan, inputs..., scalars..., outputs..., workspace, stream), on the plan
         (kind, B, length, flags) with the kind's fp32 sites.  ins: per input the tensor itself, or (shape, dtype, fill) for a
         buffer that fill(buffer) writes.  outs: per output (shape, dtype, wanted), or None for a null pointer; a direct call
         passes null for an unwanted output too.  name: what a failed call is reported as (default: entry's own name).
+        borrow: a graph-replayed call hands out the plan's own staging buffers instead of copies; they hold the results until the
+        next call on the plan (for a caller that consumes them on the same stream before it returns).
         Returns (outputs, None where not wanted; plan)."""
         plan, ws = self._engine.plan(kind, B, length, flags, dev, self._sites(kind))
         new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
@@ -801,7 +814,7 @@ class WavTokenizer(nn.Module):
             obufs = [new(*o[:2]) if o is not None and o[2] else None for o in outs]
         check(entry(plan, *map(_ptr, bufs), *scalars, *map(_ptr, obufs), _ptr(ws), _stream_ptr(dev)), name or entry.__name__)
         if graph:
-            return tuple(b.clone() if o is not None and o[2] else None for o, b in zip(outs, obufs)), plan
+            return tuple((b if borrow else b.clone()) if o is not None and o[2] else None for o, b in zip(outs, obufs)), plan
         return tuple(obufs), plan
 
     def _encode(self, audio: torch.Tensor, flags: int, dev: torch.device, want_emb: bool, want_feats: bool = True):
@@ -1205,13 +1218,13 @@ class WavTokenizer(nn.Module):
         nq = self._arch.num_quantizers if flags & _capi.WT_PLAN_FLAG_GRAPH else K
         return ((nq, B, L), torch.int64, lambda buf: fill(buf[:K]))
 
-    def _decode_codes(self, codes: torch.Tensor, bw: int, flags: int, dev: torch.device):
+    def _decode_codes(self, codes: torch.Tensor, bw: int, flags: int, dev: torch.device, borrow: bool = False):
         """The call of decode_codes: ((waveform, None), plan)."""
         K, B, L = codes.shape
         graph = flags & _capi.WT_PLAN_FLAG_GRAPH
         ins = (self._codes_staging(K, B, L, flags, lambda buf: buf.copy_(codes)),) if graph else (codes,)
         return self._call(lib.wt_decode_codes, _capi.WT_PLAN_DECODE_CODES, B, L, flags, dev, ins,
-                          (((B, self._wave_len(L)), torch.float32, True), None), (K, bw))
+                          (((B, self._wave_len(L)), torch.float32, True), None), (K, bw), borrow=borrow)
 
     def _codes_checked(self, dev: torch.device):
         """set_check_codes("sync") after a decode-from-codes call: wait for it and raise for a code outside the codebook."""
@@ -1226,6 +1239,10 @@ class WavTokenizer(nn.Module):
         gathers the codebook rows into the operand of backbone.embed.  A code outside the codebook follows set_check_codes
         like codes_to_features: "sync" raises IndexError for this call, "deferred" on the next call on this model, "off" never;
         the offending clip's waveform is NaN in every mode."""
+        return self._run_decode_codes(codes, bandwidth_id)
+
+    def _run_decode_codes(self, codes: torch.Tensor, bandwidth_id, borrow: bool = False) -> torch.Tensor:
+        """decode_codes; with borrow a graph-replayed call returns the plan's staging buffer itself (_call)."""
         dev = self._ensure_engine()
         bw = self._bandwidth_index(bandwidth_id)
         if codes.dim() == 2:
@@ -1235,16 +1252,18 @@ class WavTokenizer(nn.Module):
             raise WavTokError("decode_codes: K must be between 1 and the number of codebooks", _capi.WT_ERR_INVALID)
         codes = self._as_input(codes, dev, torch.int64)
         B = codes.shape[1]
-        wav = self._guarded(dev, lambda: self._decode_codes(codes, bw, self._decode_flags(self._graph_flags(B)), dev), self._is_strict(B))[0]
+        wav = self._guarded(dev, lambda: self._decode_codes(codes, bw, self._decode_flags(self._graph_flags(B)), dev, borrow),
+                            self._is_strict(B))[0]
         self._codes_checked(dev)
         return wav
 
     @torch.inference_mode()
-    def _run_decode_codes_mixed(self, codes_list: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None):
+    def _run_decode_codes_mixed(self, codes_list: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None,
+                                borrow: bool = False):
         """One mixed-length decode-from-codes call (WT_PLAN_DECODE_CODES_MIXED) on clips (K, L_i) int64 of 1 <= L_i <= L_pad
         frames, the counterpart of _run_decode_mixed: returns the waveforms (B, wave_len(L_pad)), clip j's own samples first and
         zeros behind them, or None when the decoder is off the route a mixed-length plan takes (_decode_mixed_route_ok).  What
-        the staging buffer holds past a clip's frames is never read."""
+        the staging buffer holds past a clip's frames is never read.  borrow: as in _call."""
         dev = dev if dev is not None else self._ensure_engine()
         B = len(codes_list)
         K = int(codes_list[0].shape[0])
@@ -1267,7 +1286,7 @@ class WavTokenizer(nn.Module):
             ins = (self._codes_staging(K, B, L_pad, flags, fill_codes),
                    ((B,), torch.int32, lambda lens: lens.copy_(torch.tensor(lengths, dtype=torch.int32), non_blocking=False)))
             return self._call(_decode_codes_mixed_entry, _capi.WT_PLAN_DECODE_CODES_MIXED, B, L_pad, flags, dev, ins, outs, (K, bw),
-                              name="wt_decode_codes_mixed")
+                              name="wt_decode_codes_mixed", borrow=borrow)
 
         try:
             wav = self._guarded(dev, call, self._is_strict(B))[0]
@@ -1275,6 +1294,20 @@ class WavTokenizer(nn.Module):
             return None
         self._codes_checked(dev)
         return wav
+
+    def _codes_clips(self, codes: Sequence[torch.Tensor], who: str) -> List[torch.Tensor]:
+        """The clips of decode_codes_many / decode_pcm_many as (K, L_i) tensors; ValueError for anything else."""
+        clips: List[torch.Tensor] = []
+        for c in codes:
+            if isinstance(c, torch.Tensor) and c.dim() == 3 and c.shape[1] == 1:
+                c = c[:, 0, :]
+            if (not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] < 1 or c.is_floating_point() or c.is_complex()
+                    or c.dtype == torch.bool):
+                raise ValueError(who + " takes a sequence of integer tensors (K, L) or (K, 1, L) with L >= 1")
+            if not 1 <= c.shape[0] <= self._arch.num_quantizers or c.shape[0] != (clips[0].shape[0] if clips else c.shape[0]):
+                raise ValueError(who + ": every clip needs the same K, between 1 and the number of codebooks")
+            clips.append(c)
+        return clips
 
     @torch.inference_mode()
     def decode_codes_many(self, codes: Sequence[torch.Tensor], bandwidth_id=None) -> List[torch.Tensor]:
@@ -1285,16 +1318,7 @@ class WavTokenizer(nn.Module):
         route, goes through decode_codes."""
         from .mixed_length import group_frames
         bw = self._bandwidth_index(bandwidth_id)
-        clips: List[torch.Tensor] = []
-        for c in codes:
-            if isinstance(c, torch.Tensor) and c.dim() == 3 and c.shape[1] == 1:
-                c = c[:, 0, :]
-            if (not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] < 1 or c.is_floating_point() or c.is_complex()
-                    or c.dtype == torch.bool):
-                raise ValueError("decode_codes_many takes a sequence of integer tensors (K, L) or (K, 1, L) with L >= 1")
-            if not 1 <= c.shape[0] <= self._arch.num_quantizers or c.shape[0] != (clips[0].shape[0] if clips else c.shape[0]):
-                raise ValueError("decode_codes_many: every clip needs the same K, between 1 and the number of codebooks")
-            clips.append(c)
+        clips = self._codes_clips(codes, "decode_codes_many")
         out: List[Optional[torch.Tensor]] = [None] * len(clips)
         solo: List[int] = []
         min_frames = 1 if self._arch.padding == "same" else 2      # (decode raises for a 'center' clip of one frame)
@@ -1311,6 +1335,180 @@ class WavTokenizer(nn.Module):
         for i in sorted(solo):
             out[i] = self.decode_codes(clips[i], bandwidth_id=bw)
         return out  # type: ignore[return-value]
+
+    # -- synthesise straight to PCM: decode from codes -> ragged emit (resample, channels, layout, sample type) into one tensor -----
+    def _emit_format(self, who: str, channels, dtype, limit, n: int) -> Tuple[List[int], Tuple[torch.dtype, float]]:
+        """(channels per clip, (dtype, limit)) of decode_pcm / decode_pcm_many over n clips, checked: ValueError for anything
+        wt_emit would refuse."""
+        if dtype not in (torch.float32, torch.int16):
+            raise ValueError(who + ": dtype must be torch.float32 or torch.int16")
+        if isinstance(channels, (int, np.integer)):
+            channels = [channels] * n
+        channels = list(channels)
+        if len(channels) != n:
+            raise ValueError(who + ": one channel count, or one per clip")
+        if any(isinstance(c, bool) or c not in (1, 2) for c in channels):
+            raise ValueError(who + ": channels must be 1 or 2")
+        limit = float(limit)
+        if not 0.0 < limit <= 1.0:
+            raise ValueError(who + ": limit must be in (0, 1]")
+        return [int(c) for c in channels], (dtype, limit)
+
+    def _emit_rows(self, rows: Sequence[torch.Tensor], specs: Sequence["_PcmSpec"], flat: torch.Tensor, offsets: Sequence[int],
+                   fmt: Tuple[torch.dtype, float], channels_last: bool, dev: torch.device):
+        """One wt_emit: rows[j], a contiguous fp32 row of at least specs[j].n_in samples at the codec rate on dev, goes to
+        flat[offsets[j]:] at the clip's rate in the layout (channels, n_out) or, with channels_last, (n_out, channels)."""
+        from . import audio
+        dtype, limit = fmt
+        B = len(rows)
+        descs = (_capi.WtEmitClip * B)()
+        base, esize = flat.data_ptr(), flat.element_size()
+        codec_rate = self.codec_rate
+        handles: Dict[int, ctypes.c_void_p] = {}
+        for d, row, sp, off in zip(descs, rows, specs, offsets):
+            channels = sp.channels
+            assert row.dtype == torch.float32 and row.stride(-1) == 1 and row.shape[-1] >= sp.n_in and off + sp.n_out * channels <= flat.numel()
+            if sp.rate not in handles:
+                handles[sp.rate] = audio.resampler(codec_rate, sp.rate, dev.index)
+            d.src, d.n_in, d.resampler, d.n_out = row.data_ptr(), sp.n_in, handles[sp.rate], sp.n_out
+            d.dst = base + int(off) * esize
+            d.dtype = _capi.WT_EMIT_I16 if dtype == torch.int16 else _capi.WT_EMIT_F32
+            d.channels, d.limit = channels, limit
+            if channels == 1:
+                d.ch_stride, d.sample_stride = 0, 1
+            else:
+                d.ch_stride, d.sample_stride = (1, channels) if channels_last else (sp.n_out, 1)
+        # up to 64 clips the library passes the descriptors with the launch and leaves the workspace alone: one small tensor serves
+        # every such call; a larger launch gets a workspace of its own (the library fills it on the stream)
+        if B <= 64:
+            ws = self._emit_ws
+            if ws is None or ws.device != dev:
+                ws = self._emit_ws = torch.empty(max(int(lib.wt_emit_workspace_bytes(64)), 8), dtype=torch.uint8, device=dev)
+        else:
+            ws = torch.empty(int(lib.wt_emit_workspace_bytes(B)), dtype=torch.uint8, device=dev)
+        check(lib.wt_emit(descs, B, _ptr(ws), _stream_ptr(dev)), "wt_emit")
+
+    @torch.inference_mode()
+    def decode_pcm(self, codes: torch.Tensor, sample_rate: Optional[int] = None, channels: int = 1, dtype: torch.dtype = torch.int16,
+                   channels_last: bool = False, limit: float = 0.99, bandwidth_id=None) -> torch.Tensor:
+        """decode_codes, then every clip resampled from the codec rate to sample_rate (default: the codec rate), expanded to
+        `channels` (1, or 2: both channels carry the same samples, convert_audio's expand) and stored as fp32 or, clamped to
+        [-limit, limit] and rounded like audio.to_pcm16, as int16: codes (K, L) or (K, B, L) -> (B, channels, n_out) or, with
+        channels_last, (B, n_out, channels) on the model's device, n_out = ceil(sample_rate * wave_len(L) / 24000).  One
+        decode_codes (graph-replayed where decode_codes is) and ONE ragged emit launch; with R = audio.convert_audio(
+        decode_codes(codes)[:, None], 24000, sample_rate, 1) every channel of the fp32 result is the bits of R, of the int16 one
+        the bits of audio.to_pcm16(R, limit=limit).  A code outside the codebook follows set_check_codes as in decode_codes; an
+        int16 result no longer shows the NaN marker of a bad code (a NaN is clamped like any sample), so under "off" nothing
+        reports it.  set_gemm_precision("f16") applies as to decode_codes.  Argument errors raise ValueError before any GPU
+        work."""
+        from . import audio
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
+            raise ValueError("decode_pcm: channels must be 1 or 2")
+        (C,), fmt = self._emit_format("decode_pcm", channels, dtype, limit, 1)
+        rate = self.codec_rate if sample_rate is None else int(sample_rate)
+        audio.resampler_geometry(self.codec_rate, rate)                                     # (ValueError for a refused ratio)
+        if not isinstance(codes, torch.Tensor) or codes.dim() not in (2, 3):
+            raise ValueError("decode_pcm takes codes (K, L) or (K, B, L)")
+        B, L = (1 if codes.dim() == 2 else int(codes.shape[1])), int(codes.shape[-1])
+        n_in = self._wave_len(L)
+        n_out = audio.resampled_length(self.codec_rate, rate, n_in)
+        wav = self._run_decode_codes(codes, bandwidth_id, borrow=True)                      # (raises for a clip without samples)
+        dev = wav.device
+        out = torch.empty((B, n_out, C) if channels_last else (B, C, n_out), dtype=fmt[0], device=dev)
+        spec = _PcmSpec(None, L, rate, n_in, n_out, C)
+        self._emit_rows(list(wav), [spec] * B, out.view(-1), [b * n_out * C for b in range(B)], fmt, bool(channels_last), dev)
+        return out
+
+    def _run_decode_pcm_mixed(self, specs: Sequence["_PcmSpec"], L_pad: int, bw: int, flat: torch.Tensor, offsets: Sequence[int],
+                              fmt: Tuple[torch.dtype, float], channels_last: bool):
+        """One group of decode_pcm_many: one wt_decode_codes_mixed, one wt_emit from the plan's output rows into flat at the
+        clips' offsets.  Returns True, or None when the decoder is off the route a mixed-length plan takes."""
+        wav = self._run_decode_codes_mixed([sp.codes for sp in specs], L_pad, bw, borrow=True)
+        if wav is None:
+            return None
+        self._emit_rows(list(wav), specs, flat, offsets, fmt, channels_last, wav.device)
+        return True
+
+    def _decode_pcm_solo(self, specs: Sequence["_PcmSpec"], bw: int, flat: torch.Tensor, offsets: Sequence[int],
+                         fmt: Tuple[torch.dtype, float], channels_last: bool):
+        """Clips that are decoded one at a time (a group of one, a 'center' clip under two frames, every clip while the decoder
+        is off its mixed route): decode_codes per clip, then one wt_emit for the lot, at most MAX_GROUP clips per launch."""
+        from .mixed_length import MAX_GROUP
+        for c0 in range(0, len(specs), MAX_GROUP):
+            part, offs = specs[c0:c0 + MAX_GROUP], offsets[c0:c0 + MAX_GROUP]
+            rows = [self.decode_codes(sp.codes, bandwidth_id=bw)[0] for sp in part]
+            self._emit_rows(rows, part, flat, offs, fmt, channels_last, rows[0].device)
+
+    @torch.inference_mode()
+    def decode_pcm_many(self, codes: Sequence[torch.Tensor], sample_rates=None, channels=1, dtype: torch.dtype = torch.int16,
+                        channels_last: bool = False, limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None):
+        """Synthesise a set of clips straight to PCM.  codes[i] is (K, L_i) or (K, 1, L_i) as decode_codes_many takes it;
+        sample_rates is one rate or one per clip (default: the codec rate); channels is 1 or 2 for every clip, or one such
+        count per clip; dtype, channels_last and limit as in decode_pcm.  Returns [pcm (channels, n_out_i)] or, with
+        channels_last, [(n_out_i, channels)] in input order, n_out_i = ceil(rate_i * wave_len(L_i) / 24000), each a view into
+        ONE flat tensor of sum n_out_i * channels_i elements;
+        packed=True returns (that flat tensor, offsets [n + 1] on the CPU, in elements).  With R_i = audio.convert_audio(
+        decode_codes(codes[i])[:, None], 24000, rate_i, 1), clip i is on every channel the bits of R_i (fp32) or of
+        audio.to_pcm16(R_i, limit=limit) (int16), whatever the other clips, their order and the grouping.
+        device="cpu" returns the flat tensor in pinned host memory: ONE device-to-host copy and one stream wait behind the last
+        group; the default leaves everything on the model's device and waits for nothing.
+        Per group of decode_codes_many's grouping: one mixed-length decode from codes and one ragged emit launch from the plan's
+        output rows into the flat tensor (no copy per clip).  A clip that forms a group alone, a 'center' clip under two frames
+        (decode_codes raises for it) and every clip while the decoder is off its mixed route are decoded one at a time and
+        emitted together, at most 64 per launch.  A code outside the codebook follows set_check_codes as in decode_codes; an
+        int16 result no longer shows the NaN marker of a bad code (a NaN is clamped like any sample), so under "off" nothing
+        reports it.  Argument errors raise ValueError before any GPU work."""
+        from . import audio
+        from .mixed_length import group_frames
+        who = "decode_pcm_many"
+        bw = self._bandwidth_index(bandwidth_id)
+        clips = self._codes_clips(codes, who)
+        chans, fmt = self._emit_format(who, channels, dtype, limit, len(clips))
+        channels_last = bool(channels_last)
+        codec_rate = self.codec_rate
+        if sample_rates is None:
+            rates = [codec_rate] * len(clips)
+        elif isinstance(sample_rates, (int, np.integer)):
+            rates = [int(sample_rates)] * len(clips)
+        else:
+            rates = [int(r) for r in sample_rates]
+            if len(rates) != len(clips):
+                raise ValueError(who + ": one sample rate, or one per clip")
+        to_host = device is not None and torch.device(device).type == "cpu"
+        if device is not None and not to_host:
+            want, own = torch.device(device), self._device()
+            if want.type != own.type or (want.index is not None and want.index != (own.index if own.index is not None else 0)):
+                raise ValueError(who + ": device is None, the model's own device or 'cpu'")
+        specs: List[_PcmSpec] = []
+        offsets = [0]
+        for c, sr, ch in zip(clips, rates, chans):
+            L = int(c.shape[1])
+            n_in = self._wave_len(L)
+            n_out = audio.resampled_length(codec_rate, sr, n_in)                            # (ValueError for a refused ratio)
+            specs.append(_PcmSpec(c, L, sr, n_in, n_out, ch))
+            offsets.append(offsets[-1] + n_out * ch)
+        flat = torch.empty(offsets[-1], dtype=fmt[0], device=self._device())
+        solo: List[int] = []
+        min_frames = 1 if self._arch.padding == "same" else 2      # (decode_codes raises for a 'center' clip of one frame)
+        for L_pad, idx in group_frames([sp.frames for sp in specs]):
+            if len(idx) == 1 or specs[idx[0]].frames < min_frames:
+                solo.extend(idx)
+                continue
+            if self._run_decode_pcm_mixed([specs[i] for i in idx], L_pad, bw, flat, [offsets[i] for i in idx], fmt, channels_last) is None:
+                solo.extend(idx)
+        if solo:
+            solo = sorted(solo)
+            self._decode_pcm_solo([specs[i] for i in solo], bw, flat, [offsets[i] for i in solo], fmt, channels_last)
+        if to_host:
+            host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
+            if flat.numel():
+                host.copy_(flat, non_blocking=True)
+                torch.cuda.current_stream(flat.device).synchronize()
+            flat = host
+        if packed:
+            return flat, torch.tensor(offsets, dtype=torch.int64)
+        return [flat[offsets[i]:offsets[i + 1]].view((sp.n_out, sp.channels) if channels_last else (sp.channels, sp.n_out))
+                for i, sp in enumerate(specs)]
 
     def _run_head(self, x: torch.Tensor) -> torch.Tensor:
         dev = self._ensure_engine()

@@ -347,12 +347,44 @@ int wt_conv1d_s32(const float* x, const float* w, const float* bias, float* y, i
 /* Replaces: EuclideanCodebook.quantize (encoder/quantization/core_vq.py:175-183): x [N][D] rows,
  * embed [bins][D]; codes_out [N] int64 = argmax_j -(|x|^2 - 2 x.e_j + |e_j|^2), ties -> lowest j.
  * wt_vq_nearest: the encoder plan's kernels (distances on gemm16s.hip with the per-slab argmax epilogue, then
- * vq_finalize; D % 32 == 0); wt_vq_nearest_f32: the fp32 MFMA chain.  workspace: wt_vq_workspace_bytes(N, D, bins). */
+ * vq_finalize; D % 32 == 0); wt_vq_nearest_f32: the fp32 MFMA chain.  workspace: wt_vq_workspace_bytes(N, D, bins).
+ * Both return codes only; wt_vq_probe (below) runs the same launches and also hands out the per-slab candidates of the
+ * argmax epilogue and vq_finalize's feature output. */
 size_t wt_vq_workspace_bytes(int64_t N, int32_t D, int32_t bins);
 int wt_vq_nearest(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
                   void* workspace, void* stream);
 int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
                       void* workspace, void* stream);
+
+/* The vector quantiser as the encoder plan runs it, one launch each through the plans' launchers: row_sumsq (|x|^2, and
+ * |e|^2 unless `ee` is given), the distance GEMM with the argmax epilogue (kernel 0: gemm16s.hip on split-f16 operands
+ * scaled per tensor as in wt_vq_nearest; kernel 1: the fp32 MFMA chain of gemm.hip) and ONE vq_finalize over B clips of
+ * L frames.  x [B*L][D] and embed [bins][D] fp32; ee (optional) [bins]: the |e|^2 table to use as is (the models hold one
+ * summed serially on the host); codes [B*L] int64; feat (optional) [B][D][L] = embed[codes] transposed; pval / pidx
+ * [B*L][nparts]: the GEMM writes its per-slab (value, index) candidates there (nparts: wt_vq_form, 2 per column tile; a slab
+ * without columns reads (-inf, 0x7fffffff)).  Kernel 0 needs bins % 4 == 0 and D % 32 == 0, vq_finalize D % 256 == 0; kernel
+ * 1 takes any bins >= 1.  Everything is checked before the first HIP call: a refused problem returns WT_ERR_INVALID and
+ * launches nothing.  workspace: wt_vq_workspace_bytes(B * L, D, bins), 256-byte aligned. */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_vq_desc) */
+    int32_t kernel;                 /* 0 gemm16s.hip (split-f16), 1 gemm.hip (fp32) */
+    int32_t B, L, D, bins;
+    const float* x;
+    const float* embed;
+    const float* ee;                /* optional */
+    int64_t* codes;
+    float* feat;                    /* optional */
+    float* pval;
+    int32_t* pidx;
+    uint32_t* status;               /* optional device word (range report of the S32 split) */
+} wt_vq_desc;
+typedef struct {
+    int32_t BM, BN, waves_m, waves_n, grid, ntiles;     /* the distance GEMM: grid < ntiles = persistent, tiles walked */
+    int32_t group_m, group_n;                           /* its tile order (row tiles per group; column tiles per block, 0 = all) */
+    int32_t nparts;                                     /* candidates per row: (column tiles) x (wave columns) */
+    int32_t fin_grid_x, fin_grid_y;                     /* vq_finalize: (32-frame tiles, clips) */
+} wt_vq_form;
+int wt_vq_probe(const wt_vq_desc* d, wt_vq_form* form, void* workspace, void* stream);
 
 /* One GEMM launch through the plans' own launchers, with every argument a plan sets: the unit tests' view of each
  * (epilogue, output format) pair and of each tile form the launchers pick.  Operands are fp32 device arrays in the
@@ -363,7 +395,7 @@ int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, 
  * engine 1 (gemm.hip) reads the fp32 arrays directly.  engine 2 is engine 0 on the one-product twin of the kernel
  * (WT_PLAN_FLAG_F16_GEMM: same operand split, workspace, checks and tile form; the decode plans' (epi, out) pairs only, no
  * mix_geom).  epi / out / pro take the values of the library's Epi, Out16s,
- * Pro enums (the argmax epilogue is reached through wt_vq_nearest instead).  C (and C2) are written in the format
+ * Pro enums (the argmax epilogue is reached through wt_vq_probe instead).  C (and C2) are written in the format
  * `out` names (S32: 128-byte groups [32 x f16 hi | 32 x f16 lo]).  status: optional device word that the S32
  * producers OR WT_STATUS_BIT_RANGE into.  The whole descriptor is checked before any HIP call: a problem the
  * launchers refuse returns WT_ERR_INVALID and touches no memory.  form (optional): the launch the launcher chose.

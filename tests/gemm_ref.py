@@ -17,7 +17,7 @@ EPI_NAMES = {0: "BIAS", 1: "BIAS_RES", 2: "BIAS_GELU", 3: "BIAS_GAMMA_RES", 4: "
 OUT_NAMES = {0: "F32", 1: "S32", 2: "S32_DUAL_ELU", 3: "F32_AND_S32"}
 
 # The pairs the launchers instantiate (gemm16s.hip WT_GEMM16S_PAIRS, gemm.hip WT_GEMM_PAIRS) minus the argmax epilogue,
-# which has its own test (test_vq_nearest_kernel_and_ties): gemm16s (epi, out), gemm (pro, epi)
+# which has its own reference and tests (tests/vq_ref.py, tests/test_vq_ops.py): gemm16s (epi, out), gemm (pro, epi)
 PAIRS16 = [(EPI_BIAS, OUT_F32), (EPI_BIAS, OUT_S32), (EPI_BIAS, OUT_S32_DUAL_ELU), (EPI_BIAS, OUT_F32_AND_S32),
            (EPI_BIAS_RES, OUT_F32), (EPI_BIAS_ELU, OUT_S32), (EPI_BIAS_RES_ELU, OUT_S32), (EPI_BIAS_GELU, OUT_S32),
            (EPI_BIAS_GAMMA_RES, OUT_F32), (EPI_HEAD, OUT_S32), (EPI_SCALE, OUT_F32), (EPI_BIAS_ROW, OUT_S32)]

@@ -4,8 +4,8 @@ the plans' own launchers with the plans' operand splitting.  Per case: a per-ele
 the write contract (NaN-filled logical region all written and finite, sentinel-filled padding untouched except the
 zeroed partial run of 4 that EPI_SCALE / EPI_BIAS_ROW document) and, on gemm16s, a clear range status word.  Per pair:
 the union of launch forms the cases reached must be the forms its launcher can choose, so that a launcher change that
-strands a form fails here instead of going uncovered.  The argmax epilogue has its own test
-(test_gpu_parity.py::test_vq_nearest_kernel_and_ties)."""
+strands a form fails here instead of going uncovered.  The argmax epilogue has its own file
+(tests/test_vq_ops.py, through wt_vq_probe: every partial candidate, code and feature word against tests/vq_ref.py)."""
 import ctypes
 
 import numpy as np

@@ -26,7 +26,7 @@ EXPORTS = [
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
     "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe", "wt_lstm_probe_workspace_bytes", "wt_lstm_probe",
     "wt_decode_codes", "wt_decode_codes_mixed", "wt_ingest_workspace_bytes", "wt_ingest", "wt_codes_unpack",
-    "wt_emit_workspace_bytes", "wt_emit",
+    "wt_emit_workspace_bytes", "wt_emit", "wt_vq_probe",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -106,6 +106,17 @@ class WtResblockDesc(ctypes.Structure):
 
 class WtResblockForm(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("kernel", "C", "fold", "down", "fpw", "grid", "block", "lds", "tiles")]
+
+
+class WtVqDesc(ctypes.Structure):
+    """wt_vq_desc: the encoder plan's VQ launches on caller-owned arrays (wt_vq_probe)."""
+    _fields_ = ([(n, c_int32) for n in ("size", "kernel", "B", "L", "D", "bins")]
+                + [(n, c_void_p) for n in ("x", "embed", "ee", "codes", "feat", "pval", "pidx", "status")])
+
+
+class WtVqForm(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("BM", "BN", "waves_m", "waves_n", "grid", "ntiles", "group_m", "group_n", "nparts",
+                                       "fin_grid_x", "fin_grid_y")]
 
 
 LSTM_PERSIST, LSTM_STEP_F16, LSTM_STEP_F32 = 0, 1, 2
@@ -247,6 +258,7 @@ def _load() -> ctypes.CDLL:
     lib.wt_gemm_probe.argtypes = [POINTER(WtGemmDesc), POINTER(WtLaunchForm), c_void_p, c_void_p]
     lib.wt_op_probe.argtypes = [POINTER(WtOpDesc), POINTER(WtOpForm), c_void_p]
     lib.wt_resblock_probe.argtypes = [POINTER(WtResblockDesc), POINTER(WtResblockForm), c_void_p]
+    lib.wt_vq_probe.argtypes = [POINTER(WtVqDesc), POINTER(WtVqForm), c_void_p, c_void_p]
     lib.wt_lstm_probe_workspace_bytes.argtypes = [POINTER(WtLstmDesc)]
     lib.wt_lstm_probe_workspace_bytes.restype = c_size_t
     lib.wt_lstm_probe.argtypes = [c_void_p, POINTER(WtLstmDesc), POINTER(WtLstmForm), c_void_p, c_void_p]

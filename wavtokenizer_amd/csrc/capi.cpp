@@ -83,6 +83,8 @@ int wt_model_create(const wt_arch* arch, const wt_tensor* tensors, int32_t n_ten
     if (arch->input_channels != 512) { set_error("input_channels must be 512 (SEANet dimension)"); return WT_ERR_INVALID; }
     if (arch->dim % 256 || arch->intermediate_dim % 32) { set_error("dim must be a multiple of 256, intermediate_dim of 32"); return WT_ERR_INVALID; }
     if (arch->dim % 32 || (arch->dim / 32) % 4) { set_error("dim/32 (GroupNorm group width) must be a multiple of 4"); return WT_ERR_INVALID; }
+    // the shipped encode plan runs the VQ distances on gemm16s.hip, whose argmax epilogue reads |e|^2 four columns at a time
+    if (arch->vq_bins < 4 || arch->vq_bins % 4) { set_error("vq_bins must be a positive multiple of 4 (the VQ distance kernel takes four codebook columns at a time)"); return WT_ERR_INVALID; }
     DeviceGuard dg(device);
     if (!dg.ok) { set_error("wt_model_create: hipSetDevice failed"); return WT_ERR_HIP; }
     if (int rc = check_device(device, "wt_model_create")) return rc;

@@ -240,6 +240,7 @@ struct LaunchForm {
     int ks = 1, prod = 0;        // gemm16s: K tiles per barrier, loader-wave sets
     int staged = 0, bias_cache = 0;   // gemm16s: epilogue staged through LDS; bias (and gamma) cached in LDS
     int G = 0, tiles = 0;        // workgroups per z slice (grid.x) and output tiles per z slice: G < tiles = persistent
+    int group_m = 0, group_n = 0;     // the tile order the launcher chose (GemmArgs::group_m / group_n as the kernel reads them)
 };
 
 struct GemmArgs {

@@ -335,7 +335,7 @@ static int launch_one(const GemmArgs& a, hipStream_t s) {
     })) return rc;
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, a.nz);
-    if (a.form) *a.form = LaunchForm{BM, BN, WMs, WNs, 2, 1, 0, 0, 0, tiles_m * tiles_n, tiles_m * tiles_n};
+    if (a.form) *a.form = LaunchForm{BM, BN, WMs, WNs, 2, 1, 0, 0, 0, tiles_m * tiles_n, tiles_m * tiles_n, a.group_m, 0};
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
     WT_HIP_CHECK(hipGetLastError());
     return 0;

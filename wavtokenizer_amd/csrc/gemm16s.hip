@@ -457,7 +457,7 @@ static int launch16s_one(const GemmArgs& a, hipStream_t s, const int* mix_geom =
         b.stamp_start = g_launch.stamp_start; b.stamp_end = g_launch.stamp_end;
         g_launch.stamp_used = true;
     }
-    if (a.form) *a.form = LaunchForm{BM, BN, WMs, WNs, NSTAGE, KS, PROD, b.stage_epi, b.pc_off ? 1 : 0, G, ntiles};
+    if (a.form) *a.form = LaunchForm{BM, BN, WMs, WNs, NSTAGE, KS, PROD, b.stage_epi, b.pc_off ? 1 : 0, G, ntiles, a.group_m, a.group_n};
     if constexpr (MIX)
         hipLaunchKernelGGL((gemm16s_mixed_kernel<BM, BN, WMs, WNs, NSTAGE, EPI, OUT, LABDBG, WT_GEMM16S_MF, WPS, KS, PROD>),
                            dim3(G, 1, a.nz), dim3(64 * WMs * WNs * (1 + PROD)), smem, s, b, mix_geom);

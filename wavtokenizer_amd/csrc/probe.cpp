@@ -1,6 +1,7 @@
 // Entry points that launch kernels outside a plan: wt_codes_to_features, the single-stage calls and the probes through
 // which the tests reach every GEMM form (wt_gemm_probe), every non-GEMM kernel (wt_op_probe), the fused resblocks
-// (wt_resblock_probe), the LSTM recurrence (wt_lstm_probe) and the mixed-length geometry step (wt_geometry_probe) on their own.
+// (wt_resblock_probe), the LSTM recurrence (wt_lstm_probe), the vector quantiser (wt_vq_probe) and the mixed-length geometry
+// step (wt_geometry_probe) on their own.
 #include "model.h"
 
 using namespace wt;
@@ -101,7 +102,7 @@ static int probe_args(const wt_gemm_desc* d, char* ws, GemmArgs& a) {
     if (mix && (!e16 || (reinterpret_cast<uintptr_t>(mix) & 3))) { set_error("wt_gemm_probe: mix_geom is a 4-byte aligned device table for gemm16s"); return WT_ERR_INVALID; }
     if (d->engine < 0 || d->engine > 2) { set_error("wt_gemm_probe: engine is 0 (gemm16s), 1 (gemm) or 2 (gemm16s, one product)"); return WT_ERR_INVALID; }
     if (!d->A || !d->B || !d->C) { set_error("wt_gemm_probe: A, B and C are required"); return WT_ERR_INVALID; }
-    if (d->epi == EPI_ARGMAX) { set_error("wt_gemm_probe: the argmax epilogue is reached through wt_vq_nearest"); return WT_ERR_INVALID; }
+    if (d->epi == EPI_ARGMAX) { set_error("wt_gemm_probe: the argmax epilogue is reached through wt_vq_probe"); return WT_ERR_INVALID; }
     if (d->M <= 0 || d->N <= 0 || d->K <= 0 || d->T_out <= 0 || d->T_in <= 0 || d->M % d->T_out || d->nz < 1 || d->taps < 1 ||
         d->stride < 1 || d->dil < 1 || d->pad_left < 0 || (d->pad_mode != PAD_ZERO && d->pad_mode != PAD_REFLECT) ||
         d->a_bstride < 0 || d->a_rstride < 0 || d->a2_bstride < 0 || d->a2_rstride < 0 || d->w_rstride < d->K ||
@@ -317,34 +318,55 @@ size_t wt_vq_workspace_bytes(int64_t N, int32_t D, int32_t bins) {
            2 * al256((size_t)N * np * sizeof(float)) + al256((size_t)bins * sizeof(float)) + 512;
 }
 
-// the ee[] table here is rebuilt per call on the device by row_sumsq (same kernel as |x|^2)
+// The workspace of wt_vq_nearest / wt_vq_probe (wt_vq_workspace_bytes): S32 copies of x and the codebook, |x|^2, the partial
+// (value, index) candidates, |e|^2, then the scales of split_pair
+struct VqLayout { char *xs, *es; float* xx; float* pv; int* pi; float* ee; char* tail; int np; };
+static VqLayout vq_layout(void* workspace, int64_t N, int32_t D, int32_t bins, bool s32) {
+    VqLayout L;
+    L.np = s32 ? gemm16s_vq_parts(bins) : gemm_vq_parts(bins);
+    char* ws = static_cast<char*>(workspace);
+    L.xs = ws; ws += al256((size_t)N * D * 4);
+    L.es = ws; ws += al256((size_t)bins * D * 4);
+    L.xx = reinterpret_cast<float*>(ws); ws += al256((size_t)N * sizeof(float));
+    L.pv = reinterpret_cast<float*>(ws); ws += al256((size_t)N * L.np * sizeof(float));
+    L.pi = reinterpret_cast<int*>(ws); ws += al256((size_t)N * L.np * sizeof(float));
+    L.ee = reinterpret_cast<float*>(ws); ws += al256((size_t)bins * sizeof(float));
+    L.tail = ws;
+    return L;
+}
+// the distance GEMM's arguments as the encoder plan sets them (plan.cpp, "VQ"); ee: the caller's table, or the workspace's
+static GemmArgs vq_args(const VqLayout& L, const float* x, const float* embed, const float* ee, int64_t N, int32_t D, int32_t bins,
+                        float* pv, int* pi, bool s32) {
+    GemmArgs a = linear_args(embed, nullptr, N, bins, D);
+    a.A = x; a.vq_xx = L.xx; a.vq_ee = ee ? ee : L.ee; a.vq_pval = pv; a.vq_pidx = pi; a.vq_nparts = L.np;
+    if (s32) { a.A = reinterpret_cast<const float*>(L.xs); a.W_hi = L.es; }
+    return a;
+}
+// |x|^2, |e|^2 (rebuilt per call on the device by row_sumsq unless the caller brings the table) and the distance GEMM with
+// its per-slab argmax epilogue
+static int vq_distances(const VqLayout& L, GemmArgs a, const float* x, const float* embed, bool own_ee, int64_t N, int32_t D,
+                        int32_t bins, bool s32, hipStream_t s) {
+    if (int rc = launch_row_sumsq(x, L.xx, N, D, s)) return rc;
+    if (own_ee) if (int rc = launch_row_sumsq(embed, L.ee, bins, D, s)) return rc;
+    if (s32) {
+        // what the encoder plan launches: distances on gemm16s.hip, per-slab argmax in its epilogue
+        if (int rc = split_pair(embed, (long)bins * D, x, (long)N * D, L.es, L.xs, L.tail, a, s)) return rc;
+        return launch_gemm16s(a, EPI_ARGMAX, OUT_F32, s);
+    }
+    return launch_gemm(a, PRO_NONE, EPI_ARGMAX, s);
+}
+
 static int vq_nearest(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
                       void* workspace, void* stream, bool s32) {
     if (!x || !embed || !codes_out || !workspace) { set_error("wt_vq_nearest: null argument"); return WT_ERR_INVALID; }
     if (s32 && (D % 32)) { set_error("wt_vq_nearest: the split-f16 kernel needs D % 32 == 0"); return WT_ERR_INVALID; }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int np = s32 ? gemm16s_vq_parts(bins) : gemm_vq_parts(bins);
-    char* ws = static_cast<char*>(workspace);
-    char* xs = ws; ws += al256((size_t)N * D * 4);
-    char* es = ws; ws += al256((size_t)bins * D * 4);
-    float* xx = reinterpret_cast<float*>(ws); ws += al256((size_t)N * sizeof(float));
-    float* pv = reinterpret_cast<float*>(ws); ws += al256((size_t)N * np * sizeof(float));
-    int* pi = reinterpret_cast<int*>(ws); ws += al256((size_t)N * np * sizeof(float));
-    float* ee = reinterpret_cast<float*>(ws); ws += al256((size_t)bins * sizeof(float));
-    if (int rc = launch_row_sumsq(x, xx, N, D, s)) return rc;
-    if (int rc = launch_row_sumsq(embed, ee, bins, D, s)) return rc;
-    GemmArgs a = linear_args(embed, nullptr, N, bins, D);
-    a.A = x; a.vq_xx = xx; a.vq_ee = ee; a.vq_pval = pv; a.vq_pidx = pi; a.vq_nparts = np;
-    if (s32) {
-        // what the encoder plan launches: distances on gemm16s.hip, per-slab argmax in its epilogue
-        if (int rc = split_pair(embed, (long)bins * D, x, (long)N * D, es, xs, ws, a, s)) return rc;
-        if (int rc = launch_gemm16s(a, EPI_ARGMAX, OUT_F32, s)) return rc;
-    } else {
-        if (int rc = launch_gemm(a, PRO_NONE, EPI_ARGMAX, s)) return rc;
-    }
+    const VqLayout L = vq_layout(workspace, N, D, bins, s32);
+    const int np = L.np;
+    if (int rc = vq_distances(L, vq_args(L, x, embed, nullptr, N, D, bins, L.pv, L.pi, s32), x, embed, true, N, D, bins, s32, s)) return rc;
     for (int64_t r0 = 0; r0 < N; r0 += 8192) {
         const int n = (int)std::min<int64_t>(8192, N - r0);
-        if (int rc = launch_vq_finalize(pv + r0 * np, pi + r0 * np, np, embed, codes_out + r0, nullptr, 1, n, D, bins, s)) return rc;
+        if (int rc = launch_vq_finalize(L.pv + r0 * np, L.pi + r0 * np, np, embed, codes_out + r0, nullptr, 1, n, D, bins, s)) return rc;
     }
     return WT_OK;
 }
@@ -355,6 +377,42 @@ int wt_vq_nearest(const float* x, const float* embed, int64_t N, int32_t D, int3
 int wt_vq_nearest_f32(const float* x, const float* embed, int64_t N, int32_t D, int32_t bins, int64_t* codes_out,
                       void* workspace, void* stream) {
     return vq_nearest(x, embed, N, D, bins, codes_out, workspace, stream, false);
+}
+
+// wt_vq_probe: the launches of the encoder plan's VQ steps (row_sumsq, the argmax GEMM, ONE vq_finalize over B clips of L
+// frames) with the partial candidates in the caller's memory.  Every check that needs no HIP call comes first, the launchers'
+// own included (check_gemm16s / check_gemm; vq_finalize's D % 256), so a refused problem launches nothing.
+int wt_vq_probe(const wt_vq_desc* d, wt_vq_form* form, void* workspace, void* stream) {
+    auto bad = [](const char* m) { set_error(std::string("wt_vq_probe: ") + m); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_vq_desc)) return bad("descriptor missing or of another size");
+    if (d->kernel != 0 && d->kernel != 1) return bad("kernel is 0 (gemm16s, split-f16) or 1 (gemm, fp32)");
+    if (!d->x || !d->embed || !d->codes || !d->pval || !d->pidx) return bad("x, embed, codes, pval and pidx are required");
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) return bad("needs a 256-byte aligned workspace");
+    if (d->B < 1 || d->B > 65535 || d->L < 1 || d->D < 1 || d->bins < 1 || (long)d->B * d->L >= (long)INT_MAX / 2)
+        return bad("needs 1 <= B <= 65535, L >= 1, D >= 1, bins >= 1 and B * L < 2^30");
+    const void* p16[] = {d->x, d->embed, d->ee};
+    for (const void* p : p16) if (reinterpret_cast<uintptr_t>(p) & 15) return bad("x, embed and ee must be 16-byte aligned");
+    const void* p4[] = {d->feat, d->pval, d->pidx, d->status};
+    for (const void* p : p4) if (reinterpret_cast<uintptr_t>(p) & 3) return bad("feat, pval, pidx and status must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d->codes) & 7) return bad("codes must be 8-byte aligned");
+    if (d->D % 4) return bad("row_sumsq needs D % 4 == 0");
+    if (d->D % 256) return bad("vq_finalize: codebook width must be a multiple of 256");
+    const bool s32 = d->kernel == 0;
+    const int64_t N = (int64_t)d->B * d->L;
+    const VqLayout L = vq_layout(workspace, N, d->D, d->bins, s32);
+    GemmArgs a = vq_args(L, d->x, d->embed, d->ee, N, d->D, d->bins, d->pval, d->pidx, s32);
+    if (s32 ? check_gemm16s(a, EPI_ARGMAX, OUT_F32, nullptr, GEMM16S_F16X3) : check_gemm(a, PRO_NONE, EPI_ARGMAX)) return WT_ERR_INVALID;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LaunchForm lf;
+    a.form = &lf;
+    const LaunchCtx saved = g_launch;
+    g_launch.status = reinterpret_cast<unsigned*>(d->status);
+    int rc = vq_distances(L, a, d->x, d->embed, d->ee == nullptr, N, d->D, d->bins, s32, s);
+    if (!rc) rc = launch_vq_finalize(d->pval, d->pidx, L.np, d->embed, d->codes, d->feat, d->B, d->L, d->D, d->bins, s);
+    g_launch = saved;
+    if (rc) return rc;
+    if (form) *form = wt_vq_form{lf.BM, lf.BN, lf.waves_m, lf.waves_n, lf.G, lf.tiles, lf.group_m, lf.group_n, L.np, (d->L + 31) / 32, d->B};
+    return WT_OK;
 }
 
 int wt_resblock(const float* x, const float* wav, const float* e0_w, const float* e0_b, const float* w3, const float* b3,

@@ -800,7 +800,7 @@ static int validate_imported(const wt_model* M) {
     };
     const int nf = 32, H = 512, D = a.dim, I = a.intermediate_dim;
     if (a.n_ratios < 1 || a.n_ratios > 8 || a.num_quantizers < 1 || a.num_quantizers > 32 || a.input_channels != 512 || D % 256 || I % 32 || a.num_layers < 1 || a.num_layers > 32 ||
-        a.adanorm_num_embeddings < 1 || a.vq_bins < 1 || a.n_fft < 4 || a.hop_length < 1) return bad("the architecture itself");
+        a.adanorm_num_embeddings < 1 || a.vq_bins < 4 || a.vq_bins % 4 || a.n_fft < 4 || a.hop_length < 1) return bad("the architecture itself");
     int hop = 1;
     for (int i = 0; i < a.n_ratios; ++i) { if (a.ratios[i] < 1 || a.ratios[i] > 64) return bad("a ratio"); hop *= a.ratios[i]; }
     if (M->hop != hop || M->H != H || (int)M->enc_ratios.size() != a.n_ratios || (int)M->stages.size() != a.n_ratios) return bad("the encoder's shape");

@@ -325,11 +325,11 @@ def test_plan_is_the_decode_plan_with_its_first_step_replaced(model, flags):
     assert "mix.lengths" in sm and "code_rows" in sm and "bb.in" not in sm
 
 
-@pytest.mark.parametrize("what", ["range_report", "fp32_site", "step_lstm_flag"])
+@pytest.mark.parametrize("what", ["range_report", "fp32_site", "fp32_site_attn", "fp32_site_cnx1", "fp32_site_head", "step_lstm_flag"])
 def test_every_decode_plan_variant_runs_from_codes(what):
     """WT_PLAN_FLAG_RANGE_REPORT (code_rows feeds the report with bb.in), backbone.embed on fp32 operands (bb.in in fp32 on an
-    otherwise split-f16 plan), and a flag the decoder ignores: the codes plan and the features plan of the same flags and
-    sites return the same bits."""
+    otherwise split-f16 plan), a range site behind it on fp32 operands (bb.in stays split-f16), and a flag the decoder ignores:
+    the codes plan and the features plan of the same flags and sites return the same bits."""
     from wavtokenizer_amd import _capi
     from wavtokenizer_amd.pretrained import _ptr, _stream_ptr
     m = _cached("hop600")
@@ -338,7 +338,8 @@ def test_every_decode_plan_variant_runs_from_codes(what):
     dev = torch.device("cuda", torch.cuda.current_device())
     B, L = 2, 33
     flags, sites = {"range_report": (_capi.WT_PLAN_FLAG_RANGE_REPORT, 0), "fp32_site": (0, 1 << _capi.WT_SITE_BB_EMBED),
-                    "step_lstm_flag": (_capi.WT_PLAN_FLAG_STEP_LSTM, 0)}[what]
+                    "fp32_site_attn": (0, 1 << _capi.WT_SITE_ATTN), "fp32_site_cnx1": (0, 1 << (_capi.WT_SITE_CNX0 + 1)),
+                    "fp32_site_head": (0, 1 << _capi.WT_SITE_HEAD), "step_lstm_flag": (_capi.WT_PLAN_FLAG_STEP_LSTM, 0)}[what]
     codes = _codes(m, 1, B, L, seed=3)
     feats = m.codes_to_features(codes)
     pd, wsd = m._engine.plan(_capi.WT_PLAN_DECODE, B, L, flags, dev, sites)
@@ -352,7 +353,13 @@ def test_every_decode_plan_variant_runs_from_codes(what):
     _capi.check(lib.wt_decode_codes(pc, _ptr(codes), 1, 2, _ptr(wc), _ptr(bbc), _ptr(wsc), st), "wt_decode_codes")
     torch.cuda.synchronize()
     assert bool(torch.isfinite(wd).all()) and torch.equal(wc, wd) and torch.equal(bbc, bbd)      # (the backbone output too)
-    assert _buffer(lib, pc, "bb.in")[1] == (0 if sites else _capi.BUF_S32)
+    assert _buffer(lib, pc, "bb.in")[1] == (0 if sites & (1 << _capi.WT_SITE_BB_EMBED) else _capi.BUF_S32)
+    if sites:                                                # (the site is in force: other bits than the shipped plan's)
+        p0, ws0 = m._engine.plan(_capi.WT_PLAN_DECODE_CODES, B, L, 0, dev)
+        w0 = torch.empty_like(wd)
+        _capi.check(lib.wt_decode_codes(p0, _ptr(codes), 1, 2, _ptr(w0), _ptr(None), _ptr(ws0), st), "wt_decode_codes")
+        torch.cuda.synchronize()
+        assert not torch.equal(w0, wc)
     if what == "range_report":
         step, buf, amax = ctypes.c_char_p(), ctypes.c_char_p(), ctypes.c_float()
         assert lib.wt_plan_range_report(pc, 0, ctypes.byref(step), ctypes.byref(buf), ctypes.byref(amax)) == 0

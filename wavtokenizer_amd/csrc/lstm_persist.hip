@@ -249,30 +249,40 @@ __global__ __launch_bounds__(64 * PW) void lstm_persist_kernel(const LstmPersist
                 const char* ape = ap0 + (ch_h >> 3) * 128;
                 const char* apo = ap0 + (1 ^ (ch_h >> 3)) * 128;
                 const int lo_d = (ch_h & 4) ? -64 : 64;             // (chunk ^ 4) - chunk, in bytes
-                f32x4p accm = {0.f, 0.f, 0.f, 0.f}, accc = accm;
+                // The two correction products are summed in two chains of their own, each in block order, and combined exactly as
+                // the SMALL form combines them (its accc rows 0-7 and its accm rows 8-15): a clip's gate pre-activations are then
+                // the same words in either form, i.e. at any batch size.  A third accumulator does not fit beside both operand
+                // double buffers in a one-pass loop (it spills), so the blocks are walked twice: pass 1 with the hi operand feeds
+                // the main term and hi.W_lo, pass 2 with the lo operand feeds lo.W_hi.  MFMA count and LDS reads are unchanged.
+                f32x4p accm = {0.f, 0.f, 0.f, 0.f}, acc_hl = accm, acc_lh = accm;
                 // the state reads of the twelve waves pace this phase: the next block's operand is requested before this
                 // block's MFMAs are issued
-                f16x8p ahb[2], alb[2];
-                ahb[0] = *reinterpret_cast<const f16x8p*>(ape);
-                alb[0] = *reinterpret_cast<const f16x8p*>(ape + lo_d);
+                {
+                    f16x8p ahb[2];
+                    ahb[0] = *reinterpret_cast<const f16x8p*>(ape);
 #pragma unroll
-                for (int blk = 0; blk < 16; ++blk) {
-                    if (blk + 1 < 16) {
-                        const char* pb = (((blk + 1) & 1) ? apo : ape) + ((blk + 1) >> 1) * 256;
-                        ahb[(blk + 1) & 1] = *reinterpret_cast<const f16x8p*>(pb);
-                        alb[(blk + 1) & 1] = *reinterpret_cast<const f16x8p*>(pb + lo_d);
+                    for (int blk = 0; blk < 16; ++blk) {
+                        if (blk + 1 < 16) ahb[(blk + 1) & 1] = *reinterpret_cast<const f16x8p*>((((blk + 1) & 1) ? apo : ape) + ((blk + 1) >> 1) * 256);
+                        const f16x8p ah = ahb[blk & 1];
+                        const f16x8p wlb = blk < 16 - NLDS ? wl[blk < 16 - NLDS ? blk : 0]
+                                                           : __builtin_bit_cast(f16x8p, wlds[(blk - (16 - NLDS)) * 64]);
+                        accm = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wh[blk], accm, 0, 0, 0);
+                        acc_hl = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wlb, acc_hl, 0, 0, 0);
                     }
-                    const f16x8p ah = ahb[blk & 1], al = alb[blk & 1];
-                    const f16x8p wlb = blk < 16 - NLDS ? wl[blk < 16 - NLDS ? blk : 0]
-                                                       : __builtin_bit_cast(f16x8p, wlds[(blk - (16 - NLDS)) * 64]);
-                    accm = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wh[blk], accm, 0, 0, 0);
-                    accc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wlb, accc, 0, 0, 0);
-                    accc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wh[blk], accc, 0, 0, 0);
+                }
+                {
+                    f16x8p alb[2];
+                    alb[0] = *reinterpret_cast<const f16x8p*>(ape + lo_d);
+#pragma unroll
+                    for (int blk = 0; blk < 16; ++blk) {
+                        if (blk + 1 < 16) alb[(blk + 1) & 1] = *reinterpret_cast<const f16x8p*>((((blk + 1) & 1) ? apo : ape) + ((blk + 1) >> 1) * 256 + lo_d);
+                        acc_lh = __builtin_amdgcn_mfma_f32_16x16x32_f16(alb[blk & 1], wh[blk], acc_lh, 0, 0, 0);
+                    }
                 }
                 // D: col = lane & 15 (gate row), row = 4 (lane >> 4) + reg (clip)
                 float* gb = gbuf + ((role * 4 + ntile) * 16) * 17;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) gb[(4 * lk + r) * 17 + li] = accm[r] + accc[r] * (1.f / 2048.f);
+                for (int r = 0; r < 4; ++r) gb[(4 * lk + r) * 17 + li] = accm[r] + (acc_hl[r] + acc_lh[r]) * (1.f / 2048.f);
             }
         }
         LP_TRACE(3);

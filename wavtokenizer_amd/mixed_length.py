@@ -10,8 +10,8 @@ from typing import List, Sequence, Tuple
 
 MAX_FRAMES = 12000       # frames per clip of one plan (wt_plan_create): a bucket never goes past it
 MIN_CLIP = 1024          # the shortest clip a mixed-length plan takes (wt_plan_min_clip_length: the fused stage-1 kernel)
-MAX_GROUP = 64           # clips per call: up to 64 the persistent LSTM gives every clip the bits of a call of its own (above
-                         # 64 it still runs, up to 128, but its results move by an ulp against a solo call's)
+MAX_GROUP = 64           # clips per call: the wt_ingest / wt_emit descriptor blocks and the plan buckets are sized for it (the
+                         # persistent LSTM gives every clip the bits of a call of its own at any size it takes, up to 128)
 BUCKET_STEPS = 8         # buckets per octave of length: at most 1/8 of a call is padding from the bucket
 
 

@@ -13,6 +13,14 @@
  *   - the caller owns every buffer, including the workspace (size from
  *     wt_plan_workspace_bytes).  Kernels are enqueued on `stream`; nothing synchronises,
  *     allocates or frees inside wt_encode / wt_decode / wt_codes_to_features.
+ *   - the workspace of a plan may hold anything when a call starts (another call's activations, NaNs, another tenant's
+ *     bytes): every word that can reach a result has been written by an earlier step of the SAME call, so a call's
+ *     outputs are a function of its inputs alone.  Its address must be a multiple of 256 bytes: stage buffers sit at multiples of 256
+ *     bytes from its start, and the kernels rely on that for their 16-byte fills, vector loads and buffer loads, the
+ *     128-byte split-f16 groups and 256-byte rows.  Every run entry point of a plan (wt_encode, wt_encode_mixed, wt_decode,
+ *     wt_decode_mixed, wt_decode_codes, wt_decode_codes_mixed, wt_head, wt_seanet_decode, wt_unit_run) returns
+ *     WT_ERR_INVALID for any other address, before it launches anything.  The library never writes outside
+ *     [workspace, workspace + wt_plan_workspace_bytes).
  *   - a wt_model is immutable after creation (folded + packed weights in HBM) and may be shared
  *     by host threads.  A wt_plan may be shared too: host calls on one plan are serialised by a
  *     per-plan lock (they only enqueue), and calls that may be in flight on the GPU at the same

@@ -194,7 +194,18 @@ static int run_graph(const wt_plan* p, const RunCtx& c, bool* eager) {
     return WT_OK;
 }
 
+// The workspace is the caller's: the library assumes nothing about its contents (every word that can reach a result has been
+// written by a step of the same call) and one thing about its address.  Buffers sit at multiples of 256 bytes from its start (wt_plan::buf),
+// and what the kernels need of a buffer's address is the largest of: the 16-byte stores of the fills and the 16-byte vector and
+// buffer loads of every kernel, the 128-byte S32 groups, and the 256-byte pitch itself, which the GEMMs' LDS-DMA rows and the
+// persistent LSTM's 2 KB state rows take for granted.  So the start must be a multiple of 256.
+constexpr uintptr_t WS_ALIGN = 256;
+
 static int run_plan(const wt_plan* p, const RunCtx& c) {
+    if (reinterpret_cast<uintptr_t>(c.ws) % WS_ALIGN) {      // before any launch, and before an earlier call's status is consumed
+        set_error("the workspace must be 256-byte aligned");
+        return WT_ERR_INVALID;
+    }
     std::lock_guard<std::mutex> lock(p->mu);
     DeviceGuard dg(p->model->device);
     if (!dg.ok) { set_error("hipSetDevice failed"); return WT_ERR_HIP; }

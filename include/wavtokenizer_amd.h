@@ -701,6 +701,40 @@ int    wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stre
 int wt_linear_overlap_add(const float* frames, const float* weight, int32_t n_frames, int64_t rows, int64_t frame_len,
                           int64_t last_len, int64_t stride, float* out, void* stream);
 
+/* Ragged overlap-add: wt_linear_overlap_add for B recordings in one launch, each with its own number of frames, frame length,
+ * stride and total length, its frames read where the decode calls left them.  Recording b's frame f is the row rows[f] (rows: a
+ * DEVICE array of n_frames device pointers), of which the first len_f = min(frame_len, total - f * stride) samples are the
+ * frame: every frame ends at `total` at the latest, so with stride < frame_len several trailing frames are short (the frames
+ * EncodecModel.encode cuts, encoder/model.py:139-145).  Nothing is read past rows[f][len_f - 1] (a decode row is longer than its
+ * segment, frames(len) * hop >= len, and holds something else there) and nothing is written outside out[0, total).
+ *   out[t] = (sum_f weight[t - f * stride] * rows[f][t - f * stride]) / (sum_f weight[t - f * stride])
+ * over the frames covering t in ascending f, products and sums rounded separately, one division: the bits of the reference's
+ * `out += weight[:len] * frame; sum_weight += weight[:len]; out / sum_weight` (encoder/utils.py:17-56) and of
+ * wt_linear_overlap_add on the same frames.  weight is the reference's triangle built on the host (see wt_linear_overlap_add)
+ * over the length of the recording's FIRST frame, min(frame_len, total) entries: a recording shorter than frame_len is one
+ * frame, and the reference builds its triangle from that frame.  Recordings of one first-frame length may share a table.
+ * clips is a HOST array; rows, the pointers it holds, weight and out are device pointers.  The library uploads the descriptors
+ * into workspace (device, wt_overlap_add_ragged_workspace_bytes(B) bytes, 8-byte aligned; its content must stay untouched until
+ * the launch has run) on `stream`; up to 64 recordings travel in the launch's own argument block instead and leave the workspace
+ * untouched (it must be passed all the same).  Every descriptor is checked before any device call: a null rows, weight or out,
+ * n_frames, frame_len, stride or total below 1, n_frames other than ceil(total / stride), stride > frame_len with more than one
+ * frame (uncovered samples), total > stride * (n_frames - 1) + frame_len (the last frame would not reach the end), or a
+ * misaligned pointer returns WT_ERR_INVALID with a message and touches no memory.  The row pointers themselves live on the device
+ * and are the caller's to get right.  The launch goes to the calling thread's current device.
+ * Like wt_emit, a call with more than 64 recordings is a host-side call around its launch (it shares wt_ingest's pinned
+ * descriptor blocks, their events and their lock) and must NOT be made on a stream that is being captured into a graph. */
+typedef struct {
+    const float* const* rows;         /* device: n_frames device pointers, frame f's row */
+    int64_t n_frames;                 /* ceil(total / stride) */
+    int64_t frame_len;                /* samples of a full frame */
+    int64_t stride;                   /* samples between the starts of two frames */
+    int64_t total;                    /* samples of the recording */
+    const float* weight;              /* device [min(frame_len, total)] */
+    float* out;                       /* device [total] */
+} wt_overlap_add_clip;
+size_t wt_overlap_add_ragged_workspace_bytes(int32_t B);
+int    wt_overlap_add_ragged(const wt_overlap_add_clip* clips, int32_t B, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

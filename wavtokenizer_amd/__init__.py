@@ -5,7 +5,8 @@
 Importing the class loads the HIP C-ABI library; it raises if the library is missing.
 Beyond the reference's surface the class batches clips of different lengths (``encode_infer_many``, ``decode_many``) and
 goes straight between PCM and codes: ``encode_codes`` / ``encode_codes_many`` in, ``decode_codes`` / ``decode_codes_many`` and
-``decode_pcm`` / ``decode_pcm_many`` (any rate, mono or stereo, fp32 or int16, one flat tensor) out.
+``decode_pcm`` / ``decode_pcm_many`` (any rate, mono or stereo, fp32 or int16, one flat tensor) out; recordings longer than a
+plan takes go through in overlapping segments (``encode_codes_segmented`` / ``decode_pcm_segmented``, ``wavtokenizer_amd.segmented``).
 """
 from .config import ArchConfig, ARCH_HOP600, ARCH_HOP320, NAMED_ARCHS, arch_from_yaml  # noqa: F401
 

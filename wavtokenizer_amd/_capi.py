@@ -26,7 +26,7 @@ EXPORTS = [
     "wt_linear_overlap_add", "wt_encode_mixed", "wt_plan_min_clip_length", "wt_sconv_geometry", "wt_decode_mixed",
     "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe", "wt_lstm_probe_workspace_bytes", "wt_lstm_probe",
     "wt_decode_codes", "wt_decode_codes_mixed", "wt_ingest_workspace_bytes", "wt_ingest", "wt_codes_unpack",
-    "wt_emit_workspace_bytes", "wt_emit", "wt_vq_probe",
+    "wt_emit_workspace_bytes", "wt_emit", "wt_vq_probe", "wt_overlap_add_ragged_workspace_bytes", "wt_overlap_add_ragged",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -161,6 +161,12 @@ class WtEmitClip(ctypes.Structure):
                 ("dtype", c_int32), ("channels", c_int32), ("ch_stride", c_int64), ("sample_stride", c_int64), ("limit", c_float)]
 
 
+class WtOverlapAddClip(ctypes.Structure):
+    """wt_overlap_add_clip: one recording of a ragged overlap-add launch (wt_overlap_add_ragged)."""
+    _fields_ = [("rows", c_void_p), ("n_frames", c_int64), ("frame_len", c_int64), ("stride", c_int64), ("total", c_int64),
+                ("weight", c_void_p), ("out", c_void_p)]
+
+
 class WavTokError(RuntimeError):
     def __init__(self, msg, status=0):
         super().__init__(msg)
@@ -279,6 +285,9 @@ def _load() -> ctypes.CDLL:
     lib.wt_emit_workspace_bytes.argtypes = [c_int32]
     lib.wt_emit_workspace_bytes.restype = c_size_t
     lib.wt_emit.argtypes = [POINTER(WtEmitClip), c_int32, c_void_p, c_void_p]
+    lib.wt_overlap_add_ragged_workspace_bytes.argtypes = [c_int32]
+    lib.wt_overlap_add_ragged_workspace_bytes.restype = c_size_t
+    lib.wt_overlap_add_ragged.argtypes = [POINTER(WtOverlapAddClip), c_int32, c_void_p, c_void_p]
     return lib
 
 

@@ -5,7 +5,8 @@
     linear_overlap_add(frames, stride)                   encoder/utils.py:17-56   (bit-identical)
     segment_offsets(length, segment_length, stride)      encoder/model.py:133-145 (the frame offsets of EncodecModel.encode)
 
-All take and return torch tensors on the GPU; there is no CPU fallback."""
+All take and return torch tensors on the GPU; there is no CPU fallback.  Recordings of any length, from and to PCM, with codes in
+between: WavTokenizer.encode_codes_segmented(_many) / decode_pcm_segmented(_many) (wavtokenizer_amd/segmented.py)."""
 import ctypes
 import functools
 from typing import Dict, List, Sequence, Tuple

@@ -370,6 +370,37 @@ __global__ __launch_bounds__(256) void overlap_add_kernel(const float* __restric
     out[r * total + t] = acc / sw;
 }
 
+// overlap_add_kernel over recordings of different frame counts, frame lengths, strides and lengths in one launch (wt_overlap_add_ragged):
+// grid (ceil(max total / 256), B), block (x, b) writes 256 consecutive outputs of recording b.  Frame f of a recording is the row
+// rows[f], valid up to len_f = min(frame_len, total - f * stride): every frame covering t < total holds t, so a row is never read
+// past len_f - 1.  The same frames in the same order with the same separately rounded products and sums as overlap_add_kernel, one
+// division: bit-identical to it and to the reference's loop.  The descriptor is uniform over the block; reads of a frame and the
+// writes are consecutive along t.
+__device__ __forceinline__ void overlap_add_block(const wt_overlap_add_clip& d) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= d.total) return;
+    const global_ptr<const float> w = (global_ptr<const float>)d.weight;
+    const global_ptr<const float* const> rows = (global_ptr<const float* const>)d.rows;
+    const long flen = d.frame_len, stride = d.stride, nf = d.n_frames;
+    long f = t >= flen ? (t - flen) / stride + 1 : 0;       // first frame with f * stride + flen > t
+    float acc = 0.f, sw = 0.f;
+    for (; f < nf && f * stride <= t; ++f) {
+        const long o = t - f * stride;                       // (o < flen by the choice of the first frame, f * stride + o = t < total)
+        const global_ptr<const float> row = (global_ptr<const float>)rows[f];
+        const float wo = w[o];
+        acc = __fadd_rn(acc, __fmul_rn(wo, row[o]));
+        sw = __fadd_rn(sw, wo);
+    }
+    ((global_ptr<float>)d.out)[t] = acc / sw;
+}
+
+__global__ __launch_bounds__(256) void overlap_add_ragged_kernel(const wt_overlap_add_clip* __restrict__ clips) { overlap_add_block(clips[blockIdx.y]); }
+
+// The same launch with the descriptors in the kernel's argument block (as emit_args_kernel): up to OLA_ARG_CLIPS recordings need no upload.
+constexpr int OLA_ARG_CLIPS = 64;
+struct OlaArgs { wt_overlap_add_clip clip[OLA_ARG_CLIPS]; };
+__global__ __launch_bounds__(256) void overlap_add_ragged_args_kernel(const OlaArgs a) { overlap_add_block(a.clip[blockIdx.y]); }
+
 }  // namespace wt
 
 using namespace wt;
@@ -626,6 +657,50 @@ int wt_linear_overlap_add(const float* frames, const float* weight, int32_t n_fr
     dim3 grid((unsigned)((total + 255) / 256), (unsigned)rows);
     hipLaunchKernelGGL(overlap_add_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), frames, weight, n_frames,
                        (long)rows, (long)frame_len, (long)last_len, (long)stride, total, out);
+    WT_HIP_CHECK(hipGetLastError());
+    return WT_OK;
+}
+
+size_t wt_overlap_add_ragged_workspace_bytes(int32_t B) { return B > 0 ? (size_t)B * sizeof(wt_overlap_add_clip) : 0; }
+
+int wt_overlap_add_ragged(const wt_overlap_add_clip* clips, int32_t B, void* workspace, void* stream) {
+    if (!clips || !workspace || B < 1 || B > 65535) { set_error("wt_overlap_add_ragged: bad argument"); return WT_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error("wt_overlap_add_ragged: workspace misaligned"); return WT_ERR_INVALID; }
+    int64_t max_total = 0;
+    for (int b = 0; b < B; ++b) {
+        const wt_overlap_add_clip& c = clips[b];
+        const std::string who = "wt_overlap_add_ragged: recording " + std::to_string(b) + ": ";
+        if (!c.rows) { set_error(who + "null row table"); return WT_ERR_INVALID; }
+        if (!c.weight) { set_error(who + "null weight"); return WT_ERR_INVALID; }
+        if (!c.out) { set_error(who + "null destination"); return WT_ERR_INVALID; }
+        if (c.n_frames < 1) { set_error(who + "n_frames < 1"); return WT_ERR_INVALID; }
+        if (c.total < 1) { set_error(who + "total < 1"); return WT_ERR_INVALID; }
+        if (c.frame_len < 1) { set_error(who + "frame_len < 1"); return WT_ERR_INVALID; }
+        if (c.stride < 1) { set_error(who + "stride < 1"); return WT_ERR_INVALID; }
+        if (c.n_frames != (c.total - 1) / c.stride + 1) { set_error(who + "n_frames is not ceil(total / stride)"); return WT_ERR_INVALID; }
+        if (c.stride > c.frame_len && c.n_frames > 1) { set_error(who + "stride beyond the frame length leaves uncovered samples"); return WT_ERR_INVALID; }
+        // (n_frames - 1 < total / stride: the product cannot overflow)
+        if (c.total - c.stride * (c.n_frames - 1) > c.frame_len) { set_error(who + "total beyond the last frame's end"); return WT_ERR_INVALID; }
+        if (reinterpret_cast<uintptr_t>(c.rows) % sizeof(void*) || reinterpret_cast<uintptr_t>(c.weight) % sizeof(float) ||
+            reinterpret_cast<uintptr_t>(c.out) % sizeof(float)) {
+            set_error(who + "misaligned pointer"); return WT_ERR_INVALID;
+        }
+        max_total = std::max(max_total, c.total);
+    }
+    if ((max_total + 255) / 256 > 0x7fffffffLL) { set_error("wt_overlap_add_ragged: recording too long for one launch"); return WT_ERR_INVALID; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    dim3 grid((unsigned)((max_total + 255) / 256), (unsigned)B);
+    if (B <= OLA_ARG_CLIPS) {
+        OlaArgs args{};
+        memcpy(args.clip, clips, (size_t)B * sizeof(wt_overlap_add_clip));      // (blocks read clip[blockIdx.y < B] alone)
+        hipLaunchKernelGGL(overlap_add_ragged_args_kernel, grid, dim3(256), 0, s, args);
+    } else {
+        int device = 0;
+        WT_HIP_CHECK(hipGetDevice(&device));
+        if (device < 0 || device >= 64) { set_error("wt_overlap_add_ragged: device index"); return WT_ERR_INVALID; }
+        if (int rc = stage_descriptors(device, clips, (size_t)B * sizeof(wt_overlap_add_clip), 128 * sizeof(wt_overlap_add_clip), workspace, s)) return rc;
+        hipLaunchKernelGGL(overlap_add_ragged_kernel, grid, dim3(256), 0, s, static_cast<const wt_overlap_add_clip*>(workspace));
+    }
     WT_HIP_CHECK(hipGetLastError());
     return WT_OK;
 }

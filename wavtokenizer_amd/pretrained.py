@@ -377,6 +377,9 @@ class WavTokenizer(nn.Module):
         self._pin_events: List[Any] = [None, None]
         self._pin_next = 0
         self._emit_ws: Optional[torch.Tensor] = None      # decode_pcm / decode_pcm_many: the workspace of wt_emit launches of up to 64 clips
+        # encode_codes_segmented_many: uniform batches of full segments on the mixed-length plan instead of the plain one (the same
+        # bits; tools/segmented_bench.py case (d) measures both, the plain plan is not slower)
+        self._segment_uniform_mixed = False
         for m in (feature_extractor, backbone, head):
             m._bind(self)
 
@@ -999,8 +1002,14 @@ class WavTokenizer(nn.Module):
         if not self._mixed_route_ok():          # (before anything is uploaded; checked again on every attempt below)
             return None
         B = len(specs)
-        L = self._arch.frames(T_pad)
         descs, ws, lengths, spans, _alive = self._ingest_stage(specs, offsets, dev)
+        return self._encode_ingested_mixed(descs, ws, B, T_pad, lengths, spans, flat, dev)
+
+    def _encode_ingested_mixed(self, descs, ws: torch.Tensor, B: int, T_pad: int, lengths: torch.Tensor, spans: torch.Tensor,
+                               flat: torch.Tensor, dev: torch.device):
+        """The launches of a mixed-length group whose wt_ingest descriptors, lengths (int32) and code spans (int64 {frames,
+        offset}) are on hand, the latter two on the GPU: True, or None off the mixed route."""
+        L = self._arch.frames(T_pad)
 
         def fill_wav(buf: torch.Tensor):        # (columns past a clip's length are never read)
             check(lib.wt_ingest(descs, B, T_pad, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
@@ -1038,6 +1047,35 @@ class WavTokenizer(nn.Module):
                 codes = self.encode_codes(wav[j:j + 1, :sp.n_out])
                 flat[off:off + codes.shape[-1]].copy_(codes.view(-1))
 
+    def _clip_specs(self, who: str, clips: Sequence[torch.Tensor], sample_rates, channels_last: bool) -> List["_ClipSpec"]:
+        """The clips of encode_codes_many / encode_codes_segmented_many, checked: ValueError for anything wt_ingest would refuse."""
+        from . import audio
+        clips = list(clips)
+        codec_rate = self.codec_rate
+        if sample_rates is None:
+            rates = [codec_rate] * len(clips)
+        elif isinstance(sample_rates, (int, np.integer)):
+            rates = [int(sample_rates)] * len(clips)
+        else:
+            rates = [int(r) for r in sample_rates]
+            if len(rates) != len(clips):
+                raise ValueError(who + ": one sample rate, or one per clip")
+        specs: List[_ClipSpec] = []
+        for c, sr in zip(clips, rates):
+            if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2):
+                raise ValueError(who + " takes tensors (T,), (C, T) or, with channels_last, (T, C)")
+            if c.dtype not in (torch.float32, torch.int16):
+                raise ValueError(who + " takes fp32 or int16 clips")
+            ch = 1 if c.dim() == 1 else int(c.shape[1 if channels_last else 0])
+            n_in = int(c.shape[0]) if c.dim() == 1 or channels_last else int(c.shape[1])
+            if ch not in (1, 2):
+                raise ValueError(who + ": audio must be mono or stereo")
+            if n_in < 1:
+                raise ValueError(who + ": empty clip")
+            specs.append(_ClipSpec(c, ch, n_in, bool(channels_last and c.dim() == 2), sr,
+                                   audio.resampled_length(sr, codec_rate, n_in)))       # (ValueError for a refused ratio)
+        return specs
+
     @torch.inference_mode()
     def encode_codes_many(self, clips: Sequence[torch.Tensor], sample_rates=None, channels_last: bool = False, packed: bool = False,
                           bandwidth_id=None):
@@ -1050,34 +1088,10 @@ class WavTokenizer(nn.Module):
         ingest launch, one mixed-length encode without a feature tensor, one launch that hands out the codes.  Clips under the
         mixed-length plans' minimum, and every clip while the encoder is off its shipped route, are ingested the same way and
         encoded one at a time.  Argument errors raise ValueError before any GPU work."""
-        from . import audio
         from .mixed_length import group_clips
         if bandwidth_id is not None:
             _ = self.feature_extractor.bandwidths[self._bandwidth_index(bandwidth_id)]
-        clips = list(clips)
-        codec_rate = self.codec_rate
-        if sample_rates is None:
-            rates = [codec_rate] * len(clips)
-        elif isinstance(sample_rates, (int, np.integer)):
-            rates = [int(sample_rates)] * len(clips)
-        else:
-            rates = [int(r) for r in sample_rates]
-            if len(rates) != len(clips):
-                raise ValueError("encode_codes_many: one sample rate, or one per clip")
-        specs: List[_ClipSpec] = []
-        for c, sr in zip(clips, rates):
-            if not isinstance(c, torch.Tensor) or c.dim() not in (1, 2):
-                raise ValueError("encode_codes_many takes tensors (T,), (C, T) or, with channels_last, (T, C)")
-            if c.dtype not in (torch.float32, torch.int16):
-                raise ValueError("encode_codes_many takes fp32 or int16 clips")
-            ch = 1 if c.dim() == 1 else int(c.shape[1 if channels_last else 0])
-            n_in = int(c.shape[0]) if c.dim() == 1 or channels_last else int(c.shape[1])
-            if ch not in (1, 2):
-                raise ValueError("encode_codes_many: audio must be mono or stereo")
-            if n_in < 1:
-                raise ValueError("encode_codes_many: empty clip")
-            specs.append(_ClipSpec(c, ch, n_in, bool(channels_last and c.dim() == 2), sr,
-                                   audio.resampled_length(sr, codec_rate, n_in)))       # (ValueError for a refused ratio)
+        specs = self._clip_specs("encode_codes_many", clips, sample_rates, channels_last)
         offsets = [0]
         frames = self._arch.frames
         for sp in specs:
@@ -1093,6 +1107,155 @@ class WavTokenizer(nn.Module):
         if packed:
             return flat, torch.tensor(offsets, dtype=torch.int64)
         return [flat[offsets[i]:offsets[i + 1]].view(1, 1, -1) for i in range(len(specs))]
+
+    # -- long recordings in overlapping segments (segmented.py): tokenise ---------------------------------------------------------
+    def _upload_tables(self, tables: Sequence[torch.Tensor], dev: torch.device) -> List[torch.Tensor]:
+        """Small host tensors (lengths, code spans, row pointers, weights) through one pinned buffer and ONE copy: their device twins."""
+        up = lambda n: -(-n // 16) * 16
+        where, pos = [], 0
+        for t in tables:
+            where.append(pos)
+            pos = up(pos + t.numel() * t.element_size())
+        if not pos:
+            return [torch.empty(0, dtype=t.dtype, device=dev) for t in tables]
+        slot, pin = self._pinned(pos)
+        for t, o in zip(tables, where):
+            pin[o:o + t.numel() * t.element_size()].view(t.dtype).copy_(t.reshape(-1))
+        blob = torch.empty(pos, dtype=torch.uint8, device=dev)
+        blob.copy_(pin[:pos], non_blocking=True)
+        ev = self._pin_events[slot] = self._pin_events[slot] or torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        return [blob[o:o + t.numel() * t.element_size()].view(t.dtype).view(t.shape) for t, o in zip(tables, where)]
+
+    def _encode_ingested_uniform(self, descs, ws: torch.Tensor, B: int, T: int, spans: torch.Tensor, flat: torch.Tensor, dev: torch.device):
+        """One batch of B segments of one length T on the plain encode plan (encode_codes' own: same recording, same staging
+        buffers), filled by one wt_ingest: True, or None when the encoder is off its shipped route (the segments then run one
+        at a time, like a mixed-length group's)."""
+        L = self._arch.frames(T)
+
+        def fill_wav(buf: torch.Tensor):
+            check(lib.wt_ingest(descs, B, T, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
+
+        ins = (((B, T), torch.float32, fill_wav),)
+        outs = (((B, 512, L), torch.float32, False), ((1, B, L), torch.int64, True), ((B, 512, L), torch.float32, False))
+
+        def call():
+            if not self._mixed_route_ok():
+                raise _OffRoute()
+            return self._call(lib.wt_encode, _capi.WT_PLAN_ENCODE, B, T, self._graph_flags(B), dev, ins, outs, name="wt_encode")
+
+        try:
+            codes = self._guarded(dev, call, self._is_strict(B))[1]
+        except _OffRoute:
+            return None
+        check(lib.wt_codes_unpack(_ptr(codes), B, L, _ptr(spans), _ptr(flat), flat.numel(), _stream_ptr(dev)), "wt_codes_unpack")
+        return True
+
+    @torch.inference_mode()
+    def encode_codes_segmented_many(self, clips: Sequence[torch.Tensor], segment_length: int, stride: int, sample_rates=None,
+                                    channels_last: bool = False, bandwidth_id=None):
+        """Tokenise long recordings in overlapping segments (the reference's EncodecModel.encode, encoder/model.py:122-145).
+        clips and sample_rates as encode_codes_many takes them (any rate, mono or stereo, planar or interleaved, fp32 or int16,
+        on the CPU or on the model's device); segment_length and stride are samples at the codec rate, stride <= segment_length.
+        Returns one segmented.SegmentedCodes per recording, all views of one flat int64 tensor.
+        With W = audio.convert_audio(clip as planar fp32, rate, 24000, 1)[0] and (offsets, lengths) = segmented.segment_plan(
+        len(W), segment_length, stride), segment i's codes are the bits of encode_codes(W[None, off_i:off_i + len_i]), whatever
+        the other recordings, their order and the grouping: the recording is resampled first and cut second.  Near a cut the
+        codes differ from the whole recording's by construction.
+        Per <= 64 recordings one upload of the CPU clips and one ragged ingest launch write every W into one buffer; the segments
+        are then wt_ingest descriptors at equal rates into W (no copy per segment): full segments fill uniform calls of up to 64
+        on the plain encode plan, the short tails of all recordings share mixed-length groups (mixed_length.group_clips), each
+        call one ingest launch, one encode without a feature tensor and one launch that hands out the codes.  Tails under the
+        mixed-length plans' minimum, and every segment while the encoder is off its shipped route, are encoded one at a time.
+        Status, fallbacks, strict mode and graphs behave as in encode_codes_many.  Argument errors (segmented.segment_plan's, a
+        segment beyond 12 000 frames, an ISTFT head with padding="center") raise ValueError before any GPU work."""
+        from . import audio
+        from .mixed_length import MAX_GROUP, group_clips
+        from .segmented import SegmentedCodes, check_geometry, segment_plan
+        who = "encode_codes_segmented_many"
+        if bandwidth_id is not None:
+            _ = self.feature_extractor.bandwidths[self._bandwidth_index(bandwidth_id)]
+        segment_plan(1, segment_length, stride)                 # (the geometry's own refusals, also for an empty list)
+        specs = self._clip_specs(who, clips, sample_rates, channels_last)
+        S, stride = int(segment_length), int(stride)
+        seg_rec: List[int] = []                                  # per segment: recording, offset in W, samples, offset in flat
+        seg_off: List[int] = []
+        seg_len: List[int] = []
+        seg_code: List[int] = []
+        bounds = [0]                                             # per recording: its first segment's offset in flat
+        rec_offsets: List[List[int]] = []
+        for r, sp in enumerate(specs):
+            offs, lens, frs = check_geometry(self._arch, sp.n_out, S, stride)
+            pos = [bounds[-1]]
+            for L in frs:
+                pos.append(pos[-1] + L)
+            seg_rec += [r] * len(offs)
+            seg_off += offs
+            seg_len += lens
+            seg_code += pos[:-1]
+            rec_offsets.append([v - pos[0] for v in pos])
+            bounds.append(pos[-1])
+        if not specs:
+            return []
+        dev = self._ensure_engine()
+        flat = torch.empty(bounds[-1], dtype=torch.int64, device=dev)
+        # every recording at the codec rate: W of recording r is row where[r][1] of the buffer where[r][0]
+        where: List[Tuple[torch.Tensor, int]] = []
+        c0 = 0
+        while c0 < len(specs):
+            c1, T_pad = c0, 0
+            while c1 < len(specs) and c1 - c0 < MAX_GROUP and (c1 == c0 or (c1 - c0 + 1) * max(T_pad, specs[c1].n_out) <= 1 << 28):
+                T_pad = max(T_pad, specs[c1].n_out)
+                c1 += 1
+            part = specs[c0:c1]
+            descs, ws, _lengths, _spans, _alive = self._ingest_stage(part, [0] * len(part), dev)
+            W = torch.empty((len(part), T_pad), dtype=torch.float32, device=dev)
+            check(lib.wt_ingest(descs, len(part), T_pad, _ptr(W), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
+            where += [(W, j) for j in range(len(part))]
+            c0 = c1
+        frames = self._arch.frames
+        on_route = self._mixed_route_ok()
+        full = [k for k in range(len(seg_len)) if seg_len[k] == S] if on_route else []
+        tails = [k for k in range(len(seg_len)) if seg_len[k] != S] if on_route else []
+        groups, short = group_clips([seg_len[k] for k in tails], self._arch.hop)
+        solo = [tails[i] for i in short] if on_route else list(range(len(seg_len)))
+        # the calls: (padded length or 0 for a uniform batch, segments)
+        calls = [(0, full[i:i + MAX_GROUP]) for i in range(0, len(full), MAX_GROUP)] + [(T_pad, [tails[i] for i in idx]) for T_pad, idx in groups]
+        tables = []
+        for _T, ks in calls:
+            tables.append(torch.tensor([seg_len[k] for k in ks], dtype=torch.int32))
+            tables.append(torch.tensor([v for k in ks for v in (frames(seg_len[k]), seg_code[k])], dtype=torch.int64))
+        on_gpu = self._upload_tables(tables, dev)
+        same = audio.resampler(self.codec_rate, self.codec_rate, dev.index)
+        mixed_uniform = self._segment_uniform_mixed
+        for n, (T_pad, ks) in enumerate(calls):
+            B = len(ks)
+            descs = (_capi.WtIngestClip * B)()
+            for d, k in zip(descs, ks):
+                W, j = where[seg_rec[k]]
+                d.src = W.data_ptr() + 4 * (j * W.shape[1] + seg_off[k])
+                d.dtype, d.channels, d.n_in, d.n_out = _capi.WT_INGEST_F32, 1, seg_len[k], seg_len[k]
+                d.ch_stride, d.sample_stride, d.resampler = 0, 1, same
+            ws = torch.empty(max(int(lib.wt_ingest_workspace_bytes(B)), 8), dtype=torch.uint8, device=dev)
+            lengths, spans = on_gpu[2 * n], on_gpu[2 * n + 1]
+            if T_pad == 0 and not mixed_uniform:
+                done = self._encode_ingested_uniform(descs, ws, B, S, spans, flat, dev)
+            else:
+                done = self._encode_ingested_mixed(descs, ws, B, T_pad or S, lengths, spans, flat, dev)
+            if not done:
+                solo.extend(ks)
+        for k in sorted(solo):
+            W, j = where[seg_rec[k]]
+            codes = self.encode_codes(W[j:j + 1, seg_off[k]:seg_off[k] + seg_len[k]])
+            flat[seg_code[k]:seg_code[k] + codes.shape[-1]].copy_(codes.view(-1))
+        return [SegmentedCodes(flat[bounds[r]:bounds[r + 1]], rec_offsets[r], sp.n_out, S, stride) for r, sp in enumerate(specs)]
+
+    @torch.inference_mode()
+    def encode_codes_segmented(self, clip: torch.Tensor, segment_length: int, stride: int, sample_rate: Optional[int] = None,
+                               channels_last: bool = False, bandwidth_id=None):
+        """encode_codes_segmented_many for one recording: its segmented.SegmentedCodes."""
+        return self.encode_codes_segmented_many([clip], segment_length, stride, sample_rates=sample_rate, channels_last=channels_last,
+                                                bandwidth_id=bandwidth_id)[0]
 
     def _bandwidth_index(self, bandwidth_id) -> int:
         if bandwidth_id is None:
@@ -1466,19 +1629,7 @@ class WavTokenizer(nn.Module):
         chans, fmt = self._emit_format(who, channels, dtype, limit, len(clips))
         channels_last = bool(channels_last)
         codec_rate = self.codec_rate
-        if sample_rates is None:
-            rates = [codec_rate] * len(clips)
-        elif isinstance(sample_rates, (int, np.integer)):
-            rates = [int(sample_rates)] * len(clips)
-        else:
-            rates = [int(r) for r in sample_rates]
-            if len(rates) != len(clips):
-                raise ValueError(who + ": one sample rate, or one per clip")
-        to_host = device is not None and torch.device(device).type == "cpu"
-        if device is not None and not to_host:
-            want, own = torch.device(device), self._device()
-            if want.type != own.type or (want.index is not None and want.index != (own.index if own.index is not None else 0)):
-                raise ValueError(who + ": device is None, the model's own device or 'cpu'")
+        rates, to_host = self._pcm_rates_device(who, len(clips), sample_rates, device)
         specs: List[_PcmSpec] = []
         offsets = [0]
         for c, sr, ch in zip(clips, rates, chans):
@@ -1499,6 +1650,29 @@ class WavTokenizer(nn.Module):
         if solo:
             solo = sorted(solo)
             self._decode_pcm_solo([specs[i] for i in solo], bw, flat, [offsets[i] for i in solo], fmt, channels_last)
+        return self._pcm_result(flat, offsets, specs, packed, to_host, channels_last)
+
+    def _pcm_rates_device(self, who: str, n: int, sample_rates, device) -> Tuple[List[int], bool]:
+        """(rate per clip, whether the result goes to the host) of decode_pcm_many / decode_pcm_segmented_many, checked."""
+        if sample_rates is None:
+            rates = [self.codec_rate] * n
+        elif isinstance(sample_rates, (int, np.integer)):
+            rates = [int(sample_rates)] * n
+        else:
+            rates = [int(r) for r in sample_rates]
+            if len(rates) != n:
+                raise ValueError(who + ": one sample rate, or one per clip")
+        to_host = device is not None and torch.device(device).type == "cpu"
+        if device is not None and not to_host:
+            want, own = torch.device(device), self._device()
+            if want.type != own.type or (want.index is not None and want.index != (own.index if own.index is not None else 0)):
+                raise ValueError(who + ": device is None, the model's own device or 'cpu'")
+        return rates, to_host
+
+    @staticmethod
+    def _pcm_result(flat: torch.Tensor, offsets: Sequence[int], specs: Sequence["_PcmSpec"], packed: bool, to_host: bool, channels_last: bool):
+        """What decode_pcm_many and decode_pcm_segmented_many return: the flat tensor (to_host: through ONE copy into pinned memory
+        and one stream wait) with its offsets, or the clips' views of it."""
         if to_host:
             host = torch.empty(flat.shape, dtype=flat.dtype, pin_memory=True)
             if flat.numel():
@@ -1509,6 +1683,146 @@ class WavTokenizer(nn.Module):
             return flat, torch.tensor(offsets, dtype=torch.int64)
         return [flat[offsets[i]:offsets[i + 1]].view((sp.n_out, sp.channels) if channels_last else (sp.channels, sp.n_out))
                 for i, sp in enumerate(specs)]
+
+    # -- long recordings in overlapping segments (segmented.py): synthesise -------------------------------------------------------
+    @torch.inference_mode()
+    def decode_pcm_segmented_many(self, segs, sample_rates=None, channels=1, dtype: torch.dtype = torch.int16, channels_last: bool = False,
+                                  limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None):
+        """Synthesise long recordings from their segments' codes (the reference's EncodecModel.decode, encoder/model.py:167-178):
+        segs[r] is a segmented.SegmentedCodes, from encode_codes_segmented(_many) or built by hand; the other arguments and the
+        forms of the result (views of one flat tensor, packed=True, device="cpu" into pinned memory with one copy and one wait)
+        are decode_pcm_many's, with n_out_r = ceil(rate_r * length_r / 24000).
+        With X = audio.linear_overlap_add([decode_codes(c_i)[..., :len_i] for i], stride)[..., :length] over recording r's
+        segments, every channel of the result is the bits of audio.convert_audio(X[:, None], 24000, rate_r, 1) (fp32) or of
+        audio.to_pcm16(that, limit=limit) (int16), whatever the other recordings and the grouping.
+        All segments of all recordings are decoded in groups: segments of a full segment's frame count in decode_codes batches of
+        up to 64 (fewer where the attention score cells say so), the tails through decode_codes_many's grouping; then, per <= 64
+        recordings, one ragged overlap-add launch (wt_overlap_add_ragged) reads the decoded rows where those calls left them,
+        through a device table of row pointers, into one 24 kHz row per recording, and one wt_emit converts those rows.  The
+        decoded segments stay allocated until the overlap-add is enqueued: about length * segment_length / stride floats per
+        recording, plus one 24 kHz row each.  set_gemm_precision("f16"), set_check_codes and the fallbacks apply as to
+        decode_codes (under "sync" there is one wait behind the last uniform batch, not one per batch).  Argument errors
+        (SegmentedCodes.validate's among them: offsets or length that contradict segment_plan, padding="center") raise
+        ValueError before any GPU work."""
+        from . import audio
+        from .mixed_length import MAX_GROUP, MAX_SCORE_CELLS, group_frames, score_cells
+        from .segmented import SegmentedCodes
+        who = "decode_pcm_segmented_many"
+        bw = self._bandwidth_index(bandwidth_id)
+        segs = list(segs)
+        if any(not isinstance(sc, SegmentedCodes) for sc in segs):
+            raise ValueError(who + " takes a sequence of segmented.SegmentedCodes")
+        geo = [sc.validate(self._arch) for sc in segs]
+        chans, fmt = self._emit_format(who, channels, dtype, limit, len(segs))
+        channels_last = bool(channels_last)
+        rates, to_host = self._pcm_rates_device(who, len(segs), sample_rates, device)
+        specs: List[_PcmSpec] = []
+        offsets = [0]
+        for sc, sr, ch in zip(segs, rates, chans):
+            n_out = audio.resampled_length(self.codec_rate, sr, sc.length)                  # (ValueError for a refused ratio)
+            specs.append(_PcmSpec(None, int(sc.offsets[-1]), sr, sc.length, n_out, ch))
+            offsets.append(offsets[-1] + n_out * ch)
+        if not segs:
+            return self._pcm_result(torch.empty(0, dtype=fmt[0], device=self._device()), offsets, specs, packed, to_host, channels_last)
+        dev = self._ensure_engine()
+        flat = torch.empty(offsets[-1], dtype=fmt[0], device=dev)
+        codes = [sc.codes.to(device=dev, dtype=torch.int64).contiguous() for sc in segs]
+        # every segment of every recording: (recording, segment, first code, frames)
+        items = [(r, i, int(o), L) for r, sc in enumerate(segs) for i, (o, L) in enumerate(zip(sc.offsets.tolist(), geo[r][2]))]
+        on_route = self._decode_mixed_route_ok()
+        full_frames = {geo[r][2][0] for r, sc in enumerate(segs) if geo[r][1][0] == sc.segment_length} if on_route else set()
+        rows: List[List[Optional[torch.Tensor]]] = [[None] * sc.n_segments for sc in segs]      # (they keep the decoded batches alive)
+        solo: List[int] = [] if on_route else list(range(len(items)))
+        by_frames: Dict[int, List[int]] = {}
+        rest: List[int] = []
+        for k, (_r, _i, _o, L) in enumerate(items):
+            if L in full_frames:
+                by_frames.setdefault(L, []).append(k)
+            elif on_route:
+                rest.append(k)
+        for L, ks in by_frames.items():
+            per_call = max(1, min(MAX_GROUP, MAX_SCORE_CELLS // score_cells(1, L)))
+            for c0 in range(0, len(ks), per_call):
+                part = ks[c0:c0 + per_call]
+                B = len(part)
+                runs: List[List[int]] = []                           # consecutive segments of one recording are one slice of its codes
+                for k in part:
+                    r, _i, o, _L = items[k]
+                    if runs and runs[-1][0] == r and runs[-1][2] == o:
+                        runs[-1][2] = o + L
+                    else:
+                        runs.append([r, o, o + L])
+                pieces = [codes[r][a:b] for r, a, b in runs]
+                batch = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).view(1, B, L)
+
+                def call():
+                    if not self._decode_mixed_route_ok():
+                        raise _OffRoute()
+                    return self._decode_codes(batch, bw, self._decode_flags(self._graph_flags(B)), dev)
+
+                try:
+                    wav = self._guarded(dev, call, self._is_strict(B))[0]
+                except _OffRoute:
+                    solo.extend(part)
+                    continue
+                for j, k in enumerate(part):
+                    rows[items[k][0]][items[k][1]] = wav[j]
+        if by_frames:
+            self._codes_checked(dev)
+        seg_codes = lambda k: codes[items[k][0]][items[k][2]:items[k][2] + items[k][3]].view(1, -1)
+        for L_pad, idx in group_frames([items[k][3] for k in rest]):
+            part = [rest[i] for i in idx]
+            wav = self._run_decode_codes_mixed([seg_codes(k) for k in part], L_pad, bw, dev) if len(part) > 1 else None
+            if wav is None:
+                solo.extend(part)
+                continue
+            for j, k in enumerate(part):
+                rows[items[k][0]][items[k][1]] = wav[j]
+        for k in sorted(solo):
+            rows[items[k][0]][items[k][1]] = self.decode_codes(seg_codes(k), bandwidth_id=bw)[0]
+        # the cross-fade: one launch per <= 64 recordings from one upload of the row pointers and the triangles
+        x_off = [0]
+        for sc in segs:
+            x_off.append(x_off[-1] + -(-sc.length // 4) * 4)         # (rows start on 16 bytes: wt_emit's wide loads)
+        X = torch.empty(x_off[-1], dtype=torch.float32, device=dev)
+        flens = sorted({min(sc.segment_length, sc.length) for sc in segs})
+        tri = []
+        for flen in flens:                                           # the reference's triangle, from the same torch.linspace
+            t = torch.linspace(0, 1, flen + 2, dtype=torch.float32)[1:-1]
+            tri.append(0.5 - (t - 0.5).abs())
+        ptrs = torch.tensor([row.data_ptr() for rr in rows for row in rr], dtype=torch.int64)
+        on_gpu = self._upload_tables([ptrs] + tri, dev)
+        table, weight = on_gpu[0], dict(zip(flens, on_gpu[1:]))
+        first = [0]
+        for sc in segs:
+            first.append(first[-1] + sc.n_segments)
+        for c0 in range(0, len(segs), MAX_GROUP):
+            part = range(c0, min(c0 + MAX_GROUP, len(segs)))
+            descs = (_capi.WtOverlapAddClip * len(part))()
+            for d, r in zip(descs, part):
+                sc = segs[r]
+                flen = min(sc.segment_length, sc.length)
+                assert all(row.shape[-1] >= n for row, n in zip(rows[r], geo[r][1]))
+                d.rows = table.data_ptr() + 8 * first[r]
+                d.n_frames, d.frame_len, d.stride, d.total = sc.n_segments, flen, sc.stride, sc.length
+                d.weight, d.out = weight[flen].data_ptr(), X.data_ptr() + 4 * x_off[r]
+            ws = torch.empty(max(int(lib.wt_overlap_add_ragged_workspace_bytes(len(part))), 8), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(lib.wt_overlap_add_ragged(descs, len(part), _ptr(ws), _stream_ptr(dev)), "wt_overlap_add_ragged")
+            self._emit_rows([X[x_off[r]:x_off[r] + segs[r].length] for r in part], [specs[r] for r in part], flat,
+                            [offsets[r] for r in part], fmt, channels_last, dev)
+        return self._pcm_result(flat, offsets, specs, packed, to_host, channels_last)
+
+    @torch.inference_mode()
+    def decode_pcm_segmented(self, seg, sample_rate: Optional[int] = None, channels: int = 1, dtype: torch.dtype = torch.int16,
+                             channels_last: bool = False, limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None):
+        """decode_pcm_segmented_many for one recording: (channels, n_out) or, with channels_last, (n_out, channels); packed=True
+        returns the flat tensor and its offsets."""
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
+            raise ValueError("decode_pcm_segmented: channels must be 1 or 2")
+        out = self.decode_pcm_segmented_many([seg], sample_rates=sample_rate, channels=channels, dtype=dtype, channels_last=channels_last,
+                                             limit=limit, packed=packed, device=device, bandwidth_id=bandwidth_id)
+        return out if packed else out[0]
 
     def _run_head(self, x: torch.Tensor) -> torch.Tensor:
         dev = self._ensure_engine()

@@ -600,6 +600,58 @@ typedef struct {
 size_t wt_lstm_probe_workspace_bytes(const wt_lstm_desc* d);
 int wt_lstm_probe(const wt_model* m, const wt_lstm_desc* d, wt_lstm_form* form, void* workspace, void* stream);
 
+/* The weights as loaded: every device array of a model that a plan can read, by name, read-only.  One walk over the model
+ * (weights.cpp model_weights) lists them in a fixed order; `index` runs over [0, count).  Conv weights are "<layer>.w"
+ * [cout][k][cin] and "<layer>.b", GEMM weights "<layer>" [rows][cols]; the S32 copy of either is "<layer>.s32" and names the
+ * fp32 array it stands for in `of`.
+ *   format     0: fp32; 1: S32 (128-byte groups [32 x f16 hi | 32 x f16 lo], value = (hi + lo / 2048) * acc_scale);
+ *              2: the LSTM step kernel's f16 lane packing; 3: the persistent LSTM kernel's f16 lane packing
+ *   numel      in 4-byte words (an S32 copy has the footprint of its fp32 array; the f16 packings hold two halves per word)
+ *   acc_scale  S32: the factor that undoes the copy's power-of-two storage scale (1: stored as it is);  tap_pair  S32: the
+ *              copy holds its taps in paired order (q -> (q >> 1) + (q & 1) * stride)
+ *   lazy       1: an fp32 array that a packed image does not store and that is rebuilt from its S32 copy (lazy_scale = the
+ *              storage scale of that copy) before the first plan on fp32 operands; asking for it here rebuilds it first.
+ *              2: an fp32 array that nothing reads after the load (the tap-paired repacking of a down conv): a model made
+ *              from a packed image holds no defined values there.  0: stored
+ *   archived   1: the pointer is one that the packed image's model section writes
+ *   alloc      index of the model allocation that starts at `data`, in the order of the packed image's allocation table (-1: the
+ *              pointer is no allocation's base) */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_weight_info), set by the caller */
+    int32_t format;
+    char name[64], of[64];
+    const void* data;
+    int64_t numel;
+    int32_t ndim;
+    int32_t tap_pair;
+    int64_t dims[4];
+    float acc_scale, lazy_scale;
+    int32_t lazy, archived;
+    int32_t alloc, reserved;
+} wt_weight_info;
+int wt_model_weight_count(const wt_model* m);
+int wt_model_weight_info(const wt_model* m, int32_t index, wt_weight_info* out);
+
+/* The format converters under every S32 operand, through the launchers the plans and the loader call, on caller-owned arrays:
+ *   op 0  fp32 x[n] -> S32 out (n words), the values multiplied by scale[0] first when `scale` (device) is given
+ *   op 1  S32 x (n words) -> fp32 out[n] = (hi + lo / 2048) * inv_scale
+ *   op 2  the per-tensor power-of-two scales of the single-stage entry points: bits[0], bits[1] = bit patterns of max |x|, max |b|
+ *         over x[n], b[nb]; out[0], out[1] = the scales, out[2] = 1 / (out[0] * out[1])
+ * n is a multiple of 32 for ops 0 and 1.  status: optional device word that op 0 ORs WT_STATUS_BIT_RANGE into when a value it
+ * converts is beyond the f16 range.  Arrays are 4-byte aligned, device memory; nothing else is touched. */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_split_desc) */
+    int32_t op;
+    int64_t n, nb;
+    const void *x, *b;
+    void* out;
+    const float* scale;
+    uint32_t* bits;
+    float inv_scale;
+    uint32_t* status;
+} wt_split_desc;
+int wt_split_probe(const wt_split_desc* d, void* stream);
+
 /* After wt_codes_to_features, wt_decode_codes or wt_decode_codes_mixed has completed on its stream: 1 if a call since the last
  * query met a code outside [0, bins) (the frames it touched were written as NaN), else 0; the flag is cleared. */
 int wt_model_take_bad_codes(const wt_model* m);

@@ -15,18 +15,22 @@ def act_hi(x):
 
 
 def s32_weight_scale(amax):
-    """weights.cpp s32_weight_scale: 1 for a maximum inside [2^-6, 2^12) (or zero), else the power of two that brings it into [1, 2)."""
+    """weights.cpp s32_weight_scale: 1 for a maximum inside [2^-6, 2^12) (or zero); a maximum below the window is brought into
+    [1, 2), one above it into the window's top binade [2^11, 2^12); 0 where that power or its reciprocal is no normal fp32 (a
+    maximum below 2^-126) or the maximum is not finite: the tensor is not split."""
     amax = float(np.float32(amax))
     if not amax > 0.0 or 2.0 ** -6 <= amax < 2.0 ** 12:
         return 1.0
+    if not amax >= 2.0 ** -126 or not math.isfinite(amax):
+        return 0.0
     _m, e = math.frexp(amax)
-    return math.ldexp(1.0, 1 - e)
+    return math.ldexp(1.0, (1 if amax < 1.0 else 12) - e)
 
 
 def weight_hi(w):
     """Hi half of a weight tensor as the library stores it: f16(w s) / s with the per-tensor power of two s.  -> float64"""
     w32 = w.to(torch.float32)
-    s = s32_weight_scale(float(w32.abs().max())) if w32.numel() else 1.0
+    s = (s32_weight_scale(float(w32.abs().max())) if w32.numel() else 1.0) or 1.0        # 0: not split, stored as it is (add_s32)
     return (w32 * s).to(torch.float16).to(torch.float64) / s
 
 

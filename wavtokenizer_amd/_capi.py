@@ -27,6 +27,7 @@ EXPORTS = [
     "wt_resblock_probe", "wt_geometry_words", "wt_geometry_probe", "wt_lstm_probe_workspace_bytes", "wt_lstm_probe",
     "wt_decode_codes", "wt_decode_codes_mixed", "wt_ingest_workspace_bytes", "wt_ingest", "wt_codes_unpack",
     "wt_emit_workspace_bytes", "wt_emit", "wt_vq_probe", "wt_overlap_add_ragged_workspace_bytes", "wt_overlap_add_ragged",
+    "wt_model_weight_count", "wt_model_weight_info", "wt_split_probe",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -167,6 +168,23 @@ class WtOverlapAddClip(ctypes.Structure):
                 ("weight", c_void_p), ("out", c_void_p)]
 
 
+WT_WEIGHT_F32, WT_WEIGHT_S32, WT_WEIGHT_LSTM_F16, WT_WEIGHT_LSTM_PERSIST = 0, 1, 2, 3
+WT_SPLIT, WT_UNSPLIT, WT_POW2_SCALES = 0, 1, 2
+
+
+class WtWeightInfo(ctypes.Structure):
+    """wt_weight_info: one device array of a model as loaded (wt_model_weight_info)."""
+    _fields_ = [("size", c_int32), ("format", c_int32), ("name", ctypes.c_char * 64), ("of", ctypes.c_char * 64), ("data", c_void_p),
+                ("numel", c_int64), ("ndim", c_int32), ("tap_pair", c_int32), ("dims", c_int64 * 4), ("acc_scale", c_float),
+                ("lazy_scale", c_float), ("lazy", c_int32), ("archived", c_int32), ("alloc", c_int32), ("reserved", c_int32)]
+
+
+class WtSplitDesc(ctypes.Structure):
+    """wt_split_desc: one launch of a format converter under the S32 operands (wt_split_probe)."""
+    _fields_ = [("size", c_int32), ("op", c_int32), ("n", c_int64), ("nb", c_int64), ("x", c_void_p), ("b", c_void_p),
+                ("out", c_void_p), ("scale", c_void_p), ("bits", c_void_p), ("inv_scale", c_float), ("status", c_void_p)]
+
+
 class WavTokError(RuntimeError):
     def __init__(self, msg, status=0):
         super().__init__(msg)
@@ -288,6 +306,9 @@ def _load() -> ctypes.CDLL:
     lib.wt_overlap_add_ragged_workspace_bytes.argtypes = [c_int32]
     lib.wt_overlap_add_ragged_workspace_bytes.restype = c_size_t
     lib.wt_overlap_add_ragged.argtypes = [POINTER(WtOverlapAddClip), c_int32, c_void_p, c_void_p]
+    lib.wt_model_weight_count.argtypes = [c_void_p]
+    lib.wt_model_weight_info.argtypes = [c_void_p, c_int32, POINTER(WtWeightInfo)]
+    lib.wt_split_probe.argtypes = [POINTER(WtSplitDesc), c_void_p]
     return lib
 
 

@@ -50,6 +50,7 @@ static int alloc_model_words(wt_model* M, const char* who) {
 }
 static void free_model(wt_model* m) {
     for (void* p : m->allocs) (void)hipFree(p);
+    for (void* p : m->load_tmp) (void)hipFree(p);
     if (m->bad_codes_host) (void)hipHostFree(m->bad_codes_host);
 }
 
@@ -169,6 +170,28 @@ int wt_device_info(int32_t device, int32_t* compute_units, int32_t* is_gfx950, i
     if (compute_units) *compute_units = prop.multiProcessorCount;
     if (is_gfx950) *is_gfx950 = strncmp(prop.gcnArchName, "gfx950", 6) == 0 ? 1 : 0;
     if (persistent_lstm) *persistent_lstm = full_chip(device) ? 1 : 0;
+    return WT_OK;
+}
+int wt_model_weight_count(const wt_model* m) { return m ? (int)model_weights(m).size() : 0; }
+int wt_model_weight_info(const wt_model* m, int32_t index, wt_weight_info* out) {
+    if (!m || !out || out->size != (int32_t)sizeof(wt_weight_info)) { set_error("wt_model_weight_info: null argument or a descriptor of another size"); return WT_ERR_INVALID; }
+    const std::vector<WeightEntry> all = model_weights(m);
+    if (index < 0 || index >= (int)all.size()) { set_error("wt_model_weight_info: index out of range"); return WT_ERR_INVALID; }
+    const WeightEntry& e = all[index];
+    if (e.lazy == 1 && m->f32_stale.load()) {       // a packed model holds nothing there yet
+        DeviceGuard dg(m->device);
+        if (!dg.ok) { set_error("hipSetDevice failed"); return WT_ERR_HIP; }
+        if (int rc = ensure_f32_weights(m)) return rc;
+    }
+    wt_weight_info w{};
+    w.size = (int32_t)sizeof(wt_weight_info);
+    w.format = e.format;
+    std::strncpy(w.name, e.name.c_str(), sizeof(w.name) - 1);
+    std::strncpy(w.of, e.of.c_str(), sizeof(w.of) - 1);
+    w.data = e.data; w.numel = e.numel; w.ndim = e.ndim; w.tap_pair = e.tap_pair ? 1 : 0;
+    for (int i = 0; i < 4; ++i) w.dims[i] = e.dims[i];
+    w.acc_scale = e.acc_scale; w.lazy_scale = e.lazy_scale; w.lazy = e.lazy; w.archived = e.archived ? 1 : 0; w.alloc = e.alloc;
+    *out = w;
     return WT_OK;
 }
 int wt_model_hop(const wt_model* m) { return m ? m->hop : 0; }

@@ -79,6 +79,7 @@ struct wt_model {
     std::vector<int> enc_ratios;
     std::vector<void*> allocs;
     std::vector<size_t> alloc_bytes;     // size of each allocation (the packed image stores them in this order)
+    std::vector<void*> load_tmp;         // device words that only the load itself reads (add_s32's scales): freed when build_splits ends
     int64_t weight_bytes = 0;
     // encoder
     float *e0_w = nullptr, *e0_b = nullptr;   // [7][32], [32]
@@ -339,7 +340,8 @@ namespace wt {
 int build_model(wt_model* M, TensorMap& tm);
 int build_splits(wt_model* M);
 // the power of two a weight whose largest |value| is amax is multiplied by in its S32 copy (1: stored as it is); the GEMMs that
-// read the copy take acc_scale = 1 / this
+// read the copy take acc_scale = 1 / this.  0: no power of two does (amax below 2^-126: the scale or its reciprocal would not be
+// a normal float), the tensor cannot be split
 float s32_weight_scale(float amax);
 // packed image of a model (weights.cpp): everything wt_model_create computes and uploads, ready to upload again
 size_t model_export_bytes(const wt_model* M);
@@ -347,6 +349,23 @@ int model_export(const wt_model* M, void* buf, size_t n);
 int model_import(wt_model* M, const void* buf, size_t n);        // M->device set; allocates and uploads
 int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint64_t* arch_hash);
 int ensure_f32_weights(const wt_model* M);                        // fills the lazy fp32 arrays of a packed model (first fp32 plan)
+// every device array of the model that a plan can read, by name (wt_model_weight_info): the one walk over the model's weights
+enum : int { WFMT_F32 = 0, WFMT_S32 = 1, WFMT_LSTM_F16 = 2, WFMT_LSTM_PERSIST = 3 };
+struct WeightEntry {
+    std::string name, of;          // of: the fp32 array an S32 copy stands for
+    const void* data = nullptr;
+    int64_t numel = 0;             // 4-byte words
+    int ndim = 0;
+    int64_t dims[4] = {0, 0, 0, 0};
+    int format = WFMT_F32;
+    float acc_scale = 1.f;
+    bool tap_pair = false;
+    int lazy = 0;                  // 1: rebuilt from the S32 copy (wt_model::lazy_f32), 2: nothing reads it after the load
+    float lazy_scale = 1.f;
+    bool archived = false;         // archive_model writes this pointer
+    int alloc = -1;                // index of the model allocation that starts at data (-1: none does)
+};
+std::vector<WeightEntry> model_weights(const wt_model* M);
 size_t packed_bytes(const void* buf, size_t n);                  // exact length of the image at buf (0: bad header)
 int packed_verify(const void* buf, size_t n);                    // header + bounds + content hash; needs no GPU
 // capi.cpp: the device is a whole MI355X (256 CUs: the persistent LSTM's one resident workgroup per CU, 32 per XCD)

@@ -165,6 +165,7 @@ int wt_gemm_probe(const wt_gemm_desc* d, wt_launch_form* form, void* workspace, 
                         amax = std::max(amax, v);
                     }
             scale = s32_weight_scale(amax);
+            if (scale == 0.f) { set_error("wt_gemm_probe: a weight whose maximum lies below 2^-126 has no S32 copy"); return WT_ERR_INVALID; }
             uint32_t bits;
             memcpy(&bits, &scale, 4);
             if (int rc = launch_fill_u32(scale_dev, bits, 16, s)) return rc;
@@ -556,6 +557,28 @@ int wt_lstm_probe(const wt_model* m, const wt_lstm_desc* d, wt_lstm_form* form, 
     if (rc) return rc;
     if (form) *form = wt_lstm_form{lf.kernel, lf.small, lf.Bx, (int32_t)lf.grid[0], (int32_t)lf.grid[1], (int32_t)lf.block, (int32_t)lf.lds, lf.launches};
     return WT_OK;
+}
+
+// wt_split_probe: launch_split_s32, launch_unsplit_s32 and launch_pow2_scales on the caller's arrays, as add_s32,
+// ensure_f32_weights and split_pair call them
+int wt_split_probe(const wt_split_desc* d, void* stream) {
+    auto bad = [](const char* msg) { set_error(std::string("wt_split_probe: ") + msg); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_split_desc)) return bad("descriptor missing or of another size");
+    if (d->op < 0 || d->op > 2) return bad("op is 0 (split), 1 (unsplit) or 2 (power-of-two scales)");
+    if (!d->x || !d->out || d->n < 1) return bad("x, out and n >= 1 are required");
+    if (d->op != 2 && (d->n % 32)) return bad("the element count must be a multiple of 32");
+    if (d->op == 2 && (!d->b || !d->bits || d->nb < 1)) return bad("op 2 needs b, nb >= 1 and bits");
+    const void* p4[] = {d->x, d->b, d->out, d->scale, d->bits, d->status};
+    for (const void* p : p4) if (reinterpret_cast<uintptr_t>(p) & 3) return bad("arrays must be 4-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const LaunchCtx saved = g_launch;
+    g_launch.status = reinterpret_cast<unsigned*>(d->status);
+    int rc;
+    if (d->op == 0) rc = launch_split_s32(static_cast<const float*>(d->x), d->out, (long)d->n, s, d->scale);
+    else if (d->op == 1) rc = launch_unsplit_s32(d->x, static_cast<float*>(d->out), (long)d->n, d->inv_scale, s);
+    else rc = launch_pow2_scales(static_cast<const float*>(d->x), (long)d->n, static_cast<const float*>(d->b), (long)d->nb, d->bits, static_cast<float*>(d->out), s);
+    g_launch = saved;
+    return rc;
 }
 
 }  // extern "C"

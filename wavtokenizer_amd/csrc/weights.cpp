@@ -435,14 +435,24 @@ int build_model(wt_model* M, TensorMap& tm) {
 
 // S32 copy of a GEMM weight.  hi = f16(w) covers |w| < 65504 with fp32-equivalent products only while the tensor's
 // largest magnitude is not far from 1 (x = hi + lo * 2^-11 has an absolute floor of 2^-36), so a tensor whose maximum
-// lies outside [2^-6, 2^12] is stored as w * 2^e (maximum brought into [1, 2)) and its GEMMs multiply their
-// accumulators by 2^-e (GemmArgs::acc_scale; powers of two: exact).  A non-finite weight cannot be split at all:
-// the model then runs on the fp32 MFMA chain (wt_model::s32_ok).  The copy goes into *out, the record of the weight.
+// lies outside [2^-6, 2^12) is stored as w * 2^e and its GEMMs multiply their accumulators by 2^-e (GemmArgs::acc_scale;
+// powers of two: exact).  A maximum below the window is brought into [1, 2).  A maximum above it is brought into the
+// window's top binade [2^11, 2^12), no further down: the floor is absolute, so every binade the maximum is lowered by costs
+// the tensor's small elements a bit (one outlier of 2^13 over weights near 0.02, brought into [1, 2), left those 17 of their
+// 22 bits: the decoder's error against float64 rose from 1.3 to 6.4 times the fp32 reference's).  A non-finite weight cannot
+// be split at all: the model then runs on the fp32 MFMA chain (wt_model::s32_ok).  The copy goes into *out, the record of
+// the weight.
+// Both the scale (what the split kernel multiplies by) and its reciprocal (what the GEMMs multiply their accumulators by)
+// have to be normal floats.  Above the window 2^(12 - e) and 2^(e - 12) are, up to the largest float.  Below it 2^(1 - e) is
+// one from 2^-127 on and its reciprocal from 2^-126 on: under 2^-127 ldexp overflows to inf (and 1 / inf = 0: a copy of inf
+// and NaN behind acc_scale 0), in [2^-127, 2^-126) acc_scale is the subnormal 2^-127.  Such a tensor is not split either
+// (return 0; add_s32 clears s32_ok).
 float s32_weight_scale(float amax) {
     if (!(amax > 0.f) || (amax >= 0x1p-6f && amax < 0x1p12f)) return 1.f;
+    if (!(amax >= 0x1p-126f) || !std::isfinite(amax)) return 0.f;
     int e = 0;
     (void)std::frexp(amax, &e);                 // amax = m * 2^e, m in [0.5, 1)
-    return std::ldexp(1.f, 1 - e);              // amax * scale in [1, 2)
+    return std::ldexp(1.f, (amax < 1.f ? 1 : 12) - e);      // amax * scale in [1, 2), or in [2^11, 2^12)
 }
 static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* split_ok = nullptr, bool gemm_only = false) {
     if (!w || n <= 0 || (n % 32)) return 0;
@@ -458,10 +468,15 @@ static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* spli
     }
     if (!finite) *split_ok = false;
     M->w_amax = std::max(M->w_amax, amax);
-    const float scale = finite ? s32_weight_scale(amax) : 1.f;
+    float scale = finite ? s32_weight_scale(amax) : 1.f;
+    if (scale == 0.f) { *split_ok = false; finite = false; scale = 1.f; }     // no usable power of two: as a non-finite weight
+    // the scale is read by the split below only: a word of its own until build_splits has waited for the splits (load_tmp, which
+    // free_model releases too), not a model allocation
     float* scale_dev = nullptr;
     if (scale != 1.f) {
-        if (int rc = upload(M, std::vector<float>{scale}, &scale_dev)) return rc;
+        WT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scale_dev), 16));
+        M->load_tmp.push_back(scale_dev);
+        WT_HIP_CHECK(hipMemcpy(scale_dev, &scale, sizeof(float), hipMemcpyHostToDevice));
         out->acc_scale = 1.f / scale;
     }
     void* d = nullptr;
@@ -471,7 +486,8 @@ static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* spli
     M->weight_bytes += n * 4;
     if (int rc = launch_split_s32(w, d, n, nullptr, scale_dev)) return rc;
     out->p = d;
-    // gemm_only: nothing but a GEMM reads this fp32 array, and the default plans multiply by the S32 copy (wt_model::lazy_f32)
+    // gemm_only: nothing but a GEMM reads this fp32 array, and the default plans multiply by the S32 copy (wt_model::lazy_f32);
+    // an array whose copy is unusable stays stored
     if (gemm_only && finite) M->lazy_f32.push_back({w, d, (int64_t)n, scale});
     return 0;
 }
@@ -539,6 +555,8 @@ int build_splits(wt_model* M) {
         }
     }
     WT_HIP_CHECK(hipDeviceSynchronize());
+    for (void* p : M->load_tmp) (void)hipFree(p);       // the splits have read their scales
+    M->load_tmp.clear();
     return 0;
 }
 
@@ -569,6 +587,7 @@ struct Archive {
     const std::map<const void*, int>* index = nullptr;      // saving: allocation base -> index
     const std::vector<void*>* allocs = nullptr;             // loading: index -> allocation base
     const std::vector<size_t>* alloc_bytes = nullptr;       // loading: index -> allocation size (pointer offsets are checked)
+    std::vector<const void*>* seen = nullptr;               // saving: every pointer written (model_weights compares its walk with it)
     void raw(void* p, size_t bytes) {
         if (saving) { const char* c = static_cast<const char*>(p); out->insert(out->end(), c, c + bytes); }
         else { if (!ok || bytes > n - pos) { ok = false; std::memset(p, 0, bytes); return; } std::memcpy(p, in + pos, bytes); pos += bytes; }
@@ -585,6 +604,7 @@ struct Archive {
         int32_t idx = -1;
         int64_t off = 0;
         if (saving && p) {
+            if (seen) seen->push_back(static_cast<const void*>(p));
             auto it = index->upper_bound(static_cast<const void*>(p));
             if (it == index->begin()) { ok = false; }
             else { --it; idx = it->second; off = reinterpret_cast<const char*>(p) - static_cast<const char*>(it->first); }
@@ -906,6 +926,130 @@ int ensure_f32_weights(const wt_model* M) {
     WT_HIP_CHECK(hipDeviceSynchronize());
     M->f32_stale.store(false);
     return WT_OK;
+}
+
+// ------------------------------------------------------------------------------------ the weights by name
+// Every device array a plan can read (wt_model_weight_info), in the order build_model and build_splits made them per layer.
+// The dims of the two f16 lane packings count halves, every other array's count 4-byte words.
+std::vector<WeightEntry> model_weights(const wt_model* Mc) {
+    wt_model* M = const_cast<wt_model*>(Mc);         // (archive_model is symmetric; saving does not modify)
+    std::vector<WeightEntry> out;
+    auto arr = [&](const std::string& name, const void* p, int fmt, std::initializer_list<int64_t> dims) -> WeightEntry* {
+        if (!p) return nullptr;
+        WeightEntry e;
+        e.name = name; e.data = p; e.format = fmt;
+        int64_t n = 1;
+        for (int64_t d : dims) { e.dims[e.ndim++] = d; n *= d; }
+        e.numel = (fmt == WFMT_LSTM_F16 || fmt == WFMT_LSTM_PERSIST) ? n / 2 : n;
+        out.push_back(e);
+        return &out.back();
+    };
+    auto copy = [&](const std::string& of, const S32Copy& s, std::initializer_list<int64_t> dims) {
+        if (WeightEntry* e = arr(of + ".s32", s.p, WFMT_S32, dims)) { e->of = of; e->acc_scale = s.acc_scale; e->tap_pair = s.tap_pair; }
+    };
+    auto conv = [&](const std::string& name, const ConvW& c) {
+        arr(name + ".w", c.w, WFMT_F32, {c.cout, c.k, c.cin});
+        arr(name + ".b", c.b, WFMT_F32, {c.cout});
+        if (WeightEntry* e = arr(name + ".s32", c.s32.p, WFMT_S32, {c.cout, c.k, c.cin})) { e->of = name + ".w"; e->acc_scale = c.s32.acc_scale; e->tap_pair = c.s32.tap_pair; }
+    };
+    auto gemm = [&](const std::string& name, const GemmW& g) {
+        arr(name, g.w, WFMT_F32, {g.rows, g.cols});
+        copy(name, g.s32, {g.rows, g.cols});
+    };
+    auto lstm = [&](const std::string& name, const LstmW& l, int H) {
+        gemm(name + ".Wih0", l.Wih0);
+        arr(name + ".b0", l.b0, WFMT_F32, {4 * H});
+        arr(name + ".W0", l.W0, WFMT_F32, {4 * H / 16, H / 16, 64, 4});
+        arr(name + ".W1", l.W1, WFMT_F32, {4 * H / 16, 2 * H / 16, 64, 4});
+        arr(name + ".b1", l.b1, WFMT_F32, {4 * H});
+        arr(name + ".W0h", l.W0h, WFMT_LSTM_F16, {4 * H / 16, H / 32, 2, 512});
+        arr(name + ".W1h", l.W1h, WFMT_LSTM_F16, {4 * H / 16, 2 * H / 32, 2, 512});
+        arr(name + ".Wp", l.Wp, WFMT_LSTM_PERSIST, {3 * 32 * 4, 16, 2, 512});
+    };
+    const wt_arch& a = M->arch;
+    const int H = M->H, D = a.dim, A = a.adanorm_num_embeddings;
+    // the tap-paired repackings of the down convs: held by lazy_f32 alone (s32 = null), in stage order
+    std::vector<const float*> paired;
+    for (const wt_model::LazyF32& z : M->lazy_f32) if (!z.s32) paired.push_back(z.w);
+    size_t next_pair = 0;
+    arr("enc.e0.w", M->e0_w, WFMT_F32, {M->e0_k, M->e0_c});
+    arr("enc.e0.b", M->e0_b, WFMT_F32, {M->e0_c});
+    for (size_t i = 0; i < M->stages.size(); ++i) {
+        const ResStage& st = M->stages[i];
+        const std::string p = "enc.stage" + std::to_string(i + 1);
+        conv(p + ".c3", st.c3); conv(p + ".c1", st.c1); conv(p + ".sc", st.sc); conv(p + ".down", st.down);
+        if (st.down.s32.tap_pair && next_pair < paired.size())
+            arr(p + ".down.wpair", paired[next_pair++], WFMT_F32, {st.down.cout, st.down.k, st.down.cin});
+        if (st.cat.w) conv(p + ".cat", st.cat);
+    }
+    lstm("enc.lstm", M->enc_lstm, H);
+    conv("enc.final", M->enc_final);
+    arr("vq.embed", M->embed.w, WFMT_F32, {a.num_quantizers, M->embed.rows, M->embed.cols});
+    copy("vq.embed", M->embed.s32, {M->embed.rows, M->embed.cols});
+    arr("vq.ee", M->ee, WFMT_F32, {a.vq_bins});
+    conv("bb.embed", M->bb_embed);
+    for (int i = 0; i < 4; ++i) {
+        const PosRes& r = M->res[i];
+        const std::string p = "bb.res." + std::to_string(i);
+        arr(p + ".n1w", r.n1w, WFMT_F32, {D}); arr(p + ".n1b", r.n1b, WFMT_F32, {D});
+        arr(p + ".n2w", r.n2w, WFMT_F32, {D}); arr(p + ".n2b", r.n2b, WFMT_F32, {D});
+        conv(p + ".c1", r.c1); conv(p + ".c2", r.c2);
+    }
+    arr("bb.attn.nw", M->at_nw, WFMT_F32, {D}); arr("bb.attn.nb", M->at_nb, WFMT_F32, {D});
+    gemm("bb.attn.Wqk", M->at_Wqk); arr("bb.attn.bqk", M->at_bqk, WFMT_F32, {2 * D});
+    gemm("bb.attn.Wv", M->at_Wv); arr("bb.attn.bv", M->at_bv, WFMT_F32, {D});
+    gemm("bb.attn.Wp", M->at_Wp); arr("bb.attn.bp", M->at_bp, WFMT_F32, {D});
+    arr("bb.gn5.w", M->gn5w, WFMT_F32, {D}); arr("bb.gn5.b", M->gn5b, WFMT_F32, {D});
+    arr("bb.ada.s", M->ada_s, WFMT_F32, {A, D}); arr("bb.ada.h", M->ada_h, WFMT_F32, {A, D});
+    for (size_t i = 0; i < M->cnx.size(); ++i) {
+        const CnxBlock& c = M->cnx[i];
+        const std::string p = "bb.cnx." + std::to_string(i);
+        arr(p + ".dw_w", c.dw_w, WFMT_F32, {7, D}); arr(p + ".dw_b", c.dw_b, WFMT_F32, {D});
+        arr(p + ".ada_s", c.ada_s, WFMT_F32, {A, D}); arr(p + ".ada_h", c.ada_h, WFMT_F32, {A, D});
+        gemm(p + ".W1", c.W1); arr(p + ".b1", c.b1, WFMT_F32, {c.W1.rows});
+        gemm(p + ".W2", c.W2); arr(p + ".b2", c.b2, WFMT_F32, {D});
+        arr(p + ".gamma", c.gamma, WFMT_F32, {D});
+    }
+    arr("bb.fln.w", M->fln_w, WFMT_F32, {D}); arr("bb.fln.b", M->fln_b, WFMT_F32, {D});
+    gemm("head.W", M->head_W); arr("head.b", M->head_b, WFMT_F32, {2 * M->Kb});
+    arr("istft.W", M->istft_W.w, WFMT_F32, {4, M->Kq, M->Kq});
+    copy("istft.W", M->istft_W.s32, {4, M->Kq, M->Kq});
+    arr("istft.win", M->win, WFMT_F32, {a.n_fft}); arr("istft.wsq", M->wsq, WFMT_F32, {a.n_fft});
+    if (M->has_seadec) {
+        conv("sd.first", M->sd_first);
+        lstm("sd.lstm", M->sd_lstm, H);
+        for (size_t i = 0; i < M->sd_stages.size(); ++i) {
+            const SeaDecStage& st = M->sd_stages[i];
+            const std::string p = "sd.stage" + std::to_string(i + 1);
+            arr(p + ".tr_w", st.tr_w, WFMT_F32, {st.k, st.cin, st.cout});
+            if (st.tr_wp.w) {
+                arr(p + ".tr_wp", st.tr_wp.w, WFMT_F32, {st.r, st.cout, 2, st.cin});
+                copy(p + ".tr_wp", st.tr_wp.s32, {st.r, st.cout, 2, st.cin});
+            }
+            arr(p + ".tr_b", st.tr_b, WFMT_F32, {st.cout});
+            conv(p + ".c3", st.c3); conv(p + ".c1", st.c1); conv(p + ".sc", st.sc);
+            if (st.cat.w) conv(p + ".cat", st.cat);
+        }
+        arr("sd.last.w", M->sd_last_w, WFMT_F32, {7, 32});
+        arr("sd.last.b", M->sd_last_b, WFMT_F32, {1});
+    }
+    // what archive_model writes, and the arrays a packed image leaves out
+    std::map<const void*, int> index;
+    for (size_t i = 0; i < M->allocs.size(); ++i) index[M->allocs[i]] = (int)i;
+    std::vector<char> sink;
+    std::vector<const void*> seen;
+    Archive ar;
+    ar.saving = true; ar.out = &sink; ar.index = &index; ar.seen = &seen;
+    archive_model(ar, M);
+    std::sort(seen.begin(), seen.end());
+    for (WeightEntry& e : out) {
+        e.archived = std::binary_search(seen.begin(), seen.end(), e.data);
+        auto at = index.find(e.data);
+        if (at != index.end()) e.alloc = at->second;
+        for (const wt_model::LazyF32& z : M->lazy_f32)
+            if (static_cast<const void*>(z.w) == e.data) { e.lazy = z.s32 ? 1 : 2; e.lazy_scale = z.scale; }
+    }
+    return out;
 }
 
 }  // namespace wt

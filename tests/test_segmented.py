@@ -260,3 +260,38 @@ def test_round_trip_against_the_oracle():
         print(f"segmented round trip ({seg_len}, {stride}): rel_l2 {err:.3e}")
         assert err < WAV_REL_TOL, (seg_len, stride, err)
     _no_status(m)
+
+
+def test_uniform_batches_share_the_single_calls_plans_and_recordings():
+    """What the one staging layout per plan kind protects: a uniform batch of full segments runs on encode_codes' (decode_codes')
+    own plan and REPLAYS its recording, which it can only while both hand _call the same staging buffers.  Three full segments and a
+    tail; B = 3 is within the graph limit."""
+    from wavtokenizer_amd import NAMED_ARCHS, WavTokenizer, _capi, synth
+    arch = NAMED_ARCHS["hop600"]
+    m = WavTokenizer.from_arch(arch)                         # a model of its own: every plan it holds was made here
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, seed=321).items()}, strict=False)
+    m = m.eval().to("cuda")
+    seg, stride = 4800, 4200
+    rec = torch.from_numpy(synth.make_clips(1, 3 * stride + 2000, seed=5)[0]).cuda()         # segments at 0, 4200, 8400 and a tail of 2000
+    replays = _capi.lib.wt_plan_graph_replays
+
+    def the_plan(kind, length):
+        keys = [k for k in m._engine.plans if k[0] == kind and k[1] == 3 and k[2] == length]
+        assert len(keys) == 1 and not keys[0][3] & _capi.WT_PLAN_FLAG_MIXED_LENGTH and keys[0][3] & _capi.WT_PLAN_FLAG_GRAPH, keys
+        return m._engine.plans[keys[0]][0]
+
+    batch = torch.stack([rec[o:o + seg] for o in (0, stride, 2 * stride)])
+    for _ in range(2):
+        codes = m.encode_codes(batch)
+    before = replays(the_plan(_capi.WT_PLAN_ENCODE, seg))
+    coded = m.encode_codes_segmented(rec, seg, stride)
+    assert coded.n_segments == 4 and torch.equal(torch.stack(coded.segments()[:3]).view(1, 3, 8), codes)
+    assert replays(the_plan(_capi.WT_PLAN_ENCODE, seg)) == before + 1
+
+    for _ in range(2):
+        m.decode_codes(codes, bandwidth_id=_bw())
+    before = replays(the_plan(_capi.WT_PLAN_DECODE_CODES, 8))
+    pcm = m.decode_pcm_segmented(coded, bandwidth_id=_bw())
+    assert pcm.shape == (1, rec.shape[0])
+    assert replays(the_plan(_capi.WT_PLAN_DECODE_CODES, 8)) == before + 1
+    _no_status(m)

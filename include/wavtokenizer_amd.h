@@ -104,7 +104,9 @@ typedef enum {
     WT_PLAN_DECODE_MIXED = 5,    /* features (B,512,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_mixed; `len` = Lpad */
     WT_PLAN_DECODE_CODES = 6,    /* codes (K,B,L) -> audio (B, L*hop): wt_decode_codes; WT_PLAN_DECODE with its first step (the transpose
                                     of the features) replaced by the gather of the codebook rows; `len` = L */
-    WT_PLAN_DECODE_CODES_MIXED = 7   /* codes (K,B,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_codes_mixed; `len` = Lpad */
+    WT_PLAN_DECODE_CODES_MIXED = 7,  /* codes (K,B,Lpad) + lengths (B) -> audio (B, wave_len(Lpad)): wt_decode_codes_mixed; `len` = Lpad */
+    WT_PLAN_QUANTIZE = 8         /* features (B,512,L) -> codes (n_q,B,L): greedy residual VQ with the call's n_q codebooks
+                                    (wt_quantize); `len` = L.  Takes FP32_GEMM, GRAPH, KEEP_STAGES and RANGE_REPORT */
 } wt_plan_kind;
 
 enum {
@@ -126,13 +128,18 @@ enum {
     WT_PLAN_FLAG_MIXED_LENGTH = 64,/* WT_PLAN_ENCODE: clips of different lengths in one call (wt_encode_mixed); `len` is the padded
                                       length.  Only the shipped route takes it: refused together with UNFUSED, FP32_GEMM,
                                       KEEP_STAGES or RANGE_REPORT, with the encoder site on fp32, or for weights without S32 copies */
-    WT_PLAN_FLAG_F16_GEMM = 128    /* the decode kinds (WT_PLAN_DECODE, _MIXED, _CODES, _CODES_MIXED): half-precision inference mode for
+    WT_PLAN_FLAG_F16_GEMM = 128,   /* the decode kinds (WT_PLAN_DECODE, _MIXED, _CODES, _CODES_MIXED): half-precision inference mode for
                                       callers that hold codes and want audio.  Every dense layer that runs on split-f16 operands
                                       multiplies their f16 hi halves alone: one f16 MFMA per product instead of three, fp32
                                       accumulate, operands rounded to f16 (waveform error near 1e-3 relative instead of 1e-5).
                                       Buffers, producers and weights are those of the default plan; a range site on fp32 stays
                                       on the fp32 chain.  Combines with KEEP_STAGES, RANGE_REPORT and GRAPH; refused (WT_ERR_INVALID)
                                       for every other plan kind and together with FP32_GEMM or UNFUSED */
+    WT_PLAN_FLAG_RVQ = 256         /* WT_PLAN_ENCODE: the plan's VQ tail is greedy residual VQ over up to num_quantizers codebooks
+                                      (wt_encode_rvq, wt_encode_rvq_mixed): codes (n_q,B,L) alone, n_q an argument of the call.
+                                      The encoder in front of it is the plan's own; combines with every flag an encode plan takes,
+                                      WT_PLAN_FLAG_MIXED_LENGTH included.  The first creation on a model builds the S32 copies and
+                                      |e|^2 tables of codebooks 1 .. num_quantizers - 1 (wt_model_codebook_tables) */
 };
 
 /* Range sites: the units in which a plan can leave the split-f16 form on its own (wt_plan_create_ex, wt_plan_range_sites).
@@ -257,6 +264,21 @@ int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* code
  * wt_encode refuses a mixed-length plan, and wt_encode_mixed every other plan. */
 int wt_encode_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, float* features, int64_t* codes, float* emb_out,
                     void* workspace, void* stream);
+/* Replaces: SEANetEncoder (encoder/modules/seanet.py:143) + ResidualVectorQuantizer.encode (encoder/quantization/vq.py:159-168)
+ * -> LanguageVectorQuantization.encode (core_vq.py:403-413) on a WT_PLAN_FLAG_RVQ encode plan: per round k < n_q the nearest row
+ * of codebook k to the residual (lowest index on ties), r -= that row in fp32.  The codes of n_q = K are the first K rows of
+ * n_q = K + 1; row 0 is wt_encode's.
+ *   wav   [B][T] fp32 (device);  n_q in [1, num_quantizers] (else WT_ERR_INVALID before any launch);  codes [n_q][B][L] int64 (out)
+ * A graph plan's recording is keyed by n_q.  wt_encode refuses a WT_PLAN_FLAG_RVQ plan, and wt_encode_rvq every other plan. */
+int wt_encode_rvq(const wt_plan* p, const float* wav, int32_t n_q, int64_t* codes, void* workspace, void* stream);
+/* The same on a WT_PLAN_FLAG_RVQ | WT_PLAN_FLAG_MIXED_LENGTH plan (B, Tpad), lengths as in wt_encode_mixed: clip b gets in every
+ * one of the n_q rows the codes of a plan of its own length; codes [n_q][B][Lpad] are -1 past a clip's frames and over the whole
+ * row of a clip whose length is outside the range. */
+int wt_encode_rvq_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, int32_t n_q, int64_t* codes, void* workspace,
+                        void* stream);
+/* Replaces: ResidualVectorQuantizer.encode (encoder/quantization/vq.py:159-168) on features the caller holds, on a
+ * WT_PLAN_QUANTIZE plan (B, L): features [B][512][L] fp32 -> codes [n_q][B][L] int64, the rounds of wt_encode_rvq. */
+int wt_quantize(const wt_plan* p, const float* features, int32_t n_q, int64_t* codes, void* workspace, void* stream);
 /* The shortest clip a mixed-length plan takes (samples); 0 for any other plan. */
 int64_t wt_plan_min_clip_length(const wt_plan* p);
 /* SConv1d geometry (encoder/modules/conv.py:54-61, 86-91, 195-211) of a non-causal conv over T samples, the function the plans
@@ -393,6 +415,33 @@ typedef struct {
     int32_t fin_grid_x, fin_grid_y;                     /* vq_finalize: (32-frame tiles, clips) */
 } wt_vq_form;
 int wt_vq_probe(const wt_vq_desc* d, wt_vq_form* form, void* workspace, void* stream);
+
+/* One round of residual VQ between two distance GEMMs, the kernel of the WT_PLAN_FLAG_RVQ / WT_PLAN_QUANTIZE plans alone, on
+ * caller-owned arrays.  pval / pidx [rows][nparts]: the per-slab (value, index) candidates as the distance GEMM leaves them (the
+ * first part that reaches the maximum wins; an index outside [0, bins) gives code 0).  x [rows][D], embed [bins][D] fp32;
+ * codes [rows] int64; r [rows][D] = x - embed[code] in fp32 (r may be x); r_s32 (optional) the S32 form of r, the bits of
+ * wt_split_probe op 0 on r; xx [rows] = |r|^2, the bits of row_sumsq on r; status (optional): WT_STATUS_BIT_RANGE when a
+ * non-NaN |r| >= 65504 is converted.  D % 256 == 0.  Everything is checked before the first HIP call: a refused descriptor
+ * returns WT_ERR_INVALID and launches nothing. */
+typedef struct {
+    int32_t size;                   /* sizeof(wt_vq_residual_desc) */
+    int32_t D, bins, nparts;
+    int64_t rows;
+    const float* pval;
+    const int32_t* pidx;
+    const float* x;
+    const float* embed;
+    int64_t* codes;
+    float* r;
+    void* r_s32;                    /* optional */
+    float* xx;
+    uint32_t* status;               /* optional device word */
+} wt_vq_residual_desc;
+typedef struct {
+    int32_t grid, block;            /* one wave per row, four rows per workgroup */
+    int32_t out_s32;
+} wt_vq_residual_form;
+int wt_vq_residual_probe(const wt_vq_residual_desc* d, wt_vq_residual_form* form, void* stream);
 
 /* One GEMM launch through the plans' own launchers, with every argument a plan sets: the unit tests' view of each
  * (epilogue, output format) pair and of each tile form the launchers pick.  Operands are fp32 device arrays in the
@@ -631,6 +680,12 @@ typedef struct {
 } wt_weight_info;
 int wt_model_weight_count(const wt_model* m);
 int wt_model_weight_info(const wt_model* m, int32_t index, wt_weight_info* out);
+/* What the distance GEMM of residual VQ round k reads of codebook k, 0 <= k < num_quantizers: its S32 copy ([bins][512], stored
+ * with a power-of-two scale of its own; acc_scale undoes it) and its |e|^2 table [bins] fp32, summed serially on the host.  k = 0
+ * returns the listed arrays ("vq.embed.s32", "vq.ee"); the tables of k >= 1 are derived state, built from the fp32 codebooks on
+ * the device the first time they are asked for (here or by a residual VQ plan), outside the weight listing and the packed image,
+ * and freed with the model.  Any output pointer may be NULL. */
+int wt_model_codebook_tables(const wt_model* m, int32_t k, const void** s32, const float** ee, float* acc_scale);
 
 /* The format converters under every S32 operand, through the launchers the plans and the loader call, on caller-owned arrays:
  *   op 0  fp32 x[n] -> S32 out (n words), the values multiplied by scale[0] first when `scale` (device) is given

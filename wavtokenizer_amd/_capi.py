@@ -28,11 +28,13 @@ EXPORTS = [
     "wt_decode_codes", "wt_decode_codes_mixed", "wt_ingest_workspace_bytes", "wt_ingest", "wt_codes_unpack",
     "wt_emit_workspace_bytes", "wt_emit", "wt_vq_probe", "wt_overlap_add_ragged_workspace_bytes", "wt_overlap_add_ragged",
     "wt_model_weight_count", "wt_model_weight_info", "wt_split_probe",
+    "wt_encode_rvq", "wt_encode_rvq_mixed", "wt_quantize", "wt_vq_residual_probe", "wt_model_codebook_tables",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
 WT_PLAN_DECODE_MIXED = 5
 WT_PLAN_DECODE_CODES, WT_PLAN_DECODE_CODES_MIXED = 6, 7
+WT_PLAN_QUANTIZE = 8
 WT_PLAN_FLAG_KEEP_STAGES = 1
 WT_PLAN_FLAG_FP32_GEMM = 2
 WT_PLAN_FLAG_F16_GEMM = 128
@@ -41,6 +43,7 @@ WT_PLAN_FLAG_GRAPH = 8
 WT_PLAN_FLAG_UNFUSED = 16
 WT_PLAN_FLAG_RANGE_REPORT = 32
 WT_PLAN_FLAG_MIXED_LENGTH = 64
+WT_PLAN_FLAG_RVQ = 256
 WT_SITE_ENCODER, WT_SITE_BB_EMBED, WT_SITE_RES0, WT_SITE_RES1, WT_SITE_ATTN, WT_SITE_RES2, WT_SITE_RES3 = 0, 1, 2, 3, 4, 5, 6
 WT_SITE_CNX0, WT_SITE_HEAD, WT_SITE_SEANET_DECODER = 7, 40, 41
 WT_ERR_INVALID = -1
@@ -118,6 +121,16 @@ class WtVqDesc(ctypes.Structure):
 class WtVqForm(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("BM", "BN", "waves_m", "waves_n", "grid", "ntiles", "group_m", "group_n", "nparts",
                                        "fin_grid_x", "fin_grid_y")]
+
+
+class WtVqResidualDesc(ctypes.Structure):
+    """wt_vq_residual_desc: one residual VQ round's kernel on caller-owned arrays (wt_vq_residual_probe)."""
+    _fields_ = ([(n, c_int32) for n in ("size", "D", "bins", "nparts")] + [("rows", c_int64)]
+                + [(n, c_void_p) for n in ("pval", "pidx", "x", "embed", "codes", "r", "r_s32", "xx", "status")])
+
+
+class WtVqResidualForm(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("grid", "block", "out_s32")]
 
 
 LSTM_PERSIST, LSTM_STEP_F16, LSTM_STEP_F32 = 0, 1, 2
@@ -309,6 +322,11 @@ def _load() -> ctypes.CDLL:
     lib.wt_model_weight_count.argtypes = [c_void_p]
     lib.wt_model_weight_info.argtypes = [c_void_p, c_int32, POINTER(WtWeightInfo)]
     lib.wt_split_probe.argtypes = [POINTER(WtSplitDesc), c_void_p]
+    lib.wt_encode_rvq.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.wt_encode_rvq_mixed.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.wt_quantize.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.wt_vq_residual_probe.argtypes = [POINTER(WtVqResidualDesc), POINTER(WtVqResidualForm), c_void_p]
+    lib.wt_model_codebook_tables.argtypes = [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float)]
     return lib
 
 

@@ -234,25 +234,40 @@ class _BatchedCalls:
         check(lib.wt_ingest(descs, len(specs), T_pad, _ptr(rows), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
         return rows
 
-    def _run_encode_codes_mixed(self, specs: Sequence["_ClipSpec"], T_pad: int, flat: torch.Tensor, offsets: Sequence[int]):
+    def _run_encode_codes_mixed(self, specs: Sequence["_ClipSpec"], T_pad: int, flat: torch.Tensor, offsets: Sequence[int],
+                                n_q: Optional[int] = None):
         """One group of encode_codes_many: one upload, one wt_ingest into the plan's staging tensor, one wt_encode_mixed (no
         feature buffer unless the plan is graph-replayed), one wt_codes_unpack into flat at the clips' offsets.  Returns True, or
-        None when the encoder is off the route a mixed-length plan takes (_route_ok)."""
+        None when the encoder is off the route a mixed-length plan takes (_route_ok).  n_q: residual VQ (_encode_ingested)."""
         dev = self._ensure_engine()
         if not self._route_ok(_capi.WT_PLAN_ENCODE):          # (before anything is uploaded; checked again on every attempt below)
             return None
         descs, ws, lengths, spans, _alive = self._ingest_stage(specs, offsets, dev)
-        return self._encode_ingested(descs, ws, len(specs), T_pad, lengths, spans, flat, dev)
+        return self._encode_ingested(descs, ws, len(specs), T_pad, lengths, spans, flat, dev, n_q)
 
     def _encode_ingested(self, descs, ws: torch.Tensor, B: int, T_pad: int, lengths: Optional[torch.Tensor], spans: torch.Tensor,
-                         flat: torch.Tensor, dev: torch.device):
+                         flat: torch.Tensor, dev: torch.device, n_q: Optional[int] = None):
         """The launches of a group whose wt_ingest descriptors, lengths (int32) and code spans (int64 {frames, offset}) are on
         hand, the latter two on the GPU: one wt_ingest into the plan's staging tensor, one encode without a feature tensor, one
         wt_codes_unpack into flat.  lengths=None: B clips of T_pad samples each on the plain encode plan (encode_codes' own: same
-        recording, same staging buffers).  True, or None off the mixed route (a uniform batch then goes clip by clip as well)."""
+        recording, same staging buffers).  True, or None off the mixed route (a uniform batch then goes clip by clip as well).
+        n_q: the encode is residual VQ with n_q codebooks (WT_PLAN_FLAG_RVQ), flat is [n_q][sum L_i] and every plane is handed
+        out by a wt_codes_unpack of its own."""
         def fill_wav(buf: torch.Tensor):
             check(lib.wt_ingest(descs, B, T_pad, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
 
+        if n_q is not None:
+            if lengths is None:
+                thunk = lambda: self._encode_rvq(B, T_pad, fill_wav, n_q, self._graph_flags(B), dev)
+            else:
+                thunk = lambda: self._encode_rvq_mixed(B, T_pad, fill_wav, lengths, n_q, dev)
+            res = self._guarded_mixed(_capi.WT_PLAN_ENCODE, B, thunk, dev)
+            if res is None:
+                return None
+            for k in range(n_q):
+                check(lib.wt_codes_unpack(_ptr(res[0][k]), B, self._arch.frames(T_pad), _ptr(spans), _ptr(flat[k]), flat[k].numel(),
+                                          _stream_ptr(dev)), "wt_codes_unpack")
+            return True
         if lengths is None:
             thunk = lambda: self._encode(B, T_pad, fill_wav, self._graph_flags(B), dev, want_emb=False, want_feats=False)
         else:
@@ -264,15 +279,19 @@ class _BatchedCalls:
               "wt_codes_unpack")
         return True
 
-    def _encode_codes_solo(self, specs: Sequence["_ClipSpec"], flat: torch.Tensor, offsets: Sequence[int]):
+    def _encode_codes_solo(self, specs: Sequence["_ClipSpec"], flat: torch.Tensor, offsets: Sequence[int], n_q: Optional[int] = None):
         """Clips that run one at a time (shorter than a mixed-length plan takes, or the encoder off its shipped route): ingested
-        together like a group, at most MAX_GROUP per launch, then encode_codes per clip."""
+        together like a group, at most MAX_GROUP per launch, then encode_codes per clip (with n_q: into the planes of flat)."""
         from .mixed_length import MAX_GROUP
         dev = self._ensure_engine()
         for c0 in range(0, len(specs), MAX_GROUP):
             part, offs = specs[c0:c0 + MAX_GROUP], offsets[c0:c0 + MAX_GROUP]
             wav = self._ingest_rows(part, dev)
             for j, (sp, off) in enumerate(zip(part, offs)):
+                if n_q is not None:
+                    codes = self.encode_codes(wav[j:j + 1, :sp.n_out], n_q=n_q)
+                    flat[:, off:off + codes.shape[-1]].copy_(codes[:, 0, :])
+                    continue
                 codes = self.encode_codes(wav[j:j + 1, :sp.n_out])
                 flat[off:off + codes.shape[-1]].copy_(codes.view(-1))
 
@@ -300,7 +319,7 @@ class _BatchedCalls:
 
     @torch.inference_mode()
     def encode_codes_many(self, clips: Sequence[torch.Tensor], sample_rates=None, channels_last: bool = False, packed: bool = False,
-                          bandwidth_id=None):
+                          bandwidth_id=None, n_q: Optional[int] = None):
         """Tokenise a set of clips straight from PCM.  clips[i] is (T,), (C, T) or, with channels_last, (T, C), C in {1, 2}, fp32
         or int16 (scaled by 1 / 32768), on the CPU or on the model's device; sample_rates is one rate or one per clip (default:
         the codec rate).  Returns [codes (1, 1, L_i)] in input order, views into one flat int64 tensor, L_i =
@@ -309,20 +328,29 @@ class _BatchedCalls:
         Per group of encode_infer_many's grouping (on the resampled lengths): one upload of the group's CPU clips, one ragged
         ingest launch, one mixed-length encode without a feature tensor, one launch that hands out the codes.  Clips under the
         mixed-length plans' minimum, and every clip while the encoder is off its shipped route, are ingested the same way and
-        encoded one at a time.  Argument errors raise ValueError before any GPU work."""
+        encoded one at a time.  Argument errors raise ValueError before any GPU work.
+        n_q, an int in [1, num_quantizers]: residual VQ with the first n_q codebooks, clip i's codes the bits of
+        encode_codes(..., n_q=n_q).  Returns [codes (n_q, 1, L_i)], views into one flat tensor laid out [n_q][sum L_i];
+        packed=True returns (that tensor as (n_q, sum L_i), offsets).  Per group one ingest, one mixed-length residual VQ encode
+        and n_q launches that hand out the codes, one per plane."""
         from .mixed_length import group_clips
         self._check_bandwidth(bandwidth_id)
+        if n_q is not None:
+            n_q = self._check_n_q("encode_codes_many", n_q)
         specs = self._clip_specs("encode_codes_many", clips, sample_rates, channels_last)
         offsets = [0]
         frames = self._arch.frames
         for sp in specs:
             offsets.append(offsets[-1] + frames(sp.n_out))
-        flat = torch.empty(offsets[-1], dtype=torch.int64, device=self._device())
+        flat = torch.empty(offsets[-1] if n_q is None else (n_q, offsets[-1]), dtype=torch.int64, device=self._device())
+        rvq = () if n_q is None else (n_q,)       # (n_q=None: today's calls, argument for argument)
         self._run_groups_of(specs, offsets, *group_clips([sp.n_out for sp in specs], self._arch.hop),
-                            lambda T_pad, part, offs: self._run_encode_codes_mixed(part, T_pad, flat, offs),
-                            lambda part, offs: self._encode_codes_solo(part, flat, offs))
+                            lambda T_pad, part, offs: self._run_encode_codes_mixed(part, T_pad, flat, offs, *rvq),
+                            lambda part, offs: self._encode_codes_solo(part, flat, offs, *rvq))
         if packed:
             return flat, torch.tensor(offsets, dtype=torch.int64)
+        if n_q is not None:
+            return [flat[:, offsets[i]:offsets[i + 1]].unsqueeze(1) for i in range(len(specs))]
         return [flat[offsets[i]:offsets[i + 1]].view(1, 1, -1) for i in range(len(specs))]
 
     # -- long recordings in overlapping segments (segmented.py): tokenise ---------------------------------------------------------

@@ -51,6 +51,7 @@ static int alloc_model_words(wt_model* M, const char* who) {
 static void free_model(wt_model* m) {
     for (void* p : m->allocs) (void)hipFree(p);
     for (void* p : m->load_tmp) (void)hipFree(p);
+    for (void* p : m->rvq.allocs) (void)hipFree(p);
     if (m->bad_codes_host) (void)hipHostFree(m->bad_codes_host);
 }
 
@@ -194,6 +195,21 @@ int wt_model_weight_info(const wt_model* m, int32_t index, wt_weight_info* out) 
     *out = w;
     return WT_OK;
 }
+int wt_model_codebook_tables(const wt_model* m, int32_t k, const void** s32, const float** ee, float* acc_scale) {
+    if (!m || k < 0 || k >= m->arch.num_quantizers) { set_error("wt_model_codebook_tables: no model, or k outside [0, num_quantizers)"); return WT_ERR_INVALID; }
+    S32Copy c = m->embed.s32;
+    const float* e = m->ee;
+    if (k > 0) {
+        DeviceGuard dg(m->device);
+        if (!dg.ok) { set_error("hipSetDevice failed"); return WT_ERR_HIP; }
+        if (int rc = ensure_rvq_tables(m)) return rc;
+        c = m->rvq.s32[k - 1]; e = m->rvq.ee[k - 1];
+    }
+    if (s32) *s32 = c.p;
+    if (ee) *ee = e;
+    if (acc_scale) *acc_scale = c.acc_scale;
+    return WT_OK;
+}
 int wt_model_hop(const wt_model* m) { return m ? m->hop : 0; }
 int64_t wt_model_weight_bytes(const wt_model* m) { return m ? m->weight_bytes : 0; }
 
@@ -217,6 +233,7 @@ static const PlanKind kPlanKinds[] = {
     {WT_PLAN_DECODE_MIXED, build_decode, -1, true, false},      // build_decode with the clip lengths threaded to its steps
     // build_decode with its first step replaced: bb.in gathered from the call's codes instead of transposed from its features
     {WT_PLAN_DECODE_CODES, build_decode, -1, true, false},  {WT_PLAN_DECODE_CODES_MIXED, build_decode, -1, true, false},
+    {WT_PLAN_QUANTIZE, build_quantize, SITE_ENC, false, false},     // the residual VQ rounds alone, on the caller's features
 };
 
 int wt_plan_create_ex(const wt_model* m, int32_t kind, int32_t B, int64_t len, int32_t flags, uint64_t fp32_sites, wt_plan** out) {
@@ -225,6 +242,16 @@ int wt_plan_create_ex(const wt_model* m, int32_t kind, int32_t B, int64_t len, i
     if (B < 1 || len < 1) { set_error("wt_plan_create: B and len must be >= 1"); return WT_ERR_INVALID; }
     if ((flags & WT_PLAN_FLAG_MIXED_LENGTH) && kind != WT_PLAN_ENCODE) {
         set_error("wt_plan_create: WT_PLAN_FLAG_MIXED_LENGTH is an encode-plan flag"); return WT_ERR_INVALID;
+    }
+    if ((flags & WT_PLAN_FLAG_RVQ) && kind != WT_PLAN_ENCODE) {
+        set_error("wt_plan_create: WT_PLAN_FLAG_RVQ is an encode-plan flag (WT_PLAN_QUANTIZE runs the rounds on features)"); return WT_ERR_INVALID;
+    }
+    if (kind == WT_PLAN_QUANTIZE) {
+        const struct { int flag; const char* name; } refused[] = {
+            {WT_PLAN_FLAG_UNFUSED, "WT_PLAN_FLAG_UNFUSED"}, {WT_PLAN_FLAG_STEP_LSTM, "WT_PLAN_FLAG_STEP_LSTM"},
+            {WT_PLAN_FLAG_MIXED_LENGTH, "WT_PLAN_FLAG_MIXED_LENGTH"}, {WT_PLAN_FLAG_F16_GEMM, "WT_PLAN_FLAG_F16_GEMM"}};
+        for (const auto& r : refused)
+            if (flags & r.flag) { set_error(std::string("wt_plan_create: ") + r.name + " has no meaning for WT_PLAN_QUANTIZE"); return WT_ERR_INVALID; }
     }
     if (flags & WT_PLAN_FLAG_F16_GEMM) {
         const bool decode_kind = kind == WT_PLAN_DECODE || kind == WT_PLAN_DECODE_MIXED || kind == WT_PLAN_DECODE_CODES ||

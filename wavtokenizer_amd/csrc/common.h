@@ -57,7 +57,9 @@ enum OpKernel : int {
     // the length-aware launches of a WT_PLAN_DECODE_MIXED plan (ops_kernel.inc, OPS_MIX 1)
     OPK_TRANSPOSE_MIXED, OPK_GN_MIXED, OPK_DWCONV_LN_MIXED, OPK_SOFTMAX_REG_MIXED, OPK_SOFTMAX_RMW_MIXED, OPK_ISTFT_OLA_MIXED,
     // the first step of the decode-from-codes plans (WT_PLAN_DECODE_CODES / _MIXED) and its length-aware twin
-    OPK_CODE_ROWS, OPK_CODE_ROWS_MIXED
+    OPK_CODE_ROWS, OPK_CODE_ROWS_MIXED,
+    // one round of residual VQ between two distance GEMMs (the RVQ encode and quantize plans)
+    OPK_VQ_RESIDUAL
 };
 struct OpForm {
     int kernel = OPK_NONE;       // OpKernel
@@ -343,6 +345,10 @@ int launch_softmax(float* S, int rows, int L, int ld, hipStream_t s, float* P_s3
 int launch_row_sumsq(const float* x, float* out, long rows, int D, hipStream_t s);
 int launch_vq_finalize(const float* pval, const int* pidx, int nparts, const float* embed, int64_t* codes,
                        float* feat_ncl, int B, int L, int D, int bins, hipStream_t s);
+// One round of residual VQ (ops.hip vq_residual_kernel): codes [rows] from the candidates by vq_finalize's rule, r = x - embed[code]
+// (fp32; r may be x), r_s32 (optional) its S32 form as launch_split_s32 writes it, xx [rows] = |r|^2 as launch_row_sumsq sums it
+int launch_vq_residual(const float* pval, const int* pidx, int nparts, const float* x, const float* embed, int64_t* codes,
+                       float* r, float* r_s32, float* xx, long rows, int D, int bins, hipStream_t s);
 int launch_codes_to_features(const int64_t* codes, const float* embed, int K, int bins, int B, long L, int D,
                              float* feat_ncl, hipStream_t s, unsigned* bad = nullptr);
 // Codes [K][B][L] int64 -> y [B][L][C], one row per frame: the sum over k of table[(k * bins + code_k) * C ...] in the order and

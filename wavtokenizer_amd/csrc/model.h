@@ -130,6 +130,19 @@ struct wt_model {
     unsigned* status_host = nullptr;
     unsigned* status_dev = nullptr;
     mutable std::atomic<bool> persist_ok{true};
+    // Residual VQ encode (WT_PLAN_FLAG_RVQ, WT_PLAN_QUANTIZE): the S32 copy and the |e|^2 table of codebooks 1 .. num_quantizers - 1,
+    // as `embed.s32` and `ee` are codebook 0's.  Derived state, not weights: built from the fp32 codebooks on the device when the
+    // first plan that needs them is created (weights.cpp ensure_rvq_tables), kept outside `allocs` (the packed image and the
+    // weight listing do not know them) and freed with the model.  Entry k - 1 belongs to codebook k
+    struct RvqTables {
+        std::vector<wt::S32Copy> s32;
+        std::vector<float*> ee;
+        std::vector<void*> allocs;
+        bool built = false;
+        bool s32_ok = true;              // every further codebook has a usable S32 copy (else the rounds run on fp32 operands)
+    };
+    mutable RvqTables rvq;
+    mutable std::mutex rvq_mu;
 };
 
 namespace wt {
@@ -160,7 +173,8 @@ struct RunCtx {
     int bw_id;
     const int* lengths = nullptr;    // mixed-length encode / decode: the clip lengths in samples / frames (device int32 [B])
     const int64_t* in_codes = nullptr;   // decode from codes (WT_PLAN_DECODE_CODES / _MIXED): codes [n_q][B][L] instead of in_f
-    int n_q = 0;                     // ... and the number of codebooks the call sums (an argument of the call, not of the plan)
+    int n_q = 0;                     // ... and the number of codebooks the call sums (an argument of the call, not of the plan);
+                                     // residual VQ encode (WT_PLAN_FLAG_RVQ, WT_PLAN_QUANTIZE): the rounds the call runs, codes [n_q][B][L]
 };
 // Range sites (wt_plan_create_ex, wt_plan_range_sites): the units in which a plan can leave the split-f16 (S32) form.  Every
 // S32 tensor is produced and consumed inside ONE site, so a site can run on fp32 operands (gemm.hip) on its own while the
@@ -255,7 +269,7 @@ struct wt_plan {
     struct GraphKey {
         const void *ws = nullptr, *in = nullptr, *out = nullptr, *codes = nullptr, *aux = nullptr, *lengths = nullptr;
         int bw = -1;
-        int K = 0;                        // decode from codes: a recording bakes the call's codebook count in
+        int K = 0;                        // decode from codes, residual VQ encode: a recording bakes the call's codebook count in
         bool operator==(const GraphKey& o) const {
             return ws == o.ws && in == o.in && out == o.out && codes == o.codes && aux == o.aux && lengths == o.lengths && bw == o.bw &&
                    K == o.K;
@@ -348,6 +362,7 @@ size_t model_export_bytes(const wt_model* M);
 int model_export(const wt_model* M, void* buf, size_t n);
 int model_import(wt_model* M, const void* buf, size_t n);        // M->device set; allocates and uploads
 int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint64_t* arch_hash);
+int ensure_rvq_tables(const wt_model* M);                         // builds wt_model::rvq once (thread-safe); the current device is the model's
 int ensure_f32_weights(const wt_model* M);                        // fills the lazy fp32 arrays of a packed model (first fp32 plan)
 // every device array of the model that a plan can read, by name (wt_model_weight_info): the one walk over the model's weights
 enum : int { WFMT_F32 = 0, WFMT_S32 = 1, WFMT_LSTM_F16 = 2, WFMT_LSTM_PERSIST = 3 };
@@ -380,6 +395,9 @@ int build_decode(wt_plan* P);
 int build_head(wt_plan* P);
 int build_seanet_decoder(wt_plan* P);
 int build_unit_lstm(wt_plan* P);
+int build_quantize(wt_plan* P);
+// a plan whose calls write n_q rows of codes, n_q an argument of the call (WT_PLAN_FLAG_RVQ encode plans, WT_PLAN_QUANTIZE)
+inline bool plan_rvq(const wt_plan* P) { return P->kind == WT_PLAN_QUANTIZE || (P->kind == WT_PLAN_ENCODE && (P->flags & WT_PLAN_FLAG_RVQ)); }
 // the recurrence of an SLSTM on one of its three kernels, as the plans' LSTM step and wt_lstm_probe issue it (plan.cpp)
 enum : int { LSTM_PERSIST = 0, LSTM_STEP_F16 = 1, LSTM_STEP_F32 = 2 };
 size_t lstm_step_state_numel(int B, int H);

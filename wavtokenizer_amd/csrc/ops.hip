@@ -772,6 +772,78 @@ int launch_vq_finalize(const float* pval, const int* pidx, int nparts, const flo
     return 0;
 }
 
+// One round of residual VQ between two distance GEMMs (core_vq.py:403-413), one wave per row m of [rows]: the code of round k
+// from the GEMM's candidates by vq_finalize_kernel's rule (parts scanned in ascending order per lane, lanes merged
+// lowest-part-first: the first part that reaches the maximum wins; an index outside [0, bins) gives code 0), then
+// r[m] = x[m] - embed[code] in fp32 (one rounding per element), its S32 form if asked (split_s32_kernel's expressions on the
+// stored value, unscaled) and xx[m] = |r[m]|^2 in row_sumsq_kernel's order (the same per-lane sum over 256-channel passes, the
+// same wave_sum).  x and r may be the same array (a lane reads the elements it writes); D % 256 == 0.  No LDS: 16-byte
+// accesses along the row, the codebook row (2 KB at D = 512) read coalesced like the residual.
+__global__ __launch_bounds__(256) void vq_residual_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, int nparts,
+                                                          const float* x, const float* __restrict__ embed,
+                                                          int64_t* __restrict__ codes, float* r, float* r_s32,
+                                                          float* __restrict__ xx, long rows, int D, int bins, unsigned* status) {
+    // every product and sum below is rounded on its own, in the order written: row_sumsq_kernel's bits, not a fused variant of them
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= rows) return;
+    float best = -INFINITY;
+    int bi = 0x7fffffff, bq = 0x7fffffff;
+    for (int q = lane; q < nparts; q += 64) {
+        const float v = pval[m * nparts + q];
+        if (v > best) { best = v; bi = pidx[m * nparts + q]; bq = q; }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float ov = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(bi, off, 64), oq = __shfl_xor(bq, off, 64);
+        if (ov > best || (ov == best && oq < bq)) { best = ov; bi = oi; bq = oq; }
+    }
+    if ((unsigned)bi >= (unsigned)bins) bi = 0;       // a row of NaN distances selects nothing: code 0 (vq_finalize_kernel)
+    if (lane == 0) codes[m] = (int64_t)bi;
+    const float* e = embed + (long)bi * D;
+    float s = 0.f, amax = 0.f;
+    for (int c = lane * 4; c < D; c += 256) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(x + m * D + c);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(e + c);
+        const f32x4 v = a - b;
+        *reinterpret_cast<f32x4*>(r + m * D + c) = v;
+        if (r_s32) {
+            // launch_split_s32's words for every value.  Its kernel computes hi = f16(x * 1 + 0) and lo = f16((x - hi) * 2048 + 0) on
+            // v_fma_mix instructions, whose +0 addend turns the halves of x = -0 into +0 and changes nothing else: adding +0
+            // first gives those words whichever instructions the compiler picks here
+            f16x4s hi, lo;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float w = v[i] + 0.f;
+                amax = amax1(amax, w);
+                const _Float16 h = (_Float16)w;
+                hi[i] = h;
+                lo[i] = (_Float16)((w - (float)h) * 2048.f);
+            }
+            _Float16* p = reinterpret_cast<_Float16*>(r_s32 + m * D) + ((c >> 5) * 64 + (c & 31));
+            *reinterpret_cast<f16x4s*>(p) = hi;
+            *reinterpret_cast<f16x4s*>(p + 32) = lo;
+        }
+        s += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    }
+    range_report(status, amax);
+    s = wave_sum(s);
+    if (lane == 0) xx[m] = s;
+}
+
+int launch_vq_residual(const float* pval, const int* pidx, int nparts, const float* x, const float* embed, int64_t* codes,
+                       float* r, float* r_s32, float* xx, long rows, int D, int bins, hipStream_t s) {
+    if (D % 256) { set_error("vq_residual: codebook width must be a multiple of 256"); return -1; }
+    if (nparts < 1 || rows < 1 || rows >= (1L << 33)) { set_error("vq_residual: needs nparts >= 1 and 1 <= rows < 2^33"); return -1; }
+    note_form(OPK_VQ_RESIDUAL, r_s32 ? 1 : 0, 0, dim3((unsigned)((rows + 3) / 4)), 256);
+    hipLaunchKernelGGL(vq_residual_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, pval, pidx, nparts, x, embed, codes, r,
+                       r_s32, xx, rows, D, bins, g_launch.status);
+    WT_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // WavTokenizer.codes_to_features (decoder/pretrained.py:227-237): sum over the K codebooks of
 // embed[codes[k] + k*bins], transposed to (B, D, L).  F.embedding (pretrained.py:236) raises on an index outside
 // the table; here such a code never reaches the gather (row 0 is read instead), the frame's features become NaN and

@@ -271,10 +271,85 @@ static int plan_resblock_s32(wt_plan* P, const ConvW& c3, const ConvW& sc, const
     return o;
 }
 
+// Greedy residual VQ (core_vq.py:403-413) on the rows x [B * L][512] (fp32; xs: their S32 form when the distance GEMMs run on
+// gemm16s.hip): the plan holds num_quantizers rounds and a call launches the first RunCtx::n_q.  Round k: distance GEMM
+// against codebook k with the argmax epilogue, then vq_residual (code row k, r -= E_k[code], its S32 form and |r|^2 for the
+// next GEMM); the call's last round needs the codes only and ends in vq_finalize.  Round 0 reads x, writes vq.r; the later
+// rounds update vq.r in place.  Codes [n_q][B][L]; geom >= 0 (mixed-length): every row is -1 past a clip's frames.
+static int plan_rvq_rounds(wt_plan* P, int x, int xs, bool s32, int geom, int l_word) {
+    const wt_model* M = P->model;
+    const int B = P->B, L = (int)P->L, bins = M->arch.vq_bins, D = M->embed.cols, nq = M->arch.num_quantizers;
+    const long rows = (long)B * L;
+    const int np = s32 ? gemm16s_vq_parts(bins) : gemm_vq_parts(bins);
+    const int xx = P->buf("vq.xx", (size_t)rows);
+    const int pv = P->buf("vq.pval", (size_t)rows * np);
+    const int pi = P->buf("vq.pidx", (size_t)rows * np);
+    const int r = nq > 1 ? P->buf("vq.r", (size_t)rows * D) : -1;
+    const int rs = nq > 1 && s32 ? P->buf("vq.r.s32", (size_t)rows * D, BUF_S32) : -1;
+    P->n_codes = rows;                   // per round: the guard step takes the call's n_q (plan_end)
+    P->step({x, xx}, [=](const RunCtx& c) { return launch_row_sumsq(P->ptr(c, x), P->ptr(c, xx), rows, D, c.stream); });
+    for (int k = 0; k < nq; ++k) {
+        GemmW W;
+        W.w = M->embed.w + (size_t)k * bins * D; W.rows = bins; W.cols = D;
+        W.s32 = k ? M->rvq.s32[k - 1] : M->embed.s32;
+        const float* ee = k ? M->rvq.ee[k - 1] : M->ee;
+        const GemmArgs av = linear_args(W, nullptr, rows, bins, D);
+        const int a_f = k ? r : x, a_s = k ? rs : xs;
+        const std::string tag = k ? "." + std::to_string(k) : "";
+        P->step({a_f, s32 ? a_s : -1, xx, pv, pi}, [=](const RunCtx& c) {
+            if (k >= c.n_q) return 0;
+            GemmArgs a = av; a.A = P->ptr(c, s32 ? a_s : a_f);
+            a.vq_xx = P->ptr(c, xx); a.vq_ee = ee; a.vq_pval = P->ptr(c, pv);
+            a.vq_pidx = reinterpret_cast<int*>(P->ptr(c, pi)); a.vq_nparts = np;
+            return dense(P, s32, a, PRO_NONE, EPI_ARGMAX, OUT_F32, c.stream);
+        }, 1, "vq.argmin" + tag);
+        P->step({geom, pv, pi, a_f, r, rs, xx}, [=](const RunCtx& c) {
+            if (k >= c.n_q) return 0;
+            int64_t* codes = c.codes + (long)k * rows;
+            const float* pval = P->ptr(c, pv);
+            const int* pidx = reinterpret_cast<const int*>(P->ptr(c, pi));
+            int rc;
+            if (k == c.n_q - 1) rc = launch_vq_finalize(pval, pidx, np, W.w, codes, nullptr, B, L, D, bins, c.stream);
+            else rc = launch_vq_residual(pval, pidx, np, P->ptr(c, a_f), W.w, codes, P->ptr(c, r), rs >= 0 ? P->ptr(c, rs) : nullptr,
+                                         P->ptr(c, xx), rows, D, bins, c.stream);
+            if (!rc && geom >= 0)
+                rc = launch_mixed_pad(reinterpret_cast<const int*>(P->ptr(c, geom)), l_word, codes, nullptr, nullptr, B, L, 1, c.stream);
+            return rc;
+        }, geom >= 0 ? 2 : 1, (k == nq - 1 ? "vq.finalize" : "vq.residual") + tag);
+    }
+    return 0;
+}
+
+// the checks the two residual VQ plan shapes share, and the tables of codebooks 1 .. num_quantizers - 1 (weights.cpp)
+static int rvq_prepare(const wt_plan* P) {
+    const wt_model* M = P->model;
+    if (M->arch.input_channels != M->embed.cols || M->enc_final.cout != M->embed.cols) {
+        set_error("residual VQ plans need input_channels and the encoder width equal to the codebook width"); return WT_ERR_INVALID;
+    }
+    if ((long)P->B * P->L >= (long)INT_MAX) { set_error("batch too large for one residual VQ plan (32-bit frame index)"); return WT_ERR_INVALID; }
+    return ensure_rvq_tables(M);
+}
+
+// WT_PLAN_QUANTIZE: features (B, 512, L) fp32 -> codes (n_q, B, L): transpose to rows, split, |x|^2, then the rounds
+int build_quantize(wt_plan* P) {
+    const wt_model* M = P->model;
+    if (int rc = rvq_prepare(P)) return rc;
+    const int B = P->B, L = (int)P->L, D = M->embed.cols;
+    const long rows = (long)B * L;
+    const bool s32 = plan_s32(P) && M->embed.s32.p && M->rvq.s32_ok;
+    const int x = P->buf("vq.in", (size_t)rows * D);
+    const int xs = s32 ? P->buf("vq.in.s32", (size_t)rows * D, BUF_S32) : -1;
+    P->step({x}, [=](const RunCtx& c) { return launch_transpose(c.in_f, P->ptr(c, x), B, D, L, c.stream); });
+    if (s32) P->step({x, xs}, [=](const RunCtx& c) { return launch_split_s32(P->ptr(c, x), P->ptr(c, xs), rows * D, c.stream); });
+    return plan_rvq_rounds(P, x, xs, s32, -1, 0);
+}
+
 int build_encode(wt_plan* P) {
     const wt_model* M = P->model;
     const int B = P->B;
     const long T = P->T;
+    const bool rvq = P->flags & WT_PLAN_FLAG_RVQ;
+    if (rvq) if (int rc = rvq_prepare(P)) return rc;
     // the first conv is folded into the fused stage-1 resblock unless stage taps are kept
     const bool fold_e0 = !plan_unfused(P) && !M->stages.empty() && M->stages[0].C == 32 &&
                          M->e0_k == 7 && resblock_fusable(32);
@@ -401,6 +476,11 @@ int build_encode(wt_plan* P) {
     GemmBufs bf{x, -1, emb, emb_s32};
     bf.mix_word = mixed ? geom_final(n_st) : -1;
     gemm_step(P, tail_s32, af, bf, fuse_elu ? PRO_NONE : PRO_ELU, EPI_BIAS, OUT_F32_AND_S32);
+    // ---- residual VQ with the call's n_q codebooks (WT_PLAN_FLAG_RVQ: codes alone, no features, no emb_out)
+    if (rvq) {
+        P->n_out = P->n_aux = 0;
+        return plan_rvq_rounds(P, emb, emb_s32, tail_s32 && M->rvq.s32_ok, geom, geom_L(n_st));
+    }
     // ---- VQ (core_vq.py:175-183, 206-231)
     const int bins = M->arch.vq_bins;
     GemmArgs av = linear_args(M->embed, nullptr, (long)B * L, bins, 512);
@@ -742,9 +822,10 @@ void plan_end(wt_plan* P) {
     const wt_model* M = P->model;
     const int ctl = P->ctl;
     const long nc = P->n_codes, n0 = P->n_out, n1 = P->n_aux;      // what the builder said a call writes
+    const bool per_round = plan_rvq(P);      // codes [n_q][B][L], n_q the call's
     P->step({ctl}, [=](const RunCtx& c) {
         return launch_plan_guard(reinterpret_cast<const unsigned*>(P->ptr(c, ctl)), CTL_WORDS, CTL_SITE0, P->status_dev, M->status_dev,
-                                 nc ? c.codes : nullptr, nc, c.out_f, n0, n1 ? c.aux : nullptr, n1, nullptr, 0, c.stream);
+                                 nc ? c.codes : nullptr, per_round ? nc * c.n_q : nc, c.out_f, n0, n1 ? c.aux : nullptr, n1, nullptr, 0, c.stream);
     }, 1, "guard");
 }
 

@@ -416,6 +416,31 @@ int wt_vq_probe(const wt_vq_desc* d, wt_vq_form* form, void* workspace, void* st
     return WT_OK;
 }
 
+// wt_vq_residual_probe: one launch of vq_residual_kernel on the caller's arrays (the candidates are the caller's, so any code
+// can be forced).  Everything is checked before the first HIP call.
+int wt_vq_residual_probe(const wt_vq_residual_desc* d, wt_vq_residual_form* form, void* stream) {
+    auto bad = [](const char* m) { set_error(std::string("wt_vq_residual_probe: ") + m); return (int)WT_ERR_INVALID; };
+    if (!d || d->size != (int32_t)sizeof(wt_vq_residual_desc)) return bad("descriptor missing or of another size");
+    if (!d->pval || !d->pidx || !d->x || !d->embed || !d->codes || !d->r || !d->xx) return bad("pval, pidx, x, embed, codes, r and xx are required");
+    if (d->rows < 1 || d->rows >= (int64_t)INT_MAX || d->bins < 1 || d->nparts < 1 || d->D < 1) return bad("needs 1 <= rows < 2^31, D >= 1, bins >= 1 and nparts >= 1");
+    if (d->D % 256) return bad("vq_residual: codebook width must be a multiple of 256");
+    const void* p16[] = {d->x, d->embed, d->r, d->r_s32};
+    for (const void* p : p16) if (reinterpret_cast<uintptr_t>(p) & 15) return bad("x, embed, r and r_s32 must be 16-byte aligned");
+    const void* p4[] = {d->pval, d->pidx, d->xx, d->status};
+    for (const void* p : p4) if (reinterpret_cast<uintptr_t>(p) & 3) return bad("pval, pidx, xx and status must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d->codes) & 7) return bad("codes must be 8-byte aligned");
+    OpForm of;
+    const LaunchCtx saved = g_launch;
+    g_launch.status = reinterpret_cast<unsigned*>(d->status);
+    g_launch.form = &of;
+    const int rc = launch_vq_residual(d->pval, d->pidx, d->nparts, d->x, d->embed, d->codes, d->r, static_cast<float*>(d->r_s32), d->xx,
+                                      (long)d->rows, d->D, d->bins, static_cast<hipStream_t>(stream));
+    g_launch = saved;
+    if (rc) return rc;
+    if (form) *form = wt_vq_residual_form{(int32_t)of.grid[0], (int32_t)of.block, of.variant};
+    return WT_OK;
+}
+
 int wt_resblock(const float* x, const float* wav, const float* e0_w, const float* e0_b, const float* w3, const float* b3,
                 const float* w1, const float* b1, const float* ws, const float* bs, float* y, int32_t B, int64_t T,
                 int32_t C, int32_t elu_out, int32_t out_s32, int32_t fp32_chain, void* stream) {

@@ -352,6 +352,7 @@ int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* code
               void* stream) {
     if (int rc = check_kind(p, WT_PLAN_ENCODE, -1, "wt_encode: not an encode plan")) return rc;
     if (int rc = check_kind(p, WT_PLAN_ENCODE, 0, "wt_encode: a mixed-length plan runs through wt_encode_mixed")) return rc;
+    if (p->flags & WT_PLAN_FLAG_RVQ) { set_error("wt_encode: a WT_PLAN_FLAG_RVQ plan runs through wt_encode_rvq"); return WT_ERR_INVALID; }
     if (!wav || !codes || !workspace) { set_error("wt_encode: null buffer"); return WT_ERR_INVALID; }
     RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), wav, features, codes, emb_out, 0};
     return run_plan(p, c);
@@ -360,6 +361,7 @@ int wt_encode(const wt_plan* p, const float* wav, float* features, int64_t* code
 int wt_encode_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, float* features, int64_t* codes, float* emb_out,
                     void* workspace, void* stream) {
     if (int rc = check_kind(p, WT_PLAN_ENCODE, 1, "wt_encode_mixed: not a mixed-length encode plan (WT_PLAN_FLAG_MIXED_LENGTH)")) return rc;
+    if (p->flags & WT_PLAN_FLAG_RVQ) { set_error("wt_encode_mixed: a WT_PLAN_FLAG_RVQ plan runs through wt_encode_rvq_mixed"); return WT_ERR_INVALID; }
     if (!wav || !lengths || !codes || !workspace) { set_error("wt_encode_mixed: null buffer"); return WT_ERR_INVALID; }
     RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), wav, features, codes, emb_out, 0, lengths};
     return run_plan(p, c);
@@ -385,6 +387,43 @@ int wt_decode_mixed(const wt_plan* p, const float* features, const int32_t* leng
         set_error("wt_decode_mixed: bandwidth_id out of range"); return WT_ERR_INVALID;
     }
     RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features, wav_out, nullptr, nullptr, bandwidth_id, lengths};
+    return run_plan(p, c);
+}
+
+// residual VQ encode: the call's number of rounds, checked before any launch
+static int check_n_q(const wt_plan* p, int32_t n_q, const char* who) {
+    if (n_q >= 1 && n_q <= p->model->arch.num_quantizers) return WT_OK;
+    set_error(std::string(who) + ": n_q must be between 1 and the number of codebooks");
+    return WT_ERR_INVALID;
+}
+
+int wt_encode_rvq(const wt_plan* p, const float* wav, int32_t n_q, int64_t* codes, void* workspace, void* stream) {
+    if (int rc = check_kind(p, WT_PLAN_ENCODE, 0, "wt_encode_rvq: not a plain encode plan with WT_PLAN_FLAG_RVQ")) return rc;
+    if (!(p->flags & WT_PLAN_FLAG_RVQ)) { set_error("wt_encode_rvq: not a WT_PLAN_FLAG_RVQ plan (wt_encode runs the others)"); return WT_ERR_INVALID; }
+    if (!wav || !codes || !workspace) { set_error("wt_encode_rvq: null buffer"); return WT_ERR_INVALID; }
+    if (int rc = check_n_q(p, n_q, "wt_encode_rvq")) return rc;
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), wav, nullptr, codes, nullptr, 0};
+    c.n_q = n_q;
+    return run_plan(p, c);
+}
+
+int wt_encode_rvq_mixed(const wt_plan* p, const float* wav, const int32_t* lengths, int32_t n_q, int64_t* codes, void* workspace,
+                        void* stream) {
+    if (int rc = check_kind(p, WT_PLAN_ENCODE, 1, "wt_encode_rvq_mixed: not a mixed-length encode plan with WT_PLAN_FLAG_RVQ")) return rc;
+    if (!(p->flags & WT_PLAN_FLAG_RVQ)) { set_error("wt_encode_rvq_mixed: not a WT_PLAN_FLAG_RVQ plan (wt_encode_mixed runs the others)"); return WT_ERR_INVALID; }
+    if (!wav || !lengths || !codes || !workspace) { set_error("wt_encode_rvq_mixed: null buffer"); return WT_ERR_INVALID; }
+    if (int rc = check_n_q(p, n_q, "wt_encode_rvq_mixed")) return rc;
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), wav, nullptr, codes, nullptr, 0, lengths};
+    c.n_q = n_q;
+    return run_plan(p, c);
+}
+
+int wt_quantize(const wt_plan* p, const float* features, int32_t n_q, int64_t* codes, void* workspace, void* stream) {
+    if (int rc = check_kind(p, WT_PLAN_QUANTIZE, -1, "wt_quantize: not a WT_PLAN_QUANTIZE plan")) return rc;
+    if (!features || !codes || !workspace) { set_error("wt_quantize: null buffer"); return WT_ERR_INVALID; }
+    if (int rc = check_n_q(p, n_q, "wt_quantize")) return rc;
+    RunCtx c{static_cast<char*>(workspace), static_cast<hipStream_t>(stream), features, nullptr, codes, nullptr, 0};
+    c.n_q = n_q;
     return run_plan(p, c);
 }
 

@@ -560,6 +560,65 @@ int build_splits(wt_model* M) {
     return 0;
 }
 
+// The distance GEMM of residual VQ round k >= 1 reads codebook k as add_s32 stores codebook 0 (the S32 copy with its own
+// power-of-two storage scale, acc_scale = 1 / scale) and its |e|^2 table summed serially like `ee` above.  Built once per
+// model from the fp32 codebooks on the device; nothing here touches `allocs`, the listing or the packed image.
+int ensure_rvq_tables(const wt_model* M) {
+    std::lock_guard<std::mutex> lock(M->rvq_mu);
+    wt_model::RvqTables& t = M->rvq;
+    if (t.built) return 0;
+    const int nq = M->arch.num_quantizers, bins = M->arch.vq_bins, D = 512;
+    const long n = (long)bins * D;
+    auto fail = [&](int rc) {
+        for (void* p : t.allocs) (void)hipFree(p);
+        t = wt_model::RvqTables{};
+        return rc;
+    };
+    auto alloc = [&](size_t bytes, void** out) {
+        if (hipMalloc(out, bytes) != hipSuccess) { set_error("residual VQ tables: out of device memory"); return (int)WT_ERR_HIP; }
+        t.allocs.push_back(*out);
+        return 0;
+    };
+    std::vector<float> h((size_t)n), ee((size_t)bins);
+    const LaunchCtx saved = g_launch;
+    g_launch = LaunchCtx{};                  // the splits below belong to no call: no status word, no form
+    int rc = 0;
+    for (int k = 1; k < nq && !rc; ++k) {
+        const float* w = M->embed.w + (size_t)k * n;
+        if (hipMemcpy(h.data(), w, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { set_error("residual VQ tables: reading codebook failed"); rc = WT_ERR_HIP; break; }
+        float amax = 0.f;
+        bool finite = true;
+        for (long i = 0; i < n; ++i) {
+            const float v = std::fabs(h[i]);
+            if (!(v <= 3.0e38f)) finite = false;
+            else amax = std::max(amax, v);
+        }
+        float scale = finite ? s32_weight_scale(amax) : 1.f;
+        if (scale == 0.f) { finite = false; scale = 1.f; }
+        if (!finite) t.s32_ok = false;
+        for (int r = 0; r < bins; ++r) {     // embed.pow(2).sum(0), as codebook 0's table
+            float s = 0.f;
+            for (int c = 0; c < D; ++c) s += h[(size_t)r * D + c] * h[(size_t)r * D + c];
+            ee[r] = s;
+        }
+        S32Copy copy;
+        void *d = nullptr, *de = nullptr, *ds = nullptr;
+        if ((rc = alloc((size_t)n * 4, &d)) || (rc = alloc(((size_t)bins * 4 + 15) / 16 * 16, &de)) || (rc = alloc(16, &ds))) break;
+        if (hipMemcpy(de, ee.data(), (size_t)bins * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(ds, &scale, sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { set_error("residual VQ tables: upload failed"); rc = WT_ERR_HIP; break; }
+        if (scale != 1.f) copy.acc_scale = 1.f / scale;
+        rc = launch_split_s32(w, d, n, nullptr, scale != 1.f ? static_cast<const float*>(ds) : nullptr);
+        copy.p = d;
+        t.s32.push_back(copy);
+        t.ee.push_back(static_cast<float*>(de));
+    }
+    g_launch = saved;
+    if (!rc && hipDeviceSynchronize() != hipSuccess) { set_error("residual VQ tables: the splits failed"); rc = WT_ERR_HIP; }
+    if (rc) return fail(rc);
+    t.built = true;
+    return 0;
+}
+
 
 // ------------------------------------------------------------------------------------ packed image
 // a packed on-disk weight format "folded, pre-tiled".  The image is what wt_model_create leaves in HBM —

@@ -396,7 +396,7 @@ class WavTokenizer(_BatchedCalls, nn.Module):
     def _sites(self, kind: int) -> int:
         """The fp32 range sites that matter to a plan kind (so that an overflow in the decoder does not re-plan the encoder)."""
         m = self._fp32_sites
-        if kind in (_capi.WT_PLAN_ENCODE, _capi.WT_PLAN_UNIT_LSTM):
+        if kind in (_capi.WT_PLAN_ENCODE, _capi.WT_PLAN_UNIT_LSTM, _capi.WT_PLAN_QUANTIZE):
             return m & (1 << _capi.WT_SITE_ENCODER)
         if kind == _capi.WT_PLAN_HEAD:
             return m & (1 << _capi.WT_SITE_HEAD)
@@ -540,6 +540,61 @@ class WavTokenizer(_BatchedCalls, nn.Module):
                           dev, (((B, T_pad), torch.float32, fill_wav), self._lengths_input(lengths)),
                           (((B, 512, L), torch.float32, want_feats), ((1, B, L), torch.int64, True), None), name="wt_encode_mixed")
 
+    def _rvq_codes_out(self, n_q: int, B: int, L: int, flags: int):
+        """The codes output of a residual VQ _call.  n_q is an argument of the call, not of the plan, while a graph plan keeps ONE
+        staging buffer: it is sized for every codebook, [num_quantizers][B][L], and a call writes its first n_q slabs (the
+        recording is keyed by n_q).  The caller takes [:n_q] of what _call returns."""
+        nq = self._arch.num_quantizers if flags & _capi.WT_PLAN_FLAG_GRAPH else n_q
+        return ((nq, B, L), torch.int64, True)
+
+    def _encode_rvq(self, B: int, T: int, wav, n_q: int, flags: int, dev: torch.device):
+        """WT_PLAN_ENCODE with WT_PLAN_FLAG_RVQ, plain: wav, a tensor (B, T) or the fill of one -> ((codes [n_q, B, L],), plan)."""
+        L = self._arch.frames(T)
+        wav = wav if isinstance(wav, torch.Tensor) else ((B, T), torch.float32, wav)
+        flags |= _capi.WT_PLAN_FLAG_RVQ
+        (codes,), plan = self._call(lib.wt_encode_rvq, _capi.WT_PLAN_ENCODE, B, T, flags, dev, (wav,),
+                                    (self._rvq_codes_out(n_q, B, L, flags),), (n_q,), name="wt_encode_rvq")
+        return (codes[:n_q],), plan
+
+    def _encode_rvq_mixed(self, B: int, T_pad: int, fill_wav, lengths, n_q: int, dev: torch.device):
+        """WT_PLAN_ENCODE with WT_PLAN_FLAG_RVQ | WT_PLAN_FLAG_MIXED_LENGTH: ((codes [n_q, B, L_pad],), plan), -1 past each clip's
+        frames in every row; samples past a clip's length are never read."""
+        L = self._arch.frames(T_pad)
+        flags = self._graph_flags(B) | _capi.WT_PLAN_FLAG_MIXED_LENGTH | _capi.WT_PLAN_FLAG_RVQ
+        (codes,), plan = self._call(lib.wt_encode_rvq_mixed, _capi.WT_PLAN_ENCODE, B, T_pad, flags, dev,
+                                    (((B, T_pad), torch.float32, fill_wav), self._lengths_input(lengths)),
+                                    (self._rvq_codes_out(n_q, B, L, flags),), (n_q,), name="wt_encode_rvq_mixed")
+        return (codes[:n_q],), plan
+
+    def _quantize(self, features: torch.Tensor, n_q: int, flags: int, dev: torch.device):
+        """WT_PLAN_QUANTIZE: features (B, 512, L) fp32 -> ((codes [n_q, B, L],), plan)."""
+        B, _, L = features.shape
+        (codes,), plan = self._call(lib.wt_quantize, _capi.WT_PLAN_QUANTIZE, B, L, flags, dev, (features,),
+                                    (self._rvq_codes_out(n_q, B, L, flags),), (n_q,))
+        return (codes[:n_q],), plan
+
+    def _check_n_q(self, who: str, n_q) -> int:
+        """The number of residual VQ rounds of a call, checked before any GPU work."""
+        if isinstance(n_q, bool) or not isinstance(n_q, (int, np.integer)):
+            raise ValueError(who + ": n_q must be an int between 1 and the number of codebooks, or None")
+        if not 1 <= int(n_q) <= self._arch.num_quantizers:
+            raise WavTokError(who + ": n_q must be between 1 and the number of codebooks", _capi.WT_ERR_INVALID)
+        return int(n_q)
+
+    def _run_quantize(self, x: torch.Tensor, n_q: int) -> torch.Tensor:
+        """quantizer.encode: features (B, 512, L) -> codes (n_q, B, L) on WT_PLAN_QUANTIZE."""
+        n_q = self._check_n_q("quantizer.encode", n_q)
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.feature_extractor.encodec.quantizer.dimension:
+            raise ValueError("quantizer.encode takes features (B, %d, L): the codebook width" % self.feature_extractor.encodec.quantizer.dimension)
+        if x.shape[1] != self._arch.input_channels:
+            raise WavTokError("residual VQ plans need input_channels and the encoder width equal to the codebook width", _capi.WT_ERR_INVALID)
+        if x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError("quantizer.encode: empty features")
+        dev = self._ensure_engine()
+        x = self._as_input(x, dev)
+        B = x.shape[0]
+        return self._guarded(dev, lambda: self._quantize(x, n_q, self._graph_flags(B), dev), self._is_strict(B))[0]
+
     def _decode(self, features: torch.Tensor, bw: int, flags: int, dev: torch.device, want_backbone: bool):
         """WT_PLAN_DECODE: features (B, 512, L) -> ((waveform, backbone output), plan)."""
         B, _, L = features.shape
@@ -592,12 +647,23 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         return self._guarded(dev, lambda: self._encode(B, T, audio, self._graph_flags(B), dev, want_emb), self._is_strict(B))
 
     @torch.inference_mode()
-    def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None) -> torch.Tensor:
+    def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None, n_q: Optional[int] = None) -> torch.Tensor:
         """encode_infer(audio_input, bandwidth_id=...)[1], the same bits, for a caller that wants the codes alone: (B, T) fp32 at
         the codec rate -> (1, B, L) int64.  A call that is not graph-replayed passes no feature buffer to the library (nothing
         gathers or writes the (B, 512, L) tensor); a graph-replayed one shares encode_infer's recording and staging buffers.
-        Status, fallbacks and graphs behave as in encode_infer."""
+        Status, fallbacks and graphs behave as in encode_infer.
+        n_q, an int in [1, num_quantizers]: residual VQ with the first n_q codebooks (the reference's quantizer.encode on the
+        encoder output: nearest row of codebook k to the residual, subtract, next codebook) -> (n_q, B, L), on a plan of its own
+        (WT_PLAN_FLAG_RVQ); the rows of n_q = K are the first K rows of n_q = K + 1, row 0 is the n_q=None result.  Anything
+        else raises WavTokError or ValueError before any GPU work."""
         self._check_bandwidth(bandwidth_id)
+        if n_q is not None:
+            n_q = self._check_n_q("encode_codes", n_q)
+            assert audio_input.dim() == 2, "expected audio of shape (B, T)"
+            dev = self._ensure_engine()
+            audio = self._as_input(audio_input, dev)
+            B, T = audio.shape
+            return self._guarded(dev, lambda: self._encode_rvq(B, T, audio, n_q, self._graph_flags(B), dev), self._is_strict(B))[0]
         dev = self._ensure_engine()
         assert audio_input.dim() == 2, "expected audio of shape (B, T)"
         audio = self._as_input(audio_input, dev)

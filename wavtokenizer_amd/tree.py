@@ -1,6 +1,7 @@
 """The reference-shaped parameter tree: its callables hand their work to the ``WavTokenizer`` that owns them (``pretrained.py``)."""
 from __future__ import annotations
 
+import math
 import weakref
 from typing import Optional, Tuple
 
@@ -66,7 +67,27 @@ class _CodebookLayer(_Holder):
 
 
 class ResidualVectorQuantizer(_Holder):
-    pass
+    """encodec.quantizer: the parameter holder, the reference's bandwidth arithmetic and encode (encoder/quantization/vq.py)."""
+
+    def get_bandwidth_per_quantizer(self, frame_rate: int) -> float:      # vq.py:153-157
+        """kbps one codebook adds: log2(bins) * frame_rate."""
+        return math.log2(self.bins) * frame_rate
+
+    def get_num_quantizers_for_bandwidth(self, frame_rate: int, bandwidth: Optional[float] = None) -> int:      # vq.py:142-151
+        """Codebooks that fit `bandwidth` (kbps): all of them for None or a value <= 0, else
+        max(1, floor(bandwidth * 1000 / (log2(bins) * frame_rate))); as in the reference the value is not cut to the number of
+        layers here (encode does that: core_vq.py:407 takes layers[:n_q])."""
+        n_q = self.n_q
+        if bandwidth and bandwidth > 0.:
+            n_q = int(max(1, math.floor(bandwidth * 1000 / self.get_bandwidth_per_quantizer(frame_rate))))
+        return n_q
+
+    @torch.inference_mode()
+    def encode(self, x: torch.Tensor, frame_rate: int, bandwidth: Optional[float] = None) -> torch.Tensor:      # vq.py:159-168
+        """Features (B, 512, L) -> codes (K, B, L) int64, K = get_num_quantizers_for_bandwidth(frame_rate, bandwidth) cut to the
+        number of layers: greedy residual VQ (nearest row of codebook k to the residual, lowest index on ties; subtract in fp32;
+        next codebook)."""
+        return self._root()._run_quantize(x, min(self.get_num_quantizers_for_bandwidth(frame_rate, bandwidth), self.n_q))
 
 
 class EncodecModel(_Holder):

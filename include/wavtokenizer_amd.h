@@ -842,6 +842,59 @@ typedef struct {
 size_t wt_overlap_add_ragged_workspace_bytes(int32_t B);
 int    wt_overlap_add_ragged(const wt_overlap_add_clip* clips, int32_t B, void* workspace, void* stream);
 
+/* ---- evaluation metric: log-mel spectrograms and their L1 distance ---------------------------- */
+
+/* Replaces: MelSpecReconstructionLoss (decoder/loss.py:12-39) with safe_log (decoder/modules.py:194-205), the reference's
+ * val/mel_loss (decoder/experiment.py:257-304), as a metric: no gradient.  The transform restates what
+ * torchaudio.transforms.MelSpectrogram(sample_rate, n_fft=1024, hop_length, n_mels, center=True, power=1) computes with its
+ * defaults (torchaudio is not in this image: restated from its published algorithm, parity unpinned, like the resampler).  For a
+ * clip x of T samples: reflect padding by n_fft / 2 on both sides (T > n_fft / 2, as torch.stft demands), F = 1 + T / hop_length
+ * frames of n_fft samples, periodic Hann window, magnitudes S of the n_fft / 2 + 1 bins of the real FFT, triangular filters on the
+ * HTK mel scale without area normalisation:
+ *   all_freqs = linspace(0, sample_rate / 2 (integer division), n_fft / 2 + 1)
+ *   m_pts = linspace(0, 2595 log10(1 + (sample_rate / 2) / 700), n_mels + 2),  f_pts = 700 (10^(m_pts / 2595) - 1)
+ *   fb[k][m] = max(0, min((all_freqs[k] - f_pts[m]) / (f_pts[m+1] - f_pts[m]), (f_pts[m+2] - all_freqs[k]) / (f_pts[m+2] - f_pts[m+1])))
+ *   M[m][f] = sum_k fb[k][m] S[k][f],  L = log(max(M, 1e-7)),  distance = mean over the clip's n_mels * F entries of |L(a) - L(b)|.
+ * Window, twiddles and filters are computed in float64 on the host when the handle is made and rounded once; the FFT runs in fp32.
+ * A frame's values depend on that frame's n_fft samples alone, and a clip's spectrogram and distance have the same bits alone, in
+ * any batch and at any position of it (no float atomics; fixed summation orders that depend on the clip's F alone).
+ * n_fft must be 1024, hop_length in 1..1024, n_mels in 1..128, sample_rate >= 2: anything else is refused (WT_ERR_INVALID).
+ * The create call puts its tables on `device` and leaves the calling thread's current device as it found it; the spectrogram
+ * and distance calls launch on the current device, which must be the handle's. */
+typedef struct wt_mel wt_mel;
+int     wt_mel_create(int32_t sample_rate, int32_t n_fft, int32_t hop_length, int32_t n_mels, int32_t device, wt_mel** out);
+void    wt_mel_destroy(wt_mel* m);
+/* 1 + T / hop_length, or -1 when T <= n_fft / 2 (or m is null) */
+int64_t wt_mel_frames(const wt_mel* m, int64_t T);
+/* Host only, no device needed: the tables a handle of these parameters uploads.  window [n_fft] and fb, dense
+ * [n_fft / 2 + 1][n_mels]; either may be null. */
+int     wt_mel_tables(int32_t sample_rate, int32_t n_fft, int32_t n_mels, float* window, float* fb);
+/* One clip of a launch.  a, b and out are device pointers, fp32; length counts samples (of a, and of b in a distance call).
+ *   spectrogram: out [n_mels][F], F = 1 + length / hop_length; b is ignored
+ *   distance:    out is one float */
+typedef struct {
+    const float* a;
+    const float* b;
+    int64_t length;
+    float* out;
+} wt_mel_clip;
+/* Bytes of the device workspace of a call with B clips whose frame counts add up to total_frames (a spectrogram call may pass
+ * total_frames = 0): the descriptors, then one partial sum per frame of a distance call. */
+size_t  wt_mel_workspace_bytes(int32_t B, int64_t total_frames);
+/* One launch computes the spectrograms of B clips of any lengths (log = 0: M, else L); a distance call is that launch on both
+ * signals of every clip, which writes per frame the sum over the filters of |La - Lb| (the same bits L has in a spectrogram call)
+ * to the workspace, and a second small launch that adds each clip's partials and divides by n_mels * F.  Nothing outside
+ * [0, length) of a or b is read and nothing outside out's n_mels * F (or one) floats and the workspace is written; the content of
+ * the workspace before the call does not matter.  clips is a HOST array.  workspace: device, the bytes above, 8-byte aligned, its
+ * content untouched until the launches have run.  Up to 64 clips travel in the launches' own argument blocks: the call then makes
+ * no host wait and no copy and may be captured into a graph.  More clips go through the pinned descriptor blocks of wt_ingest and
+ * wt_emit (their events and their lock): such a call must NOT be made on a stream that is being captured.  Every descriptor is
+ * checked before any device call: a null handle, a null a or out, a null b in a distance call, length <= n_fft / 2, a pointer
+ * not aligned to 4 bytes, B outside 1..65535, or a handle of another device than the calling thread's current one returns
+ * WT_ERR_INVALID with a message and touches no memory. */
+int     wt_mel_spectrogram(const wt_mel* m, const wt_mel_clip* clips, int32_t B, int32_t log, void* workspace, void* stream);
+int     wt_mel_distance(const wt_mel* m, const wt_mel_clip* clips, int32_t B, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,7 +131,30 @@ def stage1(DOWN=4):
     return extra
 
 
+# ------------------------------------------------------------------------------- mel.hip: 512-point radix-8 Stockham FFT of one wave
+def mel_swz(i):
+    """mel.hip mel_swz: point i of a float plane sits at word i ^ ((i >> 3) & 7) ^ (((i >> 6) & 3) << 3)"""
+    return i ^ ((i >> 3) & 7) ^ (((i >> 6) & 3) << 3)
+
+
+def mel_fft():
+    print("--- mel_frame (mel.hip): two float planes of 512 points per wave, per wave-instruction")
+    pats = [("pass 1 store, point 8 lane + q", "ds_write_b32", lambda l, q: 8 * l + q),
+            ("pass 2 / 3 load, point lane + 64 r", "ds_read_b32", lambda l, r: l + 64 * r),
+            ("pass 2 store, point 64 (lane / 8) + lane % 8 + 8 q", "ds_write_b32", lambda l, q: 64 * (l >> 3) + (l & 7) + 8 * q),
+            ("pass 3 store, point lane + 64 q", "ds_write_b32", lambda l, q: l + 64 * q),
+            ("split pass load, point (512 - lane - 64 r) % 512", "ds_read_b32", lambda l, r: (512 - l - 64 * r) & 511)]
+    for label, swz in (("plain layout", lambda i: i), ("mel_swz", mel_swz)):
+        extra = 0
+        for name, instr, fn in pats:
+            extra += report(f"{label}: {name}", instr, lambda l, v: 4 * swz(fn(l, v)), list(range(8)))
+        print(f"      extra LDS cycles (above the conflict-free count) summed over the listed variants: {extra}")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["mel"]:
+        mel_fft()
+        sys.exit(0)
     for new in (False, True):
         NEW = new
         print(f"===== {'round 3' if new else 'round 2'} layouts")

@@ -29,6 +29,7 @@ EXPORTS = [
     "wt_emit_workspace_bytes", "wt_emit", "wt_vq_probe", "wt_overlap_add_ragged_workspace_bytes", "wt_overlap_add_ragged",
     "wt_model_weight_count", "wt_model_weight_info", "wt_split_probe",
     "wt_encode_rvq", "wt_encode_rvq_mixed", "wt_quantize", "wt_vq_residual_probe", "wt_model_codebook_tables",
+    "wt_mel_create", "wt_mel_destroy", "wt_mel_frames", "wt_mel_tables", "wt_mel_workspace_bytes", "wt_mel_spectrogram", "wt_mel_distance",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -181,6 +182,11 @@ class WtOverlapAddClip(ctypes.Structure):
                 ("weight", c_void_p), ("out", c_void_p)]
 
 
+class WtMelClip(ctypes.Structure):
+    """wt_mel_clip: one clip of a mel launch (wt_mel_spectrogram, wt_mel_distance)."""
+    _fields_ = [("a", c_void_p), ("b", c_void_p), ("length", c_int64), ("out", c_void_p)]
+
+
 WT_WEIGHT_F32, WT_WEIGHT_S32, WT_WEIGHT_LSTM_F16, WT_WEIGHT_LSTM_PERSIST = 0, 1, 2, 3
 WT_SPLIT, WT_UNSPLIT, WT_POW2_SCALES = 0, 1, 2
 
@@ -327,6 +333,16 @@ def _load() -> ctypes.CDLL:
     lib.wt_quantize.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
     lib.wt_vq_residual_probe.argtypes = [POINTER(WtVqResidualDesc), POINTER(WtVqResidualForm), c_void_p]
     lib.wt_model_codebook_tables.argtypes = [c_void_p, c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_float)]
+    lib.wt_mel_create.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]
+    lib.wt_mel_destroy.argtypes = [c_void_p]
+    lib.wt_mel_destroy.restype = None
+    lib.wt_mel_frames.argtypes = [c_void_p, c_int64]
+    lib.wt_mel_frames.restype = c_int64
+    lib.wt_mel_tables.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.wt_mel_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_mel_workspace_bytes.restype = c_size_t
+    lib.wt_mel_spectrogram.argtypes = [c_void_p, POINTER(WtMelClip), c_int32, c_int32, c_void_p, c_void_p]
+    lib.wt_mel_distance.argtypes = [c_void_p, POINTER(WtMelClip), c_int32, c_void_p, c_void_p]
     return lib
 
 

@@ -560,6 +560,20 @@ class _BatchedCalls:
                                 lambda cs, L_pad: self._run_decode_codes_mixed(cs, L_pad, bw),
                                 lambda c: self.decode_codes(c, bandwidth_id=bw))
 
+    def round_trip_mel_distance(self, wavs: Sequence[torch.Tensor], *, n_q: Optional[int] = None, bandwidth_id=None, **kw) -> torch.Tensor:
+        """How well the codec gives a set of clips back, as the reference's val/mel_loss per clip: wavs is a list of 1-D fp32 clips
+        at the codec rate on the model's device; returns (n,) fp32.  It is encode_codes_many -> decode_codes_many -> each output
+        cropped to its input's length -> metrics.mel_distance_many(outputs, wavs, **kw), and nothing else; n_q and bandwidth_id
+        go to the two codec calls (the decoder needs a bandwidth_id, as in decode), kw (sample_rate, n_fft, hop_length, n_mels) to
+        the metric."""
+        from . import metrics
+        wavs = list(wavs)
+        if not wavs:
+            return torch.zeros(0, dtype=torch.float32, device=self._ensure_engine())
+        codes = self.encode_codes_many(wavs, bandwidth_id=bandwidth_id, n_q=n_q)
+        outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
+        return metrics.mel_distance_many([o[0, :w.shape[-1]] for o, w in zip(outs, wavs)], wavs, **kw)
+
     # -- synthesise straight to PCM: decode from codes -> ragged emit (resample, channels, layout, sample type) into one tensor -----
     def _emit_format(self, who: str, channels, dtype, limit, n: int) -> Tuple[List[int], Tuple[torch.dtype, float]]:
         """(channels per clip, (dtype, limit)) of decode_pcm / decode_pcm_many over n clips, checked: ValueError for anything

@@ -474,6 +474,10 @@ int wt_convert_audio(const wt_resampler* r, const float* wav, int32_t B, int32_t
     return WT_OK;
 }
 
+}  // extern "C"
+
+namespace wt {
+
 // The host-side staging of wt_ingest's and wt_emit's descriptors: two pinned blocks per device, each guarded by the event recorded behind
 // the copy that last read it, so the upload never waits for the stream and never reads a block that is being rewritten.
 struct IngestStage {
@@ -486,8 +490,8 @@ struct IngestStage {
 static IngestStage g_ingest_stage[64];
 
 // Uploads a launch's device-form descriptors (wt_ingest, wt_emit) into its workspace on s through the device's next pinned block
-// (a block that has to grow is given at least min_bytes).
-static int stage_descriptors(int device, const void* descs, size_t bytes, size_t min_bytes, void* workspace, hipStream_t s) {
+// (a block that has to grow is given at least min_bytes).  Shared with wt_mel_spectrogram / wt_mel_distance (mel.hip).
+int stage_descriptors(int device, const void* descs, size_t bytes, size_t min_bytes, void* workspace, hipStream_t s) {
     IngestStage& st = g_ingest_stage[device];
     std::lock_guard<std::mutex> lock(st.mu);
     const int k = st.next;
@@ -505,6 +509,10 @@ static int stage_descriptors(int device, const void* descs, size_t bytes, size_t
     WT_HIP_CHECK(hipEventRecord(st.ev[k], s));
     return WT_OK;
 }
+
+}  // namespace wt
+
+extern "C" {
 
 static size_t resampler_window_bytes(const wt_resampler* r) {
     return (size_t)(256 / r->nw + 2) * r->orig * sizeof(float) + (size_t)r->K * sizeof(float);

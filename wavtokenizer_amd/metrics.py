@@ -1,0 +1,149 @@
+"""The codec's evaluation metric on the GPU: log-mel spectrograms and their L1 distance, the reference's val/mel_loss
+(MelSpecReconstructionLoss, decoder/loss.py:12-39, with safe_log, decoder/modules.py:194-205) as a number for inference users.
+
+    mel_spectrogram(wav, ...)                 (T,), (B, T) or (B, 1, T) -> (..., n_mels, F), F = 1 + T // hop_length
+    mel_spectrogram_many(wavs, ...)           clips of different lengths, one launch -> [(n_mels, F_i)] views of one flat tensor
+    mel_distance(y_hat, y, ...)               0-dim: the mean of the per-clip distances (equal lengths: the reference's l1_loss mean)
+    mel_distance_many(y_hats, ys, ...)        (n,) per-clip distances, one launch pair
+
+The transform restates torchaudio.transforms.MelSpectrogram(sample_rate, n_fft=1024, hop_length=256, n_mels=100, center=True,
+power=1) (include/wavtokenizer_amd.h gives the definition; parity with torchaudio itself is unpinned, it is not available to the
+tests).  A clip's spectrogram and distance have the same bits alone, in any batch and at any position.  Tensors are fp32 on the
+GPU; there is no CPU path.  `MelSpecReconstructionLoss()(y_hat, y)` becomes `mel_distance(y_hat, y)`."""
+import ctypes
+from typing import Dict, List, Sequence, Tuple
+
+import torch
+
+from ._capi import WtMelClip, check, lib
+
+_handles: Dict[Tuple[int, int, int, int, int], ctypes.c_void_p] = {}
+
+
+def _need_gpu(t: torch.Tensor):
+    if t.device.type != "cuda":
+        raise RuntimeError("wavtokenizer_amd.metrics runs only on an AMD GPU: move the tensor with .to('cuda'). "
+                           "There is no CPU path in this package.")
+
+
+def mel_handle(sample_rate: int, n_fft: int, hop_length: int, n_mels: int, device_index: int) -> ctypes.c_void_p:
+    """The wt_mel of a parameter set on a device, created once per process."""
+    key = (int(sample_rate), int(n_fft), int(hop_length), int(n_mels), int(device_index))
+    if key not in _handles:
+        h = ctypes.c_void_p()
+        check(lib.wt_mel_create(*key, ctypes.byref(h)), "wt_mel_create")
+        _handles[key] = h
+    return _handles[key]
+
+
+def mel_frames(length: int, n_fft: int = 1024, hop_length: int = 256) -> int:
+    """wt_mel_frames on the host: 1 + length // hop_length; ValueError for a clip reflect padding cannot take."""
+    if int(length) <= n_fft // 2:
+        raise ValueError(f"a clip of {int(length)} samples is too short for reflect padding by {n_fft // 2}")
+    return 1 + int(length) // int(hop_length)
+
+
+def _clips(who: str, wavs: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], torch.device]:
+    wavs = list(wavs)
+    for w in wavs:
+        if not isinstance(w, torch.Tensor) or w.dim() != 1:
+            raise ValueError(who + ": every clip must be a 1-D tensor")
+        _need_gpu(w)
+    dev = wavs[0].device
+    if any(w.device != dev for w in wavs):
+        raise ValueError(who + ": all clips must be on one device")
+    return [w.to(torch.float32).contiguous() for w in wavs], dev
+
+
+def _run(dev: torch.device, a: List[torch.Tensor], b, outs_numel: int, out_offsets: List[int], log, sample_rate, n_fft, hop_length, n_mels):
+    """One wt_mel_spectrogram (b is None) or wt_mel_distance call over the clips; returns the flat output tensor."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    n = len(a)
+    frames = [mel_frames(w.shape[0], n_fft, hop_length) for w in a]
+    with torch.cuda.device(idx):
+        h = mel_handle(sample_rate, n_fft, hop_length, n_mels, idx)
+        out = torch.empty(outs_numel, dtype=torch.float32, device=dev)
+        ws_bytes = int(lib.wt_mel_workspace_bytes(n, sum(frames) if b is not None else 0))
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        descs = (WtMelClip * n)()
+        for i in range(n):
+            descs[i].a = a[i].data_ptr()
+            descs[i].b = b[i].data_ptr() if b is not None else None
+            descs[i].length = a[i].shape[0]
+            descs[i].out = out.data_ptr() + 4 * out_offsets[i]
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if b is None:
+            check(lib.wt_mel_spectrogram(h, descs, n, 1 if log else 0, ctypes.c_void_p(ws.data_ptr()), stream), "wt_mel_spectrogram")
+        else:
+            check(lib.wt_mel_distance(h, descs, n, ctypes.c_void_p(ws.data_ptr()), stream), "wt_mel_distance")
+        # (the launches are queued on the current stream: the caching allocator hands ws and the inputs' copies out again only to
+        # work queued behind them on that stream)
+    return out, frames
+
+
+def mel_spectrogram_many(wavs: Sequence[torch.Tensor], *, sample_rate: int = 24000, n_fft: int = 1024, hop_length: int = 256,
+                         n_mels: int = 100, log: bool = True) -> List[torch.Tensor]:
+    """Log-mel (log=False: linear mel) spectrograms of 1-D clips of different lengths in one launch: [(n_mels, F_i)], views of one
+    flat tensor.  Clip i's result is the bits of mel_spectrogram(wavs[i])."""
+    if not len(wavs):
+        return []
+    a, dev = _clips("mel_spectrogram_many", wavs)
+    frames = [mel_frames(w.shape[0], n_fft, hop_length) for w in a]
+    offs = [0]
+    for f in frames:
+        offs.append(offs[-1] + n_mels * f)
+    flat, _ = _run(dev, a, None, offs[-1], offs[:-1], log, sample_rate, n_fft, hop_length, n_mels)
+    return [flat[offs[i]: offs[i + 1]].view(n_mels, frames[i]) for i in range(len(a))]
+
+
+def mel_spectrogram(wav: torch.Tensor, *, sample_rate: int = 24000, n_fft: int = 1024, hop_length: int = 256, n_mels: int = 100,
+                    log: bool = True) -> torch.Tensor:
+    """(T,), (B, T) or (B, 1, T) fp32 on the GPU -> (n_mels, F), (B, n_mels, F) or (B, 1, n_mels, F)."""
+    _need_gpu(wav)
+    if wav.dim() not in (1, 2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
+        raise ValueError("mel_spectrogram: wav must be (T,), (B, T) or (B, 1, T)")
+    T = int(wav.shape[-1])
+    rows = wav.to(torch.float32).contiguous().view(-1, T)
+    F = mel_frames(T, n_fft, hop_length)
+    if rows.shape[0] == 0:
+        return torch.empty((*wav.shape[:-1], n_mels, F), dtype=torch.float32, device=wav.device)
+    a = list(rows.unbind(0))
+    offs = [i * n_mels * F for i in range(len(a))]
+    flat, _ = _run(wav.device, a, None, len(a) * n_mels * F, offs, log, sample_rate, n_fft, hop_length, n_mels)
+    return flat.view(*wav.shape[:-1], n_mels, F)
+
+
+def mel_distance_many(y_hats: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], *, sample_rate: int = 24000, n_fft: int = 1024,
+                      hop_length: int = 256, n_mels: int = 100) -> torch.Tensor:
+    """Per pair of 1-D clips the mean of |log-mel(y_hat) - log-mel(y)| over the pair's n_mels * F entries: (n,) fp32, one launch
+    pair for all clips.  The two clips of a pair must have one length (ValueError otherwise); pairs may differ."""
+    y_hats, ys = list(y_hats), list(ys)
+    if len(y_hats) != len(ys):
+        raise ValueError("mel_distance_many: as many y_hats as ys")
+    for i, (p, q) in enumerate(zip(y_hats, ys)):
+        if isinstance(p, torch.Tensor) and isinstance(q, torch.Tensor) and p.dim() == 1 and q.dim() == 1 and p.shape[0] != q.shape[0]:
+            raise ValueError(f"mel_distance_many: pair {i}: lengths {p.shape[0]} and {q.shape[0]} differ")
+    if not y_hats:
+        return torch.zeros(0, dtype=torch.float32, device="cuda")
+    a, dev = _clips("mel_distance_many", y_hats)
+    b, dev_b = _clips("mel_distance_many", ys)
+    if dev_b != dev:
+        raise ValueError("mel_distance_many: all clips must be on one device")
+    out, _ = _run(dev, a, b, len(a), list(range(len(a))), True, sample_rate, n_fft, hop_length, n_mels)
+    return out
+
+
+def mel_distance(y_hat: torch.Tensor, y: torch.Tensor, *, sample_rate: int = 24000, n_fft: int = 1024, hop_length: int = 256,
+                 n_mels: int = 100) -> torch.Tensor:
+    """0-dim tensor: the mean over the clips of mel_distance_many's per-clip distances; y_hat and y are (T,), (B, T) or (B, 1, T)
+    of one shape.  Every clip has the same number of entries, so this is the reference's l1_loss mean over the whole batch."""
+    if y_hat.shape != y.shape:
+        raise ValueError(f"mel_distance: shapes {tuple(y_hat.shape)} and {tuple(y.shape)} differ")
+    if y.dim() not in (1, 2, 3) or (y.dim() == 3 and y.shape[1] != 1):
+        raise ValueError("mel_distance: inputs must be (T,), (B, T) or (B, 1, T)")
+    _need_gpu(y_hat)
+    _need_gpu(y)
+    T = int(y.shape[-1])
+    p = list(y_hat.to(torch.float32).contiguous().view(-1, T).unbind(0))
+    q = list(y.to(torch.float32).contiguous().view(-1, T).unbind(0))
+    return mel_distance_many(p, q, sample_rate=sample_rate, n_fft=n_fft, hop_length=hop_length, n_mels=n_mels).mean()

@@ -650,7 +650,7 @@ size_t wt_lstm_probe_workspace_bytes(const wt_lstm_desc* d);
 int wt_lstm_probe(const wt_model* m, const wt_lstm_desc* d, wt_lstm_form* form, void* workspace, void* stream);
 
 /* The weights as loaded: every device array of a model that a plan can read, by name, read-only.  One walk over the model
- * (weights.cpp model_weights) lists them in a fixed order; `index` runs over [0, count).  Conv weights are "<layer>.w"
+ * (packed.cpp model_weights) lists them in a fixed order; `index` runs over [0, count).  Conv weights are "<layer>.w"
  * [cout][k][cin] and "<layer>.b", GEMM weights "<layer>" [rows][cols]; the S32 copy of either is "<layer>.s32" and names the
  * fp32 array it stands for in `of`.
  *   format     0: fp32; 1: S32 (128-byte groups [32 x f16 hi | 32 x f16 lo], value = (hi + lo / 2048) * acc_scale);
@@ -662,7 +662,8 @@ int wt_lstm_probe(const wt_model* m, const wt_lstm_desc* d, wt_lstm_form* form, 
  *              storage scale of that copy) before the first plan on fp32 operands; asking for it here rebuilds it first.
  *              2: an fp32 array that nothing reads after the load (the tap-paired repacking of a down conv): a model made
  *              from a packed image holds no defined values there.  0: stored
- *   archived   1: the pointer is one that the packed image's model section writes
+ *   archived   1: the pointer is one that the packed image's model section writes.  Always 1: the listing and the section
+ *              come from the same walk over the model
  *   alloc      index of the model allocation that starts at `data`, in the order of the packed image's allocation table (-1: the
  *              pointer is no allocation's base) */
 typedef struct {

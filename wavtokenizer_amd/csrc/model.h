@@ -1,4 +1,4 @@
-// Internal types of the host side of libwavtok_hip.so: the packed model (weights.cpp), launch plans (plan.cpp)
+// Internal types of the host side of libwavtok_hip.so: the packed model (weights.cpp, packed.cpp), launch plans (plan.cpp)
 // and what the extern "C" entry points (capi.cpp, run.cpp, probe.cpp) share with them.
 #pragma once
 #include "../../include/wavtokenizer_amd.h"
@@ -357,14 +357,15 @@ int build_splits(wt_model* M);
 // read the copy take acc_scale = 1 / this.  0: no power of two does (amax below 2^-126: the scale or its reciprocal would not be
 // a normal float), the tensor cannot be split
 float s32_weight_scale(float amax);
-// packed image of a model (weights.cpp): everything wt_model_create computes and uploads, ready to upload again
+int ensure_rvq_tables(const wt_model* M);                         // builds wt_model::rvq once (thread-safe); the current device is the model's
+int ensure_f32_weights(const wt_model* M);                        // fills the lazy fp32 arrays of a packed model (first fp32 plan)
+// packed.cpp: one walk over the model's arrays (walk_model) serves the packed image, its validation and the listing.
+// packed image of a model: everything wt_model_create computes and uploads, ready to upload again
 size_t model_export_bytes(const wt_model* M);
 int model_export(const wt_model* M, void* buf, size_t n);
 int model_import(wt_model* M, const void* buf, size_t n);        // M->device set; allocates and uploads
 int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint64_t* arch_hash);
-int ensure_rvq_tables(const wt_model* M);                         // builds wt_model::rvq once (thread-safe); the current device is the model's
-int ensure_f32_weights(const wt_model* M);                        // fills the lazy fp32 arrays of a packed model (first fp32 plan)
-// every device array of the model that a plan can read, by name (wt_model_weight_info): the one walk over the model's weights
+// every device array of the model that a plan can read, by name (wt_model_weight_info): the arrays of the one walk
 enum : int { WFMT_F32 = 0, WFMT_S32 = 1, WFMT_LSTM_F16 = 2, WFMT_LSTM_PERSIST = 3 };
 struct WeightEntry {
     std::string name, of;          // of: the fp32 array an S32 copy stands for
@@ -377,7 +378,7 @@ struct WeightEntry {
     bool tap_pair = false;
     int lazy = 0;                  // 1: rebuilt from the S32 copy (wt_model::lazy_f32), 2: nothing reads it after the load
     float lazy_scale = 1.f;
-    bool archived = false;         // archive_model writes this pointer
+    bool archived = false;         // the image's model section writes this pointer: true of every entry (the listing is the image's walk)
     int alloc = -1;                // index of the model allocation that starts at data (-1: none does)
 };
 std::vector<WeightEntry> model_weights(const wt_model* M);

@@ -1,6 +1,6 @@
 // Weight folding / packing, done once at wt_model_create: weight-norm fold (fp64), conv repacking to [Cout][tap][Cin],
 // LSTM gate-row packings (fp32 and split-f16 per-lane forms), the packed ISTFT head and inverse-DFT basis, and the
-// split-f16 (S32 / f16x2) copies of every GEMM weight.
+// split-f16 (S32 / f16x2) copies of every GEMM weight.  What lists, stores and checks the result is packed.cpp.
 #include "model.h"
 
 namespace wt {
@@ -454,22 +454,28 @@ float s32_weight_scale(float amax) {
     (void)std::frexp(amax, &e);                 // amax = m * 2^e, m in [0.5, 1)
     return std::ldexp(1.f, (amax < 1.f ? 1 : 12) - e);      // amax * scale in [1, 2), or in [2^11, 2^12)
 }
+// The scale a host tensor's S32 copy is stored with, and its largest finite |w|.  finite = false: the copy is unusable and is
+// stored as it is (scale 1): a non-finite element, or no usable power of two, which counts as one
+struct S32Scale { float scale, amax; bool finite; };
+static S32Scale s32_scale_of(const std::vector<float>& h) {
+    float amax = 0.f;                            // (locals: the scan runs over some 180 M words per model)
+    bool finite = true;
+    for (const float x : h) {
+        const float v = std::fabs(x);
+        if (!(v <= 3.0e38f)) finite = false;
+        else amax = std::max(amax, v);
+    }
+    const float scale = finite ? s32_weight_scale(amax) : 1.f;
+    return scale == 0.f ? S32Scale{1.f, amax, false} : S32Scale{scale, amax, finite};
+}
 static int add_s32(wt_model* M, const float* w, long n, S32Copy* out, bool* split_ok = nullptr, bool gemm_only = false) {
     if (!w || n <= 0 || (n % 32)) return 0;
     if (!split_ok) split_ok = &M->s32_ok;
     std::vector<float> h((size_t)n);
     WT_HIP_CHECK(hipMemcpy(h.data(), w, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    float amax = 0.f;
-    bool finite = true;
-    for (long i = 0; i < n; ++i) {
-        const float v = std::fabs(h[i]);
-        if (!(v <= 3.0e38f)) finite = false;
-        else amax = std::max(amax, v);
-    }
+    const auto [scale, amax, finite] = s32_scale_of(h);
     if (!finite) *split_ok = false;
     M->w_amax = std::max(M->w_amax, amax);
-    float scale = finite ? s32_weight_scale(amax) : 1.f;
-    if (scale == 0.f) { *split_ok = false; finite = false; scale = 1.f; }     // no usable power of two: as a non-finite weight
     // the scale is read by the split below only: a word of its own until build_splits has waited for the splits (load_tmp, which
     // free_model releases too), not a model allocation
     float* scale_dev = nullptr;
@@ -586,15 +592,7 @@ int ensure_rvq_tables(const wt_model* M) {
     for (int k = 1; k < nq && !rc; ++k) {
         const float* w = M->embed.w + (size_t)k * n;
         if (hipMemcpy(h.data(), w, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { set_error("residual VQ tables: reading codebook failed"); rc = WT_ERR_HIP; break; }
-        float amax = 0.f;
-        bool finite = true;
-        for (long i = 0; i < n; ++i) {
-            const float v = std::fabs(h[i]);
-            if (!(v <= 3.0e38f)) finite = false;
-            else amax = std::max(amax, v);
-        }
-        float scale = finite ? s32_weight_scale(amax) : 1.f;
-        if (scale == 0.f) { finite = false; scale = 1.f; }
+        const auto [scale, amax, finite] = s32_scale_of(h);
         if (!finite) t.s32_ok = false;
         for (int r = 0; r < bins; ++r) {     // embed.pow(2).sum(0), as codebook 0's table
             float s = 0.f;
@@ -619,359 +617,6 @@ int ensure_rvq_tables(const wt_model* M) {
     return 0;
 }
 
-
-// ------------------------------------------------------------------------------------ packed image
-// a packed on-disk weight format "folded, pre-tiled".  The image is what wt_model_create leaves in HBM —
-// folded conv weights in [Cout][tap][Cin], LSTM gate-row packings, the packed head and inverse-DFT basis, the S32 and
-// f16x2 split copies with their per-tensor scales — as the list of device allocations in creation order, preceded by a
-// header (magic, version, the wt_arch and a hash of it) and the model struct with every pointer written as
-// (allocation index).  Loading it is allocate + upload + fix up pointers: nothing is folded, packed or split again.
-static constexpr uint32_t PACK_MAGIC = 0x4b505457u;     // "WTPK"
-static constexpr int32_t PACK_VERSION = 7;
-
-static uint64_t arch_hash_of(const wt_arch& a) {        // FNV-1a over the architecture struct and the layout version
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; ++i) { h ^= static_cast<const unsigned char*>(p)[i]; h *= 1099511628211ull; } };
-    mix(&a, sizeof(a));
-    mix(&PACK_VERSION, sizeof(PACK_VERSION));
-    return h;
-}
-
-struct Archive {
-    bool saving;
-    std::vector<char>* out = nullptr;          // saving
-    const char* in = nullptr;                  // loading
-    size_t pos = 0, n = 0;
-    bool ok = true;
-    const std::map<const void*, int>* index = nullptr;      // saving: allocation base -> index
-    const std::vector<void*>* allocs = nullptr;             // loading: index -> allocation base
-    const std::vector<size_t>* alloc_bytes = nullptr;       // loading: index -> allocation size (pointer offsets are checked)
-    std::vector<const void*>* seen = nullptr;               // saving: every pointer written (model_weights compares its walk with it)
-    void raw(void* p, size_t bytes) {
-        if (saving) { const char* c = static_cast<const char*>(p); out->insert(out->end(), c, c + bytes); }
-        else { if (!ok || bytes > n - pos) { ok = false; std::memset(p, 0, bytes); return; } std::memcpy(p, in + pos, bytes); pos += bytes; }
-    }
-    // an element count read from the file: bounded before anything is resized by it
-    int32_t count(size_t have, int32_t limit) {
-        int32_t c = (int32_t)have;
-        pod(c);
-        if (!saving && (c < 0 || c > limit)) { ok = false; c = 0; }
-        return c;
-    }
-    template <class T> void pod(T& v) { raw(&v, sizeof(T)); }
-    template <class T> void ptr(T*& p) {       // a device pointer = (allocation index, byte offset); -1 = null
-        int32_t idx = -1;
-        int64_t off = 0;
-        if (saving && p) {
-            if (seen) seen->push_back(static_cast<const void*>(p));
-            auto it = index->upper_bound(static_cast<const void*>(p));
-            if (it == index->begin()) { ok = false; }
-            else { --it; idx = it->second; off = reinterpret_cast<const char*>(p) - static_cast<const char*>(it->first); }
-        }
-        pod(idx); pod(off);
-        if (!saving) {
-            if (idx < 0) p = nullptr;
-            else if (!ok || idx >= (int)allocs->size() || off < 0 || (size_t)off >= (*alloc_bytes)[idx]) { ok = false; p = nullptr; }
-            else p = reinterpret_cast<T*>(static_cast<char*>((*allocs)[idx]) + off);
-        }
-    }
-    void s32(S32Copy& s) { ptr(s.p); pod(s.acc_scale); pod(s.tap_pair); }
-    void conv(ConvW& c) { ptr(c.w); ptr(c.b); pod(c.cout); pod(c.cin); pod(c.k); s32(c.s32); }
-    void gemm(GemmW& g) { ptr(g.w); pod(g.rows); pod(g.cols); s32(g.s32); }
-    void lstm(LstmW& l) { gemm(l.Wih0); ptr(l.b0); ptr(l.W0); ptr(l.W1); ptr(l.b1); ptr(l.W0h); ptr(l.W1h); ptr(l.Wp); }
-};
-
-static void archive_model(Archive& ar, wt_model* M) {
-    ar.pod(M->hop); ar.pod(M->H); ar.pod(M->weight_bytes); ar.pod(M->s32_ok); ar.pod(M->sd_s32_ok); ar.pod(M->w_amax);
-    int32_t n = ar.count(M->enc_ratios.size(), 8);
-    M->enc_ratios.resize(n);
-    for (int& r : M->enc_ratios) ar.pod(r);
-    ar.ptr(M->e0_w); ar.ptr(M->e0_b); ar.pod(M->e0_k); ar.pod(M->e0_c);
-    n = ar.count(M->stages.size(), 8); M->stages.resize(n);
-    for (ResStage& st : M->stages) { ar.conv(st.c3); ar.conv(st.c1); ar.conv(st.sc); ar.conv(st.down); ar.conv(st.cat); ar.pod(st.C); ar.pod(st.r); }
-    ar.lstm(M->enc_lstm); ar.conv(M->enc_final); ar.gemm(M->embed); ar.ptr(M->ee);
-    ar.conv(M->bb_embed);
-    for (PosRes& r : M->res) { ar.ptr(r.n1w); ar.ptr(r.n1b); ar.ptr(r.n2w); ar.ptr(r.n2b); ar.conv(r.c1); ar.conv(r.c2); }
-    ar.ptr(M->at_nw); ar.ptr(M->at_nb); ar.gemm(M->at_Wqk); ar.ptr(M->at_bqk); ar.gemm(M->at_Wv); ar.ptr(M->at_bv); ar.gemm(M->at_Wp); ar.ptr(M->at_bp);
-    ar.ptr(M->gn5w); ar.ptr(M->gn5b); ar.ptr(M->ada_s); ar.ptr(M->ada_h);
-    n = ar.count(M->cnx.size(), 64); M->cnx.resize(n);
-    for (CnxBlock& c : M->cnx) { ar.ptr(c.dw_w); ar.ptr(c.dw_b); ar.ptr(c.ada_s); ar.ptr(c.ada_h); ar.gemm(c.W1); ar.ptr(c.b1); ar.gemm(c.W2); ar.ptr(c.b2); ar.ptr(c.gamma); }
-    ar.ptr(M->fln_w); ar.ptr(M->fln_b); ar.gemm(M->head_W); ar.ptr(M->head_b);
-    ar.pod(M->Kb); ar.pod(M->Kq); ar.pod(M->bins_f); ar.pod(M->R);
-    ar.gemm(M->istft_W); ar.ptr(M->wsq); ar.ptr(M->win);
-    ar.pod(M->has_seadec); ar.conv(M->sd_first); ar.lstm(M->sd_lstm);
-    n = ar.count(M->sd_stages.size(), 8); M->sd_stages.resize(n);
-    for (SeaDecStage& st : M->sd_stages) {
-        ar.ptr(st.tr_w); ar.gemm(st.tr_wp); ar.ptr(st.tr_b); ar.pod(st.cin); ar.pod(st.cout); ar.pod(st.k); ar.pod(st.r);
-        ar.conv(st.c3); ar.conv(st.c1); ar.conv(st.sc); ar.conv(st.cat);
-    }
-    ar.ptr(M->sd_last_w); ar.ptr(M->sd_last_b);
-    n = ar.count(M->lazy_f32.size(), 1 << 12); M->lazy_f32.resize(n);
-    for (wt_model::LazyF32& z : M->lazy_f32) { ar.ptr(z.w); ar.ptr(z.s32); ar.pod(z.n); ar.pod(z.scale); }
-}
-
-struct PackHeader {
-    uint32_t magic;
-    int32_t version;
-    wt_arch arch;
-    uint64_t arch_hash;
-    uint64_t n_allocs, struct_bytes, payload_bytes;
-    uint64_t body_hash;        // over the allocation table, the model section and the payload (everything behind the header)
-};
-
-// 64-bit hash of a byte range, four interleaved multiply-xor lanes over 8-byte words (a serial FNV over ~0.7 GB would
-// take longer than the upload itself); the tail bytes and the length go into lane 0
-static uint64_t body_hash_of(const char* p, size_t n) {
-    uint64_t h[4] = {0x9e3779b97f4a7c15ull, 0xc2b2ae3d27d4eb4full, 0x165667b19e3779f9ull, 0x27d4eb2f165667c5ull};
-    const uint64_t K = 0x100000001b3ull * 0x9e3779b1ull | 1ull;
-    size_t i = 0;
-    for (; i + 32 <= n; i += 32) {
-        uint64_t w[4];
-        std::memcpy(w, p + i, 32);
-        for (int l = 0; l < 4; ++l) { h[l] = (h[l] ^ w[l]) * K; h[l] ^= h[l] >> 29; }
-    }
-    for (; i < n; ++i) { h[0] = (h[0] ^ (unsigned char)p[i]) * K; h[0] ^= h[0] >> 29; }
-    h[0] = (h[0] ^ (uint64_t)n) * K;
-    return (h[0] ^ (h[1] * 3) ^ (h[2] * 5) ^ (h[3] * 7)) * K;
-}
-
-// allocation table entry of an array the image does not store (wt_model::lazy_f32): its size with this bit set
-static constexpr uint64_t PACK_NOT_STORED = 1ull << 63;
-
-static std::vector<bool> lazy_allocs(const wt_model* M) {
-    std::vector<bool> lazy(M->allocs.size(), false);
-    for (const wt_model::LazyF32& z : M->lazy_f32)
-        for (size_t i = 0; i < M->allocs.size(); ++i)
-            if (M->allocs[i] == static_cast<const void*>(z.w)) lazy[i] = true;       // lazy arrays are whole allocations
-    return lazy;
-}
-
-size_t model_export_bytes(const wt_model* M) {
-    size_t total = sizeof(PackHeader) + M->allocs.size() * sizeof(uint64_t) + (1u << 17);      // struct section: generous bound
-    const std::vector<bool> lazy = lazy_allocs(M);
-    for (size_t i = 0; i < M->allocs.size(); ++i) if (!lazy[i]) total += (M->alloc_bytes[i] + 255) / 256 * 256;
-    return total + 256;
-}
-
-int model_export(const wt_model* Mc, void* buf, size_t n) {
-    wt_model* M = const_cast<wt_model*>(Mc);         // archive_model is symmetric; saving does not modify
-    std::map<const void*, int> index;
-    for (size_t i = 0; i < M->allocs.size(); ++i) index[M->allocs[i]] = (int)i;
-    std::vector<char> st;
-    Archive ar;
-    ar.saving = true; ar.out = &st; ar.index = &index;
-    archive_model(ar, M);
-    if (!ar.ok) { set_error("wt_model_export: a model pointer lies outside the model's allocations"); return WT_ERR_INVALID; }
-    PackHeader h{};
-    h.magic = PACK_MAGIC; h.version = PACK_VERSION; h.arch = M->arch; h.arch_hash = arch_hash_of(M->arch);
-    h.n_allocs = M->allocs.size(); h.struct_bytes = st.size();
-    if (M->f32_stale.load()) if (int rc = ensure_f32_weights(M)) return rc;       // (nothing lazy is exported, but keep the model whole)
-    const std::vector<bool> lazy = lazy_allocs(M);
-    size_t pos = sizeof(PackHeader) + M->allocs.size() * sizeof(uint64_t) + st.size();
-    pos = (pos + 255) / 256 * 256;
-    const size_t payload0 = pos;
-    for (size_t i = 0; i < M->allocs.size(); ++i) if (!lazy[i]) pos += (M->alloc_bytes[i] + 255) / 256 * 256;
-    h.payload_bytes = pos - payload0;
-    if (pos > n) { set_error("wt_model_export: buffer too small (wt_model_export_bytes)"); return WT_ERR_INVALID; }
-    char* o = static_cast<char*>(buf);
-    std::memset(o, 0, payload0);
-    for (size_t i = 0; i < M->allocs.size(); ++i) { uint64_t b = M->alloc_bytes[i] | (lazy[i] ? PACK_NOT_STORED : 0); std::memcpy(o + sizeof(h) + i * 8, &b, 8); }
-    std::memcpy(o + sizeof(h) + M->allocs.size() * 8, st.data(), st.size());
-    pos = payload0;
-    WT_HIP_CHECK(hipDeviceSynchronize());
-    for (size_t i = 0; i < M->allocs.size(); ++i) {
-        if (lazy[i]) continue;
-        const size_t b = M->alloc_bytes[i], padded = (b + 255) / 256 * 256;
-        WT_HIP_CHECK(hipMemcpy(o + pos, M->allocs[i], b, hipMemcpyDeviceToHost));
-        std::memset(o + pos + b, 0, padded - b);
-        pos += padded;
-    }
-    h.body_hash = body_hash_of(o + sizeof(h), pos - sizeof(h));
-    std::memcpy(o, &h, sizeof(h));
-    return (int)0;
-}
-
-int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint64_t* arch_hash) {
-    if (!buf || n < sizeof(PackHeader)) { set_error("packed image: too short"); return WT_ERR_INVALID; }
-    PackHeader h;
-    std::memcpy(&h, buf, sizeof(h));
-    if (h.magic != PACK_MAGIC) { set_error("packed image: bad magic (not a wavtokenizer_amd packed file)"); return WT_ERR_INVALID; }
-    if (version) *version = h.version;
-    if (arch) *arch = h.arch;
-    if (arch_hash) *arch_hash = h.arch_hash;
-    if (h.version != PACK_VERSION) { set_error("packed image: layout version " + std::to_string(h.version) + ", this library reads " + std::to_string(PACK_VERSION)); return WT_ERR_INVALID; }
-    if (h.arch_hash != arch_hash_of(h.arch)) { set_error("packed image: architecture hash mismatch (corrupt header)"); return WT_ERR_INVALID; }
-    // every term is checked against what is left of the file before it is added: nothing here can wrap
-    size_t left = n - sizeof(PackHeader);
-    if (h.n_allocs > (1u << 16) || h.n_allocs * 8 > left) { set_error("packed image: truncated (allocation table)"); return WT_ERR_INVALID; }
-    left -= h.n_allocs * 8;
-    if (h.struct_bytes > (1u << 24) || h.struct_bytes > left) { set_error("packed image: truncated (model section)"); return WT_ERR_INVALID; }
-    const size_t head = sizeof(PackHeader) + h.n_allocs * 8 + h.struct_bytes, head_pad = (head + 255) / 256 * 256;
-    if (head_pad > n || h.payload_bytes > n - head_pad) { set_error("packed image: truncated (payload)"); return WT_ERR_INVALID; }
-    return WT_OK;
-}
-
-// length of the image that starts at buf (wt_model_export_bytes is an upper bound taken before the model section is written)
-size_t packed_bytes(const void* buf, size_t n) {
-    if (packed_info(buf, n, nullptr, nullptr, nullptr)) return 0;
-    PackHeader h;
-    std::memcpy(&h, buf, sizeof(h));
-    return (sizeof(PackHeader) + h.n_allocs * 8 + h.struct_bytes + 255) / 256 * 256 + h.payload_bytes;
-}
-
-// full check of an image that needs no GPU: header, table and section bounds, and the hash of everything behind the header
-int packed_verify(const void* buf, size_t n) {
-    if (int rc = packed_info(buf, n, nullptr, nullptr, nullptr)) return rc;
-    PackHeader h;
-    std::memcpy(&h, buf, sizeof(h));
-    const char* in = static_cast<const char*>(buf);
-    const size_t head_pad = (sizeof(PackHeader) + h.n_allocs * 8 + h.struct_bytes + 255) / 256 * 256;
-    size_t pos = head_pad;
-    for (size_t i = 0; i < h.n_allocs; ++i) {
-        uint64_t b;
-        std::memcpy(&b, in + sizeof(h) + i * 8, 8);
-        if (b & PACK_NOT_STORED) {               // allocated on import, filled in later (wt_model::lazy_f32): bounded, no payload
-            if ((b & ~PACK_NOT_STORED) == 0 || (b & ~PACK_NOT_STORED) > (1ull << 32)) { set_error("packed image: bad size of an unstored array"); return WT_ERR_INVALID; }
-            continue;
-        }
-        if (b == 0 || b > n - pos || (b + 255) / 256 * 256 > n - pos) { set_error("packed image: allocation table does not fit the payload"); return WT_ERR_INVALID; }
-        pos += (b + 255) / 256 * 256;
-    }
-    if (pos - head_pad != h.payload_bytes) { set_error("packed image: allocation table and payload size disagree"); return WT_ERR_INVALID; }
-    if (body_hash_of(in + sizeof(h), pos - sizeof(h)) != h.body_hash) { set_error("packed image: content hash mismatch (corrupt file)"); return WT_ERR_INVALID; }
-    return WT_OK;
-}
-
-// The model section of a packed image is data from a file: after archive_model every dimension is recomputed from the
-// header's wt_arch (what build_model would have set) and compared, and every pointer's EXTENT - not only its start - must lie
-// inside the allocation it points into.  The body hash only detects accidental corruption (it is not cryptographic): a
-// crafted file must not be able to make a plan size its launches past an allocation.
-static int validate_imported(const wt_model* M) {
-    const wt_arch& a = M->arch;
-    auto fits = [&](const void* p, size_t bytes) {
-        if (!p) return false;
-        const char* c = static_cast<const char*>(p);
-        for (size_t i = 0; i < M->allocs.size(); ++i) {
-            const char* base = static_cast<const char*>(M->allocs[i]);
-            if (c >= base && c < base + M->alloc_bytes[i]) return bytes <= (size_t)(base + M->alloc_bytes[i] - c);
-        }
-        return false;
-    };
-    auto bad = [](const char* what) { set_error(std::string("packed image: ") + what + " does not match the architecture in its header"); return WT_ERR_INVALID; };
-    // an S32 copy has the footprint of the fp32 array it stands for; taps in paired order only where the plan packs them
-    // so (encoder down convs, k = 2r)
-    auto copy_ok = [&](const S32Copy& s, size_t bytes, bool pair_ok) {
-        return (!s.p || fits(s.p, bytes)) && s.acc_scale > 0.f && std::isfinite(s.acc_scale) && (pair_ok || !s.tap_pair);
-    };
-    auto conv_ok = [&](const ConvW& c, int cout, int cin, int k, bool pair_ok = false) {
-        const size_t bytes = (size_t)cout * cin * k * 4;
-        return c.cout == cout && c.cin == cin && c.k == k && fits(c.w, bytes) && fits(c.b, (size_t)cout * 4) && copy_ok(c.s32, bytes, pair_ok);
-    };
-    auto gemm_ok = [&](const GemmW& g, int rows, int cols) {
-        const size_t bytes = (size_t)rows * cols * 4;
-        return g.rows == rows && g.cols == cols && fits(g.w, bytes) && copy_ok(g.s32, bytes, false);
-    };
-    auto lstm_ok = [&](const LstmW& l, int H) {
-        const size_t hh = (size_t)4 * H * H * 4;
-        return gemm_ok(l.Wih0, 4 * H, H) && fits(l.b0, (size_t)16 * H) && fits(l.W0, hh) && fits(l.W1, 2 * hh) && fits(l.b1, (size_t)16 * H) &&
-               (!l.W0h || fits(l.W0h, hh)) && (!l.W1h || fits(l.W1h, 2 * hh)) &&
-               (!l.Wp || fits(l.Wp, (size_t)3 * 32 * 4 * 16 * 2 * 64 * 16));
-    };
-    const int nf = 32, H = 512, D = a.dim, I = a.intermediate_dim;
-    if (a.n_ratios < 1 || a.n_ratios > 8 || a.num_quantizers < 1 || a.num_quantizers > 32 || a.input_channels != 512 || D % 256 || I % 32 || a.num_layers < 1 || a.num_layers > 32 ||
-        a.adanorm_num_embeddings < 1 || a.vq_bins < 4 || a.vq_bins % 4 || a.n_fft < 4 || a.hop_length < 1) return bad("the architecture itself");
-    int hop = 1;
-    for (int i = 0; i < a.n_ratios; ++i) { if (a.ratios[i] < 1 || a.ratios[i] > 64) return bad("a ratio"); hop *= a.ratios[i]; }
-    if (M->hop != hop || M->H != H || (int)M->enc_ratios.size() != a.n_ratios || (int)M->stages.size() != a.n_ratios) return bad("the encoder's shape");
-    if (M->e0_k != 7 || M->e0_c != nf || !fits(M->e0_w, 7 * nf * 4) || !fits(M->e0_b, nf * 4)) return bad("the first conv");
-    int mult = 1;
-    for (int i = 0; i < a.n_ratios; ++i) {
-        const ResStage& st = M->stages[i];
-        const int r = a.ratios[a.n_ratios - 1 - i], C = mult * nf;
-        if (M->enc_ratios[i] != r || st.C != C || st.r != r || !conv_ok(st.c3, C / 2, C, 3) || !conv_ok(st.c1, C, C / 2, 1) || !conv_ok(st.sc, C, C, 1) ||
-            !conv_ok(st.down, 2 * C, C, 2 * r, true)) return bad("an encoder stage");
-        if ((st.cat.w || st.cat.s32.p) && !conv_ok(st.cat, C, C + C / 2, 1)) return bad("a fused shortcut weight");
-        mult *= 2;
-    }
-    if (mult * nf != H || !lstm_ok(M->enc_lstm, H) || !conv_ok(M->enc_final, 512, H, 7)) return bad("the encoder tail");
-    if (!gemm_ok(M->embed, a.vq_bins, 512) || !fits(M->embed.w, (size_t)a.num_quantizers * a.vq_bins * 512 * 4) || !fits(M->ee, (size_t)a.vq_bins * 4)) return bad("the codebook");
-    if (!conv_ok(M->bb_embed, D, 512, 7)) return bad("backbone.embed");
-    for (const PosRes& r : M->res)
-        if (!fits(r.n1w, D * 4) || !fits(r.n1b, D * 4) || !fits(r.n2w, D * 4) || !fits(r.n2b, D * 4) || !conv_ok(r.c1, D, D, 3) || !conv_ok(r.c2, D, D, 3)) return bad("a pos_net block");
-    if (!fits(M->at_nw, D * 4) || !fits(M->at_nb, D * 4) || !gemm_ok(M->at_Wqk, 2 * D, D) || !fits(M->at_bqk, 2 * D * 4) || !gemm_ok(M->at_Wv, D, D) ||
-        !fits(M->at_bv, D * 4) || !gemm_ok(M->at_Wp, D, D) || !fits(M->at_bp, D * 4)) return bad("the attention block");
-    const size_t ada = (size_t)a.adanorm_num_embeddings * D * 4;
-    if (!fits(M->gn5w, D * 4) || !fits(M->gn5b, D * 4) || !fits(M->ada_s, ada) || !fits(M->ada_h, ada)) return bad("backbone.norm");
-    if ((int)M->cnx.size() != a.num_layers) return bad("the ConvNeXt block count");
-    for (const CnxBlock& c : M->cnx)
-        if (!fits(c.dw_w, (size_t)7 * D * 4) || !fits(c.dw_b, D * 4) || !fits(c.ada_s, ada) || !fits(c.ada_h, ada) || !gemm_ok(c.W1, I, D) || !fits(c.b1, I * 4) ||
-            !gemm_ok(c.W2, D, I) || !fits(c.b2, D * 4) || !fits(c.gamma, D * 4)) return bad("a ConvNeXt block");
-    const int N = a.n_fft;
-    if (N % 4 || N % a.hop_length) return bad("n_fft / hop_length");
-    const int Kq = ((N / 4 + 1 + 31) / 32) * 32, Kb = 2 * Kq;
-    if (M->Kq != Kq || M->Kb != Kb || M->bins_f != N / 2 + 1 || M->R != N / a.hop_length) return bad("the ISTFT head's shape");
-    if (!fits(M->fln_w, D * 4) || !fits(M->fln_b, D * 4) || !gemm_ok(M->head_W, 2 * Kb, D) || !fits(M->head_b, (size_t)2 * Kb * 4) ||
-        !gemm_ok(M->istft_W, 4 * Kq, Kq) || !fits(M->win, (size_t)N * 4) || !fits(M->wsq, (size_t)N * 4)) return bad("the ISTFT head");
-    if (M->has_seadec) {
-        if ((int)M->sd_stages.size() != a.n_ratios || !conv_ok(M->sd_first, (1 << a.n_ratios) * nf, 512, 7) || !lstm_ok(M->sd_lstm, H)) return bad("the SEANetDecoder");
-        int m2 = 1 << a.n_ratios;
-        for (int i = 0; i < a.n_ratios; ++i) {
-            const SeaDecStage& st = M->sd_stages[i];
-            const int r = a.ratios[i], cin = m2 * nf, h = cin / 2;
-            if (st.cin != cin || st.cout != h || st.k != 2 * r || st.r != r || !fits(st.tr_w, (size_t)2 * r * cin * h * 4) || ((st.tr_wp.w || st.tr_wp.s32.p) && !gemm_ok(st.tr_wp, r * h, 2 * cin)) ||
-                !fits(st.tr_b, h * 4) || !conv_ok(st.c3, h / 2, h, 3) || !conv_ok(st.c1, h, h / 2, 1) || !conv_ok(st.sc, h, h, 1)) return bad("a SEANetDecoder stage");
-            if ((st.cat.w || st.cat.s32.p) && !conv_ok(st.cat, h, h + h / 2, 1)) return bad("a SEANetDecoder fused shortcut");
-            m2 /= 2;
-        }
-        if (!fits(M->sd_last_w, 7 * nf * 4) || !fits(M->sd_last_b, 4)) return bad("the SEANetDecoder's last conv");
-    }
-    return WT_OK;
-}
-
-int model_import(wt_model* M, const void* buf, size_t n) {
-    PackHeader h;
-    if (int rc = packed_verify(buf, n)) return rc;
-    std::memcpy(&h, buf, sizeof(h));
-    M->arch = h.arch;
-    const char* in = static_cast<const char*>(buf);
-    size_t pos = (sizeof(PackHeader) + h.n_allocs * 8 + h.struct_bytes + 255) / 256 * 256;
-    for (size_t i = 0; i < h.n_allocs; ++i) {
-        uint64_t b;
-        std::memcpy(&b, in + sizeof(h) + i * 8, 8);
-        const bool stored = !(b & PACK_NOT_STORED);
-        b &= ~PACK_NOT_STORED;
-        const size_t padded = (b + 255) / 256 * 256;
-        if (stored && pos + padded > n) { set_error("packed image: truncated payload"); return WT_ERR_INVALID; }
-        void* d = nullptr;
-        WT_HIP_CHECK(hipMalloc(&d, b));
-        M->allocs.push_back(d);
-        M->alloc_bytes.push_back(b);
-        if (stored) {
-            WT_HIP_CHECK(hipMemcpy(d, in + pos, b, hipMemcpyHostToDevice));
-            pos += padded;
-        } else {
-            M->f32_stale.store(true);
-        }
-    }
-    Archive ar;
-    ar.saving = false; ar.in = in + sizeof(h) + h.n_allocs * 8; ar.n = h.struct_bytes; ar.allocs = &M->allocs; ar.alloc_bytes = &M->alloc_bytes;
-    archive_model(ar, M);
-    if (!ar.ok || ar.pos != ar.n) { set_error("packed image: model section does not match this library's layout"); return WT_ERR_INVALID; }
-    // every lazy entry must name whole arrays of plausible size (the file is not trusted)
-    for (const wt_model::LazyF32& z : M->lazy_f32) {
-        size_t iw = M->allocs.size(), is = M->allocs.size();
-        for (size_t i = 0; i < M->allocs.size(); ++i) {
-            if (M->allocs[i] == static_cast<const void*>(z.w)) iw = i;
-            if (z.s32 && M->allocs[i] == z.s32) is = i;
-        }
-        if (iw == M->allocs.size() || z.n <= 0 || (z.n % 32) || (size_t)z.n * 4 > M->alloc_bytes[iw] ||
-            (z.s32 && (is == M->allocs.size() || (size_t)z.n * 4 > M->alloc_bytes[is])) || !(z.scale > 0.f) || !std::isfinite(z.scale)) {
-            set_error("packed image: bad entry in the list of unstored fp32 arrays"); return WT_ERR_INVALID;
-        }
-    }
-    return validate_imported(M);
-}
-
 // The fp32 GEMM weights a packed image does not store, rebuilt from their S32 copies: w = (hi + lo * 2^-11) / scale.  Called
 // when the first plan on the fp32 chain is created for a model that came from a packed image (and before such a model is
 // exported again).  22 of fp32's 24 significant bits survive; a model made from a state dict keeps the exact arrays.
@@ -985,130 +630,6 @@ int ensure_f32_weights(const wt_model* M) {
     WT_HIP_CHECK(hipDeviceSynchronize());
     M->f32_stale.store(false);
     return WT_OK;
-}
-
-// ------------------------------------------------------------------------------------ the weights by name
-// Every device array a plan can read (wt_model_weight_info), in the order build_model and build_splits made them per layer.
-// The dims of the two f16 lane packings count halves, every other array's count 4-byte words.
-std::vector<WeightEntry> model_weights(const wt_model* Mc) {
-    wt_model* M = const_cast<wt_model*>(Mc);         // (archive_model is symmetric; saving does not modify)
-    std::vector<WeightEntry> out;
-    auto arr = [&](const std::string& name, const void* p, int fmt, std::initializer_list<int64_t> dims) -> WeightEntry* {
-        if (!p) return nullptr;
-        WeightEntry e;
-        e.name = name; e.data = p; e.format = fmt;
-        int64_t n = 1;
-        for (int64_t d : dims) { e.dims[e.ndim++] = d; n *= d; }
-        e.numel = (fmt == WFMT_LSTM_F16 || fmt == WFMT_LSTM_PERSIST) ? n / 2 : n;
-        out.push_back(e);
-        return &out.back();
-    };
-    auto copy = [&](const std::string& of, const S32Copy& s, std::initializer_list<int64_t> dims) {
-        if (WeightEntry* e = arr(of + ".s32", s.p, WFMT_S32, dims)) { e->of = of; e->acc_scale = s.acc_scale; e->tap_pair = s.tap_pair; }
-    };
-    auto conv = [&](const std::string& name, const ConvW& c) {
-        arr(name + ".w", c.w, WFMT_F32, {c.cout, c.k, c.cin});
-        arr(name + ".b", c.b, WFMT_F32, {c.cout});
-        if (WeightEntry* e = arr(name + ".s32", c.s32.p, WFMT_S32, {c.cout, c.k, c.cin})) { e->of = name + ".w"; e->acc_scale = c.s32.acc_scale; e->tap_pair = c.s32.tap_pair; }
-    };
-    auto gemm = [&](const std::string& name, const GemmW& g) {
-        arr(name, g.w, WFMT_F32, {g.rows, g.cols});
-        copy(name, g.s32, {g.rows, g.cols});
-    };
-    auto lstm = [&](const std::string& name, const LstmW& l, int H) {
-        gemm(name + ".Wih0", l.Wih0);
-        arr(name + ".b0", l.b0, WFMT_F32, {4 * H});
-        arr(name + ".W0", l.W0, WFMT_F32, {4 * H / 16, H / 16, 64, 4});
-        arr(name + ".W1", l.W1, WFMT_F32, {4 * H / 16, 2 * H / 16, 64, 4});
-        arr(name + ".b1", l.b1, WFMT_F32, {4 * H});
-        arr(name + ".W0h", l.W0h, WFMT_LSTM_F16, {4 * H / 16, H / 32, 2, 512});
-        arr(name + ".W1h", l.W1h, WFMT_LSTM_F16, {4 * H / 16, 2 * H / 32, 2, 512});
-        arr(name + ".Wp", l.Wp, WFMT_LSTM_PERSIST, {3 * 32 * 4, 16, 2, 512});
-    };
-    const wt_arch& a = M->arch;
-    const int H = M->H, D = a.dim, A = a.adanorm_num_embeddings;
-    // the tap-paired repackings of the down convs: held by lazy_f32 alone (s32 = null), in stage order
-    std::vector<const float*> paired;
-    for (const wt_model::LazyF32& z : M->lazy_f32) if (!z.s32) paired.push_back(z.w);
-    size_t next_pair = 0;
-    arr("enc.e0.w", M->e0_w, WFMT_F32, {M->e0_k, M->e0_c});
-    arr("enc.e0.b", M->e0_b, WFMT_F32, {M->e0_c});
-    for (size_t i = 0; i < M->stages.size(); ++i) {
-        const ResStage& st = M->stages[i];
-        const std::string p = "enc.stage" + std::to_string(i + 1);
-        conv(p + ".c3", st.c3); conv(p + ".c1", st.c1); conv(p + ".sc", st.sc); conv(p + ".down", st.down);
-        if (st.down.s32.tap_pair && next_pair < paired.size())
-            arr(p + ".down.wpair", paired[next_pair++], WFMT_F32, {st.down.cout, st.down.k, st.down.cin});
-        if (st.cat.w) conv(p + ".cat", st.cat);
-    }
-    lstm("enc.lstm", M->enc_lstm, H);
-    conv("enc.final", M->enc_final);
-    arr("vq.embed", M->embed.w, WFMT_F32, {a.num_quantizers, M->embed.rows, M->embed.cols});
-    copy("vq.embed", M->embed.s32, {M->embed.rows, M->embed.cols});
-    arr("vq.ee", M->ee, WFMT_F32, {a.vq_bins});
-    conv("bb.embed", M->bb_embed);
-    for (int i = 0; i < 4; ++i) {
-        const PosRes& r = M->res[i];
-        const std::string p = "bb.res." + std::to_string(i);
-        arr(p + ".n1w", r.n1w, WFMT_F32, {D}); arr(p + ".n1b", r.n1b, WFMT_F32, {D});
-        arr(p + ".n2w", r.n2w, WFMT_F32, {D}); arr(p + ".n2b", r.n2b, WFMT_F32, {D});
-        conv(p + ".c1", r.c1); conv(p + ".c2", r.c2);
-    }
-    arr("bb.attn.nw", M->at_nw, WFMT_F32, {D}); arr("bb.attn.nb", M->at_nb, WFMT_F32, {D});
-    gemm("bb.attn.Wqk", M->at_Wqk); arr("bb.attn.bqk", M->at_bqk, WFMT_F32, {2 * D});
-    gemm("bb.attn.Wv", M->at_Wv); arr("bb.attn.bv", M->at_bv, WFMT_F32, {D});
-    gemm("bb.attn.Wp", M->at_Wp); arr("bb.attn.bp", M->at_bp, WFMT_F32, {D});
-    arr("bb.gn5.w", M->gn5w, WFMT_F32, {D}); arr("bb.gn5.b", M->gn5b, WFMT_F32, {D});
-    arr("bb.ada.s", M->ada_s, WFMT_F32, {A, D}); arr("bb.ada.h", M->ada_h, WFMT_F32, {A, D});
-    for (size_t i = 0; i < M->cnx.size(); ++i) {
-        const CnxBlock& c = M->cnx[i];
-        const std::string p = "bb.cnx." + std::to_string(i);
-        arr(p + ".dw_w", c.dw_w, WFMT_F32, {7, D}); arr(p + ".dw_b", c.dw_b, WFMT_F32, {D});
-        arr(p + ".ada_s", c.ada_s, WFMT_F32, {A, D}); arr(p + ".ada_h", c.ada_h, WFMT_F32, {A, D});
-        gemm(p + ".W1", c.W1); arr(p + ".b1", c.b1, WFMT_F32, {c.W1.rows});
-        gemm(p + ".W2", c.W2); arr(p + ".b2", c.b2, WFMT_F32, {D});
-        arr(p + ".gamma", c.gamma, WFMT_F32, {D});
-    }
-    arr("bb.fln.w", M->fln_w, WFMT_F32, {D}); arr("bb.fln.b", M->fln_b, WFMT_F32, {D});
-    gemm("head.W", M->head_W); arr("head.b", M->head_b, WFMT_F32, {2 * M->Kb});
-    arr("istft.W", M->istft_W.w, WFMT_F32, {4, M->Kq, M->Kq});
-    copy("istft.W", M->istft_W.s32, {4, M->Kq, M->Kq});
-    arr("istft.win", M->win, WFMT_F32, {a.n_fft}); arr("istft.wsq", M->wsq, WFMT_F32, {a.n_fft});
-    if (M->has_seadec) {
-        conv("sd.first", M->sd_first);
-        lstm("sd.lstm", M->sd_lstm, H);
-        for (size_t i = 0; i < M->sd_stages.size(); ++i) {
-            const SeaDecStage& st = M->sd_stages[i];
-            const std::string p = "sd.stage" + std::to_string(i + 1);
-            arr(p + ".tr_w", st.tr_w, WFMT_F32, {st.k, st.cin, st.cout});
-            if (st.tr_wp.w) {
-                arr(p + ".tr_wp", st.tr_wp.w, WFMT_F32, {st.r, st.cout, 2, st.cin});
-                copy(p + ".tr_wp", st.tr_wp.s32, {st.r, st.cout, 2, st.cin});
-            }
-            arr(p + ".tr_b", st.tr_b, WFMT_F32, {st.cout});
-            conv(p + ".c3", st.c3); conv(p + ".c1", st.c1); conv(p + ".sc", st.sc);
-            if (st.cat.w) conv(p + ".cat", st.cat);
-        }
-        arr("sd.last.w", M->sd_last_w, WFMT_F32, {7, 32});
-        arr("sd.last.b", M->sd_last_b, WFMT_F32, {1});
-    }
-    // what archive_model writes, and the arrays a packed image leaves out
-    std::map<const void*, int> index;
-    for (size_t i = 0; i < M->allocs.size(); ++i) index[M->allocs[i]] = (int)i;
-    std::vector<char> sink;
-    std::vector<const void*> seen;
-    Archive ar;
-    ar.saving = true; ar.out = &sink; ar.index = &index; ar.seen = &seen;
-    archive_model(ar, M);
-    std::sort(seen.begin(), seen.end());
-    for (WeightEntry& e : out) {
-        e.archived = std::binary_search(seen.begin(), seen.end(), e.data);
-        auto at = index.find(e.data);
-        if (at != index.end()) e.alloc = at->second;
-        for (const wt_model::LazyF32& z : M->lazy_f32)
-            if (static_cast<const void*>(z.w) == e.data) { e.lazy = z.s32 ? 1 : 2; e.lazy_scale = z.scale; }
-    }
-    return out;
 }
 
 }  // namespace wt

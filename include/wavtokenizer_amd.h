@@ -896,6 +896,79 @@ size_t  wt_mel_workspace_bytes(int32_t B, int64_t total_frames);
 int     wt_mel_spectrogram(const wt_mel* m, const wt_mel_clip* clips, int32_t B, int32_t log, void* workspace, void* stream);
 int     wt_mel_distance(const wt_mel* m, const wt_mel_clip* clips, int32_t B, void* workspace, void* stream);
 
+/* ---- evaluation metric: short-time objective intelligibility (STOI, ESTOI) -------------------- */
+
+/* Replaces: the per-file CPU loop `stoi(raw.cpu(), pre.cpu(), sr, extended=False)` of the reference's evaluation script
+ * (metrics/infer.py:100-105; pystoi).  STOI is Taal, Hendriks, Heusdens & Jensen 2011, ESTOI is Jensen & Taal 2016; pystoi is not in
+ * this image, so the measure is restated from the published algorithm and the parity with pystoi is unpinned (tests/stoi_ref.py
+ * holds this definition in float64).  For a pair (clean x, processed y) of T samples each at sample_rate, EPS = 2^-52:
+ *  1. Both go to 10 kHz (skipped at 10 kHz): p / q = 10000 / sample_rate reduced, fc = 1 / (2 max(p, q)),
+ *     L = ceil((60 - 8) / (28.714 fc / 10)), h = kaiser(2 L + 1, 0.1102 (60 - 8.7)) 2 p fc sinc(2 fc t) for t = -L..L, h <- p h / sum(h);
+ *     out[n] = sum over the taps k with (n q + L - k) = i p, 0 <= i < T, of h[k] in[i], for n < ceil(T p / q): zero phase, zeros
+ *     outside the clip (scipy.signal.resample_poly(in, p, q, window = h / p)).  Rates with max(p, q) <= 441 are accepted (8, 10, 16,
+ *     22.05, 24, 32, 44.1, 48 kHz among them).
+ *  2. Silent frames leave, decided on x: w = hanning(258)[1:-1]; the K0 candidate frames of 256 samples start at 0, 128, ... < n - 256;
+ *     frame f is kept when ||w x_f|| + EPS > 0.01 (max_f ||w x_f|| + EPS) (40 dB).  Both signals are rebuilt by overlap-adding their
+ *     kept windowed frames at hop 128; K frames are kept.
+ *  3. The rebuilt signals' frames start at 0, 128, ... < len - 256: J = K - 1 frames; frame j is w times rebuilt samples
+ *     [128 j, 128 j + 256), zero-padded to 512, real FFT.
+ *  4. Fifteen one-third-octave bands from 150 Hz: band i is the square root of the sum of |X|^2 over bins [e_i, e_i+1),
+ *     e = 7 9 11 14 17 22 27 34 43 55 69 87 109 138 174 219.
+ *  5. One segment per m in 30..J: the 15 x 30 blocks X, Y of frames [m - 30, m).  `row`: per band over the 30 frames.
+ *     STOI:  alpha = ||X||_row / (||Y||_row + EPS), Y' = min(alpha Y, X (1 + 10^(15/20))); X and Y' lose their row means and are
+ *            divided by (row norm + EPS); d = sum X Y' / (15 segments).
+ *     ESTOI: X and Y lose their row means and are divided by (row norm + EPS), then the same per frame over the 15 bands;
+ *            d = sum X Y / (30 segments).
+ *     J < 30 gives 1e-5 (pystoi's value; there is no warning, it would need a host wait).
+ * The tables are computed in float64 on the host and rounded once; everything on the device is fp32 with fixed summation orders
+ * and no float atomics: a pair's result has the same bits alone, in any batch and at any position of it.  The create call puts its
+ * tables on `device` and leaves the calling thread's current device as it found it; wt_stoi launches on the current device, which
+ * must be the handle's. */
+typedef struct wt_stoi_handle wt_stoi_handle;
+int     wt_stoi_create(int32_t sample_rate, int32_t device, wt_stoi_handle** out);
+void    wt_stoi_destroy(wt_stoi_handle* h);
+/* ceil(T p / q): the samples a clip of T has at 10 kHz; -1 for a null handle or T < 0 */
+int64_t wt_stoi_resampled_length(const wt_stoi_handle* h, int64_t T);
+/* Host only, no device needed: what a handle of this rate uploads.  p, q, L; filter [2 L + 1] (ask for L first); window [256];
+ * edges [16].  Every pointer may be null.  WT_ERR_INVALID for a rate that is refused. */
+int     wt_stoi_tables(int32_t sample_rate, int32_t* p, int32_t* q, int32_t* L, float* filter, float* window, int32_t* edges);
+/* One pair of a call: device pointers, fp32; length counts the samples of each of the two signals; out is one float. */
+typedef struct {
+    const float* clean;
+    const float* processed;
+    int64_t length;
+    float* out;
+} wt_stoi_clip;
+/* Where a call leaves its stages for tests; every member may be null.  With n_c = wt_stoi_resampled_length(length_c),
+ * K0_c = ceil((n_c - 256) / 128), R_c and F_c the sums of n and K0 over the clips before c:
+ *   resampled  [2 sum n]: the clean signal of clip c at 10 kHz from 2 R_c, the processed one from 2 R_c + n_c (not written by a
+ *              handle of 10 kHz, whose stages read the inputs themselves)
+ *   keep       [sum K0]: 1 for a kept candidate frame, else 0, clip c from F_c
+ *   counts     [B][2]: (K0, K)
+ *   tob        [30 sum K0]: clip c from 30 F_c as [2][15][K0_c] (clean then processed, band, frame); frames j < K - 1 are written
+ * An array given here takes the place of the workspace's own, so a call has the same results with and without taps. */
+typedef struct {
+    float* resampled;
+    int32_t* keep;
+    int32_t* counts;
+    float* tob;
+} wt_stoi_taps;
+/* Bytes of the device workspace of a call with B clips whose resampled lengths add up to total_resampled and whose candidate-frame
+ * counts K0 add up to total_frames; 0 for a null handle or B < 1. */
+size_t  wt_stoi_workspace_bytes(const wt_stoi_handle* h, int32_t B, int64_t total_resampled, int64_t total_frames);
+/* STOI (extended = 0) or ESTOI of B pairs of any lengths in six launches, each ragged over the clips.  K never comes back to the
+ * host: the launches are sized by K0.  Nothing outside [0, length) of the inputs is read and nothing outside the outs, the
+ * workspace and the taps is written; the content of the workspace before the call does not matter.  clips is a HOST array.
+ * workspace: device, the bytes above, 8-byte aligned, its content untouched until the launches have run.  Up to 32 clips travel in
+ * the launches' own argument blocks: the call then makes no host wait and no copy and may be captured into a graph.  More clips go
+ * through the pinned descriptor blocks of wt_ingest and wt_emit (their events and their lock): such a call must NOT be made on a
+ * stream that is being captured.  Every descriptor is checked before any device call: a null handle, a null clean, processed or
+ * out, a length that leaves no candidate frame (256 samples or fewer at 10 kHz), a pointer not aligned to 4 bytes, B outside
+ * 1..32767, or a handle of another device than the calling thread's current one returns WT_ERR_INVALID with a message and touches
+ * no memory. */
+int     wt_stoi(const wt_stoi_handle* h, const wt_stoi_clip* clips, int32_t B, int32_t extended, void* workspace, void* stream,
+                const wt_stoi_taps* taps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,343 @@
+"""STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) as csrc/stoi.hip computes them (include/wavtokenizer_amd.h gives the
+definition) in float64 numpy, an fp32 stand-in of the same chain (fp32 arithmetic throughout, plain sequential sums, a radix-2 FFT)
+that serves as the yardstick for the kernels' rounding error, and the signals and ctypes plumbing the STOI tests share.  Written
+from the published algorithm; pystoi is not available here, so the parity with it is unpinned.  numpy only."""
+import functools
+import math
+
+import numpy as np
+
+FS = 10000
+FRAME, HOP, NFFT = 256, 128, 512
+BANDS, F_MIN, N_SEG = 15, 150.0, 30
+EPS = 2.0 ** -52
+CLIP = 1.0 + 10.0 ** (15.0 / 20.0)               # BETA = -15 dB
+RANGE = 0.01                                     # 40 dB, as an amplitude ratio
+SHORT = 1e-5
+BAND_EDGES = ((7, 9), (9, 11), (11, 14), (14, 17), (17, 22), (22, 27), (27, 34), (34, 43), (43, 55), (55, 69), (69, 87), (87, 109),
+              (109, 138), (138, 174), (174, 219))
+RATES = (8000, 10000, 16000, 22050, 24000, 32000, 44100, 48000)
+
+
+# ------------------------------------------------------------------------------------------------ tables
+def ratio(fs: int):
+    g = math.gcd(FS, int(fs))
+    return FS // g, int(fs) // g
+
+
+@functools.lru_cache(maxsize=None)
+def resample_filter(fs: int):
+    """(h [2L + 1] float64, p, q, L): the Octave-style Kaiser design, normalised to sum 1 and scaled by p (what
+    scipy.signal.resample_poly(x, p, q, window=h / sum(h)) applies)."""
+    p, q = ratio(fs)
+    fc = 1.0 / (2.0 * max(p, q))
+    L = int(math.ceil((60.0 - 8.0) / (28.714 * fc / 10.0)))
+    t = np.arange(-L, L + 1, dtype=np.float64)
+    h = np.kaiser(2 * L + 1, 0.1102 * (60.0 - 8.7)) * 2.0 * p * fc * np.sinc(2.0 * fc * t)
+    h = h / h.sum()
+    return p * h, p, q, L
+
+
+def octave_window(fs: int):
+    """The normalised window handed to scipy (before its own scaling by p)."""
+    h, p, _q, _L = resample_filter(fs)
+    return h / p
+
+
+def window64():
+    return np.hanning(FRAME + 2)[1:-1]
+
+
+def band_edges():
+    f = np.linspace(0, FS, NFFT + 1)[:NFFT // 2 + 1]
+    out = []
+    for i in range(BANDS):
+        lo = F_MIN * 2.0 ** ((2 * i - 1) / 6.0)
+        hi = F_MIN * 2.0 ** ((2 * i + 1) / 6.0)
+        out.append((int(np.argmin(np.abs(f - lo))), int(np.argmin(np.abs(f - hi)))))
+    return tuple(out)
+
+
+def resampled_length(T: int, fs: int) -> int:
+    p, q = ratio(fs)
+    return -(-int(T) * p // q)
+
+
+def candidate_frames(n: int) -> int:
+    return len(range(0, n - FRAME, HOP))
+
+
+# ------------------------------------------------------------------------------------------------ the chain, any dtype
+def _resample(x, fs, dt):
+    """y[n] = sum over the taps k = k0, k0 + p, ... (ascending; n q - k + L = i p, 0 <= i < T) of h[k] x[i]."""
+    if int(fs) == FS:
+        return np.asarray(x, dt).copy()
+    h64, p, q, L = resample_filter(int(fs))
+    h = h64.astype(dt)
+    x = np.asarray(x, dt)
+    T = x.shape[0]
+    n_out = resampled_length(T, fs)
+    c = np.arange(n_out, dtype=np.int64) * q + L
+    k0 = c % p
+    i0 = (c - k0) // p
+    y = np.zeros(n_out, dt)
+    for j in range(2 * L // p + 1):
+        k = k0 + p * j
+        i = i0 - j
+        ok = (k <= 2 * L) & (i >= 0) & (i < T)
+        term = (h[np.where(ok, k, 0)] * x[np.where(ok, i, 0)]).astype(dt)
+        y = np.where(ok, (y + term).astype(dt), y)
+    return y
+
+
+def _seq_sum(a, axis, dt):
+    """Sum along an axis, one rounded addition per element in ascending order (float64: numpy's own sum)."""
+    if dt == np.float64:
+        return a.sum(axis=axis)
+    a = np.moveaxis(a, axis, 0)
+    s = np.zeros(a.shape[1:], dt)
+    for row in a:
+        s = (s + row).astype(dt)
+    return s
+
+
+def _frames(x, starts, dt):
+    return x[np.asarray(starts, np.int64)[:, None] + np.arange(FRAME)[None, :]]
+
+
+def _select(x, dt):
+    """(norms [K0], keep [K0] bool) of the clean resampled signal."""
+    w = window64().astype(dt)
+    K0 = candidate_frames(x.shape[0])
+    fr = (_frames(x, np.arange(K0) * HOP, dt) * w[None, :]).astype(dt)
+    norms = np.sqrt(_seq_sum((fr * fr).astype(dt), 1, dt)).astype(dt)
+    if K0 == 0:
+        return norms, np.zeros(0, bool)
+    keep = (norms + dt(EPS)).astype(dt) > (dt(RANGE) * (norms.max() + dt(EPS)).astype(dt)).astype(dt)
+    return norms, keep
+
+
+def _stft_frames(x, kept, dt):
+    """[J][256]: w times the overlap-add of the kept windowed frames, gathered through the kept-index list."""
+    w = window64().astype(dt)
+    K = len(kept)
+    J = max(K - 1, 0)
+    if J == 0:
+        return np.zeros((0, FRAME), dt)
+    fr = (_frames(x, np.asarray(kept) * HOP, dt) * w[None, :]).astype(dt)          # [K][256]
+    out = np.empty((J, FRAME), dt)
+    out[:, HOP:] = (fr[:J, HOP:] + fr[1:J + 1, :HOP]).astype(dt)
+    out[0, :HOP] = fr[0, :HOP]
+    out[1:, :HOP] = (fr[:J - 1, HOP:] + fr[1:J, :HOP]).astype(dt)
+    return (out * w[None, :]).astype(dt)
+
+
+def _bitrev(n):
+    bits = n.bit_length() - 1
+    return np.array([int(format(i, f"0{bits}b")[::-1], 2) for i in range(n)])
+
+
+def _power(fr, dt):
+    """|rfft(fr, 512)|^2 [J][257]; fp32: a plain radix-2 decimation-in-time complex FFT of the zero-padded frame."""
+    if dt == np.float64:
+        X = np.fft.rfft(fr, n=NFFT, axis=1)
+        return X.real ** 2 + X.imag ** 2
+    f32 = np.float32
+    F = fr.shape[0]
+    re = np.zeros((F, NFFT), f32)
+    re[:, :FRAME] = fr
+    re = re[:, _bitrev(NFFT)]
+    im = np.zeros_like(re)
+    half = 1
+    while half < NFFT:
+        ang = -np.pi * np.arange(half, dtype=np.float64) / half
+        wr, wi = np.cos(ang).astype(f32), np.sin(ang).astype(f32)
+        re = re.reshape(F, -1, 2, half)
+        im = im.reshape(F, -1, 2, half)
+        tr = (re[:, :, 1] * wr - im[:, :, 1] * wi).astype(f32)
+        ti = (re[:, :, 1] * wi + im[:, :, 1] * wr).astype(f32)
+        re = np.stack([re[:, :, 0] + tr, re[:, :, 0] - tr], axis=2).astype(f32).reshape(F, NFFT)
+        im = np.stack([im[:, :, 0] + ti, im[:, :, 0] - ti], axis=2).astype(f32).reshape(F, NFFT)
+        half *= 2
+    h = NFFT // 2 + 1
+    return (re[:, :h] * re[:, :h] + im[:, :h] * im[:, :h]).astype(f32)
+
+
+def _bands(fr, dt):
+    """[15][J] one-third-octave band magnitudes of the STFT frames."""
+    P = _power(fr, dt)
+    out = np.zeros((BANDS, fr.shape[0]), dt)
+    for b, (lo, hi) in enumerate(BAND_EDGES):
+        out[b] = np.sqrt(_seq_sum(P[:, lo:hi], 1, dt)).astype(dt)
+    return out
+
+
+def _rownorm(a, axis, dt):
+    """Remove the mean along an axis and divide by (norm + EPS)."""
+    n = a.shape[axis]
+    a = (a - np.expand_dims((_seq_sum(a, axis, dt) / dt(n)).astype(dt), axis)).astype(dt)
+    nrm = np.sqrt(_seq_sum((a * a).astype(dt), axis, dt)).astype(dt)
+    return (a / np.expand_dims((nrm + dt(EPS)).astype(dt), axis)).astype(dt), nrm
+
+
+def _segments(X, Y, extended, dt):
+    """(d, conditions): X, Y [15][J].  conditions: the smallest centred-norm / raw-norm ratio over every (segment, band) row."""
+    J = X.shape[1]
+    if J < N_SEG:
+        return dt(SHORT), np.inf
+    idx = np.arange(N_SEG)[None, :] + np.arange(J - N_SEG + 1)[:, None]           # [S][30]
+    Xs = X[:, idx].transpose(1, 0, 2)                                              # [S][15][30]
+    Ys = Y[:, idx].transpose(1, 0, 2)
+    S = Xs.shape[0]
+    raw_x = np.sqrt(_seq_sum((Xs * Xs).astype(dt), 2, dt)).astype(dt)
+    raw_y = np.sqrt(_seq_sum((Ys * Ys).astype(dt), 2, dt)).astype(dt)
+    if extended:
+        xn, cx = _rownorm(Xs, 2, dt)
+        yn, cy = _rownorm(Ys, 2, dt)
+        cond = min(float((cx / raw_x).min()), float((cy / raw_y).min()))
+        xn, _ = _rownorm(xn, 1, dt)
+        yn, _ = _rownorm(yn, 1, dt)
+        per = _seq_sum(_seq_sum((xn * yn).astype(dt), 1, dt), 1, dt)               # [S]: bands within a frame, then frames
+        return (_seq_sum(per, 0, dt) / dt(N_SEG * S)).astype(dt), cond
+    alpha = (raw_x / (raw_y + dt(EPS)).astype(dt)).astype(dt)
+    Yp = np.minimum((Ys * alpha[:, :, None]).astype(dt), (Xs * dt(CLIP)).astype(dt))
+    xn, cx = _rownorm(Xs, 2, dt)
+    yn, cy = _rownorm(Yp, 2, dt)
+    raw_yp = np.sqrt(_seq_sum((Yp * Yp).astype(dt), 2, dt)).astype(dt)
+    cond = min(float((cx / raw_x).min()), float((cy / raw_yp).min()))
+    per = _seq_sum(_seq_sum((xn * yn).astype(dt), 2, dt), 1, dt)                   # [S]: frames within a band, then bands
+    return (_seq_sum(per, 0, dt) / dt(BANDS * S)).astype(dt), cond
+
+
+class Stages:
+    """Every stage of one pair: xr, yr (resampled), norms, keep, K0, K, X, Y ([15][J]), d[extended], cond[extended]."""
+
+
+def stages(clean, processed, fs, dt=np.float64, keep=None) -> Stages:
+    """The whole chain in dtype dt.  keep: use this keep mask instead of the chain's own (the fp32 stand-in is given float64's, so
+    that its later stages measure rounding and not another frame set)."""
+    s = Stages()
+    s.xr, s.yr = _resample(clean, fs, dt), _resample(processed, fs, dt)
+    s.norms, s.keep = _select(s.xr, dt)
+    if keep is not None:
+        s.keep = np.asarray(keep, bool)
+    kept = np.nonzero(s.keep)[0]
+    s.K0, s.K = int(s.keep.shape[0]), int(len(kept))
+    s.X = _bands(_stft_frames(s.xr, kept, dt), dt)
+    s.Y = _bands(_stft_frames(s.yr, kept, dt), dt)
+    s.d, s.cond = {}, {}
+    for ext in (False, True):
+        s.d[ext], s.cond[ext] = _segments(s.X, s.Y, ext, dt)
+    return s
+
+
+def stoi64(clean, processed, fs, extended=False) -> float:
+    return float(stages(np.asarray(clean, np.float64), np.asarray(processed, np.float64), fs).d[bool(extended)])
+
+
+def keep_margin(s: Stages) -> float:
+    """The smallest relative distance of a candidate frame's norm from the keep threshold 0.01 max."""
+    thr = RANGE * (s.norms.max() + EPS) - EPS
+    return float((np.abs(s.norms - thr) / thr).min())
+
+
+# ------------------------------------------------------------------------------------------------ signals
+def speechlike(T: int, fs: int, seed: int = 0):
+    """An amplitude-modulated harmonic stack plus a little noise: never stationary."""
+    rng = np.random.default_rng(7919 * seed + T)
+    t = np.arange(T, dtype=np.float64) / fs
+    f0 = 110.0 + 30.0 * rng.random()
+    x = np.zeros(T)
+    for h in range(1, 25):
+        am = 0.55 + 0.45 * np.sin(2 * np.pi * (1.5 + 4.5 * rng.random()) * t + 2 * np.pi * rng.random())
+        x += am * np.sin(2 * np.pi * f0 * h * (1.0 + 0.02 * np.sin(2 * np.pi * 2.3 * t)) * t + 2 * np.pi * rng.random()) / h ** 0.7
+    x *= 0.1
+    return (x + 1e-3 * rng.standard_normal(T)).astype(np.float32)
+
+
+def noisy(x, snr_db: float, seed: int = 1):
+    rng = np.random.default_rng(104729 * seed + len(x))
+    n = rng.standard_normal(len(x))
+    x64 = np.asarray(x, np.float64)
+    n *= np.sqrt((x64 * x64).mean() / (n * n).mean()) * 10.0 ** (-snr_db / 20.0)
+    return (x64 + n).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ the call, through ctypes
+CANARY = 12345.0
+
+
+@functools.lru_cache(maxsize=None)
+def handle(fs: int):
+    from wavtokenizer_amd import metrics
+    return metrics.stoi_handle(fs, 0)
+
+
+class Run:
+    """What one wt_stoi call with taps gave: d [n]; per clip xr, yr, keep, K0, K, X, Y; intact (canaries and the tail of the
+    workspace)."""
+
+
+def run(cleans, processeds, fs, extended=False, ws_fill=0xAB, with_taps=True) -> Run:
+    """One wt_stoi call on pairs laid out in a NaN arena, the outputs between canaries, the workspace and the tap buffers filled
+    with ws_fill beforehand."""
+    import ctypes
+
+    import torch
+
+    from tests.mel_ref import Arena, Outputs
+    from wavtokenizer_amd._capi import WtStoiClip, WtStoiTaps, check, lib
+    n = len(cleans)
+    assert all(len(a) == len(b) for a, b in zip(cleans, processeds))
+    arena = Arena(list(cleans) + list(processeds))
+    outs = Outputs([1] * n)
+    h = handle(int(fs))
+    nres = [int(lib.wt_stoi_resampled_length(h, len(c))) for c in cleans]
+    K0 = [candidate_frames(r) for r in nres]
+    nbytes = int(lib.wt_stoi_workspace_bytes(h, n, sum(nres), sum(K0)))
+    ws = torch.full((nbytes + 64,), ws_fill, dtype=torch.uint8, device="cuda")
+    descs = (WtStoiClip * n)()
+    for i in range(n):
+        descs[i].clean, descs[i].processed, descs[i].length, descs[i].out = arena.ptr(i), arena.ptr(n + i), len(cleans[i]), outs.ptr(i)
+    taps, bufs = None, None
+    if with_taps:
+        def filled(words):
+            return torch.full((4 * words + 64,), ws_fill, dtype=torch.uint8, device="cuda")
+        bufs = dict(resampled=filled(2 * sum(nres)), keep=filled(sum(K0)), counts=filled(2 * n), tob=filled(2 * BANDS * sum(K0)))
+        taps = WtStoiTaps(*(bufs[k].data_ptr() for k in ("resampled", "keep", "counts", "tob")))
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    check(lib.wt_stoi(h, descs, n, 1 if extended else 0, ctypes.c_void_p(ws.data_ptr()), stream,
+                      ctypes.byref(taps) if taps is not None else None), "wt_stoi")
+    torch.cuda.synchronize()
+    r = Run()
+    got, intact = outs.read()
+    r.d = np.array([g[0] for g in got], np.float32)
+    r.intact = intact and bool((ws[nbytes:] == ws_fill).all())
+    if not with_taps:
+        return r
+    sizes = dict(resampled=2 * sum(nres), keep=sum(K0), counts=2 * n, tob=2 * BANDS * sum(K0))
+    for k, b in bufs.items():
+        r.intact = r.intact and bool((b[4 * sizes[k]:] == ws_fill).all())
+    res = bufs["resampled"][:4 * sizes["resampled"]].view(torch.float32).cpu().numpy()
+    keep = bufs["keep"][:4 * sizes["keep"]].view(torch.int32).cpu().numpy()
+    counts = bufs["counts"][:4 * sizes["counts"]].view(torch.int32).cpu().numpy()
+    tob = bufs["tob"][:4 * sizes["tob"]].view(torch.float32).cpu().numpy()
+    r.clips = []
+    ro = fo = 0
+    for i in range(n):
+        c = Stages()
+        c.K0, c.K = int(counts[2 * i]), int(counts[2 * i + 1])
+        assert c.K0 == K0[i]
+        if int(fs) != FS:
+            c.xr, c.yr = res[2 * ro: 2 * ro + nres[i]].copy(), res[2 * ro + nres[i]: 2 * ro + 2 * nres[i]].copy()
+        else:                                                     # no resampling stage: the kernels read the inputs themselves
+            c.xr, c.yr = np.asarray(cleans[i], np.float32), np.asarray(processeds[i], np.float32)
+        c.keep = keep[fo: fo + K0[i]] != 0
+        assert set(np.unique(keep[fo: fo + K0[i]])) <= {0, 1}
+        J = max(c.K - 1, 0)
+        block = tob[2 * BANDS * fo: 2 * BANDS * (fo + K0[i])].reshape(2, BANDS, K0[i]) if K0[i] else np.zeros((2, BANDS, 0), np.float32)
+        c.X, c.Y = block[0][:, :J].copy(), block[1][:, :J].copy()
+        r.clips.append(c)
+        ro += nres[i]
+        fo += K0[i]
+    return r

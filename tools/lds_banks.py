@@ -151,9 +151,35 @@ def mel_fft():
         print(f"      extra LDS cycles (above the conflict-free count) summed over the listed variants: {extra}")
 
 
+# ------------------------------------------------------------------------------- stoi.hip: 256-point radix-4 Stockham FFT of one wave
+def stoi_swz(i):
+    """stoi.hip stoi_swz: point i of a float plane sits at word i ^ b ^ (b << 2) ^ (((i >> 6) & 1) << 4), b = (i >> 5) & 3"""
+    b = (i >> 5) & 3
+    return i ^ b ^ (b << 2) ^ (((i >> 6) & 1) << 4)
+
+
+def stoi_fft():
+    print("--- stoi_frame (stoi.hip): two float planes of 256 points per wave, per wave-instruction")
+    pats = [("pass 1 store, point 4 lane + q", "ds_write_b32", lambda l, q: 4 * l + q),
+            ("pass 2-4 load, point lane + 64 r", "ds_read_b32", lambda l, r: l + 64 * r),
+            ("pass 2 store, point 16 (lane / 4) + lane % 4 + 4 q", "ds_write_b32", lambda l, q: 16 * (l >> 2) + (l & 3) + 4 * q),
+            ("pass 3 store, point 64 (lane / 16) + lane % 16 + 16 q", "ds_write_b32", lambda l, q: 64 * (l >> 4) + (l & 15) + 16 * q),
+            ("pass 4 store, point lane + 64 q", "ds_write_b32", lambda l, q: l + 64 * q),
+            ("split pass load, point (256 - lane - 64 r) % 256", "ds_read_b32", lambda l, r: (256 - l - 64 * r) & 255)]
+    for label, swz in (("plain layout", lambda i: i), ("stoi_swz", stoi_swz)):
+        extra = 0
+        for name, instr, fn in pats:
+            extra += report(f"{label}: {name}", instr, lambda l, v: 4 * swz(fn(l, v)), list(range(4)))
+        print(f"      extra LDS cycles (above the conflict-free count) summed over the listed variants: {extra}")
+    assert sorted(stoi_swz(i) for i in range(256)) == list(range(256))
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["mel"]:
         mel_fft()
+        sys.exit(0)
+    if sys.argv[1:] == ["stoi"]:
+        stoi_fft()
         sys.exit(0)
     for new in (False, True):
         NEW = new

@@ -30,6 +30,7 @@ EXPORTS = [
     "wt_model_weight_count", "wt_model_weight_info", "wt_split_probe",
     "wt_encode_rvq", "wt_encode_rvq_mixed", "wt_quantize", "wt_vq_residual_probe", "wt_model_codebook_tables",
     "wt_mel_create", "wt_mel_destroy", "wt_mel_frames", "wt_mel_tables", "wt_mel_workspace_bytes", "wt_mel_spectrogram", "wt_mel_distance",
+    "wt_stoi_create", "wt_stoi_destroy", "wt_stoi_resampled_length", "wt_stoi_tables", "wt_stoi_workspace_bytes", "wt_stoi",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -185,6 +186,16 @@ class WtOverlapAddClip(ctypes.Structure):
 class WtMelClip(ctypes.Structure):
     """wt_mel_clip: one clip of a mel launch (wt_mel_spectrogram, wt_mel_distance)."""
     _fields_ = [("a", c_void_p), ("b", c_void_p), ("length", c_int64), ("out", c_void_p)]
+
+
+class WtStoiClip(ctypes.Structure):
+    """wt_stoi_clip: one pair of a STOI call (wt_stoi)."""
+    _fields_ = [("clean", c_void_p), ("processed", c_void_p), ("length", c_int64), ("out", c_void_p)]
+
+
+class WtStoiTaps(ctypes.Structure):
+    """wt_stoi_taps: where wt_stoi leaves its stages for tests."""
+    _fields_ = [("resampled", c_void_p), ("keep", c_void_p), ("counts", c_void_p), ("tob", c_void_p)]
 
 
 WT_WEIGHT_F32, WT_WEIGHT_S32, WT_WEIGHT_LSTM_F16, WT_WEIGHT_LSTM_PERSIST = 0, 1, 2, 3
@@ -343,6 +354,15 @@ def _load() -> ctypes.CDLL:
     lib.wt_mel_workspace_bytes.restype = c_size_t
     lib.wt_mel_spectrogram.argtypes = [c_void_p, POINTER(WtMelClip), c_int32, c_int32, c_void_p, c_void_p]
     lib.wt_mel_distance.argtypes = [c_void_p, POINTER(WtMelClip), c_int32, c_void_p, c_void_p]
+    lib.wt_stoi_create.argtypes = [c_int32, c_int32, POINTER(c_void_p)]
+    lib.wt_stoi_destroy.argtypes = [c_void_p]
+    lib.wt_stoi_destroy.restype = None
+    lib.wt_stoi_resampled_length.argtypes = [c_void_p, c_int64]
+    lib.wt_stoi_resampled_length.restype = c_int64
+    lib.wt_stoi_tables.argtypes = [c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_void_p, c_void_p, c_void_p]
+    lib.wt_stoi_workspace_bytes.argtypes = [c_void_p, c_int32, c_int64, c_int64]
+    lib.wt_stoi_workspace_bytes.restype = c_size_t
+    lib.wt_stoi.argtypes = [c_void_p, POINTER(WtStoiClip), c_int32, c_int32, c_void_p, c_void_p, POINTER(WtStoiTaps)]
     return lib
 
 

@@ -574,6 +574,20 @@ class _BatchedCalls:
         outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
         return metrics.mel_distance_many([o[0, :w.shape[-1]] for o, w in zip(outs, wavs)], wavs, **kw)
 
+    def round_trip_stoi(self, wavs: Sequence[torch.Tensor], *, n_q: Optional[int] = None, bandwidth_id=None,
+                        extended: bool = False) -> torch.Tensor:
+        """How intelligible the codec gives a set of clips back: STOI (extended=True: ESTOI) per clip, (n,) fp32.  wavs is a list of
+        1-D fp32 clips at the codec rate, 24 kHz, on the model's device.  It is round_trip_mel_distance with the other metric:
+        encode_codes_many -> decode_codes_many -> each output cropped to its input's length -> metrics.stoi_many(wavs, outputs,
+        sample_rate=24000, extended=extended), and nothing else."""
+        from . import metrics
+        wavs = list(wavs)
+        if not wavs:
+            return torch.zeros(0, dtype=torch.float32, device=self._ensure_engine())
+        codes = self.encode_codes_many(wavs, bandwidth_id=bandwidth_id, n_q=n_q)
+        outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
+        return metrics.stoi_many(wavs, [o[0, :w.shape[-1]] for o, w in zip(outs, wavs)], sample_rate=24000, extended=extended)
+
     # -- synthesise straight to PCM: decode from codes -> ragged emit (resample, channels, layout, sample type) into one tensor -----
     def _emit_format(self, who: str, channels, dtype, limit, n: int) -> Tuple[List[int], Tuple[torch.dtype, float]]:
         """(channels per clip, (dtype, limit)) of decode_pcm / decode_pcm_many over n clips, checked: ValueError for anything

@@ -9,15 +9,26 @@
 The transform restates torchaudio.transforms.MelSpectrogram(sample_rate, n_fft=1024, hop_length=256, n_mels=100, center=True,
 power=1) (include/wavtokenizer_amd.h gives the definition; parity with torchaudio itself is unpinned, it is not available to the
 tests).  A clip's spectrogram and distance have the same bits alone, in any batch and at any position.  Tensors are fp32 on the
-GPU; there is no CPU path.  `MelSpecReconstructionLoss()(y_hat, y)` becomes `mel_distance(y_hat, y)`."""
+GPU; there is no CPU path.  `MelSpecReconstructionLoss()(y_hat, y)` becomes `mel_distance(y_hat, y)`.
+
+And the intelligibility measure of the reference's evaluation script (metrics/infer.py:100-105, pystoi on the CPU per file):
+
+    stoi(clean, processed, sample_rate, extended=False)          (T,) -> 0-dim; (B, T) or (B, 1, T) -> (B,)
+    stoi_many(cleans, processeds, sample_rate=..., extended=False)   pairs of different lengths (and rates) -> (n,)
+
+STOI (Taal et al. 2011) and, with extended=True, ESTOI (Jensen & Taal 2016), restated from the published algorithm
+(include/wavtokenizer_amd.h gives the definition; parity with pystoi is unpinned, it is not available to the tests).  A pair's value
+has the same bits alone, in any batch and at any position.  `stoi(raw, pre, sr, extended=False)` becomes `stoi(raw, pre, sr)`."""
 import ctypes
-from typing import Dict, List, Sequence, Tuple
+import math
+from typing import Dict, List, Sequence, Tuple, Union
 
 import torch
 
-from ._capi import WtMelClip, check, lib
+from ._capi import WtMelClip, WtStoiClip, check, lib
 
 _handles: Dict[Tuple[int, int, int, int, int], ctypes.c_void_p] = {}
+_stoi_handles: Dict[Tuple[int, int], ctypes.c_void_p] = {}
 
 
 def _need_gpu(t: torch.Tensor):
@@ -147,3 +158,113 @@ def mel_distance(y_hat: torch.Tensor, y: torch.Tensor, *, sample_rate: int = 240
     p = list(y_hat.to(torch.float32).contiguous().view(-1, T).unbind(0))
     q = list(y.to(torch.float32).contiguous().view(-1, T).unbind(0))
     return mel_distance_many(p, q, sample_rate=sample_rate, n_fft=n_fft, hop_length=hop_length, n_mels=n_mels).mean()
+
+
+# ------------------------------------------------------------------------------------------------ STOI / ESTOI
+STOI_FS = 10000
+
+
+def stoi_ratio(sample_rate: int) -> Tuple[int, int]:
+    """(p, q) = 10000 / sample_rate reduced; ValueError for a rate wt_stoi_create refuses (max(p, q) > 441)."""
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or int(sample_rate) < 1:
+        raise ValueError(f"stoi: sample_rate must be a positive integer, not {sample_rate!r}")
+    g = math.gcd(STOI_FS, int(sample_rate))
+    p, q = STOI_FS // g, int(sample_rate) // g
+    if max(p, q) > 441:
+        raise ValueError(f"stoi: sample_rate {int(sample_rate)}: 10000 / sample_rate reduces to {p} / {q}, beyond 441 "
+                         "(8, 10, 16, 22.05, 24, 32, 44.1 and 48 kHz are among the rates that work)")
+    return p, q
+
+
+def stoi_frames(length: int, sample_rate: int) -> Tuple[int, int]:
+    """(samples at 10 kHz, candidate frames K0) of a clip; ValueError for a clip too short for one frame."""
+    p, q = stoi_ratio(sample_rate)
+    n = -(-int(length) * p // q)
+    if n <= 256:
+        raise ValueError(f"stoi: a clip of {int(length)} samples at {int(sample_rate)} Hz has {n} samples at 10 kHz: one frame needs "
+                         "more than 256")
+    return n, (n - 256 + 127) // 128
+
+
+def stoi_handle(sample_rate: int, device_index: int) -> ctypes.c_void_p:
+    """The wt_stoi of a rate on a device, created once per process."""
+    key = (int(sample_rate), int(device_index))
+    if key not in _stoi_handles:
+        h = ctypes.c_void_p()
+        check(lib.wt_stoi_create(*key, ctypes.byref(h)), "wt_stoi_create")
+        _stoi_handles[key] = h
+    return _stoi_handles[key]
+
+
+def _stoi_run(dev: torch.device, a: List[torch.Tensor], b: List[torch.Tensor], sample_rate: int, extended: bool, out: torch.Tensor,
+              slots: Sequence[int]):
+    """One wt_stoi call: pair i's value goes to out[slots[i]]."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    n = len(a)
+    sizes = [stoi_frames(w.shape[0], sample_rate) for w in a]
+    with torch.cuda.device(idx):
+        h = stoi_handle(sample_rate, idx)
+        ws_bytes = int(lib.wt_stoi_workspace_bytes(h, n, sum(s[0] for s in sizes), sum(s[1] for s in sizes)))
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        descs = (WtStoiClip * n)()
+        for i in range(n):
+            descs[i].clean = a[i].data_ptr()
+            descs[i].processed = b[i].data_ptr()
+            descs[i].length = a[i].shape[0]
+            descs[i].out = out.data_ptr() + 4 * slots[i]
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        check(lib.wt_stoi(h, descs, n, 1 if extended else 0, ctypes.c_void_p(ws.data_ptr()), stream, None), "wt_stoi")
+        # (queued on the current stream, as in _run above)
+
+
+def stoi_many(cleans: Sequence[torch.Tensor], processeds: Sequence[torch.Tensor], *, sample_rate: Union[int, Sequence[int]] = 24000,
+              extended: bool = False) -> torch.Tensor:
+    """STOI (extended=True: ESTOI) of pairs of 1-D clips: (n,) fp32, one call per sample rate for all the pairs of that rate.
+    sample_rate is one rate or one per pair (any sequence, numpy array or tensor of integers).  The two clips of a pair must have one length (ValueError otherwise); pairs may
+    differ.  Pair i's value is the bits of stoi(cleans[i], processeds[i], rate_i)."""
+    cleans, processeds = list(cleans), list(processeds)
+    if len(cleans) != len(processeds):
+        raise ValueError("stoi_many: as many cleans as processeds")
+    if hasattr(sample_rate, "tolist"):          # a numpy array or a tensor of rates, or a 0-dim one or a numpy scalar: one rate
+        sample_rate = sample_rate.tolist()
+    if isinstance(sample_rate, Sequence) and not isinstance(sample_rate, (str, bytes)):
+        rates = list(sample_rate)
+        if len(rates) != len(cleans):
+            raise ValueError("stoi_many: one sample_rate, or one per pair")
+    else:
+        rates = [sample_rate] * len(cleans)
+    for r in set(rates):
+        stoi_ratio(r)
+    for i, (p, q) in enumerate(zip(cleans, processeds)):
+        if isinstance(p, torch.Tensor) and isinstance(q, torch.Tensor) and p.dim() == 1 and q.dim() == 1:
+            if p.shape[0] != q.shape[0]:
+                raise ValueError(f"stoi_many: pair {i}: lengths {p.shape[0]} and {q.shape[0]} differ")
+            stoi_frames(p.shape[0], rates[i])
+    if not cleans:
+        return torch.zeros(0, dtype=torch.float32, device="cuda")
+    a, dev = _clips("stoi_many", cleans)
+    b, dev_b = _clips("stoi_many", processeds)
+    if dev_b != dev:
+        raise ValueError("stoi_many: all clips must be on one device")
+    out = torch.empty(len(a), dtype=torch.float32, device=dev)
+    for r in sorted(set(int(r) for r in rates)):
+        sel = [i for i, ri in enumerate(rates) if int(ri) == r]
+        _stoi_run(dev, [a[i] for i in sel], [b[i] for i in sel], r, bool(extended), out, sel)
+    return out
+
+
+def stoi(clean: torch.Tensor, processed: torch.Tensor, sample_rate: int = 24000, extended: bool = False) -> torch.Tensor:
+    """STOI (extended=True: ESTOI) of processed against clean, both at sample_rate: (T,) gives a 0-dim tensor, (B, T) and (B, 1, T)
+    give (B,), one value per row."""
+    if clean.shape != processed.shape:
+        raise ValueError(f"stoi: shapes {tuple(clean.shape)} and {tuple(processed.shape)} differ")
+    if clean.dim() not in (1, 2, 3) or (clean.dim() == 3 and clean.shape[1] != 1):
+        raise ValueError("stoi: inputs must be (T,), (B, T) or (B, 1, T)")
+    T = int(clean.shape[-1])
+    stoi_frames(T, sample_rate)
+    _need_gpu(clean)
+    _need_gpu(processed)
+    p = list(clean.to(torch.float32).contiguous().view(-1, T).unbind(0))
+    q = list(processed.to(torch.float32).contiguous().view(-1, T).unbind(0))
+    d = stoi_many(p, q, sample_rate=int(sample_rate), extended=extended) if p else torch.zeros(0, dtype=torch.float32, device=clean.device)
+    return d[0] if clean.dim() == 1 else d

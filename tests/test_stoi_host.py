@@ -221,3 +221,18 @@ def test_the_float64_definition():
     s = R.stages(x.astype(np.float64), R.noisy(x, 0).astype(np.float64), fs)
     s32 = R.stages(x, R.noisy(x, 0), fs, np.float32)
     assert np.array_equal(s.keep, s32.keep) and abs(float(s32.d[False]) - s.d[False]) < 1e-5
+
+
+def test_the_cpu_side_of_the_rate_and_edge_tests():
+    """What tests/test_stoi_rates.py and tests/test_stoi_edges.py assert before they launch: the (K0, K) expectations, the margin and
+    condition numbers, the stand-in's sanity windows, and that the definition and the stand-in give exact zeros, leave the keep mask
+    alone under the edge test's change of the clean signal and are invariant under a power-of-two gain."""
+    from tests import test_stoi_edges, test_stoi_rates
+    cases, bars = test_stoi_rates.reference()
+    assert len(cases) == 3 * 5 + 2 and all(b > 0 for b in bars.values())
+    cases, bars = test_stoi_edges.reference()
+    assert all(b > 0 for b in bars.values())
+    assert len(test_stoi_edges.zero_pairs()) == 3
+    assert [int(c[2].sum()) for c in test_stoi_edges.eps_scale()] == [35, 45]
+    assert len(test_stoi_edges.influence()[5]) == 2
+    assert sorted(test_stoi_edges.gain_pairs()) == [10000, 24000]

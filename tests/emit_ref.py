@@ -115,7 +115,8 @@ def untouched(buf, dests, sentinel):
 
 def emit(rows, n_in, rates, dests, limits):
     """One wt_emit launch: row j (a 1-D fp32 view on the GPU, read up to n_in[j]) to dests[j] at rates[j]; the destination's dtype
-    decides the sample type.  Waits for it."""
+    decides the sample type.  Waits for it and returns the workspace, filled with 0xAB before the launch, as (the
+    wt_emit_workspace_bytes(B) bytes, the 64 bytes behind them)."""
     from wavtokenizer_amd import _capi, audio
     dev = torch.cuda.current_device()
     B = len(rows)
@@ -127,10 +128,12 @@ def emit(rows, n_in, rates, dests, limits):
         d.dst = dst.buf.data_ptr() + dst.off * dst.buf.element_size()
         d.dtype = _capi.WT_EMIT_I16 if dst.buf.dtype == torch.int16 else _capi.WT_EMIT_F32
         d.channels, d.ch_stride, d.sample_stride, d.limit = dst.channels, dst.cs, dst.ss, lim
-    ws = torch.empty(max(int(_capi.lib.wt_emit_workspace_bytes(B)), 8), dtype=torch.uint8, device="cuda")
+    nbytes = int(_capi.lib.wt_emit_workspace_bytes(B))
+    ws = torch.full((nbytes + 64,), 0xAB, dtype=torch.uint8, device="cuda")
     _capi.check(_capi.lib.wt_emit(descs, B, ctypes.c_void_p(ws.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                 "wt_emit")
     torch.cuda.synchronize()
+    return ws[:nbytes], ws[nbytes:]
 
 
 def composition(row, rate, kind="f32", limit=LIMIT):

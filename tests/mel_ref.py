@@ -251,9 +251,10 @@ def handle(sample_rate=24000, hop=256, n_mels=100):
     return metrics.mel_handle(sample_rate, N_FFT, hop, n_mels, 0)
 
 
-def run(clips_a, clips_b=None, log=True, sample_rate=24000, hop=256, n_mels=100, ws_fill=0xAB):
+def run(clips_a, clips_b=None, log=True, sample_rate=24000, hop=256, n_mels=100, ws_fill=0xAB, with_workspace=False):
     """One wt_mel_spectrogram (clips_b None) or wt_mel_distance call on clips laid out in a NaN arena, outputs between canaries,
-    the workspace filled with ws_fill beforehand.  Returns (outputs: [n_mels][F] arrays or floats, canaries intact)."""
+    the workspace filled with ws_fill beforehand.  Returns (outputs: [n_mels][F] arrays or floats, canaries intact) and, with
+    with_workspace, the workspace's bytes after the call as a third item."""
     import ctypes
 
     import torch
@@ -281,6 +282,5 @@ def run(clips_a, clips_b=None, log=True, sample_rate=24000, hop=256, n_mels=100,
     torch.cuda.synchronize()
     got, intact = outs.read()
     assert bool((ws[nbytes:] == ws_fill).all()), "the call wrote behind its workspace"
-    if dist:
-        return [g[0] for g in got], intact
-    return [g.reshape(n_mels, f) for g, f in zip(got, F)], intact
+    res = [g[0] for g in got] if dist else [g.reshape(n_mels, f) for g, f in zip(got, F)]
+    return (res, intact, ws[:nbytes].cpu().numpy()) if with_workspace else (res, intact)

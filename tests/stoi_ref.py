@@ -275,7 +275,7 @@ def handle(fs: int):
 
 class Run:
     """What one wt_stoi call with taps gave: d [n]; per clip xr, yr, keep, K0, K, X, Y; intact (canaries and the tail of the
-    workspace)."""
+    workspace); ws (the workspace's bytes after the call)."""
 
 
 def run(cleans, processeds, fs, extended=False, ws_fill=0xAB, with_taps=True) -> Run:
@@ -313,6 +313,7 @@ def run(cleans, processeds, fs, extended=False, ws_fill=0xAB, with_taps=True) ->
     got, intact = outs.read()
     r.d = np.array([g[0] for g in got], np.float32)
     r.intact = intact and bool((ws[nbytes:] == ws_fill).all())
+    r.ws = ws[:nbytes].cpu().numpy()
     if not with_taps:
         return r
     sizes = dict(resampled=2 * sum(nres), keep=sum(K0), counts=2 * n, tob=2 * BANDS * sum(K0))

@@ -74,12 +74,13 @@ class Launch:
         for d, ((flen, stride, total), frames, _w), fi, w, oo in zip(descs, recordings, first, self.weights, self.out_off):
             d.rows, d.n_frames, d.frame_len, d.stride, d.total = self.table.data_ptr() + 8 * fi, len(frames), flen, stride, total
             d.weight, d.out = w.data_ptr(), self.out.data_ptr() + 4 * oo
-        ws = torch.full((max(int(_capi.lib.wt_overlap_add_ragged_workspace_bytes(B)), 8),), 0xAB, dtype=torch.uint8, device="cuda")
+        nbytes = int(_capi.lib.wt_overlap_add_ragged_workspace_bytes(B))
+        ws = torch.full((nbytes + 64,), 0xAB, dtype=torch.uint8, device="cuda")
         _capi.check(_capi.lib.wt_overlap_add_ragged(descs, B, ctypes.c_void_p(ws.data_ptr()),
                                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "wt_overlap_add_ragged")
         torch.cuda.synchronize()
         self.totals = [c[2] for c, _f, _w in recordings]
-        self.workspace = ws
+        self.workspace, self.behind_workspace = ws[:nbytes], ws[nbytes:]
 
     def result(self, r):
         return self.out[self.out_off[r]:self.out_off[r] + self.totals[r]].cpu().numpy()

@@ -373,3 +373,21 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = lib.wt_last_error()
         raise WavTokError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}", rc)
+
+
+# Tensors and streams across the C ABI, for audio.py, engine.py and metrics.py (which import torch; nothing here needs it to load)
+def _ptr(t) -> c_void_p:
+    """A tensor's data pointer; None gives a null pointer."""
+    return c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _stream(device) -> c_void_p:
+    """The HIP stream that is current on the device."""
+    import torch
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _need_gpu(t, message: str) -> None:
+    """RuntimeError(message), the calling module's own wording, for a tensor that is not on the GPU."""
+    if t.device.type != "cuda":
+        raise RuntimeError(message)

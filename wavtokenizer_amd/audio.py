@@ -13,22 +13,12 @@ from typing import Dict, List, Sequence, Tuple
 
 import torch
 
-from ._capi import check, lib
+from ._capi import _need_gpu, _ptr, _stream, check, lib
 
 _resamplers: Dict[Tuple[int, int, int], ctypes.c_void_p] = {}
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _need_gpu(t: torch.Tensor):
-    if t.device.type != "cuda":
-        raise RuntimeError("wavtokenizer_amd.audio runs on the GPU only (move the tensor with .to('cuda'))")
+_GPU_ONLY = "wavtokenizer_amd.audio runs on the GPU only (move the tensor with .to('cuda'))"
 
 
 @functools.lru_cache(maxsize=None)
@@ -74,7 +64,7 @@ def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: i
     assert wav.shape[-2] in [1, 2], "Audio must be mono or stereo."
     if target_channels != 1:
         raise RuntimeError("only target_channels = 1 is implemented (what every caller of the codec path asks for)")
-    _need_gpu(wav)
+    _need_gpu(wav, _GPU_ONLY)
     *shape, channels, length = wav.shape
     dev = wav.device
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -90,7 +80,7 @@ def convert_audio(wav: torch.Tensor, sr: int, target_sr: int, target_channels: i
 
 
 def to_pcm16(wav: torch.Tensor, rescale: bool = False, limit: float = 0.99) -> torch.Tensor:
-    _need_gpu(wav)
+    _need_gpu(wav, _GPU_ONLY)
     x = wav.to(torch.float32).contiguous()
     out = torch.empty(x.shape, dtype=torch.int16, device=x.device)
     ws = torch.zeros(1, dtype=torch.int32, device=x.device)
@@ -100,7 +90,7 @@ def to_pcm16(wav: torch.Tensor, rescale: bool = False, limit: float = 0.99) -> t
 
 def linear_overlap_add(frames: Sequence[torch.Tensor], stride: int) -> torch.Tensor:
     assert len(frames)
-    _need_gpu(frames[0])
+    _need_gpu(frames[0], _GPU_ONLY)
     dev = frames[0].device
     shape = frames[0].shape[:-1]
     flen, last = int(frames[0].shape[-1]), int(frames[-1].shape[-1])
@@ -128,7 +118,7 @@ def segment_offsets(length: int, segment_length: int, stride: int) -> List[int]:
 def segmented_round_trip(model, wav: torch.Tensor, segment_length: int, stride: int, bandwidth_id=None) -> torch.Tensor:
     """encode_infer + decode of a long clip in overlapping segments, cross-faded with the reference's linear
     overlap-add (EncodecModel.encode / .decode, encoder/model.py:122-190): wav [B, T] -> [B, T]."""
-    _need_gpu(wav)
+    _need_gpu(wav, _GPU_ONLY)
     bw = bandwidth_id if bandwidth_id is not None else torch.tensor([0])
     T = wav.shape[-1]
     outs = []

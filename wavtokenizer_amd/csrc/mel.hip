@@ -25,11 +25,12 @@ struct wt_mel {
 };
 
 // FFT products must not depend on the kernel a device function is inlined into: no contraction by the compiler, fmaf where wanted
+// (over fft.h's functions too: the pragma stands before the include)
 #pragma clang fp contract(off)
+#include "fft.h"
+#include "ragged.h"
 
 namespace wt {
-
-int stage_descriptors(int device, const void* descs, size_t bytes, size_t min_bytes, void* workspace, hipStream_t s);     // audio.hip
 
 constexpr int MEL_NFFT = 1024, MEL_BINS = MEL_NFFT / 2 + 1, MEL_MAX_MELS = 128;
 constexpr int MEL_WAVES = 4;                    // frames per workgroup: one per wave
@@ -39,9 +40,6 @@ constexpr int MEL_TAB_TW = MEL_TAB_WIN + MEL_NFFT;          // [1024][2] (cos, -
 constexpr int MEL_TAB_FBW = MEL_TAB_TW + 2 * MEL_NFFT;      // [2 * 513 + 6] non-zero filter weights, filter after filter
 constexpr int MEL_TAB_FB = MEL_TAB_FBW + 2 * MEL_BINS + 6;  // int [3][128]: first bin, count, offset into the weights
 constexpr int MEL_TAB_WORDS = MEL_TAB_FB + 3 * MEL_MAX_MELS;
-
-template <class T> using global_ptr = __attribute__((address_space(1))) T*;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // One clip of a launch (device form of wt_mel_clip)
 struct MelClip {
@@ -62,37 +60,6 @@ enum : int { MEL_MODE_LINEAR = 0, MEL_MODE_LOG = 1, MEL_MODE_DISTANCE = 2 };
 // 512 complex points as two float planes: point i sits at word swz(i).  Every access of the three passes (stride-8 and stride-64
 // writes, stride-1 reads) then meets each of the 32 banks once per 32-lane half (tools/lds_banks.py, section mel)
 __device__ __forceinline__ int mel_swz(int i) { return i ^ ((i >> 3) & 7) ^ (((i >> 6) & 3) << 3); }
-
-__device__ __forceinline__ f32x2 cmul(f32x2 a, f32x2 b) {
-    return f32x2{fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x)};
-}
-__device__ __forceinline__ void bfly2(f32x2& a, f32x2& b) {
-    const f32x2 t = a;
-    a = t + b;
-    b = t - b;
-}
-__device__ __forceinline__ f32x2 mul_mi(f32x2 a) { return f32x2{a.y, -a.x}; }     // a * -i
-__device__ __forceinline__ void bfly4(f32x2& a, f32x2& b, f32x2& c, f32x2& d) {
-    bfly2(a, c);
-    bfly2(b, d);
-    d = mul_mi(d);
-    bfly2(a, b);
-    bfly2(c, d);
-}
-// 8-point DFT in place; output q is left in v[rev3(q)]
-__device__ __forceinline__ void bfly8(f32x2 (&v)[8]) {
-    const float h = 0.70710678118654752440f;
-    bfly2(v[0], v[4]);
-    bfly2(v[1], v[5]);
-    bfly2(v[2], v[6]);
-    bfly2(v[3], v[7]);
-    v[5] = f32x2{(v[5].x + v[5].y) * h, (v[5].y - v[5].x) * h};        // * (1 - i) / sqrt 2
-    v[6] = mul_mi(v[6]);
-    v[7] = f32x2{(v[7].y - v[7].x) * h, -(v[7].x + v[7].y) * h};       // * (-1 - i) / sqrt 2
-    bfly4(v[0], v[1], v[2], v[3]);
-    bfly4(v[4], v[5], v[6], v[7]);
-}
-__device__ __forceinline__ int rev3(int q) { return ((q & 1) << 2) | (q & 2) | (q >> 2); }
 
 // Frame f of clip x (T samples): mel value (log: its clipped log) of filter `lane` in m0 and of filter lane + 64 in m1 (0 where there
 // is no such filter).  zr, zi [512] and S [MEL_BINS] are the calling wave's own LDS; every wave of the block makes the call (the
@@ -167,12 +134,7 @@ __device__ __forceinline__ void mel_frame(global_ptr<const float> x, long T, lon
         const int k = lane + 64 * r;
         if (k < MEL_BINS) {
             const int o = mel_swz(k & 511), om = mel_swz((512 - k) & 511);
-            const f32x2 zk = f32x2{zr[o], zi[o]}, zm = f32x2{zr[om], zi[om]};
-            const f32x2 e = f32x2{0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)};
-            const f32x2 d = f32x2{zk.x - zm.x, zk.y + zm.y};
-            const f32x2 p = cmul(tw[k], d);
-            const float re = e.x + 0.5f * p.y, im = e.y - 0.5f * p.x;
-            S[k] = sqrtf(fmaf(re, re, im * im));
+            S[k] = sqrtf(cpower(real_split_bin(f32x2{zr[o], zi[o]}, f32x2{zr[om], zi[om]}, tw[k])));
         }
     }
     __syncthreads();
@@ -220,9 +182,7 @@ __device__ __forceinline__ void mel_block(const MelClip& d, const MelTab& tb, in
     }
     float b0, b1;
     mel_frame((global_ptr<const float>)d.b, d.T, fr, tb, zr, zi, S, lane, true, b0, b1);
-    float s = (lane < tb.n_mels ? fabsf(a0 - b0) : 0.f) + (lane + 64 < tb.n_mels ? fabsf(a1 - b1) : 0.f);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float s = wave_sum((lane < tb.n_mels ? fabsf(a0 - b0) : 0.f) + (lane + 64 < tb.n_mels ? fabsf(a1 - b1) : 0.f));
     if (valid && lane == 0) part[d.part + f] = s;
 }
 
@@ -232,27 +192,18 @@ __device__ __forceinline__ void mel_mean_block(const MelClip& d, int n_mels, con
     const int lane = threadIdx.x;
     float s = 0.f;
     for (long i = lane; i < d.F; i += 64) s += part[d.part + i];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) *(global_ptr<float>)d.out = s / ((float)n_mels * (float)d.F);
 }
 
-__global__ __launch_bounds__(256) void mel_frame_kernel(const MelClip* __restrict__ clips, const MelTab tb, int mode, float* __restrict__ part) {
-    mel_block(clips[blockIdx.y], tb, mode, part);
-}
-__global__ __launch_bounds__(64) void mel_mean_kernel(const MelClip* __restrict__ clips, int n_mels, const float* __restrict__ part) {
-    mel_mean_block(clips[blockIdx.x], n_mels, part);
-}
-
-// The same launches with the descriptors in the kernel's argument block (as emit_args_kernel): up to MEL_ARG_CLIPS clips need no
-// upload and no host wait, so the call can be captured into a graph.
+// D: the descriptors in the kernel's argument block (up to MEL_ARG_CLIPS clips: no upload and no host wait, so the call can be
+// captured into a graph) or in the workspace (ragged.h)
 constexpr int MEL_ARG_CLIPS = 64;
-struct MelArgs { MelClip clip[MEL_ARG_CLIPS]; };
-__global__ __launch_bounds__(256) void mel_frame_args_kernel(const MelArgs a, const MelTab tb, int mode, float* __restrict__ part) {
-    mel_block(a.clip[blockIdx.y], tb, mode, part);
+template <class D> __global__ __launch_bounds__(256) void mel_frame_kernel(const D d, const MelTab tb, int mode, float* __restrict__ part) {
+    mel_block(d.clip[blockIdx.y], tb, mode, part);
 }
-__global__ __launch_bounds__(64) void mel_mean_args_kernel(const MelArgs a, int n_mels, const float* __restrict__ part) {
-    mel_mean_block(a.clip[blockIdx.x], n_mels, part);
+template <class D> __global__ __launch_bounds__(64) void mel_mean_kernel(const D d, int n_mels, const float* __restrict__ part) {
+    mel_mean_block(d.clip[blockIdx.x], n_mels, part);
 }
 
 static size_t mel_desc_bytes(int B) { return ((size_t)B * sizeof(MelClip) + 15) / 16 * 16; }
@@ -295,10 +246,7 @@ static void mel_tables(int sample_rate, int n_mels, std::vector<float>& window, 
 
 static int mel_run(const wt_mel* m, const wt_mel_clip* clips, int32_t B, int mode, void* workspace, void* stream, const char* name) {
     const std::string fn = name;
-    if (!m) { set_error(fn + ": null handle"); return WT_ERR_INVALID; }
-    if (!clips || !workspace) { set_error(fn + ": null clips or workspace"); return WT_ERR_INVALID; }
-    if (B < 1 || B > 65535) { set_error(fn + ": B outside 1..65535"); return WT_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error(fn + ": workspace misaligned"); return WT_ERR_INVALID; }
+    if (!ragged_call_ok(fn, m, clips, workspace, B, 65535)) return WT_ERR_INVALID;
     if (m->n_fft != MEL_NFFT || m->hop < 1 || m->hop > MEL_NFFT || m->n_mels < 1 || m->n_mels > MEL_MAX_MELS || !m->tab) {
         set_error(fn + ": not a handle of wt_mel_create"); return WT_ERR_INVALID;
     }
@@ -321,26 +269,15 @@ static int mel_run(const wt_mel* m, const wt_mel_clip* clips, int32_t B, int mod
         total += F;
     }
     if ((max_frames + MEL_WAVES - 1) / MEL_WAVES > 0x7fffffffLL) { set_error(fn + ": clip too long for one launch"); return WT_ERR_INVALID; }
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess || device != m->device) {
-        set_error(fn + ": the handle belongs to another device than the calling thread's current one"); return WT_ERR_INVALID;
-    }
-    if (device < 0 || device >= 64) { set_error(fn + ": device index"); return WT_ERR_INVALID; }
+    if (!on_current_device(fn, m->device)) return WT_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const MelTab tb{m->tab, m->hop, m->n_mels};
     float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + mel_desc_bytes(B));
     const dim3 grid((unsigned)((max_frames + MEL_WAVES - 1) / MEL_WAVES), (unsigned)B);
-    if (B <= MEL_ARG_CLIPS) {
-        MelArgs args{};
-        memcpy(args.clip, dev.data(), dev.size() * sizeof(MelClip));      // (blocks read clip[blockIdx < B] alone)
-        hipLaunchKernelGGL(mel_frame_args_kernel, grid, dim3(64 * MEL_WAVES), 0, s, args, tb, mode, part);
-        if (mode == MEL_MODE_DISTANCE) hipLaunchKernelGGL(mel_mean_args_kernel, dim3((unsigned)B), dim3(64), 0, s, args, m->n_mels, part);
-    } else {
-        if (int rc = stage_descriptors(device, dev.data(), dev.size() * sizeof(MelClip), 128 * sizeof(MelClip), workspace, s)) return rc;
-        const MelClip* dc = static_cast<const MelClip*>(workspace);
-        hipLaunchKernelGGL(mel_frame_kernel, grid, dim3(64 * MEL_WAVES), 0, s, dc, tb, mode, part);
-        if (mode == MEL_MODE_DISTANCE) hipLaunchKernelGGL(mel_mean_kernel, dim3((unsigned)B), dim3(64), 0, s, dc, m->n_mels, part);
-    }
+    if (int rc = launch_ragged<MEL_ARG_CLIPS>(name, dev.data(), B, 128, workspace, s, [&](auto d) {
+        hipLaunchKernelGGL(mel_frame_kernel<decltype(d)>, grid, dim3(64 * MEL_WAVES), 0, s, d, tb, mode, part);
+        if (mode == MEL_MODE_DISTANCE) hipLaunchKernelGGL(mel_mean_kernel<decltype(d)>, dim3((unsigned)B), dim3(64), 0, s, d, m->n_mels, part);
+    })) return rc;
     WT_HIP_CHECK(hipGetLastError());
     return WT_OK;
 }
@@ -359,11 +296,7 @@ int wt_mel_create(int32_t sample_rate, int32_t n_fft, int32_t hop_length, int32_
     mel_tables(sample_rate, n_mels, window, fb);
     std::vector<float> tab((size_t)MEL_TAB_WORDS, 0.f);
     memcpy(tab.data() + MEL_TAB_WIN, window.data(), MEL_NFFT * sizeof(float));
-    const double pi = 3.14159265358979323846;
-    for (int n = 0; n < MEL_NFFT; ++n) {
-        tab[MEL_TAB_TW + 2 * n] = (float)std::cos(2.0 * pi * n / MEL_NFFT);
-        tab[MEL_TAB_TW + 2 * n + 1] = (float)-std::sin(2.0 * pi * n / MEL_NFFT);
-    }
+    fill_twiddles(tab.data() + MEL_TAB_TW, MEL_NFFT);
     // sparse form: a triangular filter's non-zero bins are one run; a bin lies in at most two filters, so the runs hold at most
     // 2 * 513 weights
     std::vector<int32_t> fbt((size_t)3 * MEL_MAX_MELS, 0);
@@ -381,27 +314,10 @@ int wt_mel_create(int32_t sample_rate, int32_t n_fft, int32_t hop_length, int32_
         used += cnt;
     }
     memcpy(tab.data() + MEL_TAB_FB, fbt.data(), fbt.size() * sizeof(int32_t));
-    // the table is allocated on `device`; the calling thread's current device is put back before the call returns
-    int prev = 0;
-    WT_HIP_CHECK(hipGetDevice(&prev));
-    WT_HIP_CHECK(hipSetDevice(device));
+    float* dtab = nullptr;
+    if (int rc = upload_table("wt_mel_create", device, tab, &dtab)) return rc;
     wt_mel* h = new wt_mel();
-    h->device = device; h->sample_rate = sample_rate; h->n_fft = n_fft; h->hop = hop_length; h->n_mels = n_mels;
-    const bool ok = hipMalloc(reinterpret_cast<void**>(&h->tab), tab.size() * sizeof(float)) == hipSuccess &&
-                    hipMemcpy(h->tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        set_error("wt_mel_create: device allocation failed");
-        if (h->tab) (void)hipFree(h->tab);
-        delete h;
-    }
-    const hipError_t back = hipSetDevice(prev);
-    if (!ok) return WT_ERR_HIP;
-    if (back != hipSuccess) {
-        set_error("wt_mel_create: could not restore the current device");
-        (void)hipFree(h->tab);
-        delete h;
-        return WT_ERR_HIP;
-    }
+    h->device = device; h->sample_rate = sample_rate; h->n_fft = n_fft; h->hop = hop_length; h->n_mels = n_mels; h->tab = dtab;
     *out = h;
     return WT_OK;
 }

@@ -33,11 +33,12 @@ struct wt_stoi_handle {
 };
 
 // sums and products must not depend on the kernel a device function is inlined into: no contraction by the compiler, fmaf where wanted
+// (over fft.h's functions too: the pragma stands before the include)
 #pragma clang fp contract(off)
+#include "fft.h"
+#include "ragged.h"
 
 namespace wt {
-
-int stage_descriptors(int device, const void* descs, size_t bytes, size_t min_bytes, void* workspace, hipStream_t s);     // audio.hip
 
 constexpr int STOI_FS = 10000, STOI_FRAME = 256, STOI_HOP = 128, STOI_BANDS = 15, STOI_SEG = 30;
 constexpr int STOI_MAX_RATIO = 441;             // the larger of p and q
@@ -55,9 +56,6 @@ constexpr int STOI_TAB_H = STOI_TAB_PHASE + 448;             // [2 L + 1]
 // band i sums bins [EDGE[i], EDGE[i + 1])
 __constant__ int STOI_EDGE[STOI_BANDS + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 static const int STOI_EDGE_HOST[STOI_BANDS + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
-
-template <class T> using global_ptr = __attribute__((address_space(1))) T*;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // One clip of a call (device form of wt_stoi_clip)
 struct StoiClip {
@@ -86,38 +84,7 @@ struct StoiTab {
     int p, q, L;
 };
 
-constexpr int STOI_ARG_CLIPS = 32;
-struct StoiArgs { StoiClip clip[STOI_ARG_CLIPS]; };         // descriptors in the launch's own argument block
-struct StoiPtr { const StoiClip* clip; };                   // descriptors in the workspace
-
-__device__ __forceinline__ f32x2 cmul(f32x2 a, f32x2 b) {
-    return f32x2{fmaf(a.x, b.x, -(a.y * b.y)), fmaf(a.x, b.y, a.y * b.x)};
-}
-__device__ __forceinline__ void bfly2(f32x2& a, f32x2& b) {
-    const f32x2 t = a;
-    a = t + b;
-    b = t - b;
-}
-// 4-point DFT in place; output q is left in v[rev2(q)]
-__device__ __forceinline__ void bfly4(f32x2 (&v)[4]) {
-    bfly2(v[0], v[2]);
-    bfly2(v[1], v[3]);
-    v[3] = f32x2{v[3].y, -v[3].x};              // * -i
-    bfly2(v[0], v[1]);
-    bfly2(v[2], v[3]);
-}
-__device__ __forceinline__ int rev2(int q) { return ((q & 1) << 1) | (q >> 1); }
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
-// the sum over the lane's aligned group of 32
-__device__ __forceinline__ float half_sum(float s) {
-#pragma unroll
-    for (int off = 16; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
+constexpr int STOI_ARG_CLIPS = 32;           // descriptors up to this many travel in the launches' argument blocks (ragged.h)
 
 // 256 complex points as two float planes: point i sits at word swz(i).  Every store of the four passes (strides 4, 16 and 64 between
 // a lane's points, lanes 1, 4-with-gaps and 16-with-gaps apart) and every stride-1 load then meets each of the 32 banks once per
@@ -263,7 +230,7 @@ __device__ __forceinline__ void stoi_frame(global_ptr<const float> x, global_ptr
         v[3] = f32x2{0.f, 0.f};
     }
     // pass 1 (sub-transform length 1): no twiddles; output q of lane's butterfly goes to point 4 lane + q
-    bfly4(v);
+    bfly4(v[0], v[1], v[2], v[3]);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int o = stoi_swz(4 * lane + q);
@@ -282,7 +249,7 @@ __device__ __forceinline__ void stoi_frame(global_ptr<const float> x, global_ptr
         const int k = lane & ((1 << ls) - 1);
 #pragma unroll
         for (int r = 1; r < 4; ++r) v[r] = cmul(v[r], tw[(r * k) << (7 - ls)]);
-        bfly4(v);
+        bfly4(v[0], v[1], v[2], v[3]);
         const int j0 = ((lane >> ls) << (ls + 2)) + k;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -298,12 +265,7 @@ __device__ __forceinline__ void stoi_frame(global_ptr<const float> x, global_ptr
         const int k = lane + 64 * r;
         if (k >= 7 && k < 219) {
             const int o = stoi_swz(k), om = stoi_swz(256 - k);
-            const f32x2 zk = f32x2{zr[o], zi[o]}, zm = f32x2{zr[om], zi[om]};
-            const f32x2 e = f32x2{0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y)};
-            const f32x2 d = f32x2{zk.x - zm.x, zk.y + zm.y};
-            const f32x2 p = cmul(tw[k], d);
-            const float re = e.x + 0.5f * p.y, im = e.y - 0.5f * p.x;
-            S[k] = fmaf(re, re, im * im);
+            S[k] = cpower(real_split_bin(f32x2{zr[o], zi[o]}, f32x2{zr[om], zi[om]}, tw[k]));
         }
     }
     __syncthreads();
@@ -527,36 +489,15 @@ int wt_stoi_create(int32_t sample_rate, int32_t device, wt_stoi_handle** out) {
     const int L = stoi_filter_half(p, q);
     std::vector<float> tab((size_t)STOI_TAB_H + filter.size(), 0.f);
     memcpy(tab.data() + STOI_TAB_WIN, window.data(), window.size() * sizeof(float));
-    const double pi = 3.14159265358979323846;
-    for (int n = 0; n < 512; ++n) {
-        tab[STOI_TAB_TW + 2 * n] = (float)std::cos(2.0 * pi * n / 512);
-        tab[STOI_TAB_TW + 2 * n + 1] = (float)-std::sin(2.0 * pi * n / 512);
-    }
+    fill_twiddles(tab.data() + STOI_TAB_TW, 512);
     std::vector<int32_t> phase(448, 0);
     for (int r = 0; r < p; ++r) phase[r] = (int32_t)(((int64_t)r * q + L) % p);
     memcpy(tab.data() + STOI_TAB_PHASE, phase.data(), phase.size() * sizeof(int32_t));
     memcpy(tab.data() + STOI_TAB_H, filter.data(), filter.size() * sizeof(float));
-    // the table is allocated on `device`; the calling thread's current device is put back before the call returns
-    int prev = 0;
-    WT_HIP_CHECK(hipGetDevice(&prev));
-    WT_HIP_CHECK(hipSetDevice(device));
+    float* dtab = nullptr;
+    if (int rc = upload_table("wt_stoi_create", device, tab, &dtab)) return rc;
     wt_stoi_handle* h = new wt_stoi_handle();
-    h->device = device; h->sample_rate = sample_rate; h->p = p; h->q = q; h->L = L;
-    const bool ok = hipMalloc(reinterpret_cast<void**>(&h->tab), tab.size() * sizeof(float)) == hipSuccess &&
-                    hipMemcpy(h->tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        set_error("wt_stoi_create: device allocation failed");
-        if (h->tab) (void)hipFree(h->tab);
-        delete h;
-    }
-    const hipError_t back = hipSetDevice(prev);
-    if (!ok) return WT_ERR_HIP;
-    if (back != hipSuccess) {
-        set_error("wt_stoi_create: could not restore the current device");
-        (void)hipFree(h->tab);
-        delete h;
-        return WT_ERR_HIP;
-    }
+    h->device = device; h->sample_rate = sample_rate; h->p = p; h->q = q; h->L = L; h->tab = dtab;
     *out = h;
     return WT_OK;
 }
@@ -596,10 +537,7 @@ size_t wt_stoi_workspace_bytes(const wt_stoi_handle* h, int32_t B, int64_t total
 
 int wt_stoi(const wt_stoi_handle* h, const wt_stoi_clip* clips, int32_t B, int32_t extended, void* workspace, void* stream, const wt_stoi_taps* taps) {
     const std::string fn = "wt_stoi";
-    if (!h) { set_error(fn + ": null handle"); return WT_ERR_INVALID; }
-    if (!clips || !workspace) { set_error(fn + ": null clips or workspace"); return WT_ERR_INVALID; }
-    if (B < 1 || B > 32767) { set_error(fn + ": B outside 1..32767"); return WT_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error(fn + ": workspace misaligned"); return WT_ERR_INVALID; }
+    if (!ragged_call_ok(fn, h, clips, workspace, B, 32767)) return WT_ERR_INVALID;
     if (!stoi_handle_ok(h)) { set_error(fn + ": not a handle of wt_stoi_create"); return WT_ERR_INVALID; }
     if (taps && (reinterpret_cast<uintptr_t>(taps->resampled) % 4 || reinterpret_cast<uintptr_t>(taps->keep) % 4 ||
                  reinterpret_cast<uintptr_t>(taps->counts) % 4 || reinterpret_cast<uintptr_t>(taps->tob) % 4)) {
@@ -628,11 +566,7 @@ int wt_stoi(const wt_stoi_handle* h, const wt_stoi_clip* clips, int32_t B, int32
         total_n += n;
         total_k0 += K0;
     }
-    int device = -1;
-    if (hipGetDevice(&device) != hipSuccess || device != h->device) {
-        set_error(fn + ": the handle belongs to another device than the calling thread's current one"); return WT_ERR_INVALID;
-    }
-    if (device < 0 || device >= 64) { set_error(fn + ": device index"); return WT_ERR_INVALID; }
+    if (!on_current_device(fn, h->device)) return WT_ERR_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // the workspace behind the descriptors; a tap takes the place of the workspace's own array
     float* w = reinterpret_cast<float*>(static_cast<char*>(workspace) + stoi_desc_bytes(B));
@@ -655,15 +589,8 @@ int wt_stoi(const wt_stoi_handle* h, const wt_stoi_clip* clips, int32_t B, int32
         }
     }
     const StoiTab tb{h->tab, h->p, h->q, h->L};
-    if (B <= STOI_ARG_CLIPS) {
-        StoiArgs args{};
-        memcpy(args.clip, dev.data(), dev.size() * sizeof(StoiClip));     // (blocks read clip[blockIdx < B] alone)
-        stoi_launch(args, B, tb, ws, resample, max_n, max_k0, extended ? 1 : 0, s);
-    } else {
-        // (the pinned block is at least twice the first size that comes this way, so that it seldom has to grow)
-        if (int rc = stage_descriptors(device, dev.data(), dev.size() * sizeof(StoiClip), 2 * STOI_ARG_CLIPS * sizeof(StoiClip), workspace, s)) return rc;
-        stoi_launch(StoiPtr{static_cast<const StoiClip*>(workspace)}, B, tb, ws, resample, max_n, max_k0, extended ? 1 : 0, s);
-    }
+    if (int rc = launch_ragged<STOI_ARG_CLIPS>("wt_stoi", dev.data(), B, 2 * STOI_ARG_CLIPS, workspace, s,
+                                               [&](auto d) { stoi_launch(d, B, tb, ws, resample, max_n, max_k0, extended ? 1 : 0, s); })) return rc;
     WT_HIP_CHECK(hipGetLastError());
     return WT_OK;
 }

@@ -4,13 +4,13 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Tuple
 
 import numpy as np
 import torch
 
 from . import _capi
-from ._capi import WtArch, WtTensor, check, lib
+from ._capi import WtArch, WtTensor, _ptr, _stream as _stream_ptr, check, lib  # noqa: F401  (_ptr, _stream_ptr: re-exported)
 from .config import ArchConfig
 
 
@@ -145,14 +145,6 @@ def site_name(site: int) -> str:
     if _capi.WT_SITE_CNX0 <= site < _capi.WT_SITE_HEAD:
         return "backbone.convnext.%d" % (site - _capi.WT_SITE_CNX0)
     return names.get(site, "site %d" % site)
-
-
-def _stream_ptr(device: torch.device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
 def _fill(src, buf: torch.Tensor) -> torch.Tensor:

@@ -25,16 +25,14 @@ from typing import Dict, List, Sequence, Tuple, Union
 
 import torch
 
-from ._capi import WtMelClip, WtStoiClip, check, lib
+from ._capi import WtMelClip, WtStoiClip, _need_gpu, _ptr, _stream, check, lib
 
 _handles: Dict[Tuple[int, int, int, int, int], ctypes.c_void_p] = {}
 _stoi_handles: Dict[Tuple[int, int], ctypes.c_void_p] = {}
 
 
-def _need_gpu(t: torch.Tensor):
-    if t.device.type != "cuda":
-        raise RuntimeError("wavtokenizer_amd.metrics runs only on an AMD GPU: move the tensor with .to('cuda'). "
-                           "There is no CPU path in this package.")
+_GPU_ONLY = ("wavtokenizer_amd.metrics runs only on an AMD GPU: move the tensor with .to('cuda'). "
+             "There is no CPU path in this package.")
 
 
 def mel_handle(sample_rate: int, n_fft: int, hop_length: int, n_mels: int, device_index: int) -> ctypes.c_void_p:
@@ -59,36 +57,47 @@ def _clips(who: str, wavs: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], 
     for w in wavs:
         if not isinstance(w, torch.Tensor) or w.dim() != 1:
             raise ValueError(who + ": every clip must be a 1-D tensor")
-        _need_gpu(w)
+        _need_gpu(w, _GPU_ONLY)
     dev = wavs[0].device
     if any(w.device != dev for w in wavs):
         raise ValueError(who + ": all clips must be on one device")
     return [w.to(torch.float32).contiguous() for w in wavs], dev
 
 
-def _run(dev: torch.device, a: List[torch.Tensor], b, outs_numel: int, out_offsets: List[int], log, sample_rate, n_fft, hop_length, n_mels):
-    """One wt_mel_spectrogram (b is None) or wt_mel_distance call over the clips; returns the flat output tensor."""
+def _rows(t: torch.Tensor, error: str) -> List[torch.Tensor]:
+    """(T,), (B, T) or (B, 1, T) -> its rows as 1-D fp32 contiguous tensors; ValueError(error) for any other shape."""
+    if t.dim() not in (1, 2, 3) or (t.dim() == 3 and t.shape[1] != 1):
+        raise ValueError(error)
+    return list(t.to(torch.float32).contiguous().view(-1, int(t.shape[-1])).unbind(0))
+
+
+def _call(dev: torch.device, handle, workspace_bytes, call):
+    """What the library calls here share: with dev current, handle(device index) is the table handle, workspace_bytes(handle)
+    sizes the workspace, call(handle, workspace pointer, stream pointer) makes the call on the current stream."""
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    n = len(a)
-    frames = [mel_frames(w.shape[0], n_fft, hop_length) for w in a]
     with torch.cuda.device(idx):
-        h = mel_handle(sample_rate, n_fft, hop_length, n_mels, idx)
-        out = torch.empty(outs_numel, dtype=torch.float32, device=dev)
-        ws_bytes = int(lib.wt_mel_workspace_bytes(n, sum(frames) if b is not None else 0))
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-        descs = (WtMelClip * n)()
-        for i in range(n):
-            descs[i].a = a[i].data_ptr()
-            descs[i].b = b[i].data_ptr() if b is not None else None
-            descs[i].length = a[i].shape[0]
-            descs[i].out = out.data_ptr() + 4 * out_offsets[i]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        if b is None:
-            check(lib.wt_mel_spectrogram(h, descs, n, 1 if log else 0, ctypes.c_void_p(ws.data_ptr()), stream), "wt_mel_spectrogram")
-        else:
-            check(lib.wt_mel_distance(h, descs, n, ctypes.c_void_p(ws.data_ptr()), stream), "wt_mel_distance")
+        h = handle(idx)
+        ws = torch.empty((int(workspace_bytes(h)) + 7) // 8, dtype=torch.int64, device=dev)
+        call(h, _ptr(ws), _stream(dev))
         # (the launches are queued on the current stream: the caching allocator hands ws and the inputs' copies out again only to
         # work queued behind them on that stream)
+
+
+def _run(dev: torch.device, a: List[torch.Tensor], b, outs_numel: int, out_offsets: List[int], log, sample_rate, n_fft, hop_length, n_mels):
+    """One wt_mel_spectrogram (b is None) or wt_mel_distance call over the clips; returns the flat output tensor."""
+    n = len(a)
+    frames = [mel_frames(w.shape[0], n_fft, hop_length) for w in a]
+    out = torch.empty(outs_numel, dtype=torch.float32, device=dev)
+    descs = (WtMelClip * n)()
+    for i in range(n):
+        descs[i].a = a[i].data_ptr()
+        descs[i].b = b[i].data_ptr() if b is not None else None
+        descs[i].length = a[i].shape[0]
+        descs[i].out = out.data_ptr() + 4 * out_offsets[i]
+    _call(dev, lambda idx: mel_handle(sample_rate, n_fft, hop_length, n_mels, idx),
+          lambda h: lib.wt_mel_workspace_bytes(n, sum(frames) if b is not None else 0),
+          lambda h, ws, stream: check(lib.wt_mel_spectrogram(h, descs, n, 1 if log else 0, ws, stream), "wt_mel_spectrogram") if b is None
+          else check(lib.wt_mel_distance(h, descs, n, ws, stream), "wt_mel_distance"))
     return out, frames
 
 
@@ -110,15 +119,11 @@ def mel_spectrogram_many(wavs: Sequence[torch.Tensor], *, sample_rate: int = 240
 def mel_spectrogram(wav: torch.Tensor, *, sample_rate: int = 24000, n_fft: int = 1024, hop_length: int = 256, n_mels: int = 100,
                     log: bool = True) -> torch.Tensor:
     """(T,), (B, T) or (B, 1, T) fp32 on the GPU -> (n_mels, F), (B, n_mels, F) or (B, 1, n_mels, F)."""
-    _need_gpu(wav)
-    if wav.dim() not in (1, 2, 3) or (wav.dim() == 3 and wav.shape[1] != 1):
-        raise ValueError("mel_spectrogram: wav must be (T,), (B, T) or (B, 1, T)")
-    T = int(wav.shape[-1])
-    rows = wav.to(torch.float32).contiguous().view(-1, T)
-    F = mel_frames(T, n_fft, hop_length)
-    if rows.shape[0] == 0:
+    _need_gpu(wav, _GPU_ONLY)
+    a = _rows(wav, "mel_spectrogram: wav must be (T,), (B, T) or (B, 1, T)")
+    F = mel_frames(wav.shape[-1], n_fft, hop_length)
+    if not a:
         return torch.empty((*wav.shape[:-1], n_mels, F), dtype=torch.float32, device=wav.device)
-    a = list(rows.unbind(0))
     offs = [i * n_mels * F for i in range(len(a))]
     flat, _ = _run(wav.device, a, None, len(a) * n_mels * F, offs, log, sample_rate, n_fft, hop_length, n_mels)
     return flat.view(*wav.shape[:-1], n_mels, F)
@@ -150,13 +155,9 @@ def mel_distance(y_hat: torch.Tensor, y: torch.Tensor, *, sample_rate: int = 240
     of one shape.  Every clip has the same number of entries, so this is the reference's l1_loss mean over the whole batch."""
     if y_hat.shape != y.shape:
         raise ValueError(f"mel_distance: shapes {tuple(y_hat.shape)} and {tuple(y.shape)} differ")
-    if y.dim() not in (1, 2, 3) or (y.dim() == 3 and y.shape[1] != 1):
-        raise ValueError("mel_distance: inputs must be (T,), (B, T) or (B, 1, T)")
-    _need_gpu(y_hat)
-    _need_gpu(y)
-    T = int(y.shape[-1])
-    p = list(y_hat.to(torch.float32).contiguous().view(-1, T).unbind(0))
-    q = list(y.to(torch.float32).contiguous().view(-1, T).unbind(0))
+    p, q = (_rows(t, "mel_distance: inputs must be (T,), (B, T) or (B, 1, T)") for t in (y_hat, y))
+    _need_gpu(y_hat, _GPU_ONLY)
+    _need_gpu(y, _GPU_ONLY)
     return mel_distance_many(p, q, sample_rate=sample_rate, n_fft=n_fft, hop_length=hop_length, n_mels=n_mels).mean()
 
 
@@ -199,22 +200,17 @@ def stoi_handle(sample_rate: int, device_index: int) -> ctypes.c_void_p:
 def _stoi_run(dev: torch.device, a: List[torch.Tensor], b: List[torch.Tensor], sample_rate: int, extended: bool, out: torch.Tensor,
               slots: Sequence[int]):
     """One wt_stoi call: pair i's value goes to out[slots[i]]."""
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
     n = len(a)
     sizes = [stoi_frames(w.shape[0], sample_rate) for w in a]
-    with torch.cuda.device(idx):
-        h = stoi_handle(sample_rate, idx)
-        ws_bytes = int(lib.wt_stoi_workspace_bytes(h, n, sum(s[0] for s in sizes), sum(s[1] for s in sizes)))
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-        descs = (WtStoiClip * n)()
-        for i in range(n):
-            descs[i].clean = a[i].data_ptr()
-            descs[i].processed = b[i].data_ptr()
-            descs[i].length = a[i].shape[0]
-            descs[i].out = out.data_ptr() + 4 * slots[i]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        check(lib.wt_stoi(h, descs, n, 1 if extended else 0, ctypes.c_void_p(ws.data_ptr()), stream, None), "wt_stoi")
-        # (queued on the current stream, as in _run above)
+    descs = (WtStoiClip * n)()
+    for i in range(n):
+        descs[i].clean = a[i].data_ptr()
+        descs[i].processed = b[i].data_ptr()
+        descs[i].length = a[i].shape[0]
+        descs[i].out = out.data_ptr() + 4 * slots[i]
+    _call(dev, lambda idx: stoi_handle(sample_rate, idx),
+          lambda h: lib.wt_stoi_workspace_bytes(h, n, sum(s[0] for s in sizes), sum(s[1] for s in sizes)),
+          lambda h, ws, stream: check(lib.wt_stoi(h, descs, n, 1 if extended else 0, ws, stream, None), "wt_stoi"))
 
 
 def stoi_many(cleans: Sequence[torch.Tensor], processeds: Sequence[torch.Tensor], *, sample_rate: Union[int, Sequence[int]] = 24000,
@@ -258,13 +254,9 @@ def stoi(clean: torch.Tensor, processed: torch.Tensor, sample_rate: int = 24000,
     give (B,), one value per row."""
     if clean.shape != processed.shape:
         raise ValueError(f"stoi: shapes {tuple(clean.shape)} and {tuple(processed.shape)} differ")
-    if clean.dim() not in (1, 2, 3) or (clean.dim() == 3 and clean.shape[1] != 1):
-        raise ValueError("stoi: inputs must be (T,), (B, T) or (B, 1, T)")
-    T = int(clean.shape[-1])
-    stoi_frames(T, sample_rate)
-    _need_gpu(clean)
-    _need_gpu(processed)
-    p = list(clean.to(torch.float32).contiguous().view(-1, T).unbind(0))
-    q = list(processed.to(torch.float32).contiguous().view(-1, T).unbind(0))
+    p, q = (_rows(t, "stoi: inputs must be (T,), (B, T) or (B, 1, T)") for t in (clean, processed))
+    stoi_frames(clean.shape[-1], sample_rate)
+    _need_gpu(clean, _GPU_ONLY)
+    _need_gpu(processed, _GPU_ONLY)
     d = stoi_many(p, q, sample_rate=int(sample_rate), extended=extended) if p else torch.zeros(0, dtype=torch.float32, device=clean.device)
     return d[0] if clean.dim() == 1 else d

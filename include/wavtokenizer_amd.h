@@ -969,6 +969,90 @@ size_t  wt_stoi_workspace_bytes(const wt_stoi_handle* h, int32_t B, int64_t tota
 int     wt_stoi(const wt_stoi_handle* h, const wt_stoi_clip* clips, int32_t B, int32_t extended, void* workspace, void* stream,
                 const wt_stoi_taps* taps);
 
+/* ---- evaluation metric: multi-resolution STFT distance ---------------------------------------- */
+
+/* The spectral measure codec papers report beside the mel distance (Yamamoto, Song & Kim 2020, Parallel WaveGAN; what
+ * auraloss.freq.MultiResolutionSTFTLoss()(x, y) computes with its defaults).  auraloss is not in this image: the measure is restated
+ * from the published definition and the parity with auraloss is unpinned (tests/stftd_ref.py holds this definition in float64).
+ * For a pair (estimate x, target y) of T samples each and a resolution r = (n_fft, hop, win_length):
+ *   X = stft(x) with center = True: reflect padding by n_fft / 2 on both sides (T > n_fft / 2, as torch.stft demands), F = 1 + T / hop
+ *   frames of n_fft samples, a periodic Hann window of win_length samples zero-padded to n_fft with (n_fft - win_length) / 2
+ *   (integer division) zeros on its left, the n_fft / 2 + 1 bins of the real FFT;
+ *   |X| = sqrt(max(re^2 + im^2, 1e-7));
+ *   sc_r = || |Y| - |X| ||_F / || |Y| ||_F,   mag_r = mean over the bins and frames of | log|Y| - log|X| |;
+ *   distance = mean over the resolutions of (sc_r + mag_r).
+ * The clamp keeps every logarithm and denominator finite: two silent signals give exactly 0 for every term.  The defaults of the
+ * Python surface are the Parallel WaveGAN set: n_fft (1024, 2048, 512), hop (120, 240, 50), win_length (600, 1200, 240).
+ * n_fft must be 512, 1024 or 2048, 1 <= hop <= n_fft, 1 <= win_length <= n_fft, 1 to 8 resolutions per handle, and a distance call
+ * needs T > max n_fft / 2: anything else is refused (WT_ERR_INVALID).  Windows and twiddles are computed in float64 on the host
+ * when the handle is made and rounded once; the FFT runs in fp32, each signal in a transform of its own.  A frame's values depend on
+ * that frame's n_fft samples alone, and a pair's result has the same bits alone, in any batch and at any position of it (no float
+ * atomics; fixed summation orders that depend on T alone).  The create call puts its tables on `device` and leaves the calling
+ * thread's current device as it found it; the calls launch on the current device, which must be the handle's. */
+typedef struct wt_stftd wt_stftd;
+int     wt_stftd_create(int32_t n_res, const int32_t* n_fft, const int32_t* hop, const int32_t* win_length, int32_t device,
+                        wt_stftd** out);
+void    wt_stftd_destroy(wt_stftd* h);
+/* 1 + T / hop of resolution r, or -1 when T <= n_fft / 2 of that resolution (or h is null, or there is no resolution r) */
+int64_t wt_stftd_frames(const wt_stftd* h, int32_t r, int64_t T);
+/* Host only, no device needed: the padded window [n_fft] a handle uploads for (n_fft, win_length); window may be null. */
+int     wt_stftd_tables(int32_t n_fft, int32_t win_length, float* window);
+/* One pair of a call.  estimate, target and out are device pointers, fp32; length counts the samples of each signal.
+ *   distance:  out [1 + 2 n_res]: out[0] the distance, out[1 + 2r] = sc_r, out[2 + 2r] = mag_r; out[0] is the fp32 sum of
+ *              (sc_r + mag_r) over r in ascending order, divided by n_res
+ *   magnitude: out [n_fft / 2 + 1][F], the clamped |X| of `estimate` at one resolution; target is ignored */
+typedef struct {
+    const float* estimate;
+    const float* target;
+    int64_t length;
+    float* out;
+} wt_stftd_clip;
+/* Bytes of the device workspace of a call with B pairs; total_frames is the sum over the pairs and over the handle's resolutions of
+ * wt_stftd_frames (a magnitude call may pass 0): the descriptors, then three partial sums per frame.  0 for a null handle or B < 1. */
+size_t  wt_stftd_workspace_bytes(const wt_stftd* h, int32_t B, int64_t total_frames);
+/* wt_stftd_distance: one launch per resolution, ragged over the B pairs (one wave per frame, both signals, three sums over the
+ * frame's bins to the workspace), and one small launch that adds each pair's partials.  wt_stftd_magnitude: the launch of resolution
+ * r alone, on `estimate`.  Nothing outside [0, length) of the inputs is read and nothing outside out and the workspace is written;
+ * the content of the workspace before the call does not matter.  clips is a HOST array.  workspace: device, the bytes above, 8-byte
+ * aligned, its content untouched until the launches have run.  Up to 64 pairs travel in the launches' own argument blocks: the call
+ * then makes no host wait and no copy and may be captured into a graph.  More go through the pinned descriptor blocks of wt_ingest
+ * and wt_emit (their events and their lock): such a call must NOT be made on a stream that is being captured.  Every descriptor is
+ * checked before any device call: a null handle, a null estimate or out, a null target in a distance call, length <= n_fft / 2 (the
+ * largest of the call's resolutions), a pointer not aligned to 4 bytes, B outside 1..65535, or a handle of another device than the
+ * calling thread's current one returns WT_ERR_INVALID with a message and touches no memory. */
+int     wt_stftd_distance(const wt_stftd* h, const wt_stftd_clip* clips, int32_t B, void* workspace, void* stream);
+int     wt_stftd_magnitude(const wt_stftd* h, int32_t r, const wt_stftd_clip* clips, int32_t B, void* workspace, void* stream);
+
+/* ---- evaluation metric: SI-SDR and SNR ------------------------------------------------------- */
+
+/* The scale-invariant signal-to-distortion ratio (Le Roux, Wisdom, Erdogan & Hershey 2019; torchmetrics'
+ * scale_invariant_signal_distortion_ratio) and the plain signal-to-noise ratio (torchmetrics' signal_noise_ratio; the reference's
+ * fork scripts compute it by hand in evaluate_audio_quality), both in dB.  torchmetrics is not in this image: parity with it is
+ * unpinned (tests/wavedist_ref.py holds this definition in float64).  For a pair (estimate p, target t) of T >= 1 samples, eps = 2^-23:
+ *   with zero_mean, each signal first loses its own mean;
+ *   SNR    = 10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps));
+ *   SI-SDR = 10 log10((sum (alpha t)^2 + eps) / (sum (alpha t - p)^2 + eps)),  alpha = (sum p t + eps) / (sum t^2 + eps).
+ * The residual energies are formed sample by sample in a pass that follows the one giving alpha (and that one follows the means):
+ * never from the moments sum p^2, sum p t, sum t^2, which in fp32 lose the measure above 60 dB; centred sums use x - mean.  Two
+ * silent signals give (0 + eps) / (0 + eps): exactly 0 dB for both.  fp32, no atomics; the passes run over blocks of
+ * wt_wavedist_block() samples and the order of every sum depends on T alone: a pair has the same bits alone, in any batch and at
+ * any position of it. */
+typedef struct {
+    const float* estimate;
+    const float* target;
+    int64_t length;
+    float* out;                       /* [2]: SI-SDR, SNR */
+} wt_wavedist_clip;
+/* Bytes of the device workspace of a call with B pairs whose lengths add up to total_samples; 0 for B < 1. */
+size_t  wt_wavedist_workspace_bytes(int32_t B, int64_t total_samples);
+/* The samples one workgroup of a pass adds (tests place lengths either side of it). */
+int32_t wt_wavedist_block(void);
+/* Both measures of B pairs of any lengths: four launches, six with zero_mean, each ragged over the pairs.  The rules of
+ * wt_stftd_distance hold for memory, workspace, the 64 descriptors in the argument blocks and graph capture.  Every descriptor is
+ * checked before any device call: null clips or workspace, B outside 1..65535, a null estimate, out or target, length < 1 or a
+ * pointer not aligned to 4 bytes returns WT_ERR_INVALID with a message and touches no memory. */
+int     wt_wavedist(const wt_wavedist_clip* clips, int32_t B, int32_t zero_mean, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

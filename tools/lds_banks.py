@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """LDS bank-conflict model of gfx950 (MI355X_MICROARCH.md, section LDS) applied to the access patterns of the fused encoder
-kernels (resblock16.hip): python3 tools/lds_banks.py.  For every pattern it prints the LDS-array cycles per
+kernels (resblock16.hip): python3 tools/lds_banks.py; of the frame transforms with `mel`, `stoi` or `stftd` as the argument.  For every pattern it prints the LDS-array cycles per
 wave-instruction against the conflict-free count (SQ_LDS_BANK_CONFLICT counts the difference).  No GPU needed.
 
 Model: a wave64 access is served in fixed lane groups, one LDS cycle per group when no two lanes of the group need
@@ -174,7 +174,32 @@ def stoi_fft():
     assert sorted(stoi_swz(i) for i in range(256)) == list(range(256))
 
 
+# ------------------------------------------------------------------------------- stftd.hip: 1024-point Stockham FFT of one wave, 16 points per lane
+def stftd_swz(i):
+    """stftd.hip stftd_swz<1024>: point i of a float plane sits at word i ^ ((i >> 5) & 3) ^ (((i >> 6) & 7) << 2)"""
+    return i ^ ((i >> 5) & 3) ^ (((i >> 6) & 7) << 2)
+
+
+def stftd_fft():
+    print("--- stftd_frame<2048> (stftd.hip): two float planes of 1024 points per wave, per wave-instruction")
+    print("    (the 512- and 256-point transforms of n_fft 1024 and 512 use the layouts of the sections mel and stoi)")
+    pats = [("pass 1 (radix 4) store, point 4 lane + 256 b + q", "ds_write_b32", lambda l, v: 4 * l + 256 * (v >> 2) + (v & 3)),
+            ("pass 2 / 3 load, point lane + 64 m", "ds_read_b32", lambda l, m: l + 64 * m),
+            ("pass 2 (radix 16) store, point 64 (lane / 4) + lane % 4 + 4 q", "ds_write_b32", lambda l, q: 64 * (l >> 2) + (l & 3) + 4 * q),
+            ("pass 3 (radix 16) store, point lane + 64 q", "ds_write_b32", lambda l, q: l + 64 * q),
+            ("split pass load, point (1024 - lane - 64 r) % 1024", "ds_read_b32", lambda l, r: (1024 - l - 64 * r) & 1023)]
+    for label, swz in (("plain layout", lambda i: i), ("stftd_swz", stftd_swz)):
+        extra = 0
+        for name, instr, fn in pats:
+            extra += report(f"{label}: {name}", instr, lambda l, v: 4 * swz(fn(l, v)), list(range(16)))
+        print(f"      extra LDS cycles (above the conflict-free count) summed over the listed variants: {extra}")
+    assert sorted(stftd_swz(i) for i in range(1024)) == list(range(1024))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["stftd"]:
+        stftd_fft()
+        sys.exit(0)
     if sys.argv[1:] == ["mel"]:
         mel_fft()
         sys.exit(0)

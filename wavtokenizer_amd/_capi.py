@@ -31,6 +31,8 @@ EXPORTS = [
     "wt_encode_rvq", "wt_encode_rvq_mixed", "wt_quantize", "wt_vq_residual_probe", "wt_model_codebook_tables",
     "wt_mel_create", "wt_mel_destroy", "wt_mel_frames", "wt_mel_tables", "wt_mel_workspace_bytes", "wt_mel_spectrogram", "wt_mel_distance",
     "wt_stoi_create", "wt_stoi_destroy", "wt_stoi_resampled_length", "wt_stoi_tables", "wt_stoi_workspace_bytes", "wt_stoi",
+    "wt_stftd_create", "wt_stftd_destroy", "wt_stftd_frames", "wt_stftd_tables", "wt_stftd_workspace_bytes", "wt_stftd_distance",
+    "wt_stftd_magnitude", "wt_wavedist_workspace_bytes", "wt_wavedist_block", "wt_wavedist",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -191,6 +193,16 @@ class WtMelClip(ctypes.Structure):
 class WtStoiClip(ctypes.Structure):
     """wt_stoi_clip: one pair of a STOI call (wt_stoi)."""
     _fields_ = [("clean", c_void_p), ("processed", c_void_p), ("length", c_int64), ("out", c_void_p)]
+
+
+class WtStftdClip(ctypes.Structure):
+    """wt_stftd_clip: one pair of an STFT-distance call (wt_stftd_distance, wt_stftd_magnitude)."""
+    _fields_ = [("estimate", c_void_p), ("target", c_void_p), ("length", c_int64), ("out", c_void_p)]
+
+
+class WtWavedistClip(ctypes.Structure):
+    """wt_wavedist_clip: one pair of a time-domain call (wt_wavedist)."""
+    _fields_ = [("estimate", c_void_p), ("target", c_void_p), ("length", c_int64), ("out", c_void_p)]
 
 
 class WtStoiTaps(ctypes.Structure):
@@ -363,6 +375,20 @@ def _load() -> ctypes.CDLL:
     lib.wt_stoi_workspace_bytes.argtypes = [c_void_p, c_int32, c_int64, c_int64]
     lib.wt_stoi_workspace_bytes.restype = c_size_t
     lib.wt_stoi.argtypes = [c_void_p, POINTER(WtStoiClip), c_int32, c_int32, c_void_p, c_void_p, POINTER(WtStoiTaps)]
+    lib.wt_stftd_create.argtypes = [c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_int32, POINTER(c_void_p)]
+    lib.wt_stftd_destroy.argtypes = [c_void_p]
+    lib.wt_stftd_destroy.restype = None
+    lib.wt_stftd_frames.argtypes = [c_void_p, c_int32, c_int64]
+    lib.wt_stftd_frames.restype = c_int64
+    lib.wt_stftd_tables.argtypes = [c_int32, c_int32, c_void_p]
+    lib.wt_stftd_workspace_bytes.argtypes = [c_void_p, c_int32, c_int64]
+    lib.wt_stftd_workspace_bytes.restype = c_size_t
+    lib.wt_stftd_distance.argtypes = [c_void_p, POINTER(WtStftdClip), c_int32, c_void_p, c_void_p]
+    lib.wt_stftd_magnitude.argtypes = [c_void_p, c_int32, POINTER(WtStftdClip), c_int32, c_void_p, c_void_p]
+    lib.wt_wavedist_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_wavedist_workspace_bytes.restype = c_size_t
+    lib.wt_wavedist_block.argtypes = []
+    lib.wt_wavedist.argtypes = [POINTER(WtWavedistClip), c_int32, c_int32, c_void_p, c_void_p]
     return lib
 
 

@@ -588,6 +588,31 @@ class _BatchedCalls:
         outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
         return metrics.stoi_many(wavs, [o[0, :w.shape[-1]] for o, w in zip(outs, wavs)], sample_rate=24000, extended=extended)
 
+    def round_trip_report(self, wavs: Sequence[torch.Tensor], n_q: Optional[int] = None, bandwidth_id=None,
+                          extended: bool = False) -> Dict[str, torch.Tensor]:
+        """Every measure of how the codec gives a set of clips back from one pass through the codec: one encode_codes_many, one
+        decode_codes_many, each output cropped to its input's length, then the metrics on those outputs.  wavs is a list of 1-D fp32
+        clips at the codec rate, 24 kHz, on the model's device.  Returns a dict of (n,) fp32 tensors: mel_distance, stoi, estoi (with
+        extended=True), stft_distance, si_sdr, snr; each carries the bits of the separate call (round_trip_mel_distance,
+        round_trip_stoi, metrics.stft_distance_many, si_sdr_many, snr_many) on the same outputs."""
+        from . import metrics
+        wavs = list(wavs)
+        if not wavs:
+            empty = torch.zeros(0, dtype=torch.float32, device=self._ensure_engine())
+            keys = ["mel_distance", "stoi"] + (["estoi"] if extended else []) + ["stft_distance", "si_sdr", "snr"]
+            return {k: empty.clone() for k in keys}
+        codes = self.encode_codes_many(wavs, bandwidth_id=bandwidth_id, n_q=n_q)
+        outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
+        outs = [o[0, :w.shape[-1]] for o, w in zip(outs, wavs)]
+        report = {"mel_distance": metrics.mel_distance_many(outs, wavs),
+                  "stoi": metrics.stoi_many(wavs, outs, sample_rate=24000, extended=False)}
+        if extended:
+            report["estoi"] = metrics.stoi_many(wavs, outs, sample_rate=24000, extended=True)
+        report["stft_distance"] = metrics.stft_distance_many(outs, wavs)
+        both = metrics.wavedist_many(outs, wavs, who="round_trip_report")
+        report["si_sdr"], report["snr"] = both[:, 0], both[:, 1]
+        return report
+
     # -- synthesise straight to PCM: decode from codes -> ragged emit (resample, channels, layout, sample type) into one tensor -----
     def _emit_format(self, who: str, channels, dtype, limit, n: int) -> Tuple[List[int], Tuple[torch.dtype, float]]:
         """(channels per clip, (dtype, limit)) of decode_pcm / decode_pcm_many over n clips, checked: ValueError for anything

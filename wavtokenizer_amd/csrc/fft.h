@@ -49,6 +49,26 @@ __device__ __forceinline__ void bfly8(f32x2 (&v)[8]) {
     bfly4(v[4], v[5], v[6], v[7]);
 }
 __device__ __forceinline__ int rev3(int q) { return ((q & 1) << 2) | (q & 2) | (q >> 2); }
+// 16-point DFT in place (stftd.hip: 1024 complex points at 16 per lane) as 4 x 4: four 4-point DFTs over v[r0 + 4 r1], the
+// products with exp(-2 pi i r0 q1 / 16), four 4-point DFTs over r0; output q is left in v[rev4(q)]
+__device__ __forceinline__ int rev4(int q) { return (rev2(q & 3) << 2) | rev2(q >> 2); }
+__device__ __forceinline__ void bfly16(f32x2 (&v)[16]) {
+    const float h = 0.70710678118654752440f, c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f;
+#pragma unroll
+    for (int r0 = 0; r0 < 4; ++r0) bfly4(v[r0], v[r0 + 4], v[r0 + 8], v[r0 + 12]);
+    // slot 4 rev2(q1) + r0 holds Y[r0][q1]: q1 = 1 in slots 8..11, q1 = 2 in 4..7, q1 = 3 in 12..15
+    v[9] = cmul(v[9], f32x2{c1, -s1});                                 // w^1
+    v[10] = f32x2{(v[10].x + v[10].y) * h, (v[10].y - v[10].x) * h};   // w^2 = (1 - i) / sqrt 2
+    v[11] = cmul(v[11], f32x2{s1, -c1});                               // w^3
+    v[5] = f32x2{(v[5].x + v[5].y) * h, (v[5].y - v[5].x) * h};        // w^2
+    v[6] = mul_mi(v[6]);                                               // w^4 = -i
+    v[7] = f32x2{(v[7].y - v[7].x) * h, -(v[7].x + v[7].y) * h};       // w^6 = (-1 - i) / sqrt 2
+    v[13] = cmul(v[13], f32x2{s1, -c1});                               // w^3
+    v[14] = f32x2{(v[14].y - v[14].x) * h, -(v[14].x + v[14].y) * h};  // w^6
+    v[15] = cmul(v[15], f32x2{-c1, s1});                               // w^9 = -w^1
+#pragma unroll
+    for (int s = 0; s < 4; ++s) bfly4(v[4 * s], v[4 * s + 1], v[4 * s + 2], v[4 * s + 3]);
+}
 
 // Bin k of the real transform X of 2 M points from the M-point transform Z of its even / odd samples:
 // X[k] = (Z[k] + conj Z[M - k]) / 2 - i / 2 w (Z[k] - conj Z[M - k]), zk = Z[k], zm = Z[(M - k) mod M], w = exp(-2 pi i k / (2 M))

@@ -18,14 +18,27 @@ And the intelligibility measure of the reference's evaluation script (metrics/in
 
 STOI (Taal et al. 2011) and, with extended=True, ESTOI (Jensen & Taal 2016), restated from the published algorithm
 (include/wavtokenizer_amd.h gives the definition; parity with pystoi is unpinned, it is not available to the tests).  A pair's value
-has the same bits alone, in any batch and at any position.  `stoi(raw, pre, sr, extended=False)` becomes `stoi(raw, pre, sr)`."""
+has the same bits alone, in any batch and at any position.  `stoi(raw, pre, sr, extended=False)` becomes `stoi(raw, pre, sr)`.
+
+And the three measures that need no outside model and that codec papers report beside the mel distance:
+
+    stft_distance(y_hat, y, fft_sizes=..., hop_sizes=..., win_lengths=..., components=False)   0-dim for (T,), else (B,)
+    stft_distance_many(y_hats, ys, ...)       (n,); with components=True also (n, R, 2): per resolution (sc, mag)
+    stft_magnitude(wav, n_fft, hop_length, win_length), stft_magnitude_many(wavs, ...)   the clamped |STFT|, (..., n_fft / 2 + 1, F)
+    si_sdr(estimate, target, zero_mean=False), si_sdr_many(estimates, targets, ...)       dB, 0-dim for (T,), else (B,) / (n,)
+    snr(estimate, target, zero_mean=False), snr_many(estimates, targets, ...)
+
+The multi-resolution STFT distance of Parallel WaveGAN (spectral convergence + log-magnitude L1, the mean over the resolutions),
+SI-SDR (Le Roux et al. 2019) and plain SNR, as include/wavtokenizer_amd.h defines them; parity with auraloss and torchmetrics is
+unpinned, neither is available to the tests.  `MultiResolutionSTFTLoss()(x, y)` becomes `stft_distance(x, y)`,
+`scale_invariant_signal_distortion_ratio(p, t)` becomes `si_sdr(p, t)` and `signal_noise_ratio(p, t)` becomes `snr(p, t)`."""
 import ctypes
 import math
 from typing import Dict, List, Sequence, Tuple, Union
 
 import torch
 
-from ._capi import WtMelClip, WtStoiClip, _need_gpu, _ptr, _stream, check, lib
+from ._capi import WtMelClip, WtStftdClip, WtStoiClip, WtWavedistClip, _need_gpu, _ptr, _stream, check, lib
 
 _handles: Dict[Tuple[int, int, int, int, int], ctypes.c_void_p] = {}
 _stoi_handles: Dict[Tuple[int, int], ctypes.c_void_p] = {}
@@ -260,3 +273,202 @@ def stoi(clean: torch.Tensor, processed: torch.Tensor, sample_rate: int = 24000,
     _need_gpu(processed, _GPU_ONLY)
     d = stoi_many(p, q, sample_rate=int(sample_rate), extended=extended) if p else torch.zeros(0, dtype=torch.float32, device=clean.device)
     return d[0] if clean.dim() == 1 else d
+
+
+# ------------------------------------------------------------------------------------------------ pairs of clips
+def _pairs(who: str, first: Sequence[torch.Tensor], second: Sequence[torch.Tensor], longer_than: int = 0):
+    """Two lists of 1-D clips as fp32 contiguous tensors on one device, pair i of one length above longer_than: ValueError otherwise."""
+    first, second = list(first), list(second)
+    if len(first) != len(second):
+        raise ValueError(who + ": as many estimates as targets")
+    for i, (p, q) in enumerate(zip(first, second)):
+        if isinstance(p, torch.Tensor) and isinstance(q, torch.Tensor) and p.dim() == 1 and q.dim() == 1 and p.shape[0] != q.shape[0]:
+            raise ValueError(f"{who}: pair {i}: lengths {p.shape[0]} and {q.shape[0]} differ")
+        if isinstance(p, torch.Tensor) and p.dim() == 1 and p.shape[0] <= longer_than:
+            raise ValueError(f"{who}: pair {i}: a clip of {p.shape[0]} samples is too short: more than {longer_than} are needed")
+    if not first:
+        return [], [], None
+    a, dev = _clips(who, first)
+    b, dev_b = _clips(who, second)
+    if dev_b != dev:
+        raise ValueError(who + ": all clips must be on one device")
+    return a, b, dev
+
+
+def _batch(who: str, first: torch.Tensor, second: torch.Tensor):
+    """(T,), (B, T) or (B, 1, T) tensors of one shape -> their rows."""
+    if first.shape != second.shape:
+        raise ValueError(f"{who}: shapes {tuple(first.shape)} and {tuple(second.shape)} differ")
+    p, q = (_rows(t, who + ": inputs must be (T,), (B, T) or (B, 1, T)") for t in (first, second))
+    _need_gpu(first, _GPU_ONLY)
+    _need_gpu(second, _GPU_ONLY)
+    return p, q
+
+
+# ------------------------------------------------------------------------------------------------ multi-resolution STFT distance
+STFT_FFT_SIZES, STFT_HOP_SIZES, STFT_WIN_LENGTHS = (1024, 2048, 512), (120, 240, 50), (600, 1200, 240)
+_stftd_handles: Dict[Tuple, ctypes.c_void_p] = {}
+
+
+def stft_resolutions(fft_sizes=STFT_FFT_SIZES, hop_sizes=STFT_HOP_SIZES, win_lengths=STFT_WIN_LENGTHS) -> Tuple[Tuple[int, int, int], ...]:
+    """The resolutions (n_fft, hop, win_length) of a parameter set, checked: ValueError for anything wt_stftd_create refuses."""
+    try:
+        sets = [tuple(int(v) for v in x) for x in (fft_sizes, hop_sizes, win_lengths)]
+    except TypeError:
+        raise ValueError("stft_distance: fft_sizes, hop_sizes and win_lengths are sequences of integers") from None
+    if not (len(sets[0]) == len(sets[1]) == len(sets[2])) or not 1 <= len(sets[0]) <= 8:
+        raise ValueError("stft_distance: fft_sizes, hop_sizes and win_lengths need one length, between 1 and 8")
+    res = tuple(zip(*sets))
+    for n_fft, hop, win in res:
+        if n_fft not in (512, 1024, 2048):
+            raise ValueError(f"stft_distance: n_fft {n_fft}: must be 512, 1024 or 2048")
+        if not 1 <= hop <= n_fft or not 1 <= win <= n_fft:
+            raise ValueError(f"stft_distance: hop {hop} and win_length {win} must lie in 1..n_fft = {n_fft}")
+    return res
+
+
+def stft_frames(length: int, n_fft: int, hop_length: int) -> int:
+    """wt_stftd_frames on the host: 1 + length // hop_length; ValueError for a clip reflect padding cannot take."""
+    if int(length) <= n_fft // 2:
+        raise ValueError(f"a clip of {int(length)} samples is too short for reflect padding by {n_fft // 2}")
+    return 1 + int(length) // int(hop_length)
+
+
+def stftd_handle(resolutions: Tuple[Tuple[int, int, int], ...], device_index: int) -> ctypes.c_void_p:
+    """The wt_stftd of a set of resolutions on a device, created once per process."""
+    key = (tuple(resolutions), int(device_index))
+    if key not in _stftd_handles:
+        n = len(resolutions)
+        arrays = [(ctypes.c_int32 * n)(*[r[i] for r in resolutions]) for i in range(3)]
+        h = ctypes.c_void_p()
+        check(lib.wt_stftd_create(n, *arrays, int(device_index), ctypes.byref(h)), "wt_stftd_create")
+        _stftd_handles[key] = h
+    return _stftd_handles[key]
+
+
+def _stftd_descs(a: List[torch.Tensor], b, out: torch.Tensor, offsets: Sequence[int]):
+    descs = (WtStftdClip * len(a))()
+    for i in range(len(a)):
+        descs[i].estimate = a[i].data_ptr()
+        descs[i].target = b[i].data_ptr() if b is not None else None
+        descs[i].length = a[i].shape[0]
+        descs[i].out = out.data_ptr() + 4 * offsets[i]
+    return descs
+
+
+def stft_distance_many(y_hats: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], *, fft_sizes=STFT_FFT_SIZES, hop_sizes=STFT_HOP_SIZES,
+                       win_lengths=STFT_WIN_LENGTHS, components: bool = False):
+    """The multi-resolution STFT distance of pairs of 1-D clips (estimate, target): (n,) fp32, one launch per resolution and one
+    more for all pairs.  With components=True also (n, R, 2): per resolution the spectral convergence and the log-magnitude L1; the
+    distance is their fp32 sum over the resolutions in order, divided by R.  The two clips of a pair must have one length
+    (ValueError otherwise), more than max(fft_sizes) // 2 samples; pairs may differ."""
+    res = stft_resolutions(fft_sizes, hop_sizes, win_lengths)
+    R = len(res)
+    need = max(r[0] for r in res)
+    a, b, dev = _pairs("stft_distance_many", y_hats, ys, need // 2)
+    frames = [sum(stft_frames(w.shape[0], need, r[1]) for r in res) for w in a]
+    if not a:
+        empty = torch.zeros(0, dtype=torch.float32, device="cuda")
+        return (empty, empty.view(0, R, 2)) if components else empty
+    n, width = len(a), 1 + 2 * R
+    out = torch.empty((n, width), dtype=torch.float32, device=dev)
+    descs = _stftd_descs(a, b, out, [i * width for i in range(n)])
+    _call(dev, lambda idx: stftd_handle(res, idx), lambda h: lib.wt_stftd_workspace_bytes(h, n, sum(frames)),
+          lambda h, ws, stream: check(lib.wt_stftd_distance(h, descs, n, ws, stream), "wt_stftd_distance"))
+    return (out[:, 0], out[:, 1:].view(n, R, 2)) if components else out[:, 0]
+
+
+def stft_distance(y_hat: torch.Tensor, y: torch.Tensor, *, fft_sizes=STFT_FFT_SIZES, hop_sizes=STFT_HOP_SIZES,
+                  win_lengths=STFT_WIN_LENGTHS, components: bool = False):
+    """y_hat and y are (T,), (B, T) or (B, 1, T) of one shape: (T,) gives a 0-dim tensor, the others (B,), one distance per row
+    (their mean is MultiResolutionSTFTLoss's batch value up to the order of its sums).  components=True: also (R, 2) or (B, R, 2)."""
+    res = stft_resolutions(fft_sizes, hop_sizes, win_lengths)
+    p, q = _batch("stft_distance", y_hat, y)
+    stft_frames(y.shape[-1], max(r[0] for r in res), 1)
+    if not p:
+        d, c = torch.zeros(0, dtype=torch.float32, device=y.device), torch.zeros((0, len(res), 2), dtype=torch.float32, device=y.device)
+    else:
+        d, c = stft_distance_many(p, q, fft_sizes=fft_sizes, hop_sizes=hop_sizes, win_lengths=win_lengths, components=True)
+    if y.dim() == 1:
+        d, c = d[0], c[0]
+    return (d, c) if components else d
+
+
+def stft_magnitude_many(wavs: Sequence[torch.Tensor], n_fft: int = 1024, hop_length: int = 120, win_length: int = 600) -> List[torch.Tensor]:
+    """The clamped STFT magnitudes sqrt(max(re^2 + im^2, 1e-7)) of 1-D clips of different lengths at one resolution in one launch:
+    [(n_fft / 2 + 1, F_i)], views of one flat tensor: what the distance is made of, bit for bit."""
+    res = stft_resolutions((n_fft,), (hop_length,), (win_length,))
+    if not len(wavs):
+        return []
+    a, dev = _clips("stft_magnitude_many", wavs)
+    bins = res[0][0] // 2 + 1
+    frames = [stft_frames(w.shape[0], res[0][0], res[0][1]) for w in a]
+    offs = [0]
+    for f in frames:
+        offs.append(offs[-1] + bins * f)
+    flat = torch.empty(offs[-1], dtype=torch.float32, device=dev)
+    descs = _stftd_descs(a, None, flat, offs[:-1])
+    n = len(a)
+    _call(dev, lambda idx: stftd_handle(res, idx), lambda h: lib.wt_stftd_workspace_bytes(h, n, 0),
+          lambda h, ws, stream: check(lib.wt_stftd_magnitude(h, 0, descs, n, ws, stream), "wt_stftd_magnitude"))
+    return [flat[offs[i]: offs[i + 1]].view(bins, frames[i]) for i in range(n)]
+
+
+def stft_magnitude(wav: torch.Tensor, n_fft: int = 1024, hop_length: int = 120, win_length: int = 600) -> torch.Tensor:
+    """(T,), (B, T) or (B, 1, T) fp32 on the GPU -> (bins, F), (B, bins, F) or (B, 1, bins, F), bins = n_fft / 2 + 1."""
+    res = stft_resolutions((n_fft,), (hop_length,), (win_length,))
+    a = _rows(wav, "stft_magnitude: wav must be (T,), (B, T) or (B, 1, T)")
+    bins, F = res[0][0] // 2 + 1, stft_frames(wav.shape[-1], res[0][0], res[0][1])
+    _need_gpu(wav, _GPU_ONLY)
+    if not a:
+        return torch.empty((*wav.shape[:-1], bins, F), dtype=torch.float32, device=wav.device)
+    outs = stft_magnitude_many(a, n_fft, hop_length, win_length)
+    return torch.stack(outs).view(*wav.shape[:-1], bins, F)
+
+
+# ------------------------------------------------------------------------------------------------ SI-SDR and SNR
+def wavedist_many(estimates: Sequence[torch.Tensor], targets: Sequence[torch.Tensor], *, zero_mean: bool = False,
+                  who: str = "wavedist_many") -> torch.Tensor:
+    """One wt_wavedist call over pairs of 1-D clips: (n, 2) fp32, per pair (SI-SDR, SNR) in dB."""
+    a, b, dev = _pairs(who, estimates, targets, 0)
+    if not a:
+        return torch.zeros((0, 2), dtype=torch.float32, device="cuda")
+    n = len(a)
+    out = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    descs = (WtWavedistClip * n)()
+    for i in range(n):
+        descs[i].estimate, descs[i].target, descs[i].length = a[i].data_ptr(), b[i].data_ptr(), a[i].shape[0]
+        descs[i].out = out.data_ptr() + 8 * i
+    total = sum(w.shape[0] for w in a)
+    _call(dev, lambda idx: None, lambda h: lib.wt_wavedist_workspace_bytes(n, total),
+          lambda h, ws, stream: check(lib.wt_wavedist(descs, n, 1 if zero_mean else 0, ws, stream), "wt_wavedist"))
+    return out
+
+
+def si_sdr_many(estimates: Sequence[torch.Tensor], targets: Sequence[torch.Tensor], *, zero_mean: bool = False) -> torch.Tensor:
+    """The scale-invariant signal-to-distortion ratio in dB of pairs of 1-D clips: (n,) fp32.  The two clips of a pair must have one
+    length (ValueError otherwise); pairs may differ.  zero_mean=True first takes each signal's own mean off."""
+    return wavedist_many(estimates, targets, zero_mean=zero_mean, who="si_sdr_many")[:, 0]
+
+
+def snr_many(estimates: Sequence[torch.Tensor], targets: Sequence[torch.Tensor], *, zero_mean: bool = False) -> torch.Tensor:
+    """The signal-to-noise ratio in dB of pairs of 1-D clips (estimate, target): (n,) fp32; si_sdr_many's rules."""
+    return wavedist_many(estimates, targets, zero_mean=zero_mean, who="snr_many")[:, 1]
+
+
+def _wavedist(who: str, column: int, estimate: torch.Tensor, target: torch.Tensor, zero_mean: bool) -> torch.Tensor:
+    if estimate.shape == target.shape and estimate.dim() >= 1 and estimate.shape[-1] < 1:
+        raise ValueError(who + ": the signals are empty")
+    p, q = _batch(who, estimate, target)
+    d = wavedist_many(p, q, zero_mean=zero_mean, who=who)[:, column] if p else torch.zeros(0, dtype=torch.float32, device=target.device)
+    return d[0] if target.dim() == 1 else d
+
+
+def si_sdr(estimate: torch.Tensor, target: torch.Tensor, zero_mean: bool = False) -> torch.Tensor:
+    """SI-SDR in dB of estimate against target: (T,) gives a 0-dim tensor, (B, T) and (B, 1, T) give (B,), one value per row."""
+    return _wavedist("si_sdr", 0, estimate, target, zero_mean)
+
+
+def snr(estimate: torch.Tensor, target: torch.Tensor, zero_mean: bool = False) -> torch.Tensor:
+    """SNR in dB of estimate against target: (T,) gives a 0-dim tensor, (B, T) and (B, 1, T) give (B,), one value per row."""
+    return _wavedist("snr", 1, estimate, target, zero_mean)

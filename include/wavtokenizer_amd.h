@@ -977,7 +977,8 @@ int     wt_stoi(const wt_stoi_handle* h, const wt_stoi_clip* clips, int32_t B, i
  * For a pair (estimate x, target y) of T samples each and a resolution r = (n_fft, hop, win_length):
  *   X = stft(x) with center = True: reflect padding by n_fft / 2 on both sides (T > n_fft / 2, as torch.stft demands), F = 1 + T / hop
  *   frames of n_fft samples, a periodic Hann window of win_length samples zero-padded to n_fft with (n_fft - win_length) / 2
- *   (integer division) zeros on its left, the n_fft / 2 + 1 bins of the real FFT;
+ *   (integer division) zeros on its left (win_length = 1: the window [1.], as torch.hann_window(1) gives, not the formula's [0.]),
+ *   the n_fft / 2 + 1 bins of the real FFT;
  *   |X| = sqrt(max(re^2 + im^2, 1e-7));
  *   sc_r = || |Y| - |X| ||_F / || |Y| ||_F,   mag_r = mean over the bins and frames of | log|Y| - log|X| |;
  *   distance = mean over the resolutions of (sc_r + mag_r).

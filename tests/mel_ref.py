@@ -34,6 +34,13 @@ def tables(sample_rate: int, n_mels: int):
     return window, fb
 
 
+def empty_filters(sample_rate: int, n_mels: int):
+    """The filters without a single bin in the table a handle uploads (the float64 definition rounded once to fp32): the two
+    edges of a narrow low filter can fall between two bins of the 513."""
+    fb32 = tables(sample_rate, n_mels)[1].astype(np.float32)
+    return np.nonzero((fb32 != 0).sum(axis=0) == 0)[0]
+
+
 def n_frames(T: int, hop: int) -> int:
     return 1 + T // hop
 
@@ -193,6 +200,12 @@ def signal(name: str, T: int, seed: int = 0, sample_rate: int = 24000):
     else:
         raise KeyError(name)
     return x.astype(np.float32)
+
+
+def noisy_pair(T: int):
+    """Noise and a copy of it with noise 40 dB below added: the pair of a distance near 0.005."""
+    a = signal("noise", T, seed=1)
+    return a, (a + 1e-3 * np.random.default_rng(T).standard_normal(T)).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ the calls, through ctypes

@@ -15,10 +15,11 @@ RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))       # (n_f
 
 
 def window64(n_fft: int, win: int):
-    """The periodic Hann window of win samples, zero-padded to n_fft with (n_fft - win) // 2 zeros on the left, in float64."""
+    """The periodic Hann window of win samples, zero-padded to n_fft with (n_fft - win) // 2 zeros on the left, in float64.  One
+    sample: the window [1.], as torch.hann_window(1) gives (the formula alone would give [0.])."""
     w = np.zeros(n_fft, np.float64)
     left = (n_fft - win) // 2
-    w[left:left + win] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win, dtype=np.float64) / win)
+    w[left:left + win] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win, dtype=np.float64) / win) if win > 1 else 1.0
     return w
 
 

@@ -38,7 +38,11 @@ def test_header_and_capi_agree_on_the_mel_exports():
     assert ctypes.sizeof(WtMelClip) == 32
 
 
-@pytest.mark.parametrize("sample_rate,n_mels", [(24000, 100), (16000, 100), (16000, 64)])
+GRID = [(sr, m) for sr in (8000, 16000, 22050, 24000, 44100, 48000) for m in (1, 2, 63, 64, 65, 100, 127, 128)]   # tests/test_mel_params.py
+ONE_EMPTY = {(44100, 127), (44100, 128), (48000, 127), (48000, 128)}      # a narrow low filter whose two edges fall between two bins
+
+
+@pytest.mark.parametrize("sample_rate,n_mels", [(24000, 100), (16000, 100), (16000, 64)] + [p for p in GRID if p not in ((24000, 100), (16000, 100), (16000, 64))])
 def test_tables_are_the_float64_definition_rounded_once(sample_rate, n_mels):
     window = np.zeros(1024, np.float32)
     fb = np.zeros((513, n_mels), np.float32)
@@ -52,8 +56,18 @@ def test_tables_are_the_float64_definition_rounded_once(sample_rate, n_mels):
     nz = fb64 != 0
     rel = np.abs(fb.astype(np.float64)[nz] - fb64[nz]) / fb64[nz]
     assert float(rel.max()) <= 2.0 ** -23
-    assert bool(((fb != 0).sum(axis=0) >= 1).all())                 # no empty filter
+    per_filter = (fb != 0).sum(axis=0)
+    assert int((per_filter == 0).sum()) == (1 if (sample_rate, n_mels) in ONE_EMPTY else 0)      # no empty filter but at those four
+    assert np.array_equal(np.nonzero(per_filter == 0)[0], R.empty_filters(sample_rate, n_mels))
     assert int((fb != 0).sum(axis=1).max()) <= 2                    # a bin feeds at most two filters
+    # what the sparse form a handle uploads relies on (wt_mel_create): every filter's non-zero bins are one run, and the runs fit
+    # the weight table
+    for m in np.nonzero(per_filter)[0]:
+        k = np.nonzero(fb[:, m])[0]
+        assert k[-1] - k[0] + 1 == len(k), (m, k)
+    assert int(per_filter.sum()) <= 2 * 513 + 6
+    if n_mels >= 127 and sample_rate in (8000, 16000):
+        assert int(per_filter.sum()) == 1013                        # (the fullest of the grid: every bin but the two outermost, nearly twice)
     if (sample_rate, n_mels) == (24000, 100):
         assert int((fb != 0).sum(axis=0).max()) <= 31
 

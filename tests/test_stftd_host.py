@@ -66,6 +66,27 @@ def test_window_is_the_float64_definition_rounded_once(n_fft, win):
     assert float(np.abs(padded.numpy() - w64).max()) < 1e-15
 
 
+@pytest.mark.parametrize("n_fft", [512, 1024, 2048])
+def test_window_is_torch_hann_window_at_the_edges_of_win_length(n_fft):
+    """torch.hann_window(win_length, periodic=True) centred in n_fft and rounded once, down to one sample: torch gives [1.] there,
+    where 0.5 - 0.5 cos 0 alone would give an all-zero window, every magnitude the floor and every distance 0."""
+    for win in (1, 2, 3, n_fft - 1, n_fft):
+        window = np.full(n_fft, np.nan, np.float32)
+        assert lib.wt_stftd_tables(n_fft, win, window.ctypes.data_as(ctypes.c_void_p)) == 0
+        left = (n_fft - win) // 2
+        padded = torch.zeros(n_fft, dtype=torch.float64)
+        padded[left:left + win] = torch.hann_window(win, periodic=True, dtype=torch.float64)
+        want = padded.numpy().astype(np.float32)
+        # (two float64 cosines may differ in their last bit, which can move the one rounding to fp32 by an ulp at a near-tie)
+        assert bool((np.abs(window.astype(np.float64) - want) <= np.spacing(want)).all()), (n_fft, win)
+        assert np.array_equal(window == 0, want == 0), (n_fft, win)
+        if win <= 3:
+            assert np.array_equal(window, want), (n_fft, win, window[left:left + win])
+            assert np.array_equal(window[left:left + win], {1: [1.0], 2: [0.0, 1.0], 3: [0.0, 0.75, 0.75]}[win])
+        assert float(np.abs(padded.numpy() - R.window64(n_fft, win)).max()) < 1e-15, (n_fft, win)
+    assert left == 0 and window[0] == 0 and bool((window[1:] > 0).all())
+
+
 def test_tables_and_create_refuse_other_parameters_before_any_device_call():
     for n_fft, win in ((256, 100), (4096, 100), (1000, 100), (1024, 0), (1024, 1025)):
         assert lib.wt_stftd_tables(n_fft, win, None) == WT_ERR_INVALID, (n_fft, win)

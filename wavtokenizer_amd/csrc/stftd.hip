@@ -282,12 +282,14 @@ static bool stftd_params_ok(int n_res, const int32_t* n_fft, const int32_t* hop,
     return true;
 }
 
-// The periodic Hann window of win samples, zero-padded to n_fft with (n_fft - win) / 2 zeros on the left: float64, rounded once
+// The periodic Hann window of win samples, zero-padded to n_fft with (n_fft - win) / 2 zeros on the left: float64, rounded once.
+// win = 1 is the window [1.], as torch.hann_window(1) gives (the formula alone would give [0.])
 static void stftd_window(int n_fft, int win, float* w) {
     const double pi = 3.14159265358979323846;
     const int left = (n_fft - win) / 2;
     for (int n = 0; n < n_fft; ++n) w[n] = 0.f;
     for (int n = 0; n < win; ++n) w[left + n] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * n / win));
+    if (win == 1) w[left] = 1.f;
 }
 
 template <class D> static void stftd_launch_frames(int n_fft, dim3 grid, hipStream_t s, const D& d, const StftdPar& p, int mode, float* part) {

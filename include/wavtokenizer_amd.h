@@ -1054,6 +1054,75 @@ int32_t wt_wavedist_block(void);
  * pointer not aligned to 4 bytes returns WT_ERR_INVALID with a message and touches no memory. */
 int     wt_wavedist(const wt_wavedist_clip* clips, int32_t B, int32_t zero_mean, void* workspace, void* stream);
 
+/* ---- evaluation metric: pitch, periodicity and voiced / unvoiced F1 --------------------------- */
+
+/* The periodicity family of the reference's evaluation (metrics/periodicity.py: calculate_periodicity_metrics, after cargan): a
+ * periodicity RMSE, a pitch RMSE in cents over the jointly voiced frames and the F1 of the voiced / unvoiced decision.  The frame
+ * grid, the A-weighted loudness gate and the three formulas are the reference's.  The pitch estimator is NOT: the reference runs
+ * CREPE, a network whose weights this project cannot carry; here it is YIN (de Cheveigne & Kawahara 2002) on CREPE's frame grid
+ * and search range.  Numbers are comparable between runs of this library, not with CREPE-based tables.  tests/pitch_ref.py holds
+ * this definition in float64.  Everything is at 16 kHz:
+ *   frames: window 1024, hop 160, not centred: n = 1 + (T - 1024) / 160 for T >= 1024 (torchcrepe.predict(pad=False), and the
+ *   center=False spectrogram of predict_pitch); frame f is x[160 f .. 160 f + 1023].
+ *   YIN per frame: d(lag) = sum over j < 703 of (x[j] - x[j + lag])^2 for lag = 1..321 (703 = 1024 - 321 terms for every lag),
+ *   added term by term from the differences, never as an autocorrelation identity; d'(lag) = d(lag) lag / sum over k <= lag of
+ *   d(k), 1 where that sum is 0.  The lag: the first in [30, 320] (550 Hz down to 50 Hz) with d' < threshold, d'(lag) <=
+ *   d'(lag - 1) and d'(lag) < d'(lag + 1); without one, the smallest lag that attains the minimum of d' over [30, 320].  With
+ *   a, b, c = d'(lag - 1), d'(lag), d'(lag + 1) and den = a - 2b + c: off = 0.5 (a - c) / den clamped to +-0.5 (0 for den <= 0),
+ *   f0 = 16000 / (lag + off), periodicity = clamp(1 - (b - 0.25 (a - c) off), 0, 1).
+ *   loudness gate: S = |rfft(frame * periodic Hann window of 1024)|^2, 513 bins; dB = 10 log10 max(S, 1e-10), floored at the
+ *   clip's maximum dB over all frames and bins - 80 (librosa.power_to_db's top_db, per clip); + the A-weighting of the bin's
+ *   frequency clipped below at -80 dB (bin 0: -80); - 20 (torchcrepe's REF_DB); the mean over the 513 bins is the frame's
+ *   loudness.  A frame with loudness < silence_threshold has its periodicity set to 0.
+ *   voicing: a frame with gated periodicity < unvoiced_threshold is unvoiced and its f0 is NaN.
+ *   pair (reference y, estimate y^, n frames each): periodicity_loss = sqrt(mean (p^ - p)^2); pitch_loss = sqrt(mean cents^2) over
+ *   the frames voiced in both, cents = 1200 (log2 f0 - log2 f0^), NaN without such a frame; f1 = 2 P R / (P + R) with
+ *   P = TP / (TP + FP), R = TP / (TP + FN) of the voiced flags, NaN where P or R is 0 / 0 or both are 0.
+ * The reference's constants are silence_threshold -60 and unvoiced_threshold 0.21 (CREPE has no threshold of YIN's kind); the
+ * Python surface's defaults are threshold 0.15, -60 and 0.5: 0.21 is calibrated for CREPE's confidence, while 1 - d' is about the
+ * normalised autocorrelation at the period.  Window, twiddles and A-weighting are computed in float64 on the host when the handle is made
+ * and rounded once; the kernels run in fp32, every summation order depends on the clip's length alone and there are no float
+ * atomics: a clip or pair has the same bits alone, in any batch and at any position of it.  The create call puts its tables on
+ * `device` and leaves the calling thread's current device as it found it; the calls launch on the current device, which must be
+ * the handle's. */
+typedef struct wt_pitch wt_pitch;
+int     wt_pitch_create(int32_t device, wt_pitch** out);
+void    wt_pitch_destroy(wt_pitch* h);
+/* 1 + (T - 1024) / 160, or 0 for T < 1024 */
+int64_t wt_pitch_frames(int64_t T);
+/* Host only, no device needed: the window [1024] and the A-weighting in dB [513] a handle uploads; either may be null. */
+int     wt_pitch_tables(float* window, float* a_weight);
+/* One clip of a track call.  signal, out and taps are device pointers, fp32; length counts the samples (at 16 kHz); with
+ * n = wt_pitch_frames(length): out [2][n]: f0 in Hz (NaN: unvoiced), then the gated periodicity; taps, which may be null, [2][n]:
+ * the periodicity before the gate, then the loudness in dB. */
+typedef struct {
+    const float* signal;
+    int64_t length;
+    float* out;
+    float* taps;
+} wt_pitch_clip;
+/* One pair of a pair call: out [3] = periodicity_loss, pitch_loss, f1. */
+typedef struct {
+    const float* reference;
+    const float* estimate;
+    int64_t length;
+    float* out;
+} wt_pitch_pair;
+/* Bytes of the device workspace of a call with B clips or pairs; total_frames is the sum of wt_pitch_frames over them (a pair
+ * counts once): the descriptors, ten floats per frame, two per descriptor.  0 for B < 1. */
+size_t  wt_pitch_workspace_bytes(int32_t B, int64_t total_frames);
+/* wt_pitch_track: four launches, each ragged over the B clips (one wave per frame): YIN, the frames' largest powers, the clips'
+ * maxima, the loudness with the gate.  wt_pitch_pairs: the same over both signals of every pair, the tracks left in the
+ * workspace, and a launch that reduces each pair.  The rules of wt_stftd_distance hold for memory, workspace, the 64 descriptors
+ * in the argument blocks and graph capture.  Every descriptor is checked before any device call: a null handle, clips or
+ * workspace, B outside 1..65535, a misaligned workspace, a NaN threshold, a null signal (reference, estimate) or out, length <
+ * 1024, a pointer not aligned to 4 bytes, or a handle of another device than the calling thread's current one returns
+ * WT_ERR_INVALID with a message and touches no memory. */
+int     wt_pitch_track(const wt_pitch* h, const wt_pitch_clip* clips, int32_t B, float threshold, float silence_threshold,
+                       float unvoiced_threshold, void* workspace, void* stream);
+int     wt_pitch_pairs(const wt_pitch* h, const wt_pitch_pair* pairs, int32_t B, float threshold, float silence_threshold,
+                       float unvoiced_threshold, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """LDS bank-conflict model of gfx950 (MI355X_MICROARCH.md, section LDS) applied to the access patterns of the fused encoder
-kernels (resblock16.hip): python3 tools/lds_banks.py; of the frame transforms with `mel`, `stoi` or `stftd` as the argument.  For every pattern it prints the LDS-array cycles per
+kernels (resblock16.hip): python3 tools/lds_banks.py; of the frame transforms with `mel`, `stoi` or `stftd` as the argument, of the YIN kernel with `pitch`.  For every pattern it prints the LDS-array cycles per
 wave-instruction against the conflict-free count (SQ_LDS_BANK_CONFLICT counts the difference).  No GPU needed.
 
 Model: a wave64 access is served in fixed lane groups, one LDS cycle per group when no two lanes of the group need
@@ -196,7 +196,27 @@ def stftd_fft():
     assert sorted(stftd_swz(i) for i in range(1024)) == list(range(1024))
 
 
+# ------------------------------------------------------------------------------- pitch.hip: the YIN difference function of one wave
+def pitch_yin():
+    print("--- pitch_yin_block (pitch.hip): one float plane of 1024 samples per wave, per wave-instruction")
+    print("    (the gate's 512-point transform uses the layout of the section mel)")
+    extra = 0
+    extra += report("x[j]: word 19 c + i, one address for the wave", "ds_read_b32", lambda l, j: 4 * j, list(range(703)))
+    extra += report("x[j + lag]: word 19 c + 1 + 5 lane + i", "ds_read_b32", lambda l, j: 4 * (j + 1 + 5 * l), list(range(703)))
+    extra += report("lag 321: words lane + 64 m and lane + 64 m + 321", "ds_read_b32", lambda l, v: 4 * (l + 64 * (v >> 1) + 321 * (v & 1)),
+                    list(range(20)))
+    extra += report("d' store: word 1 + 5 lane + k", "ds_write_b32", lambda l, k: 4 * (1 + 5 * l + k), list(range(5)))
+    extra += report("d' neighbours: words 5 lane and 5 lane + 6", "ds_read_b32", lambda l, k: 4 * (5 * l + 6 * k), list(range(2)))
+    print(f"      extra LDS cycles (above the conflict-free count) summed over the listed variants: {extra}")
+    print("    for comparison, an even number of lags per lane:")
+    report("x[j + lag] at four lags per lane: word j + 1 + 4 lane", "ds_read_b32", lambda l, j: 4 * (j + 1 + 4 * l), list(range(8)))
+    report("x[j + lag] at six lags per lane: word j + 1 + 6 lane", "ds_read_b32", lambda l, j: 4 * (j + 1 + 6 * l), list(range(8)))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["pitch"]:
+        pitch_yin()
+        sys.exit(0)
     if sys.argv[1:] == ["stftd"]:
         stftd_fft()
         sys.exit(0)

@@ -33,6 +33,7 @@ EXPORTS = [
     "wt_stoi_create", "wt_stoi_destroy", "wt_stoi_resampled_length", "wt_stoi_tables", "wt_stoi_workspace_bytes", "wt_stoi",
     "wt_stftd_create", "wt_stftd_destroy", "wt_stftd_frames", "wt_stftd_tables", "wt_stftd_workspace_bytes", "wt_stftd_distance",
     "wt_stftd_magnitude", "wt_wavedist_workspace_bytes", "wt_wavedist_block", "wt_wavedist",
+    "wt_pitch_create", "wt_pitch_destroy", "wt_pitch_frames", "wt_pitch_tables", "wt_pitch_workspace_bytes", "wt_pitch_track", "wt_pitch_pairs",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -203,6 +204,16 @@ class WtStftdClip(ctypes.Structure):
 class WtWavedistClip(ctypes.Structure):
     """wt_wavedist_clip: one pair of a time-domain call (wt_wavedist)."""
     _fields_ = [("estimate", c_void_p), ("target", c_void_p), ("length", c_int64), ("out", c_void_p)]
+
+
+class WtPitchClip(ctypes.Structure):
+    """wt_pitch_clip: one clip of a pitch-track call (wt_pitch_track)."""
+    _fields_ = [("signal", c_void_p), ("length", c_int64), ("out", c_void_p), ("taps", c_void_p)]
+
+
+class WtPitchPair(ctypes.Structure):
+    """wt_pitch_pair: one pair of a periodicity-metrics call (wt_pitch_pairs)."""
+    _fields_ = [("reference", c_void_p), ("estimate", c_void_p), ("length", c_int64), ("out", c_void_p)]
 
 
 class WtStoiTaps(ctypes.Structure):
@@ -389,6 +400,16 @@ def _load() -> ctypes.CDLL:
     lib.wt_wavedist_workspace_bytes.restype = c_size_t
     lib.wt_wavedist_block.argtypes = []
     lib.wt_wavedist.argtypes = [POINTER(WtWavedistClip), c_int32, c_int32, c_void_p, c_void_p]
+    lib.wt_pitch_create.argtypes = [c_int32, POINTER(c_void_p)]
+    lib.wt_pitch_destroy.argtypes = [c_void_p]
+    lib.wt_pitch_destroy.restype = None
+    lib.wt_pitch_frames.argtypes = [c_int64]
+    lib.wt_pitch_frames.restype = c_int64
+    lib.wt_pitch_tables.argtypes = [c_void_p, c_void_p]
+    lib.wt_pitch_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_pitch_workspace_bytes.restype = c_size_t
+    lib.wt_pitch_track.argtypes = [c_void_p, POINTER(WtPitchClip), c_int32, c_float, c_float, c_float, c_void_p, c_void_p]
+    lib.wt_pitch_pairs.argtypes = [c_void_p, POINTER(WtPitchPair), c_int32, c_float, c_float, c_float, c_void_p, c_void_p]
     return lib
 
 

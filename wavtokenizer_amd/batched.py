@@ -588,18 +588,34 @@ class _BatchedCalls:
         outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
         return metrics.stoi_many(wavs, [o[0, :w.shape[-1]] for o, w in zip(outs, wavs)], sample_rate=24000, extended=extended)
 
+    def round_trip_periodicity(self, wavs: Sequence[torch.Tensor], *, n_q: Optional[int] = None, bandwidth_id=None, **kw) -> torch.Tensor:
+        """How the codec keeps pitch and voicing: per clip the reference's periodicity RMSE, pitch RMSE in cents and voiced / unvoiced
+        F1 (metrics.periodicity_metrics_many: YIN, not the reference's CREPE), (n, 3) fp32.  wavs is a list of 1-D fp32 clips at the
+        codec rate, 24 kHz, on the model's device.  It is encode_codes_many -> decode_codes_many -> each output cropped to its
+        input's length -> metrics.periodicity_metrics_many(wavs, outputs, sample_rate=24000, **kw), and nothing else; kw carries
+        threshold, silence_threshold and unvoiced_threshold."""
+        from . import metrics
+        wavs = list(wavs)
+        if not wavs:
+            return torch.zeros((0, 3), dtype=torch.float32, device=self._ensure_engine())
+        codes = self.encode_codes_many(wavs, bandwidth_id=bandwidth_id, n_q=n_q)
+        outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
+        return metrics.periodicity_metrics_many(wavs, [o[0, :w.shape[-1]] for o, w in zip(outs, wavs)], sample_rate=24000, **kw)
+
     def round_trip_report(self, wavs: Sequence[torch.Tensor], n_q: Optional[int] = None, bandwidth_id=None,
-                          extended: bool = False) -> Dict[str, torch.Tensor]:
+                          extended: bool = False, periodicity: bool = False) -> Dict[str, torch.Tensor]:
         """Every measure of how the codec gives a set of clips back from one pass through the codec: one encode_codes_many, one
         decode_codes_many, each output cropped to its input's length, then the metrics on those outputs.  wavs is a list of 1-D fp32
         clips at the codec rate, 24 kHz, on the model's device.  Returns a dict of (n,) fp32 tensors: mel_distance, stoi, estoi (with
         extended=True), stft_distance, si_sdr, snr; each carries the bits of the separate call (round_trip_mel_distance,
-        round_trip_stoi, metrics.stft_distance_many, si_sdr_many, snr_many) on the same outputs."""
+        round_trip_stoi, metrics.stft_distance_many, si_sdr_many, snr_many) on the same outputs.  periodicity=True adds
+        periodicity_loss, pitch_loss and vuv_f1 behind them, the columns of round_trip_periodicity bit for bit."""
         from . import metrics
         wavs = list(wavs)
         if not wavs:
             empty = torch.zeros(0, dtype=torch.float32, device=self._ensure_engine())
             keys = ["mel_distance", "stoi"] + (["estoi"] if extended else []) + ["stft_distance", "si_sdr", "snr"]
+            keys += ["periodicity_loss", "pitch_loss", "vuv_f1"] if periodicity else []
             return {k: empty.clone() for k in keys}
         codes = self.encode_codes_many(wavs, bandwidth_id=bandwidth_id, n_q=n_q)
         outs = self.decode_codes_many(codes, bandwidth_id=bandwidth_id)
@@ -611,6 +627,9 @@ class _BatchedCalls:
         report["stft_distance"] = metrics.stft_distance_many(outs, wavs)
         both = metrics.wavedist_many(outs, wavs, who="round_trip_report")
         report["si_sdr"], report["snr"] = both[:, 0], both[:, 1]
+        if periodicity:
+            three = metrics.periodicity_metrics_many(wavs, outs, sample_rate=24000)
+            report["periodicity_loss"], report["pitch_loss"], report["vuv_f1"] = three[:, 0], three[:, 1], three[:, 2]
         return report
 
     # -- synthesise straight to PCM: decode from codes -> ragged emit (resample, channels, layout, sample type) into one tensor -----

@@ -31,14 +31,27 @@ And the three measures that need no outside model and that codec papers report b
 The multi-resolution STFT distance of Parallel WaveGAN (spectral convergence + log-magnitude L1, the mean over the resolutions),
 SI-SDR (Le Roux et al. 2019) and plain SNR, as include/wavtokenizer_amd.h defines them; parity with auraloss and torchmetrics is
 unpinned, neither is available to the tests.  `MultiResolutionSTFTLoss()(x, y)` becomes `stft_distance(x, y)`,
-`scale_invariant_signal_distortion_ratio(p, t)` becomes `si_sdr(p, t)` and `signal_noise_ratio(p, t)` becomes `snr(p, t)`."""
+`scale_invariant_signal_distortion_ratio(p, t)` becomes `si_sdr(p, t)` and `signal_noise_ratio(p, t)` becomes `snr(p, t)`.
+
+And the periodicity family of the reference's evaluation script (metrics/periodicity.py, after cargan):
+
+    pitch(wav, sample_rate=16000, threshold=0.15, silence_threshold=-60.0, unvoiced_threshold=0.5)   (T,) -> (f0 (n,), periodicity (n,))
+    pitch_many(wavs, sample_rate=..., ...)    clips of different lengths (and rates) -> [(f0_i, periodicity_i)]
+    periodicity_metrics(y, y_hat, sample_rate=16000, ...)         (T,) -> (3,): periodicity_loss, pitch_loss (cents), voiced/unvoiced F1
+    periodicity_metrics_many(ys, y_hats, sample_rate=..., ...)    (n, 3)
+
+The frame grid (1024 / 160 at 16 kHz, not centred), the A-weighted loudness gate and the three formulas are the reference's; the
+pitch estimator is YIN (de Cheveigne & Kawahara 2002) where the reference runs CREPE, whose weights are not available here, so the
+numbers are comparable between runs of this library and not with CREPE-based tables (include/wavtokenizer_amd.h gives the
+definition, tests/pitch_ref.py holds it in float64).  `calculate_periodicity_metrics(y, y_hat)` becomes
+`periodicity_metrics(y, y_hat, sample_rate)`."""
 import ctypes
 import math
 from typing import Dict, List, Sequence, Tuple, Union
 
 import torch
 
-from ._capi import WtMelClip, WtStftdClip, WtStoiClip, WtWavedistClip, _need_gpu, _ptr, _stream, check, lib
+from ._capi import WtMelClip, WtPitchClip, WtPitchPair, WtStftdClip, WtStoiClip, WtWavedistClip, _need_gpu, _ptr, _stream, check, lib
 
 _handles: Dict[Tuple[int, int, int, int, int], ctypes.c_void_p] = {}
 _stoi_handles: Dict[Tuple[int, int], ctypes.c_void_p] = {}
@@ -472,3 +485,143 @@ def si_sdr(estimate: torch.Tensor, target: torch.Tensor, zero_mean: bool = False
 def snr(estimate: torch.Tensor, target: torch.Tensor, zero_mean: bool = False) -> torch.Tensor:
     """SNR in dB of estimate against target: (T,) gives a 0-dim tensor, (B, T) and (B, 1, T) give (B,), one value per row."""
     return _wavedist("snr", 1, estimate, target, zero_mean)
+
+
+# ------------------------------------------------------------------------------------------------ pitch, periodicity, voiced / unvoiced F1
+PITCH_RATE, PITCH_WINDOW, PITCH_HOP = 16000, 1024, 160
+_pitch_handles: Dict[int, ctypes.c_void_p] = {}
+
+
+def pitch_frames(length: int) -> int:
+    """wt_pitch_frames on the host: 1 + (length - 1024) // 160 frames of a clip of `length` samples at 16 kHz, 0 below 1024."""
+    return 0 if int(length) < PITCH_WINDOW else 1 + (int(length) - PITCH_WINDOW) // PITCH_HOP
+
+
+def pitch_handle(device_index: int) -> ctypes.c_void_p:
+    """The wt_pitch of a device, created once per process."""
+    key = int(device_index)
+    if key not in _pitch_handles:
+        h = ctypes.c_void_p()
+        check(lib.wt_pitch_create(key, ctypes.byref(h)), "wt_pitch_create")
+        _pitch_handles[key] = h
+    return _pitch_handles[key]
+
+
+def _pitch_rates(who: str, sample_rate, n: int) -> List[int]:
+    """One rate per clip from one rate or a sequence of them; ValueError for anything but positive integers."""
+    if hasattr(sample_rate, "tolist"):
+        sample_rate = sample_rate.tolist()
+    rates = list(sample_rate) if isinstance(sample_rate, Sequence) and not isinstance(sample_rate, (str, bytes)) else [sample_rate] * n
+    if len(rates) != n:
+        raise ValueError(who + ": one sample_rate, or one per clip")
+    for r in rates:
+        if isinstance(r, bool) or int(r) != r or int(r) < 1:
+            raise ValueError(f"{who}: sample_rate must be a positive integer, not {r!r}")
+    return [int(r) for r in rates]
+
+
+def _pitch_check(who: str, clips: Sequence[torch.Tensor], rates: List[int]) -> None:
+    """What can be refused before any GPU work: integer samples (the loudness gate needs the scale of floating-point audio in
+    -1..1: PCM would pass it shifted by 90 dB), a clip too short for one frame at 16 kHz, a rate pair the resampler refuses."""
+    from . import audio
+    for i, (w, r) in enumerate(zip(clips, rates)):
+        if isinstance(w, torch.Tensor) and not w.is_floating_point():
+            raise ValueError(f"{who}: clip {i}: dtype {w.dtype}: the clips must be floating-point audio")
+        if isinstance(w, torch.Tensor) and w.dim() == 1:
+            n = w.shape[0] if r == PITCH_RATE else audio.resampled_length(r, PITCH_RATE, w.shape[0])
+            if n < PITCH_WINDOW:
+                raise ValueError(f"{who}: clip {i}: a clip of {w.shape[0]} samples at {r} Hz is too short: one frame needs "
+                                 f"{PITCH_WINDOW} samples at 16 kHz")
+
+
+def _pitch_at_16k(clips: List[torch.Tensor], rates: List[int]) -> List[torch.Tensor]:
+    """The clips at 16 kHz: a clip at another rate goes through the project's own resampler, as audio.convert_audio(clip, sr, 16000)."""
+    from . import audio
+    return [w if r == PITCH_RATE else audio.convert_audio(w.view(1, -1), r, PITCH_RATE)[0].contiguous() for w, r in zip(clips, rates)]
+
+
+def _pitch_thresholds(who: str, threshold, silence_threshold, unvoiced_threshold) -> Tuple[float, float, float]:
+    t = tuple(float(v) for v in (threshold, silence_threshold, unvoiced_threshold))
+    if any(math.isnan(v) for v in t):
+        raise ValueError(who + ": a threshold is NaN")
+    return t
+
+
+def pitch_many(wavs: Sequence[torch.Tensor], *, sample_rate: Union[int, Sequence[int]] = PITCH_RATE, threshold: float = 0.15,
+               silence_threshold: float = -60.0, unvoiced_threshold: float = 0.5) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """Pitch and periodicity tracks of 1-D clips of different lengths (and rates) in one call: [(f0_i, periodicity_i)], each (n_i,)
+    fp32 with n_i = pitch_frames(length at 16 kHz), views of one flat tensor; the bits of pitch(wavs[i], rate_i).  See pitch."""
+    wavs = list(wavs)
+    rates = _pitch_rates("pitch_many", sample_rate, len(wavs))
+    thr = _pitch_thresholds("pitch_many", threshold, silence_threshold, unvoiced_threshold)
+    _pitch_check("pitch_many", wavs, rates)
+    if not wavs:
+        return []
+    a, dev = _clips("pitch_many", wavs)
+    a = _pitch_at_16k(a, rates)
+    n = len(a)
+    frames = [pitch_frames(w.shape[0]) for w in a]
+    offs = [0]
+    for f in frames:
+        offs.append(offs[-1] + 2 * f)
+    flat = torch.empty(offs[-1], dtype=torch.float32, device=dev)
+    descs = (WtPitchClip * n)()
+    for i in range(n):
+        descs[i].signal, descs[i].length, descs[i].out, descs[i].taps = a[i].data_ptr(), a[i].shape[0], flat.data_ptr() + 4 * offs[i], None
+    _call(dev, pitch_handle, lambda h: lib.wt_pitch_workspace_bytes(n, sum(frames)),
+          lambda h, ws, stream: check(lib.wt_pitch_track(h, descs, n, *thr, ws, stream), "wt_pitch_track"))
+    return [(flat[offs[i]: offs[i] + frames[i]], flat[offs[i] + frames[i]: offs[i + 1]]) for i in range(n)]
+
+
+def pitch(wav: torch.Tensor, sample_rate: int = PITCH_RATE, *, threshold: float = 0.15, silence_threshold: float = -60.0,
+          unvoiced_threshold: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(f0, periodicity) of a 1-D clip, each (n,) fp32: per frame of 1024 samples at a hop of 160 at 16 kHz (not centred: n = 1 +
+    (T - 1024) // 160; a clip at another rate is first resampled with this package's resampler) the YIN estimate of the pitch in Hz
+    within 50..550 Hz and 1 - d' at its lag, a periodicity in 0..1.  A frame whose A-weighted loudness is under silence_threshold dB
+    has its periodicity set to 0, and a frame whose periodicity is under unvoiced_threshold is unvoiced: its f0 is NaN.  threshold
+    is YIN's absolute threshold on d'.  The reference's predict_pitch has these roles with CREPE as the estimator and
+    unvoiced_threshold 0.21, which is calibrated for CREPE's confidence; for YIN, 1 - d' is approximately the normalised
+    autocorrelation at the period, and the default here is 0.5."""
+    if not isinstance(wav, torch.Tensor) or wav.dim() != 1:
+        raise ValueError("pitch: wav must be a 1-D tensor")
+    return pitch_many([wav], sample_rate=sample_rate, threshold=threshold,
+                      silence_threshold=silence_threshold, unvoiced_threshold=unvoiced_threshold)[0]
+
+
+def periodicity_metrics_many(ys: Sequence[torch.Tensor], y_hats: Sequence[torch.Tensor], *, sample_rate: Union[int, Sequence[int]] = PITCH_RATE,
+                             threshold: float = 0.15, silence_threshold: float = -60.0, unvoiced_threshold: float = 0.5) -> torch.Tensor:
+    """The reference's calculate_periodicity_metrics(y, y_hat) per pair of 1-D clips (reference, estimate): (n, 3) fp32, per pair the
+    periodicity RMSE, the pitch RMSE in cents over the frames voiced in both (NaN without one) and the voiced / unvoiced F1 (NaN
+    where precision or recall is 0 / 0, as the reference's, which its caller filters with math.isnan), on the tracks of pitch();
+    one call for all pairs.  The two clips of a pair must have one length (ValueError otherwise); pairs may differ in length and
+    rate.  The estimator is YIN, not the reference's CREPE: comparable between runs of this library, not with CREPE-based tables."""
+    ys, y_hats = list(ys), list(y_hats)
+    rates = _pitch_rates("periodicity_metrics_many", sample_rate, len(ys))
+    thr = _pitch_thresholds("periodicity_metrics_many", threshold, silence_threshold, unvoiced_threshold)
+    if len(ys) == len(y_hats):
+        _pitch_check("periodicity_metrics_many", ys, rates)
+        _pitch_check("periodicity_metrics_many", y_hats, rates)
+    a, b, dev = _pairs("periodicity_metrics_many", ys, y_hats, 0)
+    if not a:
+        return torch.zeros((0, 3), dtype=torch.float32, device="cuda")
+    a, b = _pitch_at_16k(a, rates), _pitch_at_16k(b, rates)
+    n = len(a)
+    frames = [pitch_frames(w.shape[0]) for w in a]
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    descs = (WtPitchPair * n)()
+    for i in range(n):
+        descs[i].reference, descs[i].estimate, descs[i].length, descs[i].out = a[i].data_ptr(), b[i].data_ptr(), a[i].shape[0], out.data_ptr() + 12 * i
+    _call(dev, pitch_handle, lambda h: lib.wt_pitch_workspace_bytes(n, sum(frames)),
+          lambda h, ws, stream: check(lib.wt_pitch_pairs(h, descs, n, *thr, ws, stream), "wt_pitch_pairs"))
+    return out
+
+
+def periodicity_metrics(y: torch.Tensor, y_hat: torch.Tensor, sample_rate: int = PITCH_RATE, *, threshold: float = 0.15,
+                        silence_threshold: float = -60.0, unvoiced_threshold: float = 0.5) -> torch.Tensor:
+    """(3,) fp32: periodicity_loss, pitch_loss in cents and the voiced / unvoiced F1 of the estimate y_hat against the reference y,
+    two 1-D clips of one length at sample_rate.  See periodicity_metrics_many and pitch."""
+    for t in (y, y_hat):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1:
+            raise ValueError("periodicity_metrics: y and y_hat must be 1-D tensors")
+    return periodicity_metrics_many([y], [y_hat], sample_rate=sample_rate, threshold=threshold, silence_threshold=silence_threshold,
+                                    unvoiced_threshold=unvoiced_threshold)[0]

@@ -772,7 +772,7 @@ int wt_pcm16(const float* x, int64_t n, float limit, int32_t rescale, int16_t* o
  *     same ascending fmaf chain over the same fp32 table, zeros outside [0, n_in).
  *   WT_EMIT_I16: the bits of wt_pcm16(that, limit, rescale = 0): clamp to [-limit, limit], round-half-even of x * 32768 clipped
  *     to int16, in pcm16_kernel's arithmetic (a NaN becomes what it becomes there).  Per-clip rescale needs a reduction over the
- *     resampled clip and is not offered: take fp32 out and call wt_pcm16.
+ *     resampled clip: that is wt_emit_rescaled (below), two launches instead of one.
  * With channels = 2 both channels receive the same value (convert_audio's expand, encoder/utils.py:85-86).  Nothing past
  * src[n_in - 1] is read (a decode plan leaves zeros or another clip's pitch there), and nothing outside the clip's
  * n_out * channels destination elements is written.  An interleaved stereo frame (ch_stride 1, sample_stride 2, frame-aligned
@@ -802,6 +802,57 @@ typedef struct {
 } wt_emit_clip;
 size_t wt_emit_workspace_bytes(int32_t B);
 int    wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream);
+
+/* Rescaling emit: wt_emit with save_audio's rescale = True (encoder/utils.py:95-103) per clip instead of the clamp.  The
+ * descriptors are wt_emit's, unchanged, and so are their checks, but `limit` is read and checked for both sample types.  Two
+ * launches over wt_emit's grid (behind a one-block launch that zeroes the peaks): the first computes every resampled sample in wt_emit's arithmetic and keeps max |sample| per clip
+ * (an integer atomic max on the bits of a non-negative float: the same in any order), the second emits every sample times
+ * s = peak > 0 ? min(limit / peak, 1) : 1, one rounded product, in place of the clamp.
+ *   WT_EMIT_I16: the bits of wt_pcm16 with rescale = 1 on the clip's WT_EMIT_F32 output (a clip under the limit: s = 1, no clamp);
+ *   WT_EMIT_F32: that fp32 output times s.
+ * Every store form of wt_emit is kept (interleaved frames, paired int16 runs, the equal-rate copy, any strides), and nothing is
+ * read or written that wt_emit would not read or write.  workspace: wt_emit_rescaled_workspace_bytes(B) bytes, 8-byte aligned:
+ * the descriptors' place and one 32-bit peak per clip behind it.  A host-side call around its launches like wt_emit. */
+size_t wt_emit_rescaled_workspace_bytes(int32_t B);
+int    wt_emit_rescaled(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream);
+
+/* ---- per-clip level control: measure, normalise on the way in, scale on the way out ----------------------------------------
+ *
+ * Ragged level measurement: per clip out[0] = max |x| (exact) and out[1] = sqrt(sum x^2 / n), fp32.  The sum of squares is a
+ * binary tree whose shape depends on n alone: chunks of wt_level_chunk samples, a fixed tree inside a chunk, the chunks' partials
+ * added pairwise in one fixed order; no float atomics.  A clip has the same bits alone, at any position of any batch and whatever
+ * the grid.  Against the exact value the rms errs by at most (3 + ceil(log2 n)) * 2^-24 relative (n rounded squares, a tree of
+ * depth ceil(log2 n), one division, one square root).  clips is a HOST array; x and out are device pointers, 4-byte aligned.  Up
+ * to 64 descriptors travel in the launches' argument blocks, more go through workspace (device, wt_level_workspace_bytes(B,
+ * total_samples) bytes with total_samples >= the sum of the clips' n, 8-byte aligned), which also holds the chunks' partials.
+ * B outside [1, 65535], n < 1, a null or misaligned pointer returns WT_ERR_INVALID before any device call.  Two launches. */
+typedef struct {
+    const float* x;                   /* device: n samples */
+    int64_t n;
+    float* out;                       /* device [2]: peak, rms */
+} wt_level_clip;
+int32_t wt_level_chunk(void);
+size_t  wt_level_workspace_bytes(int32_t B, int64_t total_samples);
+int     wt_level(const wt_level_clip* clips, int32_t B, void* workspace, void* stream);
+
+/* Measure and apply, in place, on the rows of an ingest output rows [B][T_pad] (device): row b has n[b] valid samples (n: a HOST
+ * array, each in [1, T_pad]); columns from n[b] on are neither read nor written.  The measurement is the one above, bit for bit.
+ *   WT_NORM_PEAK: d = peak + 1e-8f; y = x / d (IEEE division), then y = y * gain only when gain != 1.  With gain = 1 a row has the
+ *     bits of torch's fp32 x / (x.abs().max() + 1e-8) (extract_features.py:27-28); gain = 10^(target_db / 20) rounded to fp32 is a
+ *     peak target in dB (the data preparation's `norm -3`, decoder/dataset.py:69-70, but AFTER the resampling, not before it).
+ *   WT_NORM_RMS:  d = 1e-8f + rms; y = x / d (EncodecModel._encode_frame, encoder/model.py:153-156, on mono audio); gain must be 1.
+ * scales[b] (device, fp32) receives the divisor d.  A silent row stays zeros (scale 1e-8).  workspace:
+ * wt_normalize_rows_workspace_bytes(B, T_pad) bytes, 8-byte aligned.  Three launches. */
+enum { WT_NORM_PEAK = 0, WT_NORM_RMS = 1 };
+size_t wt_normalize_rows_workspace_bytes(int32_t B, int64_t T_pad);
+int    wt_normalize_rows(float* rows, int32_t B, int64_t T_pad, const int64_t* n, int32_t mode, float gain, float* scales,
+                         void* workspace, void* stream);
+
+/* Ragged row scaling: rows[f][0 .. lens[f]) *= scales[f] for f < F, one rounded product per sample: EncodecModel._decode_frame's
+ * `out * scale` (encoder/model.py:180-191) on decoded segment rows, in front of wt_overlap_add_ragged (whose weight * frame is then
+ * the reference's weight * (frame * scale), both products rounded).  rows (F device pointers), lens (int64) and scales (fp32) are
+ * DEVICE arrays; max_len >= every lens[f] sizes the grid.  Nothing is written past rows[f][lens[f] - 1]. */
+int wt_scale_rows(float* const* rows, const int64_t* lens, const float* scales, int32_t F, int64_t max_len, void* stream);
 
 /* Replaces: _linear_overlap_add (encoder/utils.py:17-56), bit for bit: frames [n_frames][rows][frame_len] (the last
  * one holds last_len valid samples), weight [frame_len] = the reference's triangle 0.5 - |linspace(0,1,len+2)[1:-1] - 0.5|,

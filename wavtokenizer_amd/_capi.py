@@ -34,6 +34,8 @@ EXPORTS = [
     "wt_stftd_create", "wt_stftd_destroy", "wt_stftd_frames", "wt_stftd_tables", "wt_stftd_workspace_bytes", "wt_stftd_distance",
     "wt_stftd_magnitude", "wt_wavedist_workspace_bytes", "wt_wavedist_block", "wt_wavedist",
     "wt_pitch_create", "wt_pitch_destroy", "wt_pitch_frames", "wt_pitch_tables", "wt_pitch_workspace_bytes", "wt_pitch_track", "wt_pitch_pairs",
+    "wt_level_chunk", "wt_level_workspace_bytes", "wt_level", "wt_normalize_rows_workspace_bytes", "wt_normalize_rows", "wt_scale_rows",
+    "wt_emit_rescaled_workspace_bytes", "wt_emit_rescaled",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -178,6 +180,14 @@ class WtEmitClip(ctypes.Structure):
     """wt_emit_clip: one clip of a ragged emit launch (wt_emit)."""
     _fields_ = [("src", c_void_p), ("n_in", c_int64), ("resampler", c_void_p), ("n_out", c_int64), ("dst", c_void_p),
                 ("dtype", c_int32), ("channels", c_int32), ("ch_stride", c_int64), ("sample_stride", c_int64), ("limit", c_float)]
+
+
+WT_NORM_PEAK, WT_NORM_RMS = 0, 1
+
+
+class WtLevelClip(ctypes.Structure):
+    """wt_level_clip: one clip of a level measurement (wt_level)."""
+    _fields_ = [("x", c_void_p), ("n", c_int64), ("out", c_void_p)]
 
 
 class WtOverlapAddClip(ctypes.Structure):
@@ -410,6 +420,18 @@ def _load() -> ctypes.CDLL:
     lib.wt_pitch_workspace_bytes.restype = c_size_t
     lib.wt_pitch_track.argtypes = [c_void_p, POINTER(WtPitchClip), c_int32, c_float, c_float, c_float, c_void_p, c_void_p]
     lib.wt_pitch_pairs.argtypes = [c_void_p, POINTER(WtPitchPair), c_int32, c_float, c_float, c_float, c_void_p, c_void_p]
+    lib.wt_level_chunk.argtypes = []
+    lib.wt_level_chunk.restype = c_int32
+    lib.wt_level_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_level_workspace_bytes.restype = c_size_t
+    lib.wt_level.argtypes = [POINTER(WtLevelClip), c_int32, c_void_p, c_void_p]
+    lib.wt_normalize_rows_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_normalize_rows_workspace_bytes.restype = c_size_t
+    lib.wt_normalize_rows.argtypes = [c_void_p, c_int32, c_int64, POINTER(c_int64), c_int32, c_float, c_void_p, c_void_p, c_void_p]
+    lib.wt_scale_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]
+    lib.wt_emit_rescaled_workspace_bytes.argtypes = [c_int32]
+    lib.wt_emit_rescaled_workspace_bytes.restype = c_size_t
+    lib.wt_emit_rescaled.argtypes = [POINTER(WtEmitClip), c_int32, c_void_p, c_void_p]
     return lib
 
 

@@ -4,15 +4,20 @@
     to_pcm16(wav, rescale=False)                         encoder/utils.py:95-103 + the PCM_S 16 conversion of torchaudio.save
     linear_overlap_add(frames, stride)                   encoder/utils.py:17-56   (bit-identical)
     segment_offsets(length, segment_length, stride)      encoder/model.py:133-145 (the frame offsets of EncodecModel.encode)
+    level(wav), level_many(wavs)                         peak and rms per clip (wt_level)
+    normalize(wav, mode="peak" | "rms", target_db=0.0)   extract_features.py:27-28 / encoder/model.py:153-156 (wt_normalize_rows)
 
 All take and return torch tensors on the GPU; there is no CPU fallback.  Recordings of any length, from and to PCM, with codes in
 between: WavTokenizer.encode_codes_segmented(_many) / decode_pcm_segmented(_many) (wavtokenizer_amd/segmented.py)."""
 import ctypes
 import functools
-from typing import Dict, List, Sequence, Tuple
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
+from . import _capi
 from ._capi import _need_gpu, _ptr, _stream, check, lib
 
 _resamplers: Dict[Tuple[int, int, int], ctypes.c_void_p] = {}
@@ -86,6 +91,90 @@ def to_pcm16(wav: torch.Tensor, rescale: bool = False, limit: float = 0.99) -> t
     ws = torch.zeros(1, dtype=torch.int32, device=x.device)
     check(lib.wt_pcm16(_ptr(x), x.numel(), float(limit), 1 if rescale else 0, _ptr(out), _ptr(ws), _stream(x.device)), "wt_pcm16")
     return out
+
+
+def level_many(wavs: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Peak and rms of every clip: wavs is a sequence of non-empty 1-D fp32 tensors on one GPU; returns (n, 2) fp32 there, row i
+    = (max |x|, sqrt(mean x^2)) of clip i.  One wt_level call (two launches) over all clips; the peak is exact, and a clip's rms
+    has the same bits alone and in any batch (the order of its sum depends on its length alone)."""
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError("level_many takes at least one clip")
+    for w in wavs:
+        if not isinstance(w, torch.Tensor) or w.dim() != 1 or w.shape[0] < 1 or w.dtype != torch.float32:
+            raise ValueError("level_many takes a sequence of non-empty 1-D fp32 tensors")
+        _need_gpu(w, _GPU_ONLY)
+    dev = wavs[0].device
+    wavs = [w.contiguous() for w in wavs]
+    out = torch.empty((len(wavs), 2), dtype=torch.float32, device=dev)
+    descs = (_capi.WtLevelClip * len(wavs))()
+    for j, (d, w) in enumerate(zip(descs, wavs)):
+        if w.device != dev:
+            raise ValueError("level_many: the clips lie on different devices")
+        d.x, d.n, d.out = w.data_ptr(), int(w.shape[0]), out.data_ptr() + 8 * j
+    ws = torch.empty(int(lib.wt_level_workspace_bytes(len(wavs), sum(int(w.shape[0]) for w in wavs))), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.wt_level(descs, len(wavs), _ptr(ws), _stream(dev)), "wt_level")
+    return out
+
+
+def level(wav: torch.Tensor) -> torch.Tensor:
+    """level_many for one clip (any shape: all its samples): (2,) fp32 = (peak, rms)."""
+    return level_many([wav.reshape(-1)])[0]
+
+
+def normalize_args(who: str, normalize, target_db) -> Optional[Tuple[int, float]]:
+    """The (mode, gain) of a call's normalize / target_db arguments, None without normalisation; ValueError, before any GPU work,
+    for a mode other than "peak" and "rms" and for a target_db given without "peak" (the rms mode is Encodec's: it has no
+    target)."""
+    if isinstance(target_db, bool) or not isinstance(target_db, (int, float)) or not math.isfinite(target_db):
+        raise ValueError(who + ": target_db must be a finite number")
+    if normalize is None:
+        if target_db != 0.0:
+            raise ValueError(who + ": target_db needs normalize='peak'")
+        return None
+    if normalize == "peak":
+        return _capi.WT_NORM_PEAK, float(np.float32(10.0 ** (float(target_db) / 20.0)))
+    if normalize == "rms":
+        if target_db != 0.0:
+            raise ValueError(who + ": target_db applies to normalize='peak' only")
+        return _capi.WT_NORM_RMS, 1.0
+    raise ValueError(who + ": normalize must be None, 'peak' or 'rms'")
+
+
+def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float) -> torch.Tensor:
+    """wt_normalize_rows on rows, a contiguous (B, T_pad) fp32 tensor on the GPU, in place: row b's first n[b] samples are divided
+    by their level (+ 1e-8); returns the divisors (B,) fp32."""
+    B, T_pad = rows.shape
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and len(n) == B
+    dev = rows.device
+    scales = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.wt_normalize_rows_workspace_bytes(B, T_pad)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.wt_normalize_rows(_ptr(rows), B, T_pad, (ctypes.c_int64 * B)(*[int(v) for v in n]), int(mode), float(gain), _ptr(scales),
+                                    _ptr(ws), _stream(dev)), "wt_normalize_rows")
+    return scales
+
+
+def normalize(wav: torch.Tensor, mode: str = "peak", target_db: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-clip level normalisation of mono audio: wav is (T,), (B, T) or (B, 1, T) on the GPU; returns (wav / scale, scale), the
+    first in wav's shape, scale (B,) fp32 (a 0-d tensor for (T,)).
+      mode="peak": scale = max |x| + 1e-8, the bits of torch's fp32 x / (x.abs().max() + 1e-8) (extract_features.py:27-28); with
+        target_db the quotient is multiplied by 10^(target_db / 20) rounded to fp32 (a peak target: -3 is the data preparation's).
+      mode="rms":  scale = 1e-8 + sqrt(mean x^2), EncodecModel._encode_frame's (encoder/model.py:153-156).
+    A silent clip stays zeros.  This is the one-clip definition the batched calls (encode_codes_many(normalize=...)) are compared
+    with.  The audio is taken as it is: the reference's scripts normalise after convert_audio, sox's `norm` before the resampling,
+    and a peak moves under resampling; parity with sox is not claimed.  Loudness in LUFS is not offered."""
+    args = normalize_args("normalize", mode, target_db)
+    if args is None:
+        raise ValueError("normalize: mode must be 'peak' or 'rms'")
+    if not isinstance(wav, torch.Tensor) or wav.dim() not in (1, 2, 3) or (wav.dim() == 3 and wav.shape[1] != 1) or wav.numel() < 1:
+        raise ValueError("normalize takes non-empty mono audio (T,), (B, T) or (B, 1, T)")
+    _need_gpu(wav, _GPU_ONLY)
+    T = int(wav.shape[-1])
+    rows = wav.to(torch.float32).reshape(-1, T).clone()
+    scales = normalize_rows(rows, [T] * rows.shape[0], *args)
+    return rows.view(wav.shape), (scales[0] if wav.dim() == 1 else scales)
 
 
 def linear_overlap_add(frames: Sequence[torch.Tensor], stride: int) -> torch.Tensor:

@@ -235,26 +235,34 @@ class _BatchedCalls:
         return rows
 
     def _run_encode_codes_mixed(self, specs: Sequence["_ClipSpec"], T_pad: int, flat: torch.Tensor, offsets: Sequence[int],
-                                n_q: Optional[int] = None):
+                                n_q: Optional[int] = None, norm=None):
         """One group of encode_codes_many: one upload, one wt_ingest into the plan's staging tensor, one wt_encode_mixed (no
         feature buffer unless the plan is graph-replayed), one wt_codes_unpack into flat at the clips' offsets.  Returns True, or
-        None when the encoder is off the route a mixed-length plan takes (_route_ok).  n_q: residual VQ (_encode_ingested)."""
+        None when the encoder is off the route a mixed-length plan takes (_route_ok).  n_q: residual VQ (_encode_ingested).
+        norm: (mode, gain, sink) of a call with normalize=...: the ingested rows are normalised in place in front of the encode
+        (one wt_normalize_rows) and sink(offsets, scales) receives the group's divisors."""
         dev = self._ensure_engine()
         if not self._route_ok(_capi.WT_PLAN_ENCODE):          # (before anything is uploaded; checked again on every attempt below)
             return None
         descs, ws, lengths, spans, _alive = self._ingest_stage(specs, offsets, dev)
-        return self._encode_ingested(descs, ws, len(specs), T_pad, lengths, spans, flat, dev, n_q)
+        rows_norm = norm and (norm[0], norm[1], [sp.n_out for sp in specs], lambda scales: norm[2](offsets, scales))
+        return self._encode_ingested(descs, ws, len(specs), T_pad, lengths, spans, flat, dev, n_q, rows_norm)
 
     def _encode_ingested(self, descs, ws: torch.Tensor, B: int, T_pad: int, lengths: Optional[torch.Tensor], spans: torch.Tensor,
-                         flat: torch.Tensor, dev: torch.device, n_q: Optional[int] = None):
+                         flat: torch.Tensor, dev: torch.device, n_q: Optional[int] = None, norm=None):
         """The launches of a group whose wt_ingest descriptors, lengths (int32) and code spans (int64 {frames, offset}) are on
         hand, the latter two on the GPU: one wt_ingest into the plan's staging tensor, one encode without a feature tensor, one
         wt_codes_unpack into flat.  lengths=None: B clips of T_pad samples each on the plain encode plan (encode_codes' own: same
         recording, same staging buffers).  True, or None off the mixed route (a uniform batch then goes clip by clip as well).
         n_q: the encode is residual VQ with n_q codebooks (WT_PLAN_FLAG_RVQ), flat is [n_q][sum L_i] and every plane is handed
-        out by a wt_codes_unpack of its own."""
+        out by a wt_codes_unpack of its own.
+        norm: (mode, gain, samples per row, sink): behind the ingest, one wt_normalize_rows divides every row by its own level
+        in place (audio.normalize_rows) and sink(scales) receives the divisors (B,)."""
         def fill_wav(buf: torch.Tensor):
             check(lib.wt_ingest(descs, B, T_pad, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
+            if norm is not None:
+                from . import audio
+                norm[3](audio.normalize_rows(buf, norm[2], norm[0], norm[1]))
 
         if n_q is not None:
             if lengths is None:
@@ -279,7 +287,8 @@ class _BatchedCalls:
               "wt_codes_unpack")
         return True
 
-    def _encode_codes_solo(self, specs: Sequence["_ClipSpec"], flat: torch.Tensor, offsets: Sequence[int], n_q: Optional[int] = None):
+    def _encode_codes_solo(self, specs: Sequence["_ClipSpec"], flat: torch.Tensor, offsets: Sequence[int], n_q: Optional[int] = None,
+                           norm=None):
         """Clips that run one at a time (shorter than a mixed-length plan takes, or the encoder off its shipped route): ingested
         together like a group, at most MAX_GROUP per launch, then encode_codes per clip (with n_q: into the planes of flat)."""
         from .mixed_length import MAX_GROUP
@@ -287,6 +296,9 @@ class _BatchedCalls:
         for c0 in range(0, len(specs), MAX_GROUP):
             part, offs = specs[c0:c0 + MAX_GROUP], offsets[c0:c0 + MAX_GROUP]
             wav = self._ingest_rows(part, dev)
+            if norm is not None:                             # (as _run_encode_codes_mixed: in place, behind the ingest)
+                from . import audio
+                norm[2](offs, audio.normalize_rows(wav, [sp.n_out for sp in part], norm[0], norm[1]))
             for j, (sp, off) in enumerate(zip(part, offs)):
                 if n_q is not None:
                     codes = self.encode_codes(wav[j:j + 1, :sp.n_out], n_q=n_q)
@@ -319,7 +331,8 @@ class _BatchedCalls:
 
     @torch.inference_mode()
     def encode_codes_many(self, clips: Sequence[torch.Tensor], sample_rates=None, channels_last: bool = False, packed: bool = False,
-                          bandwidth_id=None, n_q: Optional[int] = None):
+                          bandwidth_id=None, n_q: Optional[int] = None, normalize: Optional[str] = None, target_db: float = 0.0,
+                          return_scales: bool = False):
         """Tokenise a set of clips straight from PCM.  clips[i] is (T,), (C, T) or, with channels_last, (T, C), C in {1, 2}, fp32
         or int16 (scaled by 1 / 32768), on the CPU or on the model's device; sample_rates is one rate or one per clip (default:
         the codec rate).  Returns [codes (1, 1, L_i)] in input order, views into one flat int64 tensor, L_i =
@@ -332,9 +345,22 @@ class _BatchedCalls:
         n_q, an int in [1, num_quantizers]: residual VQ with the first n_q codebooks, clip i's codes the bits of
         encode_codes(..., n_q=n_q).  Returns [codes (n_q, 1, L_i)], views into one flat tensor laid out [n_q][sum L_i];
         packed=True returns (that tensor as (n_q, sum L_i), offsets).  Per group one ingest, one mixed-length residual VQ encode
-        and n_q launches that hand out the codes, one per plane."""
+        and n_q launches that hand out the codes, one per plane.
+        normalize="peak" or "rms": every clip is level-normalised between the ingest and the encode, on its mono row at the codec
+        rate (one wt_normalize_rows per group, in place): clip i's codes are the bits of encode_infer(audio.normalize(
+        audio.convert_audio(clip i, rate_i, 24000, 1)[0], normalize, target_db)[0])[1].  "peak" is extract_features.py:27-28 (the
+        codec was trained on peak-normalised audio), target_db its peak target in dB (peak mode only); "rms" Encodec's frame
+        normalisation.  The order is the reference scripts': convert first, normalise second; sox's `norm` runs before the
+        resampling and a peak moves under resampling, so parity with sox is not claimed.  return_scales=True (with normalize)
+        appends the divisors, (n,) fp32 on the model's device, to the result: (codes list, scales) or (flat, offsets, scales);
+        decode_pcm_many(scales=...) multiplies them back in.  A target_db without "peak", an unknown mode and return_scales
+        without normalize raise ValueError before any GPU work."""
+        from . import audio
         from .mixed_length import group_clips
         self._check_bandwidth(bandwidth_id)
+        norm = audio.normalize_args("encode_codes_many", normalize, target_db)
+        if return_scales and norm is None:
+            raise ValueError("encode_codes_many: return_scales needs normalize")
         if n_q is not None:
             n_q = self._check_n_q("encode_codes_many", n_q)
         specs = self._clip_specs("encode_codes_many", clips, sample_rates, channels_last)
@@ -344,19 +370,35 @@ class _BatchedCalls:
             offsets.append(offsets[-1] + frames(sp.n_out))
         flat = torch.empty(offsets[-1] if n_q is None else (n_q, offsets[-1]), dtype=torch.int64, device=self._device())
         rvq = () if n_q is None else (n_q,)       # (n_q=None: today's calls, argument for argument)
+        parts: Dict[int, Tuple[List[int], torch.Tensor]] = {}    # a group's first code offset -> (its clips' offsets, their divisors)
+        kw = {} if norm is None else {"norm": (*norm, lambda offs, sc: parts.__setitem__(offs[0], (list(offs), sc)))}
         self._run_groups_of(specs, offsets, *group_clips([sp.n_out for sp in specs], self._arch.hop),
-                            lambda T_pad, part, offs: self._run_encode_codes_mixed(part, T_pad, flat, offs, *rvq),
-                            lambda part, offs: self._encode_codes_solo(part, flat, offs, *rvq))
+                            lambda T_pad, part, offs: self._run_encode_codes_mixed(part, T_pad, flat, offs, *rvq, **kw),
+                            lambda part, offs: self._encode_codes_solo(part, flat, offs, *rvq, **kw))
+        extra = (self._gather_scales(parts, offsets[:-1]),) if return_scales else ()
         if packed:
-            return flat, torch.tensor(offsets, dtype=torch.int64)
+            return (flat, torch.tensor(offsets, dtype=torch.int64), *extra)
         if n_q is not None:
-            return [flat[:, offsets[i]:offsets[i + 1]].unsqueeze(1) for i in range(len(specs))]
-        return [flat[offsets[i]:offsets[i + 1]].view(1, 1, -1) for i in range(len(specs))]
+            out = [flat[:, offsets[i]:offsets[i + 1]].unsqueeze(1) for i in range(len(specs))]
+        else:
+            out = [flat[offsets[i]:offsets[i + 1]].view(1, 1, -1) for i in range(len(specs))]
+        return (out, *extra) if extra else out
+
+    def _gather_scales(self, parts, keys: Sequence[int]) -> torch.Tensor:
+        """The divisors of a normalising call in input order: parts maps anything to (the keys of a launch's rows, their divisors
+        (rows,) on the GPU), keys[i] is the key of input i.  One concatenation and one gather (an index table goes up)."""
+        dev = self._device()
+        if not keys:
+            return torch.empty(0, dtype=torch.float32, device=dev)
+        where = {k: j for j, k in enumerate(k for ks, _sc in parts.values() for k in ks)}
+        cat = torch.cat([sc for _ks, sc in parts.values()])
+        return cat[torch.tensor([where[k] for k in keys], dtype=torch.int64).to(dev)]
 
     # -- long recordings in overlapping segments (segmented.py): tokenise ---------------------------------------------------------
     @torch.inference_mode()
     def encode_codes_segmented_many(self, clips: Sequence[torch.Tensor], segment_length: int, stride: int, sample_rates=None,
-                                    channels_last: bool = False, bandwidth_id=None):
+                                    channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None,
+                                    target_db: float = 0.0):
         """Tokenise long recordings in overlapping segments (the reference's EncodecModel.encode, encoder/model.py:122-145).
         clips and sample_rates as encode_codes_many takes them (any rate, mono or stereo, planar or interleaved, fp32 or int16,
         on the CPU or on the model's device); segment_length and stride are samples at the codec rate, stride <= segment_length.
@@ -371,11 +413,18 @@ class _BatchedCalls:
         call one ingest launch, one encode without a feature tensor and one launch that hands out the codes.  Tails under the
         mixed-length plans' minimum, and every segment while the encoder is off its shipped route, are encoded one at a time.
         Status, fallbacks, strict mode and graphs behave as in encode_codes_many.  Argument errors (segmented.segment_plan's, a
-        segment beyond 12 000 frames, an ISTFT head with padding="center") raise ValueError before any GPU work."""
+        segment beyond 12 000 frames, an ISTFT head with padding="center") raise ValueError before any GPU work.
+        normalize="peak" or "rms" (target_db with "peak"): every segment is normalised on its own after the cut, as
+        EncodecModel._encode_frame does with "rms" (encoder/model.py:147-165), one wt_normalize_rows per call between its ingest
+        and its encode: segment i's codes are the bits of encode_codes(audio.normalize(W[None, off_i:off_i + len_i], normalize,
+        target_db)[0]), and the divisors are kept as SegmentedCodes.scales, (n_segments,) fp32 on the model's device, for
+        decode_pcm_segmented to multiply back in."""
+        from . import audio
         from .mixed_length import MAX_GROUP, group_clips
         from .segmented import SegmentedCodes, check_geometry, segment_plan
         who = "encode_codes_segmented_many"
         self._check_bandwidth(bandwidth_id)
+        norm = audio.normalize_args(who, normalize, target_db)
         segment_plan(1, segment_length, stride)                 # (the geometry's own refusals, also for an empty list)
         specs = self._clip_specs(who, clips, sample_rates, channels_last)
         S, stride = int(segment_length), int(stride)
@@ -428,26 +477,41 @@ class _BatchedCalls:
         on_gpu = self._upload_tables(tables, dev)
         tables_of = iter(zip(on_gpu[0::2], on_gpu[1::2]))            # (_run_groups runs the calls in this order, each once)
 
+        parts: Dict[int, Tuple[List[int], torch.Tensor]] = {}    # a call's first segment -> (its segments, their divisors)
+
         def run_call(T_pad, ks):         # the segments are wt_ingest clips at equal rates: addresses in the rows
             lengths, spans = next(tables_of)
             descs, ws = self._ingest_descs([spec[seg_len[k]] for k in ks], [base[seg_rec[k]] + 4 * seg_off[k] for k in ks], dev)
             uniform = not T_pad and not self._segment_uniform_mixed
-            return self._encode_ingested(descs, ws, len(ks), T_pad or S, None if uniform else lengths, spans, flat, dev)
+            kw = {} if norm is None else {"norm": (*norm, [seg_len[k] for k in ks], lambda sc: parts.__setitem__(ks[0], (list(ks), sc)))}
+            return self._encode_ingested(descs, ws, len(ks), T_pad or S, None if uniform else lengths, spans, flat, dev, **kw)
 
         def run_solo(ks):
             for k in ks:
-                codes = self.encode_codes(rows[seg_rec[k]][None, seg_off[k]:seg_off[k] + seg_len[k]])
+                seg = rows[seg_rec[k]][None, seg_off[k]:seg_off[k] + seg_len[k]]
+                if norm is None:
+                    codes = self.encode_codes(seg)
+                else:
+                    codes, sc = self.encode_codes(seg, normalize=normalize, target_db=target_db, return_scales=True)
+                    parts[k] = ([k], sc)
                 flat[seg_code[k]:seg_code[k] + codes.shape[-1]].copy_(codes.view(-1))
 
         self._run_groups(calls, solo, run_call, run_solo)
-        return [SegmentedCodes(flat[bounds[r]:bounds[r + 1]], rec_offsets[r], sp.n_out, S, stride) for r, sp in enumerate(specs)]
+        if norm is None:
+            return [SegmentedCodes(flat[bounds[r]:bounds[r + 1]], rec_offsets[r], sp.n_out, S, stride) for r, sp in enumerate(specs)]
+        scales = self._gather_scales(parts, list(range(len(seg_len))))
+        first = [0]
+        for offs in rec_offsets:
+            first.append(first[-1] + len(offs) - 1)
+        return [SegmentedCodes(flat[bounds[r]:bounds[r + 1]], rec_offsets[r], sp.n_out, S, stride, scales[first[r]:first[r + 1]])
+                for r, sp in enumerate(specs)]
 
     @torch.inference_mode()
     def encode_codes_segmented(self, clip: torch.Tensor, segment_length: int, stride: int, sample_rate: Optional[int] = None,
-                               channels_last: bool = False, bandwidth_id=None):
+                               channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None, target_db: float = 0.0):
         """encode_codes_segmented_many for one recording: its segmented.SegmentedCodes."""
         return self.encode_codes_segmented_many([clip], segment_length, stride, sample_rates=sample_rate, channels_last=channels_last,
-                                                bandwidth_id=bandwidth_id)[0]
+                                                bandwidth_id=bandwidth_id, normalize=normalize, target_db=target_db)[0]
 
     def _run_decode_mixed(self, feats: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None):
         """One mixed-length decode call (WT_PLAN_DECODE_MIXED) on clips (512, L_i) of 1 <= L_i <= L_pad frames: returns the
@@ -646,10 +710,29 @@ class _BatchedCalls:
             raise ValueError(who + ": limit must be in (0, 1]")
         return [int(c) for c in channels], (dtype, limit)
 
+    def _scale_rows(self, rows: Sequence[torch.Tensor], lens: Sequence[int], scales: torch.Tensor, dev: torch.device):
+        """One wt_scale_rows: rows[j][:lens[j]] *= scales[j] in place; rows are contiguous fp32 rows on dev, scales (len(rows),)
+        fp32 there.  The row pointers and lengths go up in one copy."""
+        assert scales.dtype == torch.float32 and scales.is_contiguous() and scales.numel() == len(rows) and scales.device == dev
+        assert all(r.dtype == torch.float32 and r.stride(-1) == 1 and r.shape[-1] >= n >= 1 for r, n in zip(rows, lens))
+        table, lengths = self._upload_tables([torch.tensor([r.data_ptr() for r in rows], dtype=torch.int64),
+                                              torch.tensor(list(lens), dtype=torch.int64)], dev)
+        with torch.cuda.device(dev):
+            check(lib.wt_scale_rows(_ptr(table), _ptr(lengths), _ptr(scales), len(rows), max(lens), _stream_ptr(dev)), "wt_scale_rows")
+
+    def _check_scales(self, who: str, scales, n: int) -> Optional[torch.Tensor]:
+        """The scales argument of decode_pcm / decode_pcm_many, checked: None, or (n,) floating point, as fp32 on the model's device."""
+        if scales is None:
+            return None
+        if not isinstance(scales, torch.Tensor) or not scales.is_floating_point() or scales.shape != (n,):
+            raise ValueError(who + ": scales must be a floating-point tensor with one entry per clip")
+        return scales.to(device=self._device(), dtype=torch.float32).contiguous()
+
     def _emit_rows(self, rows: Sequence[torch.Tensor], specs: Sequence["_PcmSpec"], flat: torch.Tensor, offsets: Sequence[int],
-                   fmt: Tuple[torch.dtype, float], channels_last: bool, dev: torch.device):
+                   fmt: Tuple[torch.dtype, float], channels_last: bool, dev: torch.device, rescale: bool = False):
         """One wt_emit: rows[j], a contiguous fp32 row of at least specs[j].n_in samples at the codec rate on dev, goes to
-        flat[offsets[j]:] at the clip's rate in the layout (channels, n_out) or, with channels_last, (n_out, channels)."""
+        flat[offsets[j]:] at the clip's rate in the layout (channels, n_out) or, with channels_last, (n_out, channels).
+        rescale: wt_emit_rescaled instead (two launches): every clip times min(limit / its peak, 1) in place of the clamp."""
         from . import audio
         dtype, limit = fmt
         B = len(rows)
@@ -672,6 +755,10 @@ class _BatchedCalls:
                 d.ch_stride, d.sample_stride = (1, channels) if channels_last else (sp.n_out, 1)
         # up to 64 clips the library passes the descriptors with the launch and leaves the workspace alone: one small tensor serves
         # every such call; a larger launch gets a workspace of its own (the library fills it on the stream)
+        if rescale:                     # (the peaks lie in the workspace: one per call)
+            ws = torch.empty(int(lib.wt_emit_rescaled_workspace_bytes(B)), dtype=torch.uint8, device=dev)
+            check(lib.wt_emit_rescaled(descs, B, _ptr(ws), _stream_ptr(dev)), "wt_emit_rescaled")
+            return
         if B <= 64:
             ws = self._emit_ws
             if ws is None or ws.device != dev:
@@ -681,28 +768,34 @@ class _BatchedCalls:
         check(lib.wt_emit(descs, B, _ptr(ws), _stream_ptr(dev)), "wt_emit")
 
     def _run_decode_pcm_mixed(self, specs: Sequence["_PcmSpec"], L_pad: int, bw: int, flat: torch.Tensor, offsets: Sequence[int],
-                              fmt: Tuple[torch.dtype, float], channels_last: bool):
+                              fmt: Tuple[torch.dtype, float], channels_last: bool, rescale: bool = False, scales_of=None):
         """One group of decode_pcm_many: one wt_decode_codes_mixed, one wt_emit from the plan's output rows into flat at the
-        clips' offsets.  Returns True, or None when the decoder is off the route a mixed-length plan takes."""
+        clips' offsets.  Returns True, or None when the decoder is off the route a mixed-length plan takes.  scales_of(offsets):
+        the clips' scales, multiplied into the rows in front of the emit (wt_scale_rows); rescale as in _emit_rows."""
         wav = self._run_decode_codes_mixed([sp.codes for sp in specs], L_pad, bw, borrow=True)
         if wav is None:
             return None
-        self._emit_rows(list(wav), specs, flat, offsets, fmt, channels_last, wav.device)
+        if scales_of is not None:
+            self._scale_rows(list(wav), [sp.n_in for sp in specs], scales_of(offsets), wav.device)
+        self._emit_rows(list(wav), specs, flat, offsets, fmt, channels_last, wav.device, rescale)
         return True
 
     def _decode_pcm_solo(self, specs: Sequence["_PcmSpec"], bw: int, flat: torch.Tensor, offsets: Sequence[int],
-                         fmt: Tuple[torch.dtype, float], channels_last: bool):
+                         fmt: Tuple[torch.dtype, float], channels_last: bool, rescale: bool = False, scales_of=None):
         """Clips that are decoded one at a time (a group of one, a 'center' clip under two frames, every clip while the decoder
         is off its mixed route): decode_codes per clip, then one wt_emit for the lot, at most MAX_GROUP clips per launch."""
         from .mixed_length import MAX_GROUP
         for c0 in range(0, len(specs), MAX_GROUP):
             part, offs = specs[c0:c0 + MAX_GROUP], offsets[c0:c0 + MAX_GROUP]
             rows = [self.decode_codes(sp.codes, bandwidth_id=bw)[0] for sp in part]
-            self._emit_rows(rows, part, flat, offs, fmt, channels_last, rows[0].device)
+            if scales_of is not None:
+                self._scale_rows(rows, [sp.n_in for sp in part], scales_of(offs), rows[0].device)
+            self._emit_rows(rows, part, flat, offs, fmt, channels_last, rows[0].device, rescale)
 
     @torch.inference_mode()
     def decode_pcm_many(self, codes: Sequence[torch.Tensor], sample_rates=None, channels=1, dtype: torch.dtype = torch.int16,
-                        channels_last: bool = False, limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None):
+                        channels_last: bool = False, limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None,
+                        rescale: bool = False, scales: Optional[torch.Tensor] = None):
         """Synthesise a set of clips straight to PCM.  codes[i] is (K, L_i) or (K, 1, L_i) as decode_codes_many takes it;
         sample_rates is one rate or one per clip (default: the codec rate); channels is 1 or 2 for every clip, or one such
         count per clip; dtype, channels_last and limit as in decode_pcm.  Returns [pcm (channels, n_out_i)] or, with
@@ -718,11 +811,16 @@ class _BatchedCalls:
         (decode_codes raises for it) and every clip while the decoder is off its mixed route are decoded one at a time and
         emitted together, at most 64 per launch.  A code outside the codebook follows set_check_codes as in decode_codes; an
         int16 result no longer shows the NaN marker of a bad code (a NaN is clamped like any sample), so under "off" nothing
-        reports it.  Argument errors raise ValueError before any GPU work."""
+        reports it.  Argument errors raise ValueError before any GPU work.
+        rescale=True: save_audio's rescale (encoder/utils.py:95-103) per clip instead of the clamp: the emit is wt_emit_rescaled
+        (two launches per group), clip i the bits of audio.to_pcm16(R_i, rescale=True, limit=limit) (int16) or of R_i times
+        min(limit / max |R_i|, 1) (fp32).  scales: (n,) from encode_codes_many(return_scales=True): every decoded row is
+        multiplied by its clip's scale in front of the emit (one wt_scale_rows per group)."""
         from . import audio
         who = "decode_pcm_many"
         bw = self._bandwidth_index(bandwidth_id)
         clips = self._codes_clips(codes, who)
+        scales = self._check_scales(who, scales, len(clips))
         chans, fmt = self._emit_format(who, channels, dtype, limit, len(clips))
         channels_last = bool(channels_last)
         codec_rate = self.codec_rate
@@ -736,9 +834,13 @@ class _BatchedCalls:
             specs.append(_PcmSpec(c, L, sr, n_in, n_out, ch))
             offsets.append(offsets[-1] + n_out * ch)
         flat = torch.empty(offsets[-1], dtype=fmt[0], device=self._device())
+        kw = {"rescale": True} if rescale else {}
+        if scales is not None:                               # (a clip is known by its offset in flat: every clip has samples)
+            index = {off: i for i, off in enumerate(offsets[:-1])}
+            kw["scales_of"] = lambda offs: scales[torch.tensor([index[o] for o in offs], dtype=torch.int64).to(scales.device)]
         self._run_groups_of(specs, offsets, *self._decode_groups([sp.frames for sp in specs]),
-                            lambda L_pad, part, offs: self._run_decode_pcm_mixed(part, L_pad, bw, flat, offs, fmt, channels_last),
-                            lambda part, offs: self._decode_pcm_solo(part, bw, flat, offs, fmt, channels_last))
+                            lambda L_pad, part, offs: self._run_decode_pcm_mixed(part, L_pad, bw, flat, offs, fmt, channels_last, **kw),
+                            lambda part, offs: self._decode_pcm_solo(part, bw, flat, offs, fmt, channels_last, **kw))
         return self._pcm_result(flat, offsets, specs, packed, to_host, channels_last)
 
     def _pcm_rates_device(self, who: str, n: int, sample_rates, device) -> Tuple[List[int], bool]:
@@ -769,7 +871,7 @@ class _BatchedCalls:
     # -- long recordings in overlapping segments (segmented.py): synthesise -------------------------------------------------------
     @torch.inference_mode()
     def decode_pcm_segmented_many(self, segs, sample_rates=None, channels=1, dtype: torch.dtype = torch.int16, channels_last: bool = False,
-                                  limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None):
+                                  limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None, rescale: bool = False):
         """Synthesise long recordings from their segments' codes (the reference's EncodecModel.decode, encoder/model.py:167-178):
         segs[r] is a segmented.SegmentedCodes, from encode_codes_segmented(_many) or built by hand; the other arguments and the
         forms of the result (views of one flat tensor, packed=True, device="cpu" into pinned memory with one copy and one wait)
@@ -785,7 +887,11 @@ class _BatchedCalls:
         recording, plus one 24 kHz row each.  set_gemm_precision("f16"), set_check_codes and the fallbacks apply as to
         decode_codes (under "sync" there is one wait behind the last uniform batch, not one per batch).  Argument errors
         (SegmentedCodes.validate's among them: offsets or length that contradict segment_plan, padding="center") raise
-        ValueError before any GPU work."""
+        ValueError before any GPU work.
+        A recording with scales (encode_codes_segmented(normalize=...)) has segment i's decoded samples multiplied by scales[i]
+        in front of the cross-fade, EncodecModel._decode_frame's `out * scale` (one wt_scale_rows over all such segments): X is
+        then audio.linear_overlap_add([decode_codes(c_i)[..., :len_i] * scales[i] for i], stride), bit for bit.  rescale as in
+        decode_pcm_many, on the cross-faded recording."""
         from . import audio
         from .mixed_length import MAX_GROUP, MAX_SCORE_CELLS, score_cells
         from .segmented import SegmentedCodes
@@ -872,6 +978,10 @@ class _BatchedCalls:
             t = torch.linspace(0, 1, flen + 2, dtype=torch.float32)[1:-1]
             tri.append(0.5 - (t - 0.5).abs())
         ptrs = torch.tensor([row.data_ptr() for rr in rows for row in rr], dtype=torch.int64)
+        scaled = [r for r, sc in enumerate(segs) if sc.scales is not None]
+        if scaled:                                                   # _decode_frame's out * scale, on the rows, before the cross-fade
+            self._scale_rows([row for r in scaled for row in rows[r]], [n for r in scaled for n in geo[r][1]],
+                             torch.cat([segs[r].scales.to(device=dev, dtype=torch.float32).reshape(-1) for r in scaled]), dev)
         on_gpu = self._upload_tables([ptrs] + tri, dev)
         table, weight = on_gpu[0], dict(zip(flens, on_gpu[1:]))
         first = [0]
@@ -891,17 +1001,18 @@ class _BatchedCalls:
             with torch.cuda.device(dev):
                 check(lib.wt_overlap_add_ragged(descs, len(part), _ptr(ws), _stream_ptr(dev)), "wt_overlap_add_ragged")
             self._emit_rows([X[x_off[r]:x_off[r] + segs[r].length] for r in part], [specs[r] for r in part], flat,
-                            [offsets[r] for r in part], fmt, channels_last, dev)
+                            [offsets[r] for r in part], fmt, channels_last, dev, bool(rescale))
         return self._pcm_result(flat, offsets, specs, packed, to_host, channels_last)
 
     @torch.inference_mode()
     def decode_pcm_segmented(self, seg, sample_rate: Optional[int] = None, channels: int = 1, dtype: torch.dtype = torch.int16,
-                             channels_last: bool = False, limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None):
+                             channels_last: bool = False, limit: float = 0.99, packed: bool = False, device=None, bandwidth_id=None,
+                             rescale: bool = False):
         """decode_pcm_segmented_many for one recording: (channels, n_out) or, with channels_last, (n_out, channels); packed=True
         returns the flat tensor and its offsets."""
         if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
             raise ValueError("decode_pcm_segmented: channels must be 1 or 2")
         out = self.decode_pcm_segmented_many([seg], sample_rates=sample_rate, channels=channels, dtype=dtype, channels_last=channels_last,
-                                             limit=limit, packed=packed, device=device, bandwidth_id=bandwidth_id)
+                                             limit=limit, packed=packed, device=device, bandwidth_id=bandwidth_id, rescale=rescale)
         return out if packed else out[0]
 

@@ -165,17 +165,33 @@ __device__ __forceinline__ void store_i16_run(global_ptr<int16_t> base, long n, 
 // runs as 16 bytes; int16 runs as 8 bytes, two 4-byte words, or 2 + 4 + 2 bytes on an odd element; interleaved stereo frames as
 // 16 bytes (int16: four frames; fp32: two) or one store per frame.  A tail of fewer than four samples and any other strides get
 // one store per element.  The same values as emit_block's general path, bit for bit.
-__device__ __forceinline__ void emit_copy_block(const EmitClip& d) {
+// MODE (emit_block): EMIT_PLAIN as described; EMIT_RESCALED: every sample times s instead of the clamp, one rounded product
+// (pcm16_kernel's rescale); EMIT_PEAK: nothing is stored, the largest |sample| of the block goes to *peak instead (as absmax_kernel:
+// an integer atomicMax on the bits of a non-negative float, the same in any order).
+enum : int { EMIT_PLAIN = 0, EMIT_RESCALED = 1, EMIT_PEAK = 2 };
+
+// every lane of the wave calls this
+__device__ __forceinline__ void emit_peak_wave(float m, unsigned* peak) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(peak, __float_as_uint(m));
+}
+
+template <int MODE> __device__ __forceinline__ void emit_copy_block(const EmitClip& d, float s, unsigned* peak) {
     const long base = (long)blockIdx.x * EMIT_COPY_SPAN;
     if (base >= d.n_out) return;
     const global_ptr<const float> src = (global_ptr<const float>)d.src;
     const float k0 = ((global_ptr<const float>)d.kern)[0];
     const bool frames = d.C == 2 && d.cstride == 1 && d.sstride == 2;      // interleaved stereo
     const bool src16 = (uintptr_t)src % 16 == 0;
+    float mx = 0.f;
 #pragma unroll
     for (int j = 0; j < EMIT_COPY_SPAN / 1024; ++j) {
         const long n = base + j * 1024 + 4 * (long)threadIdx.x;
-        if (n >= d.n_out) return;
+        if (n >= d.n_out) {
+            if (MODE == EMIT_PEAK) break;
+            return;
+        }
         const int m = d.n_out - n < 4 ? (int)(d.n_out - n) : 4;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         if (m == 4 && src16) {
@@ -187,6 +203,15 @@ __device__ __forceinline__ void emit_copy_block(const EmitClip& d) {
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaf(k0, 0.f + v[i], 0.f);      // (resample_mono_kernel's channel sum, then its chain)
+        if (MODE == EMIT_PEAK) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (i < m) mx = fmaxf(mx, fabsf(v[i]));
+            continue;
+        }
+        if (MODE == EMIT_RESCALED) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = v[i] * s;
+        }
         if (!d.i16) {
             const global_ptr<float> o = (global_ptr<float>)d.dst;
             if (frames && (uintptr_t)o % 8 == 0) {
@@ -217,7 +242,7 @@ __device__ __forceinline__ void emit_copy_block(const EmitClip& d) {
         }
         uint32_t q[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = (uint32_t)(uint16_t)pcm16_round(fminf(fmaxf(v[i], -d.limit), d.limit));
+        for (int i = 0; i < 4; ++i) q[i] = (uint32_t)(uint16_t)pcm16_round(MODE == EMIT_RESCALED ? v[i] : fminf(fmaxf(v[i], -d.limit), d.limit));
         const global_ptr<int16_t> o = (global_ptr<int16_t>)d.dst;
         if (frames && (uintptr_t)o % 4 == 0) {
             const global_ptr<uint32_t> p = (global_ptr<uint32_t>)(o + 2 * n);
@@ -251,6 +276,7 @@ __device__ __forceinline__ void emit_copy_block(const EmitClip& d) {
                 for (int i = 0; i < 4; ++i) if (i < m) o[c * d.cstride + (n + i) * d.sstride] = (int16_t)q[i];
         }
     }
+    if (MODE == EMIT_PEAK) emit_peak_wave(mx, peak);
 }
 
 // The mirror of ingest_kernel: grid (ceil(max n_out / 256), B), block (x, b) resamples 256 consecutive outputs of row b (fp32 mono
@@ -263,9 +289,9 @@ __device__ __forceinline__ void emit_copy_block(const EmitClip& d) {
 // instead (the host sizes the grid for whichever form each clip takes).
 __host__ __device__ inline bool emit_is_copy(int orig, int nw, int K, int width) { return K == 1 && width == 0 && orig == 1 && nw == 1; }
 
-__device__ __forceinline__ void emit_block(const EmitClip& d) {
+template <int MODE> __device__ __forceinline__ void emit_block(const EmitClip& d, float s, unsigned* peak) {
     extern __shared__ float win[];
-    if (emit_is_copy(d.orig, d.nw, d.K, d.width)) { emit_copy_block(d); return; }
+    if (emit_is_copy(d.orig, d.nw, d.K, d.width)) { emit_copy_block<MODE>(d, s, peak); return; }
     const long n0 = (long)blockIdx.x * 256;
     if (n0 >= d.n_out) return;
     const long n = n0 + threadIdx.x;
@@ -290,6 +316,8 @@ __device__ __forceinline__ void emit_block(const EmitClip& d) {
         const float* wp = win + (i - i0) * d.orig;
         for (int k = 0; k < d.K; ++k) acc = fmaf(kp[k], wp[k], acc);
     }
+    if (MODE == EMIT_PEAK) { emit_peak_wave(valid ? fabsf(acc) : 0.f, peak); return; }
+    if (MODE == EMIT_RESCALED) acc = acc * s;
     const bool frames = d.C == 2 && d.cstride == 1 && d.sstride == 2;      // interleaved stereo
     if (!d.i16) {
         if (!valid) return;
@@ -301,7 +329,7 @@ __device__ __forceinline__ void emit_block(const EmitClip& d) {
         }
         return;
     }
-    const int q = pcm16_round(fminf(fmaxf(acc, -d.limit), d.limit));
+    const int q = pcm16_round(MODE == EMIT_RESCALED ? acc : fminf(fmaxf(acc, -d.limit), d.limit));
     const global_ptr<int16_t> o = (global_ptr<int16_t>)d.dst;
     if (frames && (uintptr_t)o % 4 == 0) {
         if (valid) ((global_ptr<uint32_t>)o)[n] = (uint32_t)(uint16_t)q * 0x10001u;
@@ -318,7 +346,25 @@ __device__ __forceinline__ void emit_block(const EmitClip& d) {
 constexpr int EMIT_ARG_CLIPS = 64;
 template <class D> __global__ __launch_bounds__(256) void emit_kernel(const D d) {
     const EmitClip c = d.clip[blockIdx.y];
-    emit_block(c);
+    emit_block<EMIT_PLAIN>(c, 1.f, nullptr);
+}
+
+// (a kernel, not hipMemsetAsync: a launch like the two behind it, at a launch's host cost)
+__global__ __launch_bounds__(256) void emit_zero_peaks_kernel(unsigned* __restrict__ peaks, int B) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < B) peaks[i] = 0u;
+}
+
+// wt_emit_rescaled's two launches over one grid: EMIT_PEAK leaves max |sample| of clip b's resampled output in peaks[b] (zeroed
+// before the launch), EMIT_RESCALED emits every sample times s = min(limit / peak, 1) (pcm16_kernel's rule: 1 for a silent clip)
+template <class D, int MODE> __global__ __launch_bounds__(256) void emit_level_kernel(const D d, unsigned* peaks) {
+    const EmitClip c = d.clip[blockIdx.y];
+    float s = 1.f;
+    if (MODE == EMIT_RESCALED) {
+        const float mx = __uint_as_float(peaks[blockIdx.y]);
+        s = mx > 0.f ? fminf(c.limit / mx, 1.f) : 1.f;
+    }
+    emit_block<MODE>(c, s, peaks + blockIdx.y);
 }
 
 // The ragged way out: spans [B][2] = {L_b, offset_b}; the first L_b codes of row b of codes [B][L_pad] go to out[offset_b + t].
@@ -565,16 +611,19 @@ int wt_ingest(const wt_ingest_clip* clips, int32_t B, int64_t T_pad, float* out,
 
 size_t wt_emit_workspace_bytes(int32_t B) { return B > 0 ? (size_t)B * sizeof(EmitClip) : 0; }
 
-int wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream) {
-    if (!clips || !workspace || B < 1 || B > 65535) { set_error("wt_emit: bad argument"); return WT_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error("wt_emit: workspace misaligned"); return WT_ERR_INVALID; }
-    std::vector<EmitClip> dev((size_t)B);
-    size_t smem = 0;
-    int64_t blocks = 0;
-    const int device = clips[0].resampler ? clips[0].resampler->device : 0;
+// The descriptors of wt_emit / wt_emit_rescaled (fn) checked and turned into their device form; rescaled: the limit is every
+// clip's, whatever its sample type
+static int emit_prepare(const std::string& fn, const wt_emit_clip* clips, int32_t B, const void* workspace, bool rescaled,
+                        std::vector<EmitClip>& dev, size_t& smem, int64_t& blocks, int& device) {
+    if (!clips || !workspace || B < 1 || B > 65535) { set_error(fn + ": bad argument"); return WT_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error(fn + ": workspace misaligned"); return WT_ERR_INVALID; }
+    dev.resize((size_t)B);
+    smem = 0;
+    blocks = 0;
+    device = clips[0].resampler ? clips[0].resampler->device : 0;
     for (int b = 0; b < B; ++b) {
         const wt_emit_clip& c = clips[b];
-        const std::string who = "wt_emit: clip " + std::to_string(b) + ": ";
+        const std::string who = fn + ": clip " + std::to_string(b) + ": ";
         if (!c.src) { set_error(who + "null source"); return WT_ERR_INVALID; }
         if (!c.dst) { set_error(who + "null destination"); return WT_ERR_INVALID; }
         if (!c.resampler) { set_error(who + "null resampler"); return WT_ERR_INVALID; }
@@ -590,7 +639,7 @@ int wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream)
         if (reinterpret_cast<uintptr_t>(c.dst) % (c.dtype == WT_EMIT_I16 ? sizeof(int16_t) : sizeof(float))) {
             set_error(who + "misaligned destination pointer"); return WT_ERR_INVALID;
         }
-        if (c.dtype == WT_EMIT_I16 && !(c.limit > 0.f && c.limit <= 1.f)) { set_error(who + "limit outside (0, 1]"); return WT_ERR_INVALID; }
+        if ((rescaled || c.dtype == WT_EMIT_I16) && !(c.limit > 0.f && c.limit <= 1.f)) { set_error(who + "limit outside (0, 1]"); return WT_ERR_INVALID; }
         if (c.resampler->device != device) { set_error(who + "resampler of another device"); return WT_ERR_INVALID; }
         const size_t w = resampler_window_bytes(c.resampler);
         if (w > 64 * 1024) { set_error(who + "rate ratio too large for the LDS window"); return WT_ERR_INVALID; }
@@ -600,8 +649,17 @@ int wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream)
         blocks = std::max(blocks, (c.n_out + span - 1) / span);
         dev[b] = EmitClip{c.src, c.resampler->kern, c.dst, (long)c.n_in, (long)c.n_out, (long)c.ch_stride, (long)c.sample_stride,
                           c.dtype == WT_EMIT_I16 ? 1 : 0, c.channels, c.resampler->orig, c.resampler->nw, c.resampler->K,
-                          c.resampler->width, c.dtype == WT_EMIT_I16 ? c.limit : 1.f};
+                          c.resampler->width, rescaled || c.dtype == WT_EMIT_I16 ? c.limit : 1.f};
     }
+    return WT_OK;
+}
+
+int wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream) {
+    std::vector<EmitClip> dev;
+    size_t smem = 0;
+    int64_t blocks = 0;
+    int device = 0;
+    if (int rc = emit_prepare("wt_emit", clips, B, workspace, false, dev, smem, blocks, device)) return rc;
     WT_HIP_CHECK(hipSetDevice(device));
     static PerDeviceOnce attr_once;
     if (int rc = attr_once.run([&]() -> int {
@@ -613,6 +671,38 @@ int wt_emit(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream)
     dim3 grid((unsigned)blocks, (unsigned)B);
     if (int rc = launch_ragged<EMIT_ARG_CLIPS>("wt_emit", dev.data(), B, 128, workspace, s, [&](auto d) {
         hipLaunchKernelGGL(emit_kernel<decltype(d)>, grid, dim3(256), smem, s, d);
+    })) return rc;
+    WT_HIP_CHECK(hipGetLastError());
+    return WT_OK;
+}
+
+size_t wt_emit_rescaled_workspace_bytes(int32_t B) { return B > 0 ? (size_t)B * (sizeof(EmitClip) + sizeof(unsigned)) : 0; }
+
+int wt_emit_rescaled(const wt_emit_clip* clips, int32_t B, void* workspace, void* stream) {
+    std::vector<EmitClip> dev;
+    size_t smem = 0;
+    int64_t blocks = 0;
+    int device = 0;
+    if (int rc = emit_prepare("wt_emit_rescaled", clips, B, workspace, true, dev, smem, blocks, device)) return rc;
+    WT_HIP_CHECK(hipSetDevice(device));
+    typedef PtrClips<EmitClip> P;
+    typedef ArgClips<EmitClip, EMIT_ARG_CLIPS> A;
+    static PerDeviceOnce attr_once;
+    if (int rc = attr_once.run([&]() -> int {
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(emit_level_kernel<P, EMIT_PEAK>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(emit_level_kernel<P, EMIT_RESCALED>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(emit_level_kernel<A, EMIT_PEAK>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        WT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(emit_level_kernel<A, EMIT_RESCALED>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+        return 0;
+    })) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the peaks lie behind the descriptors' place in the workspace (which a call of up to 64 clips leaves unused)
+    unsigned* peaks = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + (size_t)B * sizeof(EmitClip));
+    hipLaunchKernelGGL(emit_zero_peaks_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, peaks, (int)B);
+    dim3 grid((unsigned)blocks, (unsigned)B);
+    if (int rc = launch_ragged<EMIT_ARG_CLIPS>("wt_emit_rescaled", dev.data(), B, 128, workspace, s, [&](auto d) {
+        hipLaunchKernelGGL((emit_level_kernel<decltype(d), EMIT_PEAK>), grid, dim3(256), smem, s, d, peaks);
+        hipLaunchKernelGGL((emit_level_kernel<decltype(d), EMIT_RESCALED>), grid, dim3(256), smem, s, d, peaks);
     })) return rc;
     WT_HIP_CHECK(hipGetLastError());
     return WT_OK;

@@ -647,7 +647,8 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         return self._guarded(dev, lambda: self._encode(B, T, audio, self._graph_flags(B), dev, want_emb), self._is_strict(B))
 
     @torch.inference_mode()
-    def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None, n_q: Optional[int] = None) -> torch.Tensor:
+    def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None, n_q: Optional[int] = None, normalize: Optional[str] = None,
+                     target_db: float = 0.0, return_scales: bool = False):
         """encode_infer(audio_input, bandwidth_id=...)[1], the same bits, for a caller that wants the codes alone: (B, T) fp32 at
         the codec rate -> (1, B, L) int64.  A call that is not graph-replayed passes no feature buffer to the library (nothing
         gathers or writes the (B, 512, L) tensor); a graph-replayed one shares encode_infer's recording and staging buffers.
@@ -655,8 +656,25 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         n_q, an int in [1, num_quantizers]: residual VQ with the first n_q codebooks (the reference's quantizer.encode on the
         encoder output: nearest row of codebook k to the residual, subtract, next codebook) -> (n_q, B, L), on a plan of its own
         (WT_PLAN_FLAG_RVQ); the rows of n_q = K are the first K rows of n_q = K + 1, row 0 is the n_q=None result.  Anything
-        else raises WavTokError or ValueError before any GPU work."""
+        else raises WavTokError or ValueError before any GPU work.
+        normalize="peak" or "rms" (target_db, a peak target in dB, with "peak" alone): every clip is level-normalised first, the
+        codes the bits of encode_codes(audio.normalize(audio_input, normalize, target_db)[0], ...); return_scales=True then returns
+        (codes, scales (B,) fp32 on the device), the divisors, for decode_pcm(scales=...).  A target_db without "peak", an unknown
+        mode and return_scales without normalize raise ValueError before any GPU work."""
+        from . import audio as _audio
         self._check_bandwidth(bandwidth_id)
+        norm = _audio.normalize_args("encode_codes", normalize, target_db)
+        if norm is not None or return_scales:
+            if norm is None:
+                raise ValueError("encode_codes: return_scales needs normalize")
+            if n_q is not None:
+                n_q = self._check_n_q("encode_codes", n_q)
+            assert audio_input.dim() == 2, "expected audio of shape (B, T)"
+            dev = self._ensure_engine()
+            rows = self._as_input(audio_input, dev).clone()
+            scales = _audio.normalize_rows(rows, [rows.shape[1]] * rows.shape[0], *norm)
+            codes = self.encode_codes(rows, n_q=n_q)
+            return (codes, scales) if return_scales else codes
         if n_q is not None:
             n_q = self._check_n_q("encode_codes", n_q)
             assert audio_input.dim() == 2, "expected audio of shape (B, T)"
@@ -746,7 +764,8 @@ class WavTokenizer(_BatchedCalls, nn.Module):
 
     @torch.inference_mode()
     def decode_pcm(self, codes: torch.Tensor, sample_rate: Optional[int] = None, channels: int = 1, dtype: torch.dtype = torch.int16,
-                   channels_last: bool = False, limit: float = 0.99, bandwidth_id=None) -> torch.Tensor:
+                   channels_last: bool = False, limit: float = 0.99, bandwidth_id=None, rescale: bool = False,
+                   scales: Optional[torch.Tensor] = None) -> torch.Tensor:
         """decode_codes, then every clip resampled from the codec rate to sample_rate (default: the codec rate), expanded to
         `channels` (1, or 2: both channels carry the same samples, convert_audio's expand) and stored as fp32 or, clamped to
         [-limit, limit] and rounded like audio.to_pcm16, as int16: codes (K, L) or (K, B, L) -> (B, channels, n_out) or, with
@@ -756,7 +775,11 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         the bits of audio.to_pcm16(R, limit=limit).  A code outside the codebook follows set_check_codes as in decode_codes; an
         int16 result no longer shows the NaN marker of a bad code (a NaN is clamped like any sample), so under "off" nothing
         reports it.  set_gemm_precision("f16") applies as to decode_codes.  Argument errors raise ValueError before any GPU
-        work."""
+        work.
+        rescale=True: save_audio's rescale (encoder/utils.py:95-103) per clip instead of the clamp, on the GPU (wt_emit_rescaled,
+        two launches): clip b is the bits of audio.to_pcm16(R[b], rescale=True, limit=limit) (int16) or of R[b] times
+        min(limit / max |R[b]|, 1) (fp32).  scales: (B,) from encode_codes(return_scales=True): row b of the decoded audio is
+        multiplied by scales[b] in front of the emit (wt_scale_rows)."""
         from . import audio
         if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)):
             raise ValueError("decode_pcm: channels must be 1 or 2")
@@ -768,11 +791,14 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         B, L = (1 if codes.dim() == 2 else int(codes.shape[1])), int(codes.shape[-1])
         n_in = self._wave_len(L)
         n_out = audio.resampled_length(self.codec_rate, rate, n_in)
+        scales = self._check_scales("decode_pcm", scales, B)
         wav = self._run_decode_codes(codes, bandwidth_id, borrow=True)                      # (raises for a clip without samples)
         dev = wav.device
+        if scales is not None:
+            self._scale_rows(list(wav), [n_in] * B, scales, dev)
         out = torch.empty((B, n_out, C) if channels_last else (B, C, n_out), dtype=fmt[0], device=dev)
         spec = _PcmSpec(None, L, rate, n_in, n_out, C)
-        self._emit_rows(list(wav), [spec] * B, out.view(-1), [b * n_out * C for b in range(B)], fmt, bool(channels_last), dev)
+        self._emit_rows(list(wav), [spec] * B, out.view(-1), [b * n_out * C for b in range(B)], fmt, bool(channels_last), dev, bool(rescale))
         return out
 
     def _run_head(self, x: torch.Tensor) -> torch.Tensor:

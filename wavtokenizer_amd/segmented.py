@@ -10,7 +10,7 @@ differ from the codes of the whole recording by construction: each segment start
 state."""
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -61,12 +61,15 @@ class SegmentedCodes:
         length           samples of the recording at the codec rate
         segment_length   samples of a full segment
         stride           samples between the starts of two segments
+        scales           None, or fp32 (n_seg,): the divisor each segment was normalised by before it was encoded
+                         (encode_codes_segmented(normalize=...), Encodec's (codes, scale) frames); decode_pcm_segmented multiplies
+                         segment i's decoded samples by scales[i] before the cross-fade
 
     Built by WavTokenizer.encode_codes_segmented(_many), or by hand from a caller's own codes (a language model's output): the
     constructor takes the flat form, from_segments the list form.  validate(arch) is what decode_pcm_segmented checks."""
-    __slots__ = ("codes", "offsets", "length", "segment_length", "stride")
+    __slots__ = ("codes", "offsets", "length", "segment_length", "stride", "scales")
 
-    def __init__(self, codes: torch.Tensor, offsets, length: int, segment_length: int, stride: int):
+    def __init__(self, codes: torch.Tensor, offsets, length: int, segment_length: int, stride: int, scales: Optional[torch.Tensor] = None):
         if not isinstance(codes, torch.Tensor) or codes.dim() != 1 or codes.is_floating_point() or codes.is_complex() or codes.dtype == torch.bool:
             raise ValueError("SegmentedCodes: codes must be a flat integer tensor")
         offsets = torch.as_tensor(offsets, dtype=torch.int64, device="cpu")
@@ -74,11 +77,15 @@ class SegmentedCodes:
             raise ValueError("SegmentedCodes: offsets must be a 1-D tensor of n_seg + 1 entries")
         self.codes, self.offsets = codes, offsets
         self.length, self.segment_length, self.stride = _int(length, "length"), _int(segment_length, "segment_length"), _int(stride, "stride")
+        if scales is not None and (not isinstance(scales, torch.Tensor) or scales.dim() != 1 or not scales.is_floating_point()):
+            raise ValueError("SegmentedCodes: scales must be None or a 1-D floating-point tensor, one entry per segment")
+        self.scales = scales
 
     @classmethod
-    def from_segments(cls, segments: Sequence[torch.Tensor], length: int, segment_length: int, stride: int) -> "SegmentedCodes":
+    def from_segments(cls, segments: Sequence[torch.Tensor], length: int, segment_length: int, stride: int,
+                      scales: Optional[torch.Tensor] = None) -> "SegmentedCodes":
         """The list form: segments[i] holds segment i's codes as (L_i,), (1, L_i) or (1, 1, L_i); they are copied into one flat
-        tensor."""
+        tensor.  scales: None, or the segments' scales as one tensor (n_seg,) or a sequence of one-element tensors / numbers."""
         segments = list(segments)
         if not segments:
             raise ValueError("SegmentedCodes: no segments")
@@ -90,7 +97,11 @@ class SegmentedCodes:
         offsets = [0]
         for s in flat:
             offsets.append(offsets[-1] + int(s.numel()))
-        return cls(torch.cat(flat), offsets, length, segment_length, stride)
+        if scales is not None and not isinstance(scales, torch.Tensor):
+            scales = list(scales)
+            scales = (torch.cat([v.reshape(-1).to(torch.float32) for v in scales]) if scales and isinstance(scales[0], torch.Tensor)
+                      else torch.tensor(scales, dtype=torch.float32))
+        return cls(torch.cat(flat), offsets, length, segment_length, stride, scales)
 
     @property
     def n_segments(self) -> int:
@@ -103,7 +114,7 @@ class SegmentedCodes:
 
     def validate(self, arch) -> Tuple[List[int], List[int], List[int]]:
         """check_geometry(arch, length, segment_length, stride), after checking that offsets are the prefix sums of its frames and
-        that codes holds exactly that many: ValueError otherwise."""
+        that codes holds exactly that many and scales, when given, one entry per segment: ValueError otherwise."""
         offsets, lengths, frames = check_geometry(arch, self.length, self.segment_length, self.stride)
         want = [0]
         for L in frames:
@@ -112,8 +123,11 @@ class SegmentedCodes:
             raise ValueError("SegmentedCodes: offsets contradict segment_plan(length, segment_length, stride) under this architecture")
         if int(self.codes.numel()) != want[-1]:
             raise ValueError("SegmentedCodes: codes does not hold offsets[-1] entries")
+        if self.scales is not None and int(self.scales.numel()) != len(frames):
+            raise ValueError("SegmentedCodes: scales does not hold one entry per segment")
         return offsets, lengths, frames
 
     def __repr__(self) -> str:
         return (f"SegmentedCodes(n_segments={self.n_segments}, length={self.length}, segment_length={self.segment_length}, "
-                f"stride={self.stride}, codes={tuple(self.codes.shape)} on {self.codes.device})")
+                f"stride={self.stride}, codes={tuple(self.codes.shape)} on {self.codes.device}"
+                + ("" if self.scales is None else f", scales={tuple(self.scales.shape)} on {self.scales.device}") + ")")

@@ -854,6 +854,55 @@ int    wt_normalize_rows(float* rows, int32_t B, int64_t T_pad, const int64_t* n
  * DEVICE arrays; max_len >= every lens[f] sizes the grid.  Nothing is written past rows[f][lens[f] - 1]. */
 int wt_scale_rows(float* const* rows, const int64_t* lens, const float* scales, int32_t F, int64_t max_len, void* stream);
 
+/* ---- integrated loudness in LUFS (ITU-R BS.1770-4 / EBU R 128) ----------------------------------------------------------------
+ *
+ * K-weighting: two cascaded biquads per channel, coefficients computed in double for the integer rate fs:
+ *   high shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *     Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2; b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],
+ *     a = [1, 2 (K^2 - 1) / a0, (1 - K / Q + K^2) / a0];
+ *   high pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1], a = [1, 2 (K^2 - 1) / (1 + K / Q + K^2),
+ *     (1 - K / Q + K^2) / (1 + K / Q + K^2)]  (at 48 kHz the table of BS.1770-4).
+ * The filter starts from zero state at sample 0.  Block j covers samples [floor(j fs / 10), floor((j + 4) fs / 10)) in integer
+ * arithmetic (400 ms, step 100 ms); only complete blocks count: J = the number of j with floor((j + 4) fs / 10) <= n.  z_j = the sum
+ * over the channels (weight 1.0 each) of the mean square of the filtered block, l_j = -0.691 + 10 log10 z_j.  Absolute gate: blocks
+ * with l_j > -70; relative threshold G = -0.691 + 10 log10(mean z over those) - 10; integrated loudness L = -0.691 + 10 log10(mean
+ * z over the blocks with l_j > -70 and l_j > G).  J = 0 or no block through the gates: L = -inf.
+ * The recurrence and every sum run in fp64 on the device, in an order that depends on n and fs alone: a clip has the same bits
+ * alone, at any position of any batch and whatever the grid.  Parity with other implementations of the standard is not pinned. */
+typedef struct {
+    const float* x;                   /* device: channels planes of n samples */
+    int64_t n;
+    int32_t channels;                 /* 1 or 2 */
+    int64_t channel_stride;           /* floats between the planes (>= n; read with 2 channels only) */
+    float* out;                       /* device [3]: L, the relative threshold (-inf when L is), the blocks through both gates */
+    float* blocks;                    /* device, nullable: receives the J values l_j (the momentary loudness) */
+} wt_loudness_clip;
+/* Samples per lane of the chunked evaluation (the lengths at which a clip gains a chunk or a wave of 64 chunks). */
+int32_t wt_loudness_chunk(void);
+/* J of the definition above, on the host (no device call); 0 for n < 1 or a rate outside [8000, 192000]. */
+int64_t wt_loudness_blocks(int64_t n, int32_t sample_rate);
+/* The K-weighting of the definition above, on the host (no device call): out[0..5) = b0 b1 b2 a1 a2 of the high shelf, out[5..10)
+ * the same of the high pass.  A rate outside [8000, 192000] or a null out returns WT_ERR_INVALID. */
+int     wt_kweight_coefficients(int32_t sample_rate, double* out);
+/* Ragged loudness measurement by the definition above, one rate per call.  clips is a HOST array; x, out and blocks are device
+ * pointers, 4-byte aligned.  Up to 64 descriptors travel in the launches' argument blocks, more go through workspace (device,
+ * wt_loudness_workspace_bytes(B, total_samples) bytes with total_samples >= the sum of the clips' n * channels, 8-byte aligned),
+ * which also holds the chunks' states and partial sums.  B outside [1, 65535], a rate outside [8000, 192000], n < 1, channels other
+ * than 1 or 2, a null or misaligned pointer returns WT_ERR_INVALID before any device call.  Four launches. */
+size_t  wt_loudness_workspace_bytes(int32_t B, int64_t total_samples);
+int     wt_loudness(const wt_loudness_clip* clips, int32_t B, int32_t sample_rate, void* workspace, void* stream);
+
+/* wt_normalize_rows' third measure: rows [B][T_pad] (device, mono), row b has n[b] valid samples (n: a HOST array, each in
+ * [1, T_pad]); columns from n[b] on are neither read nor written.  L is row b's integrated loudness by the definition above,
+ * rounded to fp32 as wt_loudness reports it; d = fp32(10^((L - target_lufs) / 20)), y = x / d (IEEE division, one rounding per
+ * sample), scales[b] = d (device, fp32).  A row with L = -inf (shorter than 400 ms, silent, or all of it under -70) is left as it
+ * is, bit for bit, with d = 1.  There is no limiter: a quiet row with one loud click can exceed +-1 after the gain.  A non-finite
+ * target returns WT_ERR_INVALID like the refusals of wt_loudness, before any device call.  workspace:
+ * wt_normalize_rows_lufs_workspace_bytes(B, T_pad) bytes, 8-byte aligned.  Five launches. */
+size_t wt_normalize_rows_lufs_workspace_bytes(int32_t B, int64_t T_pad);
+int    wt_normalize_rows_lufs(float* rows, int32_t B, int64_t T_pad, const int64_t* n, int32_t sample_rate, double target_lufs,
+                              float* scales, void* workspace, void* stream);
+
 /* Replaces: _linear_overlap_add (encoder/utils.py:17-56), bit for bit: frames [n_frames][rows][frame_len] (the last
  * one holds last_len valid samples), weight [frame_len] = the reference's triangle 0.5 - |linspace(0,1,len+2)[1:-1] - 0.5|,
  * out [rows][stride * (n_frames - 1) + last_len]. */

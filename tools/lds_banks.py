@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """LDS bank-conflict model of gfx950 (MI355X_MICROARCH.md, section LDS) applied to the access patterns of the fused encoder
-kernels (resblock16.hip): python3 tools/lds_banks.py; of the frame transforms with `mel`, `stoi` or `stftd` as the argument, of the YIN kernel with `pitch`.  For every pattern it prints the LDS-array cycles per
+kernels (resblock16.hip): python3 tools/lds_banks.py; of the frame transforms with `mel`, `stoi` or `stftd` as the argument, of the YIN kernel with `pitch`, of the K-weighting walk with `loudness`.  For every pattern it prints the LDS-array cycles per
 wave-instruction against the conflict-free count (SQ_LDS_BANK_CONFLICT counts the difference).  No GPU needed.
 
 Model: a wave64 access is served in fixed lane groups, one LDS cycle per group when no two lanes of the group need
@@ -213,7 +213,22 @@ def pitch_yin():
     report("x[j + lag] at six lags per lane: word j + 1 + 6 lane", "ds_read_b32", lambda l, j: 4 * (j + 1 + 6 * l), list(range(8)))
 
 
+# ------------------------------------------------------------------------------- loudness.hip: the staged tile of the two walks
+def loudness_walk():
+    print("--- loud_walk_kernel (loudness.hip): 64 rows (one per lane's chunk) of 32 staged columns, per wave-instruction")
+    extra = 0
+    extra += report("stage: word 33 (2 i + lane / 32) + lane % 32", "ds_write_b32", lambda l, i: 4 * (33 * (2 * i + (l >> 5)) + (l & 31)),
+                    list(range(32)))
+    extra += report("walk: word 33 lane + t", "ds_read_b32", lambda l, t: 4 * (33 * l + t), list(range(32)))
+    print(f"      extra LDS cycles (above the conflict-free count) summed over the listed variants: {extra}")
+    print("    for comparison, rows at a pitch of 32 words:")
+    report("walk: word 32 lane + t", "ds_read_b32", lambda l, t: 4 * (32 * l + t), list(range(32)))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["loudness"]:
+        loudness_walk()
+        sys.exit(0)
     if sys.argv[1:] == ["pitch"]:
         pitch_yin()
         sys.exit(0)

@@ -36,6 +36,8 @@ EXPORTS = [
     "wt_pitch_create", "wt_pitch_destroy", "wt_pitch_frames", "wt_pitch_tables", "wt_pitch_workspace_bytes", "wt_pitch_track", "wt_pitch_pairs",
     "wt_level_chunk", "wt_level_workspace_bytes", "wt_level", "wt_normalize_rows_workspace_bytes", "wt_normalize_rows", "wt_scale_rows",
     "wt_emit_rescaled_workspace_bytes", "wt_emit_rescaled",
+    "wt_loudness_chunk", "wt_loudness_blocks", "wt_kweight_coefficients", "wt_loudness_workspace_bytes", "wt_loudness",
+    "wt_normalize_rows_lufs_workspace_bytes", "wt_normalize_rows_lufs",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -183,11 +185,18 @@ class WtEmitClip(ctypes.Structure):
 
 
 WT_NORM_PEAK, WT_NORM_RMS = 0, 1
+WT_NORM_LUFS = 2                 # (Python side only: audio.normalize_rows routes it to wt_normalize_rows_lufs)
 
 
 class WtLevelClip(ctypes.Structure):
     """wt_level_clip: one clip of a level measurement (wt_level)."""
     _fields_ = [("x", c_void_p), ("n", c_int64), ("out", c_void_p)]
+
+
+class WtLoudnessClip(ctypes.Structure):
+    """wt_loudness_clip: one clip of a loudness measurement (wt_loudness)."""
+    _fields_ = [("x", c_void_p), ("n", c_int64), ("channels", c_int32), ("channel_stride", c_int64), ("out", c_void_p),
+                ("blocks", c_void_p)]
 
 
 class WtOverlapAddClip(ctypes.Structure):
@@ -432,6 +441,18 @@ def _load() -> ctypes.CDLL:
     lib.wt_emit_rescaled_workspace_bytes.argtypes = [c_int32]
     lib.wt_emit_rescaled_workspace_bytes.restype = c_size_t
     lib.wt_emit_rescaled.argtypes = [POINTER(WtEmitClip), c_int32, c_void_p, c_void_p]
+    lib.wt_loudness_chunk.argtypes = []
+    lib.wt_loudness_chunk.restype = c_int32
+    lib.wt_loudness_blocks.argtypes = [c_int64, c_int32]
+    lib.wt_loudness_blocks.restype = c_int64
+    lib.wt_kweight_coefficients.argtypes = [c_int32, POINTER(ctypes.c_double)]
+    lib.wt_loudness_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_loudness_workspace_bytes.restype = c_size_t
+    lib.wt_loudness.argtypes = [POINTER(WtLoudnessClip), c_int32, c_int32, c_void_p, c_void_p]
+    lib.wt_normalize_rows_lufs_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_normalize_rows_lufs_workspace_bytes.restype = c_size_t
+    lib.wt_normalize_rows_lufs.argtypes = [c_void_p, c_int32, c_int64, POINTER(c_int64), c_int32, ctypes.c_double, c_void_p, c_void_p,
+                                           c_void_p]
     return lib
 
 

@@ -6,6 +6,8 @@
     segment_offsets(length, segment_length, stride)      encoder/model.py:133-145 (the frame offsets of EncodecModel.encode)
     level(wav), level_many(wavs)                         peak and rms per clip (wt_level)
     normalize(wav, mode="peak" | "rms", target_db=0.0)   extract_features.py:27-28 / encoder/model.py:153-156 (wt_normalize_rows)
+    loudness(wav, sample_rate), loudness_many(wavs, ...) integrated loudness in LUFS, ITU-R BS.1770-4 / EBU R 128 (wt_loudness)
+    normalize(wav, mode="lufs", target_lufs=-23.0)       to a loudness target (wt_normalize_rows_lufs)
 
 All take and return torch tensors on the GPU; there is no CPU fallback.  Recordings of any length, from and to PCM, with codes in
 between: WavTokenizer.encode_codes_segmented(_many) / decode_pcm_segmented(_many) (wavtokenizer_amd/segmented.py)."""
@@ -123,57 +125,140 @@ def level(wav: torch.Tensor) -> torch.Tensor:
     return level_many([wav.reshape(-1)])[0]
 
 
-def normalize_args(who: str, normalize, target_db) -> Optional[Tuple[int, float]]:
-    """The (mode, gain) of a call's normalize / target_db arguments, None without normalisation; ValueError, before any GPU work,
-    for a mode other than "peak" and "rms" and for a target_db given without "peak" (the rms mode is Encodec's: it has no
-    target)."""
+def loudness_many(wavs: Sequence[torch.Tensor], sample_rate=24000, momentary: bool = False):
+    """Integrated loudness of every clip (ITU-R BS.1770-4 / EBU R 128 as include/wavtokenizer_amd.h states it: K-weighting for
+    the clip's rate, 400 ms blocks on a 100 ms grid, an absolute gate at -70 LUFS and a relative gate 10 LU under the mean).  wavs
+    is a sequence of non-empty fp32 tensors on one GPU, (T,) or planar (C, T) with C <= 2 (channel weights 1.0); sample_rate is
+    one rate or one per clip, each in [8000, 192000].  Returns (n, 3) fp32 there, row i = (L in LUFS, the relative threshold, the
+    blocks through both gates); a clip shorter than 400 ms, silent or all of it under -70 LUFS reads (-inf, -inf, 0).
+    momentary=True returns (that, [l_j (J_i,) fp32 per clip]), the loudness of every 400 ms block.  The clips are grouped by rate:
+    one wt_loudness call (four launches) per rate.  The recurrence and the sums run in fp64 on the GPU; a clip has the same bits
+    alone and in any batch.  Parity with pyloudnorm or ffmpeg is not pinned: neither was on hand to compare with."""
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError("loudness_many takes at least one clip")
+    if isinstance(sample_rate, (list, tuple)):
+        rates = list(sample_rate)
+        if len(rates) != len(wavs):
+            raise ValueError("loudness_many: one sample rate per clip")
+    else:
+        rates = [sample_rate] * len(wavs)
+    for r in rates:
+        if isinstance(r, bool) or not isinstance(r, int) or not 8000 <= r <= 192000:
+            raise ValueError("loudness_many: sample rates are ints in [8000, 192000]")
+    for w in wavs:
+        if (not isinstance(w, torch.Tensor) or w.dim() not in (1, 2) or w.shape[-1] < 1 or w.dtype != torch.float32
+                or (w.dim() == 2 and w.shape[0] not in (1, 2))):
+            raise ValueError("loudness_many takes a sequence of non-empty fp32 tensors (T,) or (C, T) with C <= 2")
+    for w in wavs:
+        _need_gpu(w, _GPU_ONLY)
+    dev = wavs[0].device
+    if any(w.device != dev for w in wavs):
+        raise ValueError("loudness_many: the clips lie on different devices")
+    wavs = [w.contiguous() for w in wavs]
+    out = torch.empty((len(wavs), 3), dtype=torch.float32, device=dev)
+    blocks: List[Optional[torch.Tensor]] = [None] * len(wavs)
+    if momentary:
+        counts = [int(lib.wt_loudness_blocks(int(w.shape[-1]), r)) for w, r in zip(wavs, rates)]
+        flat = torch.empty(sum(counts), dtype=torch.float32, device=dev)
+        pos = 0
+        for i, c in enumerate(counts):
+            blocks[i] = flat[pos:pos + c]
+            pos += c
+    with torch.cuda.device(dev):
+        for rate in sorted(set(rates)):
+            idx = [i for i, r in enumerate(rates) if r == rate]
+            descs = (_capi.WtLoudnessClip * len(idx))()
+            for d, i in zip(descs, idx):
+                w = wavs[i]
+                d.x, d.n, d.channels, d.channel_stride = w.data_ptr(), int(w.shape[-1]), (1 if w.dim() == 1 else int(w.shape[0])), int(w.shape[-1])
+                d.out = out.data_ptr() + 12 * i
+                d.blocks = blocks[i].data_ptr() if momentary and blocks[i].numel() else None
+            ws = torch.empty(int(lib.wt_loudness_workspace_bytes(len(idx), sum(wavs[i].numel() for i in idx))), dtype=torch.uint8, device=dev)
+            check(lib.wt_loudness(descs, len(idx), int(rate), _ptr(ws), _stream(dev)), "wt_loudness")
+    return (out, blocks) if momentary else out
+
+
+def loudness(wav: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
+    """loudness_many for one clip, (T,) or (C, T) with C <= 2: (3,) fp32 = (L in LUFS, relative threshold, gated blocks)."""
+    return loudness_many([wav], sample_rate)[0]
+
+
+def normalize_args(who: str, normalize, target_db, target_lufs=None) -> Optional[Tuple[int, float]]:
+    """The (mode, gain) of a call's normalize / target_db / target_lufs arguments, None without normalisation; for "lufs" the
+    pair is (WT_NORM_LUFS, the target), -23.0 where target_lufs is None (not given).  ValueError, before any GPU work, for a mode other than "peak", "rms" and "lufs", for a
+    target_db given without "peak" (the rms mode is Encodec's: it has no target), for a target_lufs given without "lufs", and for
+    a target that is no finite number."""
     if isinstance(target_db, bool) or not isinstance(target_db, (int, float)) or not math.isfinite(target_db):
         raise ValueError(who + ": target_db must be a finite number")
+    if target_lufs is not None:
+        if isinstance(target_lufs, bool) or not isinstance(target_lufs, (int, float)) or not math.isfinite(target_lufs):
+            raise ValueError(who + ": target_lufs must be a finite number")
+        if normalize != "lufs":
+            raise ValueError(who + ": target_lufs needs normalize='lufs'")
     if normalize is None:
         if target_db != 0.0:
             raise ValueError(who + ": target_db needs normalize='peak'")
         return None
     if normalize == "peak":
         return _capi.WT_NORM_PEAK, float(np.float32(10.0 ** (float(target_db) / 20.0)))
-    if normalize == "rms":
+    if normalize == "rms" or normalize == "lufs":
         if target_db != 0.0:
             raise ValueError(who + ": target_db applies to normalize='peak' only")
-        return _capi.WT_NORM_RMS, 1.0
-    raise ValueError(who + ": normalize must be None, 'peak' or 'rms'")
+        return (_capi.WT_NORM_RMS, 1.0) if normalize == "rms" else (_capi.WT_NORM_LUFS, -23.0 if target_lufs is None else float(target_lufs))
+    raise ValueError(who + ": normalize must be None, 'peak', 'rms' or 'lufs'")
 
 
-def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float) -> torch.Tensor:
+def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float, sample_rate: Optional[int] = None) -> torch.Tensor:
     """wt_normalize_rows on rows, a contiguous (B, T_pad) fp32 tensor on the GPU, in place: row b's first n[b] samples are divided
-    by their level (+ 1e-8); returns the divisors (B,) fp32."""
+    by their level (+ 1e-8); returns the divisors (B,) fp32.  mode WT_NORM_LUFS goes to wt_normalize_rows_lufs instead, gain then
+    being the target in LUFS and sample_rate the rows' rate (the model's codec rate, for the tokenising calls), which that mode
+    needs."""
     B, T_pad = rows.shape
     assert rows.dtype == torch.float32 and rows.is_contiguous() and len(n) == B
     dev = rows.device
     scales = torch.empty(B, dtype=torch.float32, device=dev)
+    lens = (ctypes.c_int64 * B)(*[int(v) for v in n])
+    if mode == _capi.WT_NORM_LUFS:
+        if sample_rate is None:
+            raise ValueError("normalize_rows: WT_NORM_LUFS needs the rows' sample_rate")
+        ws = torch.empty(int(lib.wt_normalize_rows_lufs_workspace_bytes(B, T_pad)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.wt_normalize_rows_lufs(_ptr(rows), B, T_pad, lens, int(sample_rate), float(gain), _ptr(scales), _ptr(ws),
+                                             _stream(dev)), "wt_normalize_rows_lufs")
+        return scales
     ws = torch.empty(int(lib.wt_normalize_rows_workspace_bytes(B, T_pad)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        check(lib.wt_normalize_rows(_ptr(rows), B, T_pad, (ctypes.c_int64 * B)(*[int(v) for v in n]), int(mode), float(gain), _ptr(scales),
+        check(lib.wt_normalize_rows(_ptr(rows), B, T_pad, lens, int(mode), float(gain), _ptr(scales),
                                     _ptr(ws), _stream(dev)), "wt_normalize_rows")
     return scales
 
 
-def normalize(wav: torch.Tensor, mode: str = "peak", target_db: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+def normalize(wav: torch.Tensor, mode: str = "peak", target_db: float = 0.0, *, target_lufs: Optional[float] = None,
+              sample_rate: int = 24000) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-clip level normalisation of mono audio: wav is (T,), (B, T) or (B, 1, T) on the GPU; returns (wav / scale, scale), the
     first in wav's shape, scale (B,) fp32 (a 0-d tensor for (T,)).
       mode="peak": scale = max |x| + 1e-8, the bits of torch's fp32 x / (x.abs().max() + 1e-8) (extract_features.py:27-28); with
         target_db the quotient is multiplied by 10^(target_db / 20) rounded to fp32 (a peak target: -3 is the data preparation's).
       mode="rms":  scale = 1e-8 + sqrt(mean x^2), EncodecModel._encode_frame's (encoder/model.py:153-156).
+      mode="lufs": scale = fp32(10^((L - target_lufs) / 20)), target_lufs -23.0 when not given, with L = loudness(x, sample_rate)[0], the integrated loudness (ITU-R
+        BS.1770-4) at sample_rate, a rate in [8000, 192000]; the result then reads target_lufs.  A clip without a loudness
+        (shorter than 400 ms, silent, or all of it under -70 LUFS) is returned as it is, bit for bit, with scale 1.  There is no
+        limiter: a quiet clip with one loud click can exceed +-1 after the gain.
     A silent clip stays zeros.  This is the one-clip definition the batched calls (encode_codes_many(normalize=...)) are compared
     with.  The audio is taken as it is: the reference's scripts normalise after convert_audio, sox's `norm` before the resampling,
-    and a peak moves under resampling; parity with sox is not claimed.  Loudness in LUFS is not offered."""
-    args = normalize_args("normalize", mode, target_db)
+    and a peak moves under resampling; parity with sox is not claimed, nor with pyloudnorm or ffmpeg for "lufs"."""
+    args = normalize_args("normalize", mode, target_db, target_lufs)
     if args is None:
-        raise ValueError("normalize: mode must be 'peak' or 'rms'")
+        raise ValueError("normalize: mode must be 'peak', 'rms' or 'lufs'")
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or not 8000 <= sample_rate <= 192000:
+        raise ValueError("normalize: sample_rate is an int in [8000, 192000]")
     if not isinstance(wav, torch.Tensor) or wav.dim() not in (1, 2, 3) or (wav.dim() == 3 and wav.shape[1] != 1) or wav.numel() < 1:
         raise ValueError("normalize takes non-empty mono audio (T,), (B, T) or (B, 1, T)")
     _need_gpu(wav, _GPU_ONLY)
     T = int(wav.shape[-1])
     rows = wav.to(torch.float32).reshape(-1, T).clone()
-    scales = normalize_rows(rows, [T] * rows.shape[0], *args)
+    scales = normalize_rows(rows, [T] * rows.shape[0], *args, sample_rate=sample_rate)
     return rows.view(wav.shape), (scales[0] if wav.dim() == 1 else scales)
 
 

@@ -262,7 +262,7 @@ class _BatchedCalls:
             check(lib.wt_ingest(descs, B, T_pad, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
             if norm is not None:
                 from . import audio
-                norm[3](audio.normalize_rows(buf, norm[2], norm[0], norm[1]))
+                norm[3](audio.normalize_rows(buf, norm[2], norm[0], norm[1], sample_rate=self.codec_rate))
 
         if n_q is not None:
             if lengths is None:
@@ -298,7 +298,7 @@ class _BatchedCalls:
             wav = self._ingest_rows(part, dev)
             if norm is not None:                             # (as _run_encode_codes_mixed: in place, behind the ingest)
                 from . import audio
-                norm[2](offs, audio.normalize_rows(wav, [sp.n_out for sp in part], norm[0], norm[1]))
+                norm[2](offs, audio.normalize_rows(wav, [sp.n_out for sp in part], norm[0], norm[1], sample_rate=self.codec_rate))
             for j, (sp, off) in enumerate(zip(part, offs)):
                 if n_q is not None:
                     codes = self.encode_codes(wav[j:j + 1, :sp.n_out], n_q=n_q)
@@ -332,7 +332,7 @@ class _BatchedCalls:
     @torch.inference_mode()
     def encode_codes_many(self, clips: Sequence[torch.Tensor], sample_rates=None, channels_last: bool = False, packed: bool = False,
                           bandwidth_id=None, n_q: Optional[int] = None, normalize: Optional[str] = None, target_db: float = 0.0,
-                          return_scales: bool = False):
+                          return_scales: bool = False, target_lufs: Optional[float] = None):
         """Tokenise a set of clips straight from PCM.  clips[i] is (T,), (C, T) or, with channels_last, (T, C), C in {1, 2}, fp32
         or int16 (scaled by 1 / 32768), on the CPU or on the model's device; sample_rates is one rate or one per clip (default:
         the codec rate).  Returns [codes (1, 1, L_i)] in input order, views into one flat int64 tensor, L_i =
@@ -354,11 +354,16 @@ class _BatchedCalls:
         resampling and a peak moves under resampling, so parity with sox is not claimed.  return_scales=True (with normalize)
         appends the divisors, (n,) fp32 on the model's device, to the result: (codes list, scales) or (flat, offsets, scales);
         decode_pcm_many(scales=...) multiplies them back in.  A target_db without "peak", an unknown mode and return_scales
-        without normalize raise ValueError before any GPU work."""
+        without normalize raise ValueError before any GPU work.
+        normalize="lufs" (target_lufs, default -23): every clip is brought to that integrated loudness (ITU-R BS.1770-4, measured
+        on its mono row at the codec rate; one wt_normalize_rows_lufs per group): clip i's codes are the bits of encode_infer(
+        audio.normalize(converted clip i, "lufs", target_lufs=...)[0])[1], its scale that call's.  A clip without a loudness
+        (under 400 ms after conversion, silent, all under -70 LUFS) is tokenised as it is with scale 1; there is no limiter.  A
+        target_lufs without "lufs" raises ValueError like the rest."""
         from . import audio
         from .mixed_length import group_clips
         self._check_bandwidth(bandwidth_id)
-        norm = audio.normalize_args("encode_codes_many", normalize, target_db)
+        norm = audio.normalize_args("encode_codes_many", normalize, target_db, target_lufs)
         if return_scales and norm is None:
             raise ValueError("encode_codes_many: return_scales needs normalize")
         if n_q is not None:
@@ -398,7 +403,7 @@ class _BatchedCalls:
     @torch.inference_mode()
     def encode_codes_segmented_many(self, clips: Sequence[torch.Tensor], segment_length: int, stride: int, sample_rates=None,
                                     channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None,
-                                    target_db: float = 0.0):
+                                    target_db: float = 0.0, target_lufs: Optional[float] = None):
         """Tokenise long recordings in overlapping segments (the reference's EncodecModel.encode, encoder/model.py:122-145).
         clips and sample_rates as encode_codes_many takes them (any rate, mono or stereo, planar or interleaved, fp32 or int16,
         on the CPU or on the model's device); segment_length and stride are samples at the codec rate, stride <= segment_length.
@@ -418,13 +423,14 @@ class _BatchedCalls:
         EncodecModel._encode_frame does with "rms" (encoder/model.py:147-165), one wt_normalize_rows per call between its ingest
         and its encode: segment i's codes are the bits of encode_codes(audio.normalize(W[None, off_i:off_i + len_i], normalize,
         target_db)[0]), and the divisors are kept as SegmentedCodes.scales, (n_segments,) fp32 on the model's device, for
-        decode_pcm_segmented to multiply back in."""
+        decode_pcm_segmented to multiply back in.  normalize="lufs" (target_lufs) brings every segment to that integrated
+        loudness in the same place; a segment under 400 ms (the last cut of a recording may be) passes as it is with scale 1."""
         from . import audio
         from .mixed_length import MAX_GROUP, group_clips
         from .segmented import SegmentedCodes, check_geometry, segment_plan
         who = "encode_codes_segmented_many"
         self._check_bandwidth(bandwidth_id)
-        norm = audio.normalize_args(who, normalize, target_db)
+        norm = audio.normalize_args(who, normalize, target_db, target_lufs)
         segment_plan(1, segment_length, stride)                 # (the geometry's own refusals, also for an empty list)
         specs = self._clip_specs(who, clips, sample_rates, channels_last)
         S, stride = int(segment_length), int(stride)
@@ -492,7 +498,7 @@ class _BatchedCalls:
                 if norm is None:
                     codes = self.encode_codes(seg)
                 else:
-                    codes, sc = self.encode_codes(seg, normalize=normalize, target_db=target_db, return_scales=True)
+                    codes, sc = self.encode_codes(seg, normalize=normalize, target_db=target_db, return_scales=True, target_lufs=target_lufs)
                     parts[k] = ([k], sc)
                 flat[seg_code[k]:seg_code[k] + codes.shape[-1]].copy_(codes.view(-1))
 
@@ -508,10 +514,11 @@ class _BatchedCalls:
 
     @torch.inference_mode()
     def encode_codes_segmented(self, clip: torch.Tensor, segment_length: int, stride: int, sample_rate: Optional[int] = None,
-                               channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None, target_db: float = 0.0):
+                               channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None, target_db: float = 0.0,
+                               target_lufs: Optional[float] = None):
         """encode_codes_segmented_many for one recording: its segmented.SegmentedCodes."""
         return self.encode_codes_segmented_many([clip], segment_length, stride, sample_rates=sample_rate, channels_last=channels_last,
-                                                bandwidth_id=bandwidth_id, normalize=normalize, target_db=target_db)[0]
+                                                bandwidth_id=bandwidth_id, normalize=normalize, target_db=target_db, target_lufs=target_lufs)[0]
 
     def _run_decode_mixed(self, feats: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None):
         """One mixed-length decode call (WT_PLAN_DECODE_MIXED) on clips (512, L_i) of 1 <= L_i <= L_pad frames: returns the

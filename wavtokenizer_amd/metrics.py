@@ -44,7 +44,10 @@ The frame grid (1024 / 160 at 16 kHz, not centred), the A-weighted loudness gate
 pitch estimator is YIN (de Cheveigne & Kawahara 2002) where the reference runs CREPE, whose weights are not available here, so the
 numbers are comparable between runs of this library and not with CREPE-based tables (include/wavtokenizer_amd.h gives the
 definition, tests/pitch_ref.py holds it in float64).  `calculate_periodicity_metrics(y, y_hat)` becomes
-`periodicity_metrics(y, y_hat, sample_rate)`."""
+`periodicity_metrics(y, y_hat, sample_rate)`.
+
+And the level: loudness_delta(y_hat, y, sample_rate), loudness_delta_many(y_hats, ys, sample_rate=...), the difference of the
+integrated loudness in LUFS (audio.loudness) of the decoded audio and its input, in LU."""
 import ctypes
 import math
 from typing import Dict, List, Sequence, Tuple, Union
@@ -625,3 +628,29 @@ def periodicity_metrics(y: torch.Tensor, y_hat: torch.Tensor, sample_rate: int =
             raise ValueError("periodicity_metrics: y and y_hat must be 1-D tensors")
     return periodicity_metrics_many([y], [y_hat], sample_rate=sample_rate, threshold=threshold, silence_threshold=silence_threshold,
                                     unvoiced_threshold=unvoiced_threshold)[0]
+
+
+# ---- loudness: did the decoded audio keep the level of the input? -------------------------------------------------------------
+def loudness_delta_many(y_hats: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], *, sample_rate: Union[int, Sequence[int]] = 24000) -> torch.Tensor:
+    """L(y_hat) - L(y) in LU per pair, L the integrated loudness of audio.loudness (ITU-R BS.1770-4 / EBU R 128; include/
+    wavtokenizer_amd.h gives the definition, parity with pyloudnorm is unpinned): (n,) fp32.  The clips are fp32 on the GPU, (T,) or
+    planar (C, T) with C <= 2; the two of a pair share a rate (sample_rate: one, or one per pair) and may differ in length.  One
+    audio.loudness_many call over both lists.  NaN where either side has no loudness (under 400 ms, silent, all under -70 LUFS)."""
+    from . import audio
+    y_hats, ys = list(y_hats), list(ys)
+    if len(y_hats) != len(ys):
+        raise ValueError("loudness_delta_many: as many estimates as references")
+    if not ys:
+        raise ValueError("loudness_delta_many takes at least one pair")
+    if isinstance(sample_rate, (list, tuple)):
+        if len(sample_rate) != len(ys):
+            raise ValueError("loudness_delta_many: one sample rate per pair")
+        sample_rate = list(sample_rate) * 2
+    L = audio.loudness_many(y_hats + ys, sample_rate)[:, 0]
+    a, b = L[:len(ys)], L[len(ys):]
+    return torch.where(torch.isinf(a) | torch.isinf(b), torch.full_like(a, float("nan")), a - b)
+
+
+def loudness_delta(y_hat: torch.Tensor, y: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
+    """0-dim fp32: loudness_delta_many for one pair."""
+    return loudness_delta_many([y_hat], [y], sample_rate=sample_rate)[0]

@@ -648,7 +648,7 @@ class WavTokenizer(_BatchedCalls, nn.Module):
 
     @torch.inference_mode()
     def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None, n_q: Optional[int] = None, normalize: Optional[str] = None,
-                     target_db: float = 0.0, return_scales: bool = False):
+                     target_db: float = 0.0, return_scales: bool = False, target_lufs: Optional[float] = None):
         """encode_infer(audio_input, bandwidth_id=...)[1], the same bits, for a caller that wants the codes alone: (B, T) fp32 at
         the codec rate -> (1, B, L) int64.  A call that is not graph-replayed passes no feature buffer to the library (nothing
         gathers or writes the (B, 512, L) tensor); a graph-replayed one shares encode_infer's recording and staging buffers.
@@ -660,10 +660,13 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         normalize="peak" or "rms" (target_db, a peak target in dB, with "peak" alone): every clip is level-normalised first, the
         codes the bits of encode_codes(audio.normalize(audio_input, normalize, target_db)[0], ...); return_scales=True then returns
         (codes, scales (B,) fp32 on the device), the divisors, for decode_pcm(scales=...).  A target_db without "peak", an unknown
-        mode and return_scales without normalize raise ValueError before any GPU work."""
+        mode and return_scales without normalize raise ValueError before any GPU work.
+        normalize="lufs" (target_lufs, default -23): every clip is brought to that integrated loudness (ITU-R BS.1770-4 at the
+        codec rate) as audio.normalize(audio_input, "lufs", target_lufs=...) does; a clip without a loudness (under 400 ms,
+        silent) passes as it is with scale 1.  A target_lufs without "lufs" raises ValueError like the rest."""
         from . import audio as _audio
         self._check_bandwidth(bandwidth_id)
-        norm = _audio.normalize_args("encode_codes", normalize, target_db)
+        norm = _audio.normalize_args("encode_codes", normalize, target_db, target_lufs)
         if norm is not None or return_scales:
             if norm is None:
                 raise ValueError("encode_codes: return_scales needs normalize")
@@ -672,7 +675,7 @@ class WavTokenizer(_BatchedCalls, nn.Module):
             assert audio_input.dim() == 2, "expected audio of shape (B, T)"
             dev = self._ensure_engine()
             rows = self._as_input(audio_input, dev).clone()
-            scales = _audio.normalize_rows(rows, [rows.shape[1]] * rows.shape[0], *norm)
+            scales = _audio.normalize_rows(rows, [rows.shape[1]] * rows.shape[0], *norm, sample_rate=self.codec_rate)
             codes = self.encode_codes(rows, n_q=n_q)
             return (codes, scales) if return_scales else codes
         if n_q is not None:

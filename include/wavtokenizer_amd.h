@@ -896,12 +896,87 @@ int     wt_loudness(const wt_loudness_clip* clips, int32_t B, int32_t sample_rat
  * [1, T_pad]); columns from n[b] on are neither read nor written.  L is row b's integrated loudness by the definition above,
  * rounded to fp32 as wt_loudness reports it; d = fp32(10^((L - target_lufs) / 20)), y = x / d (IEEE division, one rounding per
  * sample), scales[b] = d (device, fp32).  A row with L = -inf (shorter than 400 ms, silent, or all of it under -70) is left as it
- * is, bit for bit, with d = 1.  There is no limiter: a quiet row with one loud click can exceed +-1 after the gain.  A non-finite
+ * is, bit for bit, with d = 1.  There is no limiter: a quiet row with one loud click can exceed +-1 after the gain
+ * (wt_normalize_rows_lufs_tp below bounds the gain by the row's true peak).  A non-finite
  * target returns WT_ERR_INVALID like the refusals of wt_loudness, before any device call.  workspace:
  * wt_normalize_rows_lufs_workspace_bytes(B, T_pad) bytes, 8-byte aligned.  Five launches. */
 size_t wt_normalize_rows_lufs_workspace_bytes(int32_t B, int64_t T_pad);
 int    wt_normalize_rows_lufs(float* rows, int32_t B, int64_t T_pad, const int64_t* n, int32_t sample_rate, double target_lufs,
                               float* scales, void* workspace, void* stream);
+
+/* ---- the rest of an EBU R 128 meter: true peak, short-term loudness, loudness range ----------------------------------------------
+ *
+ * True peak (ITU-R BS.1770-4 Annex 2, by oversampling).  The factor is F = 4 for fs < 96000, 2 for 96000 <= fs < 192000 and 1 at
+ * 192000.  The interpolator is a Hann-windowed sinc of 49 taps, h[j] = sinc((j - 24) / F) * 0.5 (1 - cos(2 pi j / 48)) with
+ * sinc(t) = sin(pi t) / (pi t), computed in double on the host and rounded to fp32 (h[0] = h[48] = 0).  This is this project's
+ * definition: the construction libebur128 uses, not the 48-coefficient table of the standard, and pinned against neither.  Per
+ * channel, sample i in [0, n) and phase p in [1, F):  y = sum over k = 0 .. 48 / F - 1 of h[p + F k] * x[i + 24 / F - k], samples
+ * outside [0, n) being 0, accumulated in fp32 from 0 with one fmaf per tap, k ascending.  Phase 0 is |x[i]| itself, unfiltered.
+ * The true peak is the maximum of |.| over all phases, samples and channels: never below the sample peak, bit for bit; linear
+ * (dBTP = 20 log10 of it, -inf for silence).  A maximum is exact in any order: a clip has the same bits alone, at any position of
+ * any batch and at any alignment of its pointer.  Against the interpolation in exact arithmetic a value errs by at most
+ * (48 / F + 1) * 2^-24 * max_p sum_k |h[p + F k]| * max |x|.  At F = 1 the true peak is the sample peak.
+ *
+ * Short-term loudness (EBU Tech 3341) on the 100 ms grid of the loudness section: window j covers samples [floor(j fs / 10),
+ * floor((j + 30) fs / 10)), 3 s; only complete windows count: S = the number of j with floor((j + 30) fs / 10) <= n = max(J - 26, 0).
+ * z_j = the sum over the channels (weight 1.0 each) of the mean square of the K-weighted window, s_j = -0.691 + 10 log10 z_j, no
+ * gate.  A window's energy is the sum of its 30 segment sums (100 ms each, the ones the 400 ms blocks are made of, same bits),
+ * added in ascending order from the first, ((s0 + s1) + s2) + ... + s29, in fp64, per channel; the quotients by the window's
+ * length are then added in channel order.
+ *
+ * Loudness range (EBU Tech 3342) over the S short-term values on that 100 ms grid (Tech 3342 asks for at least 2 s of overlap;
+ * libebur128 steps by 1 s, ffmpeg by 100 ms; parity with either is not pinned).  Absolute gate: s_j > -70.  Relative gate:
+ * s_j > -0.691 + 10 log10(mean z over the absolutely gated) - 20.  Of the m energies through both, in ascending order, the ranks
+ * lo = ((m - 1) + 5) / 10 and hi = (19 (m - 1) + 10) / 20 (integer division: the nearest-rank 10 % and 95 % points) are selected
+ * exactly, whatever S.  LRA = l(z_hi) - l(z_lo) with l(z) = -0.691 + 10 log10 z in double, rounded to fp32.  m = 0 (a clip under
+ * 3 s, silent, or all of it under -70): LRA, low and high are NaN.  Sums run over fixed trees in fp64, no float atomics. */
+typedef struct {
+    const float* x;                   /* device: channels planes of n samples */
+    int64_t n;
+    int32_t channels;                 /* 1 or 2 */
+    int64_t channel_stride;           /* floats between the planes (>= n; read with 2 channels only) */
+    float* out;                       /* device [2]: true peak, sample peak (max |x|), both linear */
+} wt_true_peak_clip;
+/* Samples per workgroup of the true-peak kernel (the lengths at which a clip gains a tile). */
+int32_t wt_true_peak_tile(void);
+/* Ragged true-peak measurement by the definition above, one rate per call.  clips is a HOST array; x and out are device pointers,
+ * 4-byte aligned.  Up to 64 descriptors travel in the launches' argument blocks, more go through workspace (device,
+ * wt_true_peak_workspace_bytes(B, total_samples) bytes with total_samples >= the sum of the clips' n * channels, 8-byte aligned),
+ * which also holds one pair of maxima per tile.  out[1] has the bits of wt_level's peak.  B outside [1, 65535], a rate outside
+ * [8000, 192000], n < 1, channels other than 1 or 2, a null or misaligned pointer returns WT_ERR_INVALID before any device call.
+ * Two launches. */
+size_t  wt_true_peak_workspace_bytes(int32_t B, int64_t total_samples);
+int     wt_true_peak(const wt_true_peak_clip* clips, int32_t B, int32_t sample_rate, void* workspace, void* stream);
+
+typedef struct {
+    const float* x;                   /* device: channels planes of n samples */
+    int64_t n;
+    int32_t channels;                 /* 1 or 2 */
+    int64_t channel_stride;           /* floats between the planes (>= n; read with 2 channels only) */
+    float* out;                       /* device [9]: L, the relative threshold, the gated blocks (wt_loudness's triple, same bits); LRA,
+                                         the low and the high value in LUFS; the count m through the range gates; the maximum
+                                         momentary value; the maximum short-term value (-inf without one) */
+    float* momentary;                 /* device, nullable: receives the J values l_j */
+    float* short_term;                /* device, nullable: receives the S values s_j */
+} wt_loudness_range_clip;
+/* S of the definition above, on the host (no device call); 0 for n < 1 or a rate outside [8000, 192000]. */
+int64_t wt_short_term_blocks(int64_t n, int32_t sample_rate);
+/* Ragged measurement of integrated loudness, short-term loudness and loudness range, one rate per call, on one pass of the
+ * K-weighting.  Arguments, refusals and descriptor route as wt_loudness; workspace: wt_loudness_range_workspace_bytes(B,
+ * total_samples) bytes, 8-byte aligned.  Four launches: the filter's three, then one workgroup per clip for everything else. */
+size_t  wt_loudness_range_workspace_bytes(int32_t B, int64_t total_samples);
+int     wt_loudness_range(const wt_loudness_range_clip* clips, int32_t B, int32_t sample_rate, void* workspace, void* stream);
+
+/* wt_normalize_rows_lufs under a true-peak ceiling.  For a row with a finite L: d_L = fp32(10^((L - target_lufs) / 20)) as there,
+ * d_P = fp32((double)TP / 10^(max_true_peak_db / 20)) with TP the row's true peak by the definition above, d = max(d_L, d_P),
+ * y = x / d (IEEE division), scales[b] = d: the result's true peak does not exceed the ceiling (up to the roundings of d, of the
+ * division and of the interpolation), and where d_P <= d_L the row has the bits wt_normalize_rows_lufs gives.  A row without a
+ * loudness stays as it is with scale 1.  This bounds the gain; it is no sample-wise limiter.  A non-finite target or ceiling
+ * returns WT_ERR_INVALID before any device call.  workspace: wt_normalize_rows_lufs_tp_workspace_bytes(B, T_pad) bytes, 8-byte
+ * aligned.  Eight launches: the true peak's two, the loudness's four, the ceiling, the gain. */
+size_t wt_normalize_rows_lufs_tp_workspace_bytes(int32_t B, int64_t T_pad);
+int    wt_normalize_rows_lufs_tp(float* rows, int32_t B, int64_t T_pad, const int64_t* n, int32_t sample_rate, double target_lufs,
+                                 double max_true_peak_db, float* scales, void* workspace, void* stream);
 
 /* Replaces: _linear_overlap_add (encoder/utils.py:17-56), bit for bit: frames [n_frames][rows][frame_len] (the last
  * one holds last_len valid samples), weight [frame_len] = the reference's triangle 0.5 - |linspace(0,1,len+2)[1:-1] - 0.5|,

@@ -38,6 +38,8 @@ EXPORTS = [
     "wt_emit_rescaled_workspace_bytes", "wt_emit_rescaled",
     "wt_loudness_chunk", "wt_loudness_blocks", "wt_kweight_coefficients", "wt_loudness_workspace_bytes", "wt_loudness",
     "wt_normalize_rows_lufs_workspace_bytes", "wt_normalize_rows_lufs",
+    "wt_true_peak_tile", "wt_true_peak_workspace_bytes", "wt_true_peak", "wt_short_term_blocks", "wt_loudness_range_workspace_bytes",
+    "wt_loudness_range", "wt_normalize_rows_lufs_tp_workspace_bytes", "wt_normalize_rows_lufs_tp",
 ]
 
 WT_PLAN_ENCODE, WT_PLAN_DECODE, WT_PLAN_SEANET_DECODER, WT_PLAN_HEAD, WT_PLAN_UNIT_LSTM = 0, 1, 2, 3, 4
@@ -197,6 +199,17 @@ class WtLoudnessClip(ctypes.Structure):
     """wt_loudness_clip: one clip of a loudness measurement (wt_loudness)."""
     _fields_ = [("x", c_void_p), ("n", c_int64), ("channels", c_int32), ("channel_stride", c_int64), ("out", c_void_p),
                 ("blocks", c_void_p)]
+
+
+class WtTruePeakClip(ctypes.Structure):
+    """wt_true_peak_clip: one clip of a true-peak measurement (wt_true_peak)."""
+    _fields_ = [("x", c_void_p), ("n", c_int64), ("channels", c_int32), ("channel_stride", c_int64), ("out", c_void_p)]
+
+
+class WtLoudnessRangeClip(ctypes.Structure):
+    """wt_loudness_range_clip: one clip of a loudness-range measurement (wt_loudness_range)."""
+    _fields_ = [("x", c_void_p), ("n", c_int64), ("channels", c_int32), ("channel_stride", c_int64), ("out", c_void_p),
+                ("momentary", c_void_p), ("short_term", c_void_p)]
 
 
 class WtOverlapAddClip(ctypes.Structure):
@@ -453,6 +466,20 @@ def _load() -> ctypes.CDLL:
     lib.wt_normalize_rows_lufs_workspace_bytes.restype = c_size_t
     lib.wt_normalize_rows_lufs.argtypes = [c_void_p, c_int32, c_int64, POINTER(c_int64), c_int32, ctypes.c_double, c_void_p, c_void_p,
                                            c_void_p]
+    lib.wt_true_peak_tile.argtypes = []
+    lib.wt_true_peak_tile.restype = c_int32
+    lib.wt_true_peak_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_true_peak_workspace_bytes.restype = c_size_t
+    lib.wt_true_peak.argtypes = [POINTER(WtTruePeakClip), c_int32, c_int32, c_void_p, c_void_p]
+    lib.wt_short_term_blocks.argtypes = [c_int64, c_int32]
+    lib.wt_short_term_blocks.restype = c_int64
+    lib.wt_loudness_range_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_loudness_range_workspace_bytes.restype = c_size_t
+    lib.wt_loudness_range.argtypes = [POINTER(WtLoudnessRangeClip), c_int32, c_int32, c_void_p, c_void_p]
+    lib.wt_normalize_rows_lufs_tp_workspace_bytes.argtypes = [c_int32, c_int64]
+    lib.wt_normalize_rows_lufs_tp_workspace_bytes.restype = c_size_t
+    lib.wt_normalize_rows_lufs_tp.argtypes = [c_void_p, c_int32, c_int64, POINTER(c_int64), c_int32, ctypes.c_double, ctypes.c_double,
+                                              c_void_p, c_void_p, c_void_p]
     return lib
 
 

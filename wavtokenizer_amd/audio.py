@@ -7,7 +7,12 @@
     level(wav), level_many(wavs)                         peak and rms per clip (wt_level)
     normalize(wav, mode="peak" | "rms", target_db=0.0)   extract_features.py:27-28 / encoder/model.py:153-156 (wt_normalize_rows)
     loudness(wav, sample_rate), loudness_many(wavs, ...) integrated loudness in LUFS, ITU-R BS.1770-4 / EBU R 128 (wt_loudness)
-    normalize(wav, mode="lufs", target_lufs=-23.0)       to a loudness target (wt_normalize_rows_lufs)
+    normalize(wav, mode="lufs", target_lufs=-23.0)       to a loudness target (wt_normalize_rows_lufs); with max_true_peak_db under a
+                                                         true-peak ceiling (wt_normalize_rows_lufs_tp)
+    true_peak(wav, sample_rate), true_peak_many(...)     true peak in dBTP and sample peak in dBFS, BS.1770-4 Annex 2 (wt_true_peak)
+    loudness_range(wav, sample_rate), ..._many(...)      integrated, short-term and momentary loudness and the loudness range,
+                                                         EBU Tech 3341 / 3342 (wt_loudness_range)
+    r128_many(wavs, sample_rate)                         the summary of an R 128 meter per clip
 
 All take and return torch tensors on the GPU; there is no CPU fallback.  Recordings of any length, from and to PCM, with codes in
 between: WavTokenizer.encode_codes_segmented(_many) / decode_pcm_segmented(_many) (wavtokenizer_amd/segmented.py)."""
@@ -184,6 +189,119 @@ def loudness(wav: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
     return loudness_many([wav], sample_rate)[0]
 
 
+def _r128_clips(who: str, wavs, sample_rate):
+    """(clips made contiguous, their rates, their device) of a measuring call's arguments, checked as loudness_many checks them."""
+    wavs = list(wavs)
+    if not wavs:
+        raise ValueError(who + " takes at least one clip")
+    if isinstance(sample_rate, (list, tuple)):
+        rates = list(sample_rate)
+        if len(rates) != len(wavs):
+            raise ValueError(who + ": one sample rate per clip")
+    else:
+        rates = [sample_rate] * len(wavs)
+    for r in rates:
+        if isinstance(r, bool) or not isinstance(r, int) or not 8000 <= r <= 192000:
+            raise ValueError(who + ": sample rates are ints in [8000, 192000]")
+    for w in wavs:
+        if (not isinstance(w, torch.Tensor) or w.dim() not in (1, 2) or w.shape[-1] < 1 or w.dtype != torch.float32
+                or (w.dim() == 2 and w.shape[0] not in (1, 2))):
+            raise ValueError(who + " takes a sequence of non-empty fp32 tensors (T,) or (C, T) with C <= 2")
+    for w in wavs:
+        _need_gpu(w, _GPU_ONLY)
+    dev = wavs[0].device
+    if any(w.device != dev for w in wavs):
+        raise ValueError(who + ": the clips lie on different devices")
+    return [w.contiguous() for w in wavs], rates, dev
+
+
+def _true_peak_linear(wavs, rates, dev) -> torch.Tensor:
+    """(n, 2) fp32 on dev: (true peak, sample peak), linear; one wt_true_peak call per rate."""
+    out = torch.empty((len(wavs), 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for rate in sorted(set(rates)):
+            idx = [i for i, r in enumerate(rates) if r == rate]
+            descs = (_capi.WtTruePeakClip * len(idx))()
+            for d, i in zip(descs, idx):
+                w = wavs[i]
+                d.x, d.n, d.channels, d.channel_stride = w.data_ptr(), int(w.shape[-1]), (1 if w.dim() == 1 else int(w.shape[0])), int(w.shape[-1])
+                d.out = out.data_ptr() + 8 * i
+            ws = torch.empty(int(lib.wt_true_peak_workspace_bytes(len(idx), sum(wavs[i].numel() for i in idx))), dtype=torch.uint8, device=dev)
+            check(lib.wt_true_peak(descs, len(idx), int(rate), _ptr(ws), _stream(dev)), "wt_true_peak")
+    return out
+
+
+def true_peak_many(wavs: Sequence[torch.Tensor], sample_rate=24000) -> torch.Tensor:
+    """True peak of every clip by oversampling (ITU-R BS.1770-4 Annex 2 as include/wavtokenizer_amd.h states it: 4x under 96 kHz,
+    2x under 192 kHz, a Hann-windowed sinc of 49 taps).  wavs and sample_rate as loudness_many takes them.  Returns (n, 2) fp32 on
+    the clips' GPU, row i = (the true peak in dBTP, the sample peak in dBFS), both 20 log10 of the linear value (-inf for silence);
+    the first is never below the second.  The clips are grouped by rate: one wt_true_peak call (two launches) per rate.  A maximum
+    is exact: a clip has the same bits alone and in any batch.  Parity with libebur128 or ffmpeg is not pinned."""
+    wavs, rates, dev = _r128_clips("true_peak_many", wavs, sample_rate)
+    return 20.0 * torch.log10(_true_peak_linear(wavs, rates, dev))
+
+
+def true_peak(wav: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
+    """true_peak_many for one clip, (T,) or (C, T) with C <= 2: (2,) fp32 = (dBTP, sample peak in dBFS)."""
+    return true_peak_many([wav], sample_rate)[0]
+
+
+def loudness_range_many(wavs: Sequence[torch.Tensor], sample_rate=24000, series: bool = False):
+    """Integrated loudness, loudness range and the maxima of the momentary and the short-term loudness of every clip (EBU R 128 /
+    Tech 3341 / Tech 3342 as include/wavtokenizer_amd.h states them: 3 s windows on the 100 ms grid, gates at -70 LUFS and 20 LU
+    under the mean, the nearest-rank 10 % and 95 % points).  wavs and sample_rate as loudness_many takes them.  Returns (n, 9) fp32
+    on the clips' GPU, row i = (L, the relative threshold, the gated blocks: the bits of loudness_many; LRA in LU, its low and its
+    high value in LUFS, the windows through the range gates; the maximum momentary, the maximum short-term value).  A clip under
+    3 s, silent or all of it under -70 LUFS has no range: (NaN, NaN, NaN, 0), and without a window a maximum short-term of -inf.
+    series=True returns (that, [l_j (J_i,) per clip], [s_j (S_i,) per clip]): the momentary and the short-term loudness on the
+    100 ms grid.  One wt_loudness_range call (four launches, one pass of the K-weighting) per rate; a clip has the same bits alone
+    and in any batch."""
+    wavs, rates, dev = _r128_clips("loudness_range_many", wavs, sample_rate)
+    out = torch.empty((len(wavs), 9), dtype=torch.float32, device=dev)
+    mom: List[Optional[torch.Tensor]] = [None] * len(wavs)
+    sht: List[Optional[torch.Tensor]] = [None] * len(wavs)
+    if series:
+        nm = [int(lib.wt_loudness_blocks(int(w.shape[-1]), r)) for w, r in zip(wavs, rates)]
+        ns = [int(lib.wt_short_term_blocks(int(w.shape[-1]), r)) for w, r in zip(wavs, rates)]
+        flat = torch.empty(sum(nm) + sum(ns), dtype=torch.float32, device=dev)
+        pos = 0
+        for i, (a, b) in enumerate(zip(nm, ns)):
+            mom[i], sht[i] = flat[pos:pos + a], flat[pos + a:pos + a + b]
+            pos += a + b
+    with torch.cuda.device(dev):
+        for rate in sorted(set(rates)):
+            idx = [i for i, r in enumerate(rates) if r == rate]
+            descs = (_capi.WtLoudnessRangeClip * len(idx))()
+            for d, i in zip(descs, idx):
+                w = wavs[i]
+                d.x, d.n, d.channels, d.channel_stride = w.data_ptr(), int(w.shape[-1]), (1 if w.dim() == 1 else int(w.shape[0])), int(w.shape[-1])
+                d.out = out.data_ptr() + 36 * i
+                d.momentary = mom[i].data_ptr() if series and mom[i].numel() else None
+                d.short_term = sht[i].data_ptr() if series and sht[i].numel() else None
+            ws = torch.empty(int(lib.wt_loudness_range_workspace_bytes(len(idx), sum(wavs[i].numel() for i in idx))), dtype=torch.uint8,
+                             device=dev)
+            check(lib.wt_loudness_range(descs, len(idx), int(rate), _ptr(ws), _stream(dev)), "wt_loudness_range")
+    return (out, mom, sht) if series else out
+
+
+def loudness_range(wav: torch.Tensor, sample_rate: int = 24000, series: bool = False):
+    """loudness_range_many for one clip, (T,) or (C, T) with C <= 2: (9,) fp32; with series=True (that, l_j (J,), s_j (S,))."""
+    if series:
+        out, mom, sht = loudness_range_many([wav], sample_rate, series=True)
+        return out[0], mom[0], sht[0]
+    return loudness_range_many([wav], sample_rate)[0]
+
+
+def r128_many(wavs: Sequence[torch.Tensor], sample_rate=24000) -> List[Dict[str, float]]:
+    """What an R 128 meter's summary prints, per clip: {"integrated" (LUFS), "range" (LU), "range_low", "range_high" (LUFS),
+    "true_peak" (dBTP), "sample_peak" (dBFS), "max_momentary", "max_short_term" (LUFS)} as Python floats, from one
+    loudness_range_many and one true_peak_many (one transfer to the host)."""
+    r = loudness_range_many(wavs, sample_rate)
+    both = torch.cat([r, true_peak_many(wavs, sample_rate)], dim=1).cpu().tolist()
+    return [{"integrated": v[0], "range": v[3], "range_low": v[4], "range_high": v[5], "true_peak": v[9], "sample_peak": v[10],
+             "max_momentary": v[7], "max_short_term": v[8]} for v in both]
+
+
 def normalize_args(who: str, normalize, target_db, target_lufs=None) -> Optional[Tuple[int, float]]:
     """The (mode, gain) of a call's normalize / target_db / target_lufs arguments, None without normalisation; for "lufs" the
     pair is (WT_NORM_LUFS, the target), -23.0 where target_lufs is None (not given).  ValueError, before any GPU work, for a mode other than "peak", "rms" and "lufs", for a
@@ -209,11 +327,28 @@ def normalize_args(who: str, normalize, target_db, target_lufs=None) -> Optional
     raise ValueError(who + ": normalize must be None, 'peak', 'rms' or 'lufs'")
 
 
-def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float, sample_rate: Optional[int] = None) -> torch.Tensor:
+def ceiling_arg(who: str, normalize, max_true_peak_db) -> Optional[float]:
+    """The true-peak ceiling of a call's max_true_peak_db argument as a float, None where it is not given.  ValueError, before any
+    GPU work, for a ceiling that is no finite number (a bool is none) and for one given without normalize="lufs"."""
+    if max_true_peak_db is None:
+        return None
+    if isinstance(max_true_peak_db, bool) or not isinstance(max_true_peak_db, (int, float)) or not math.isfinite(max_true_peak_db):
+        raise ValueError(who + ": max_true_peak_db must be a finite number")
+    if normalize != "lufs":
+        raise ValueError(who + ": max_true_peak_db needs normalize='lufs'")
+    return float(max_true_peak_db)
+
+
+def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float, sample_rate: Optional[int] = None, *,
+                   max_true_peak_db: Optional[float] = None) -> torch.Tensor:
     """wt_normalize_rows on rows, a contiguous (B, T_pad) fp32 tensor on the GPU, in place: row b's first n[b] samples are divided
     by their level (+ 1e-8); returns the divisors (B,) fp32.  mode WT_NORM_LUFS goes to wt_normalize_rows_lufs instead, gain then
     being the target in LUFS and sample_rate the rows' rate (the model's codec rate, for the tokenising calls), which that mode
-    needs."""
+    needs; with max_true_peak_db (dBTP, that mode only) to wt_normalize_rows_lufs_tp, which keeps every row's true peak under it."""
+    if max_true_peak_db is not None:
+        if mode != _capi.WT_NORM_LUFS:
+            raise ValueError("normalize_rows: max_true_peak_db needs WT_NORM_LUFS")
+        max_true_peak_db = ceiling_arg("normalize_rows", "lufs", max_true_peak_db)
     B, T_pad = rows.shape
     assert rows.dtype == torch.float32 and rows.is_contiguous() and len(n) == B
     dev = rows.device
@@ -222,6 +357,12 @@ def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float,
     if mode == _capi.WT_NORM_LUFS:
         if sample_rate is None:
             raise ValueError("normalize_rows: WT_NORM_LUFS needs the rows' sample_rate")
+        if max_true_peak_db is not None:
+            ws = torch.empty(int(lib.wt_normalize_rows_lufs_tp_workspace_bytes(B, T_pad)), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                check(lib.wt_normalize_rows_lufs_tp(_ptr(rows), B, T_pad, lens, int(sample_rate), float(gain), max_true_peak_db,
+                                                    _ptr(scales), _ptr(ws), _stream(dev)), "wt_normalize_rows_lufs_tp")
+            return scales
         ws = torch.empty(int(lib.wt_normalize_rows_lufs_workspace_bytes(B, T_pad)), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             check(lib.wt_normalize_rows_lufs(_ptr(rows), B, T_pad, lens, int(sample_rate), float(gain), _ptr(scales), _ptr(ws),
@@ -235,7 +376,7 @@ def normalize_rows(rows: torch.Tensor, n: Sequence[int], mode: int, gain: float,
 
 
 def normalize(wav: torch.Tensor, mode: str = "peak", target_db: float = 0.0, *, target_lufs: Optional[float] = None,
-              sample_rate: int = 24000) -> Tuple[torch.Tensor, torch.Tensor]:
+              sample_rate: int = 24000, max_true_peak_db: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-clip level normalisation of mono audio: wav is (T,), (B, T) or (B, 1, T) on the GPU; returns (wav / scale, scale), the
     first in wav's shape, scale (B,) fp32 (a 0-d tensor for (T,)).
       mode="peak": scale = max |x| + 1e-8, the bits of torch's fp32 x / (x.abs().max() + 1e-8) (extract_features.py:27-28); with
@@ -244,11 +385,15 @@ def normalize(wav: torch.Tensor, mode: str = "peak", target_db: float = 0.0, *, 
       mode="lufs": scale = fp32(10^((L - target_lufs) / 20)), target_lufs -23.0 when not given, with L = loudness(x, sample_rate)[0], the integrated loudness (ITU-R
         BS.1770-4) at sample_rate, a rate in [8000, 192000]; the result then reads target_lufs.  A clip without a loudness
         (shorter than 400 ms, silent, or all of it under -70 LUFS) is returned as it is, bit for bit, with scale 1.  There is no
-        limiter: a quiet clip with one loud click can exceed +-1 after the gain.
+        limiter: a quiet clip with one loud click can exceed +-1 after the gain, unless max_true_peak_db (dBTP, "lufs" only) is
+        given: the scale is then max(that, fp32(true peak / 10^(max_true_peak_db / 20))) with the true peak of true_peak(x,
+        sample_rate), so that the result's true peak stays under the ceiling; a clip the ceiling does not bind has the bits of the
+        call without it.  The ceiling bounds the gain of the whole clip; it is no sample-wise limiter.
     A silent clip stays zeros.  This is the one-clip definition the batched calls (encode_codes_many(normalize=...)) are compared
     with.  The audio is taken as it is: the reference's scripts normalise after convert_audio, sox's `norm` before the resampling,
     and a peak moves under resampling; parity with sox is not claimed, nor with pyloudnorm or ffmpeg for "lufs"."""
     args = normalize_args("normalize", mode, target_db, target_lufs)
+    ceiling = ceiling_arg("normalize", mode, max_true_peak_db)
     if args is None:
         raise ValueError("normalize: mode must be 'peak', 'rms' or 'lufs'")
     if isinstance(sample_rate, bool) or not isinstance(sample_rate, int) or not 8000 <= sample_rate <= 192000:
@@ -258,7 +403,7 @@ def normalize(wav: torch.Tensor, mode: str = "peak", target_db: float = 0.0, *, 
     _need_gpu(wav, _GPU_ONLY)
     T = int(wav.shape[-1])
     rows = wav.to(torch.float32).reshape(-1, T).clone()
-    scales = normalize_rows(rows, [T] * rows.shape[0], *args, sample_rate=sample_rate)
+    scales = normalize_rows(rows, [T] * rows.shape[0], *args, sample_rate=sample_rate, max_true_peak_db=ceiling)
     return rows.view(wav.shape), (scales[0] if wav.dim() == 1 else scales)
 
 

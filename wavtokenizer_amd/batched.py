@@ -239,13 +239,13 @@ class _BatchedCalls:
         """One group of encode_codes_many: one upload, one wt_ingest into the plan's staging tensor, one wt_encode_mixed (no
         feature buffer unless the plan is graph-replayed), one wt_codes_unpack into flat at the clips' offsets.  Returns True, or
         None when the encoder is off the route a mixed-length plan takes (_route_ok).  n_q: residual VQ (_encode_ingested).
-        norm: (mode, gain, sink) of a call with normalize=...: the ingested rows are normalised in place in front of the encode
-        (one wt_normalize_rows) and sink(offsets, scales) receives the group's divisors."""
+        norm: (mode, gain, sink, ceiling) of a call with normalize=...: the ingested rows are normalised in place in front of the
+        encode (one wt_normalize_rows) and sink(offsets, scales) receives the group's divisors; ceiling: max_true_peak_db or None."""
         dev = self._ensure_engine()
         if not self._route_ok(_capi.WT_PLAN_ENCODE):          # (before anything is uploaded; checked again on every attempt below)
             return None
         descs, ws, lengths, spans, _alive = self._ingest_stage(specs, offsets, dev)
-        rows_norm = norm and (norm[0], norm[1], [sp.n_out for sp in specs], lambda scales: norm[2](offsets, scales))
+        rows_norm = norm and (norm[0], norm[1], [sp.n_out for sp in specs], lambda scales: norm[2](offsets, scales), norm[3])
         return self._encode_ingested(descs, ws, len(specs), T_pad, lengths, spans, flat, dev, n_q, rows_norm)
 
     def _encode_ingested(self, descs, ws: torch.Tensor, B: int, T_pad: int, lengths: Optional[torch.Tensor], spans: torch.Tensor,
@@ -256,13 +256,13 @@ class _BatchedCalls:
         recording, same staging buffers).  True, or None off the mixed route (a uniform batch then goes clip by clip as well).
         n_q: the encode is residual VQ with n_q codebooks (WT_PLAN_FLAG_RVQ), flat is [n_q][sum L_i] and every plane is handed
         out by a wt_codes_unpack of its own.
-        norm: (mode, gain, samples per row, sink): behind the ingest, one wt_normalize_rows divides every row by its own level
-        in place (audio.normalize_rows) and sink(scales) receives the divisors (B,)."""
+        norm: (mode, gain, samples per row, sink, ceiling): behind the ingest, one wt_normalize_rows divides every row by its own
+        level in place (audio.normalize_rows, ceiling its max_true_peak_db) and sink(scales) receives the divisors (B,)."""
         def fill_wav(buf: torch.Tensor):
             check(lib.wt_ingest(descs, B, T_pad, _ptr(buf), _ptr(ws), _stream_ptr(dev)), "wt_ingest")
             if norm is not None:
                 from . import audio
-                norm[3](audio.normalize_rows(buf, norm[2], norm[0], norm[1], sample_rate=self.codec_rate))
+                norm[3](audio.normalize_rows(buf, norm[2], norm[0], norm[1], sample_rate=self.codec_rate, max_true_peak_db=norm[4]))
 
         if n_q is not None:
             if lengths is None:
@@ -298,7 +298,8 @@ class _BatchedCalls:
             wav = self._ingest_rows(part, dev)
             if norm is not None:                             # (as _run_encode_codes_mixed: in place, behind the ingest)
                 from . import audio
-                norm[2](offs, audio.normalize_rows(wav, [sp.n_out for sp in part], norm[0], norm[1], sample_rate=self.codec_rate))
+                norm[2](offs, audio.normalize_rows(wav, [sp.n_out for sp in part], norm[0], norm[1], sample_rate=self.codec_rate,
+                                                   max_true_peak_db=norm[3]))
             for j, (sp, off) in enumerate(zip(part, offs)):
                 if n_q is not None:
                     codes = self.encode_codes(wav[j:j + 1, :sp.n_out], n_q=n_q)
@@ -332,7 +333,8 @@ class _BatchedCalls:
     @torch.inference_mode()
     def encode_codes_many(self, clips: Sequence[torch.Tensor], sample_rates=None, channels_last: bool = False, packed: bool = False,
                           bandwidth_id=None, n_q: Optional[int] = None, normalize: Optional[str] = None, target_db: float = 0.0,
-                          return_scales: bool = False, target_lufs: Optional[float] = None):
+                          return_scales: bool = False, target_lufs: Optional[float] = None, *,
+                          max_true_peak_db: Optional[float] = None):
         """Tokenise a set of clips straight from PCM.  clips[i] is (T,), (C, T) or, with channels_last, (T, C), C in {1, 2}, fp32
         or int16 (scaled by 1 / 32768), on the CPU or on the model's device; sample_rates is one rate or one per clip (default:
         the codec rate).  Returns [codes (1, 1, L_i)] in input order, views into one flat int64 tensor, L_i =
@@ -359,11 +361,15 @@ class _BatchedCalls:
         on its mono row at the codec rate; one wt_normalize_rows_lufs per group): clip i's codes are the bits of encode_infer(
         audio.normalize(converted clip i, "lufs", target_lufs=...)[0])[1], its scale that call's.  A clip without a loudness
         (under 400 ms after conversion, silent, all under -70 LUFS) is tokenised as it is with scale 1; there is no limiter.  A
-        target_lufs without "lufs" raises ValueError like the rest."""
+        target_lufs without "lufs" raises ValueError like the rest.
+        max_true_peak_db (dBTP, with "lufs" only): the gain is bounded so that no clip's true peak (ITU-R BS.1770-4 Annex 2, on the
+        same row) exceeds it: one wt_normalize_rows_lufs_tp per group, clip i's codes and scale those of audio.normalize(converted
+        clip i, "lufs", target_lufs=..., max_true_peak_db=...).  Given without "lufs", or no finite number: ValueError."""
         from . import audio
         from .mixed_length import group_clips
         self._check_bandwidth(bandwidth_id)
         norm = audio.normalize_args("encode_codes_many", normalize, target_db, target_lufs)
+        ceiling = audio.ceiling_arg("encode_codes_many", normalize, max_true_peak_db)
         if return_scales and norm is None:
             raise ValueError("encode_codes_many: return_scales needs normalize")
         if n_q is not None:
@@ -376,7 +382,7 @@ class _BatchedCalls:
         flat = torch.empty(offsets[-1] if n_q is None else (n_q, offsets[-1]), dtype=torch.int64, device=self._device())
         rvq = () if n_q is None else (n_q,)       # (n_q=None: today's calls, argument for argument)
         parts: Dict[int, Tuple[List[int], torch.Tensor]] = {}    # a group's first code offset -> (its clips' offsets, their divisors)
-        kw = {} if norm is None else {"norm": (*norm, lambda offs, sc: parts.__setitem__(offs[0], (list(offs), sc)))}
+        kw = {} if norm is None else {"norm": (*norm, lambda offs, sc: parts.__setitem__(offs[0], (list(offs), sc)), ceiling)}
         self._run_groups_of(specs, offsets, *group_clips([sp.n_out for sp in specs], self._arch.hop),
                             lambda T_pad, part, offs: self._run_encode_codes_mixed(part, T_pad, flat, offs, *rvq, **kw),
                             lambda part, offs: self._encode_codes_solo(part, flat, offs, *rvq, **kw))
@@ -403,7 +409,8 @@ class _BatchedCalls:
     @torch.inference_mode()
     def encode_codes_segmented_many(self, clips: Sequence[torch.Tensor], segment_length: int, stride: int, sample_rates=None,
                                     channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None,
-                                    target_db: float = 0.0, target_lufs: Optional[float] = None):
+                                    target_db: float = 0.0, target_lufs: Optional[float] = None, *,
+                                    max_true_peak_db: Optional[float] = None):
         """Tokenise long recordings in overlapping segments (the reference's EncodecModel.encode, encoder/model.py:122-145).
         clips and sample_rates as encode_codes_many takes them (any rate, mono or stereo, planar or interleaved, fp32 or int16,
         on the CPU or on the model's device); segment_length and stride are samples at the codec rate, stride <= segment_length.
@@ -424,13 +431,15 @@ class _BatchedCalls:
         and its encode: segment i's codes are the bits of encode_codes(audio.normalize(W[None, off_i:off_i + len_i], normalize,
         target_db)[0]), and the divisors are kept as SegmentedCodes.scales, (n_segments,) fp32 on the model's device, for
         decode_pcm_segmented to multiply back in.  normalize="lufs" (target_lufs) brings every segment to that integrated
-        loudness in the same place; a segment under 400 ms (the last cut of a recording may be) passes as it is with scale 1."""
+        loudness in the same place; a segment under 400 ms (the last cut of a recording may be) passes as it is with scale 1;
+        max_true_peak_db (with "lufs" only) bounds every segment's gain by its own true peak, as in encode_codes_many."""
         from . import audio
         from .mixed_length import MAX_GROUP, group_clips
         from .segmented import SegmentedCodes, check_geometry, segment_plan
         who = "encode_codes_segmented_many"
         self._check_bandwidth(bandwidth_id)
         norm = audio.normalize_args(who, normalize, target_db, target_lufs)
+        ceiling = audio.ceiling_arg(who, normalize, max_true_peak_db)
         segment_plan(1, segment_length, stride)                 # (the geometry's own refusals, also for an empty list)
         specs = self._clip_specs(who, clips, sample_rates, channels_last)
         S, stride = int(segment_length), int(stride)
@@ -489,7 +498,7 @@ class _BatchedCalls:
             lengths, spans = next(tables_of)
             descs, ws = self._ingest_descs([spec[seg_len[k]] for k in ks], [base[seg_rec[k]] + 4 * seg_off[k] for k in ks], dev)
             uniform = not T_pad and not self._segment_uniform_mixed
-            kw = {} if norm is None else {"norm": (*norm, [seg_len[k] for k in ks], lambda sc: parts.__setitem__(ks[0], (list(ks), sc)))}
+            kw = {} if norm is None else {"norm": (*norm, [seg_len[k] for k in ks], lambda sc: parts.__setitem__(ks[0], (list(ks), sc)), ceiling)}
             return self._encode_ingested(descs, ws, len(ks), T_pad or S, None if uniform else lengths, spans, flat, dev, **kw)
 
         def run_solo(ks):
@@ -498,7 +507,8 @@ class _BatchedCalls:
                 if norm is None:
                     codes = self.encode_codes(seg)
                 else:
-                    codes, sc = self.encode_codes(seg, normalize=normalize, target_db=target_db, return_scales=True, target_lufs=target_lufs)
+                    codes, sc = self.encode_codes(seg, normalize=normalize, target_db=target_db, return_scales=True, target_lufs=target_lufs,
+                                                  max_true_peak_db=ceiling)
                     parts[k] = ([k], sc)
                 flat[seg_code[k]:seg_code[k] + codes.shape[-1]].copy_(codes.view(-1))
 
@@ -515,10 +525,11 @@ class _BatchedCalls:
     @torch.inference_mode()
     def encode_codes_segmented(self, clip: torch.Tensor, segment_length: int, stride: int, sample_rate: Optional[int] = None,
                                channels_last: bool = False, bandwidth_id=None, normalize: Optional[str] = None, target_db: float = 0.0,
-                               target_lufs: Optional[float] = None):
+                               target_lufs: Optional[float] = None, *, max_true_peak_db: Optional[float] = None):
         """encode_codes_segmented_many for one recording: its segmented.SegmentedCodes."""
         return self.encode_codes_segmented_many([clip], segment_length, stride, sample_rates=sample_rate, channels_last=channels_last,
-                                                bandwidth_id=bandwidth_id, normalize=normalize, target_db=target_db, target_lufs=target_lufs)[0]
+                                                bandwidth_id=bandwidth_id, normalize=normalize, target_db=target_db, target_lufs=target_lufs,
+                                                max_true_peak_db=max_true_peak_db)[0]
 
     def _run_decode_mixed(self, feats: List[torch.Tensor], L_pad: int, bw: int, dev: Optional[torch.device] = None):
         """One mixed-length decode call (WT_PLAN_DECODE_MIXED) on clips (512, L_i) of 1 <= L_i <= L_pad frames: returns the

@@ -26,31 +26,17 @@
 // (sums must not depend on the kernel a device function is inlined into: no contraction by the compiler)
 #pragma clang fp contract(off)
 #include "fft.h"
+#include "loudness_kernels.h"
 #include "ragged.h"
 
 namespace wt {
 
-constexpr int LOUD_CHUNK = 128;                 // samples per lane of the two walks (<= 800: at most one 100 ms boundary at 8 kHz)
+// (the chunk, the clip's device form, the 100 ms grid and the gating of one clip: loudness_kernels.h, shared with r128.hip)
 constexpr int LOUD_TILE = 32;                   // columns staged per step
 constexpr int LOUD_PITCH = LOUD_TILE + 1;       // words between the rows of the staged tile: lane l reads bank (33 l + t) % 64, all distinct
-constexpr int LOUD_THREADS = 256;               // the scan's and the gating's workgroups
-constexpr int LOUD_ARG_CLIPS = 64;              // descriptors up to this many travel in the launches' argument blocks (ragged.h);
-                                                // with the scan's matrices they fill most of an argument block: see the assertion below
 constexpr int LOUD_SPAN = 1024;                 // samples per workgroup of the gain kernel: four per thread
-constexpr int LOUD_SLOT_DOUBLES = 20;           // workspace per chunk: end state, start state, wave total, carry (4 each), 2 partials, segment, block
 
 typedef float ld_f32x4 __attribute__((ext_vector_type(4)));
-
-// One clip of a call (device form of wt_loudness_clip)
-struct LoudClip {
-    const float* x;
-    long n;
-    long ch_stride;
-    float* out;                                 // [3]: L, threshold, gated blocks
-    float* blocks;                              // nullable: J momentary values
-    int part;                                   // the clip's first chunk slot in the workspace (channel c: part + c * chunks)
-    int channels;
-};
 
 // b0 b1 b2 a1 a2 of the shelf, then of the high pass
 struct KwCoef { double c[10]; };
@@ -77,16 +63,6 @@ __host__ __device__ __forceinline__ void kw_matvec_add(const double* m, const do
 #pragma unroll
     for (int i = 0; i < 4; ++i) r[i] = ((m[4 * i] * v[0] + m[4 * i + 1] * v[1]) + (m[4 * i + 2] * v[2] + m[4 * i + 3] * v[3])) + a[i];
 }
-
-// complete 400 ms blocks of n samples at rate fs: the j with floor((j + 4) fs / 10) <= n
-__host__ __device__ __forceinline__ long loud_blocks(long n, int fs) {
-    const long m = (10 * (n + 1) - 1) / fs;     // the largest m with floor(m fs / 10) <= n
-    return m > 3 ? m - 3 : 0;
-}
-// first sample of 100 ms segment j
-__host__ __device__ __forceinline__ long loud_edge(long j, int fs) { return j * (long)fs / 10; }
-// the segment that holds sample s
-__host__ __device__ __forceinline__ long loud_segment_of(long s, int fs) { return (10 * (s + 1) - 1) / fs; }
 
 // grid (ceil(max chunks / 64), B, channels), 64 threads: lane l of block (g, b, c) walks chunk 64 g + l of channel c of clip b.
 // ENERGY false: from zero state, the end state goes to zend.  ENERGY true: from start, the sums of y^2 in front of and behind the
@@ -236,80 +212,26 @@ template <class D> __global__ __launch_bounds__(LOUD_THREADS) void loud_scan_ker
     }
 }
 
-// the workgroup's sum of v and of n: the xor butterfly over the wave, the four waves as (0 + 1) + (2 + 3); every thread gets both
-__device__ __forceinline__ void loud_block_sum(double v, int n, double& sum, int& count) {
-    __shared__ double wv[LOUD_THREADS / 64];
-    __shared__ int wn[LOUD_THREADS / 64];
-    __syncthreads();                                            // (the last call's readers are done)
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        v = v + __shfl_xor(v, off, 64);
-        n = n + __shfl_xor(n, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { wv[threadIdx.x >> 6] = v; wn[threadIdx.x >> 6] = n; }
-    __syncthreads();
-    sum = (wv[0] + wv[1]) + (wv[2] + wv[3]);
-    count = (wn[0] + wn[1]) + (wn[2] + wn[3]);
-}
-
-__device__ __forceinline__ double loud_lufs(double z) { return -0.691 + 10. * log10(z); }
-
 // grid (B), LOUD_THREADS threads: block b turns clip b's partials into segment sums, block energies, the two gates and out[0..3);
 // with scales, scales[b] = fp32(10^((L - target) / 20)) for a finite L (the value stored in out[0]), else 1
 template <class D> __global__ __launch_bounds__(LOUD_THREADS) void loud_gate_kernel(const D d, int fs, const double* __restrict__ part2,
                                                                                    double* seg, double* zblk, float* __restrict__ scales,
                                                                                    double target) {
     const LoudClip c = d.clip[blockIdx.x];
-    const long chunks = (c.n + LOUD_CHUNK - 1) / LOUD_CHUNK;
-    const long J = loud_blocks(c.n, fs);
-    const long segments = J > 0 ? J + 3 : 0;                    // (each is at least 800 samples: there are fewer than chunks)
-    for (int ch = 0; ch < c.channels; ++ch) {
-        const long base = (long)c.part + (long)ch * chunks;
-        for (long j = threadIdx.x; j < segments; j += LOUD_THREADS) {
-            const long lo = loud_edge(j, fs) / LOUD_CHUNK, hi = (loud_edge(j + 1, fs) - 1) / LOUD_CHUNK;
-            double sum = 0.;
-            for (long kk = lo; kk <= hi; ++kk)                  // the chunk began in this segment: its front part, else its back part
-                sum = sum + part2[2 * (base + kk) + (loud_segment_of(kk * LOUD_CHUNK, fs) == j ? 0 : 1)];
-            seg[base + j] = sum;
-        }
-    }
-    __syncthreads();
-    const global_ptr<float> blocks = (global_ptr<float>)c.blocks;
-    for (long j = threadIdx.x; j < J; j += LOUD_THREADS) {
-        const double len = (double)(loud_edge(j + 4, fs) - loud_edge(j, fs));
-        double z = 0.;
-        for (int ch = 0; ch < c.channels; ++ch) {
-            const double* s = seg + (long)c.part + (long)ch * chunks + j;
-            z = z + ((s[0] + s[1]) + (s[2] + s[3])) / len;
-        }
-        zblk[c.part + j] = z;
-        if (c.blocks) blocks[j] = (float)loud_lufs(z);
-    }
-    __syncthreads();
-    double v = 0., sum;
-    int n = 0, count;
-    for (long j = threadIdx.x; j < J; j += LOUD_THREADS) {
-        const double z = zblk[c.part + j];
-        if (loud_lufs(z) > -70.) { v = v + z; ++n; }
-    }
-    loud_block_sum(v, n, sum, count);
-    const double inf = __builtin_huge_val();
-    const double gamma = count > 0 ? loud_lufs(sum / (double)count) - 10. : -inf;
-    v = 0.;
-    n = 0;
-    for (long j = threadIdx.x; j < J; j += LOUD_THREADS) {
-        const double z = zblk[c.part + j];
-        const double l = loud_lufs(z);
-        if (l > -70. && l > gamma) { v = v + z; ++n; }
-    }
-    loud_block_sum(v, n, sum, count);
+    const LoudGated g = loud_gate_clip(c, fs, part2, seg, zblk);
     if (threadIdx.x != 0) return;
-    const float L = count > 0 ? (float)loud_lufs(sum / (double)count) : (float)-inf;
-    const global_ptr<float> out = (global_ptr<float>)c.out;
-    out[0] = L;
-    out[1] = count > 0 ? (float)gamma : (float)-inf;
-    out[2] = (float)count;
-    if (scales) scales[blockIdx.x] = count > 0 ? (float)exp10(((double)L - target) / 20.) : 1.f;
+    const float L = loud_store_triple(g, c.out);
+    if (scales) scales[blockIdx.x] = g.count > 0 ? (float)exp10(((double)L - target) / 20.) : 1.f;
+}
+
+// grid (ceil(B / LOUD_THREADS)): the true-peak ceiling on the divisor of a clip with a loudness (its gated blocks, out[2], are not 0):
+// scales[b] = max(scales[b], fp32((double)true_peaks[2 b] / ceiling))
+template <class D> __global__ __launch_bounds__(LOUD_THREADS) void loud_ceiling_kernel(const D d, int B, const float* __restrict__ true_peaks,
+                                                                                      double ceiling, float* __restrict__ scales) {
+    const int b = blockIdx.x * LOUD_THREADS + threadIdx.x;
+    if (b >= B) return;
+    if (((global_ptr<const float>)d.clip[b].out)[2] == 0.f) return;
+    scales[b] = fmaxf(scales[b], (float)((double)true_peaks[2 * b] / ceiling));
 }
 
 // grid (ceil(max n / LOUD_SPAN), B): x[i] = x[i] / scales[b] over clip b's n samples; a row whose divisor is 1 is not touched
@@ -331,7 +253,7 @@ template <class D> __global__ __launch_bounds__(LOUD_THREADS) void loud_apply_ke
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 
-static bool loud_rate_ok(int fs) { return fs >= 8000 && fs <= 192000; }
+bool loud_rate_ok(int fs) { return fs >= 8000 && fs <= 192000; }
 
 // The K-weighting of rate fs as the bilinear transforms of its two analogue prototypes, in double
 static KwCoef kw_coefficients(int fs) {
@@ -391,8 +313,8 @@ static KwMats kw_matrices(const KwCoef& k) {
 static size_t loud_descriptor_bytes(int B) { return (size_t)B * sizeof(LoudClip); }
 
 // The descriptors checked and turned into their device form; slots: the chunk slots the call needs, max_n: its longest clip
-static int loud_prepare(const std::string& fn, const wt_loudness_clip* clips, int B, int fs, const void* workspace, std::vector<LoudClip>& dev,
-                        int64_t& slots, int64_t& max_n, int& max_ch) {
+int loud_prepare(const std::string& fn, const wt_loudness_clip* clips, int B, int fs, const void* workspace, std::vector<LoudClip>& dev,
+                 int64_t& slots, int64_t& max_n, int& max_ch) {
     if (!clips || !workspace || B < 1 || B > 65535) { set_error(fn + ": bad argument"); return WT_ERR_INVALID; }
     if (!loud_rate_ok(fs)) { set_error(fn + ": sample_rate outside [8000, 192000]"); return WT_ERR_INVALID; }
     if (reinterpret_cast<uintptr_t>(workspace) % 8) { set_error(fn + ": workspace misaligned"); return WT_ERR_INVALID; }
@@ -422,19 +344,27 @@ static int loud_prepare(const std::string& fn, const wt_loudness_clip* clips, in
     return WT_OK;
 }
 
-// The measurement's four launches and, with scales, the gain launch behind them, all on one descriptor source
-static int loud_launch(const char* fn, const std::vector<LoudClip>& dev, int64_t slots, int64_t max_n, int max_ch, int fs, void* workspace,
-                       hipStream_t s, float* scales, double target) {
+// The chunk states' place behind the descriptors' (zend, start, gtot, carry: 4 doubles per slot each), then loud_buffers'
+static double* loud_states(void* workspace, int B) { return reinterpret_cast<double*>(static_cast<char*>(workspace) + loud_descriptor_bytes(B)); }
+
+LoudBuffers loud_buffers(void* workspace, int B, int64_t slots) {
+    double* part2 = loud_states(workspace, B) + 16 * slots;
+    return LoudBuffers{part2, part2 + 2 * slots, part2 + 3 * slots};
+}
+
+// The launches of a call on one descriptor source: the K-weighting's three, then (gate) the gating and, with scales, the ceiling
+// (with true_peaks) and the gain
+static int loud_launches(const char* fn, const std::vector<LoudClip>& dev, int64_t slots, int64_t max_n, int max_ch, int fs, void* workspace,
+                         hipStream_t s, bool gate, float* scales, double target, const float* true_peaks, double ceiling) {
     const int B = (int)dev.size();
     const KwCoef k = kw_coefficients(fs);
     const KwMats m = kw_matrices(k);
-    double* zend = reinterpret_cast<double*>(static_cast<char*>(workspace) + loud_descriptor_bytes(B));
+    double* zend = loud_states(workspace, B);
     double* start = zend + 4 * slots;
     double* gtot = start + 4 * slots;
     double* carry = gtot + 4 * slots;
-    double* part2 = carry + 4 * slots;
-    double* seg = part2 + 2 * slots;
-    double* zblk = seg + slots;
+    const LoudBuffers w = loud_buffers(workspace, B, slots);
+    double* part2 = w.part2;
     const int64_t max_chunks = (max_n + LOUD_CHUNK - 1) / LOUD_CHUNK;
     const dim3 walk((unsigned)((max_chunks + 63) / 64), (unsigned)B, (unsigned)max_ch);
     const dim3 span((unsigned)((max_n + LOUD_SPAN - 1) / LOUD_SPAN), (unsigned)B);
@@ -443,11 +373,25 @@ static int loud_launch(const char* fn, const std::vector<LoudClip>& dev, int64_t
         hipLaunchKernelGGL(loud_scan_kernel<decltype(d)>, dim3((unsigned)B, (unsigned)max_ch), dim3(LOUD_THREADS), 0, s, d, m, zend, start, gtot,
                            carry);
         hipLaunchKernelGGL((loud_walk_kernel<decltype(d), true>), walk, dim3(64), 0, s, d, k, fs, zend, start, part2);
-        hipLaunchKernelGGL(loud_gate_kernel<decltype(d)>, dim3((unsigned)B), dim3(LOUD_THREADS), 0, s, d, fs, part2, seg, zblk, scales, target);
+        if (!gate) return;
+        hipLaunchKernelGGL(loud_gate_kernel<decltype(d)>, dim3((unsigned)B), dim3(LOUD_THREADS), 0, s, d, fs, part2, w.seg, w.zblk, scales, target);
+        if (scales && true_peaks)
+            hipLaunchKernelGGL(loud_ceiling_kernel<decltype(d)>, dim3((unsigned)((B + LOUD_THREADS - 1) / LOUD_THREADS)), dim3(LOUD_THREADS), 0, s, d,
+                               B, true_peaks, ceiling, scales);
         if (scales) hipLaunchKernelGGL(loud_apply_kernel<decltype(d)>, span, dim3(LOUD_THREADS), 0, s, d, scales);
     })) return rc;
     WT_HIP_CHECK(hipGetLastError());
     return WT_OK;
+}
+
+int loud_launch(const char* fn, const std::vector<LoudClip>& dev, int64_t slots, int64_t max_n, int max_ch, int fs, void* workspace,
+                hipStream_t s, float* scales, double target, const float* true_peaks, double ceiling) {
+    return loud_launches(fn, dev, slots, max_n, max_ch, fs, workspace, s, true, scales, target, true_peaks, ceiling);
+}
+
+int loud_filter_launch(const char* fn, const std::vector<LoudClip>& dev, int64_t slots, int64_t max_n, int max_ch, int fs, void* workspace,
+                       hipStream_t s) {
+    return loud_launches(fn, dev, slots, max_n, max_ch, fs, workspace, s, false, nullptr, 0., nullptr, 1.);
 }
 
 }  // namespace wt

@@ -47,7 +47,9 @@ definition, tests/pitch_ref.py holds it in float64).  `calculate_periodicity_met
 `periodicity_metrics(y, y_hat, sample_rate)`.
 
 And the level: loudness_delta(y_hat, y, sample_rate), loudness_delta_many(y_hats, ys, sample_rate=...), the difference of the
-integrated loudness in LUFS (audio.loudness) of the decoded audio and its input, in LU."""
+integrated loudness in LUFS (audio.loudness) of the decoded audio and its input, in LU; loudness_range_delta(_many) and
+true_peak_delta(_many), the same differences of the loudness range (audio.loudness_range, LU) and of the true peak
+(audio.true_peak, dB)."""
 import ctypes
 import math
 from typing import Dict, List, Sequence, Tuple, Union
@@ -654,3 +656,49 @@ def loudness_delta_many(y_hats: Sequence[torch.Tensor], ys: Sequence[torch.Tenso
 def loudness_delta(y_hat: torch.Tensor, y: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
     """0-dim fp32: loudness_delta_many for one pair."""
     return loudness_delta_many([y_hat], [y], sample_rate=sample_rate)[0]
+
+
+def _paired(who: str, y_hats, ys, sample_rate):
+    """(y_hats + ys, the rates of that list) of a delta call's arguments."""
+    y_hats, ys = list(y_hats), list(ys)
+    if len(y_hats) != len(ys):
+        raise ValueError(who + ": as many estimates as references")
+    if not ys:
+        raise ValueError(who + " takes at least one pair")
+    if isinstance(sample_rate, (list, tuple)):
+        if len(sample_rate) != len(ys):
+            raise ValueError(who + ": one sample rate per pair")
+        sample_rate = list(sample_rate) * 2
+    return y_hats + ys, sample_rate
+
+
+def loudness_range_delta_many(y_hats: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], *,
+                              sample_rate: Union[int, Sequence[int]] = 24000) -> torch.Tensor:
+    """LRA(y_hat) - LRA(y) in LU per pair, LRA the loudness range of audio.loudness_range (EBU Tech 3342 on the 100 ms grid;
+    include/wavtokenizer_amd.h gives the definition): (n,) fp32.  Arguments as loudness_delta_many takes them.  One
+    audio.loudness_range_many call over both lists.  NaN where either side has no range (under 3 s, silent, all under -70 LUFS)."""
+    from . import audio
+    both, rates = _paired("loudness_range_delta_many", y_hats, ys, sample_rate)
+    r = audio.loudness_range_many(both, rates)[:, 3]
+    return r[:len(both) // 2] - r[len(both) // 2:]
+
+
+def loudness_range_delta(y_hat: torch.Tensor, y: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
+    """0-dim fp32: loudness_range_delta_many for one pair."""
+    return loudness_range_delta_many([y_hat], [y], sample_rate=sample_rate)[0]
+
+
+def true_peak_delta_many(y_hats: Sequence[torch.Tensor], ys: Sequence[torch.Tensor], *,
+                         sample_rate: Union[int, Sequence[int]] = 24000) -> torch.Tensor:
+    """dBTP(y_hat) - dBTP(y) in dB per pair, the true peak of audio.true_peak (ITU-R BS.1770-4 Annex 2): (n,) fp32.  Arguments as
+    loudness_delta_many takes them.  One audio.true_peak_many call over both lists.  NaN where either side is silent."""
+    from . import audio
+    both, rates = _paired("true_peak_delta_many", y_hats, ys, sample_rate)
+    t = audio.true_peak_many(both, rates)[:, 0]
+    a, b = t[:len(both) // 2], t[len(both) // 2:]
+    return torch.where(torch.isinf(a) | torch.isinf(b), torch.full_like(a, float("nan")), a - b)
+
+
+def true_peak_delta(y_hat: torch.Tensor, y: torch.Tensor, sample_rate: int = 24000) -> torch.Tensor:
+    """0-dim fp32: true_peak_delta_many for one pair."""
+    return true_peak_delta_many([y_hat], [y], sample_rate=sample_rate)[0]

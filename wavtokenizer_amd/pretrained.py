@@ -648,7 +648,8 @@ class WavTokenizer(_BatchedCalls, nn.Module):
 
     @torch.inference_mode()
     def encode_codes(self, audio_input: torch.Tensor, bandwidth_id=None, n_q: Optional[int] = None, normalize: Optional[str] = None,
-                     target_db: float = 0.0, return_scales: bool = False, target_lufs: Optional[float] = None):
+                     target_db: float = 0.0, return_scales: bool = False, target_lufs: Optional[float] = None, *,
+                     max_true_peak_db: Optional[float] = None):
         """encode_infer(audio_input, bandwidth_id=...)[1], the same bits, for a caller that wants the codes alone: (B, T) fp32 at
         the codec rate -> (1, B, L) int64.  A call that is not graph-replayed passes no feature buffer to the library (nothing
         gathers or writes the (B, 512, L) tensor); a graph-replayed one shares encode_infer's recording and staging buffers.
@@ -663,10 +664,13 @@ class WavTokenizer(_BatchedCalls, nn.Module):
         mode and return_scales without normalize raise ValueError before any GPU work.
         normalize="lufs" (target_lufs, default -23): every clip is brought to that integrated loudness (ITU-R BS.1770-4 at the
         codec rate) as audio.normalize(audio_input, "lufs", target_lufs=...) does; a clip without a loudness (under 400 ms,
-        silent) passes as it is with scale 1.  A target_lufs without "lufs" raises ValueError like the rest."""
+        silent) passes as it is with scale 1.  A target_lufs without "lufs" raises ValueError like the rest.
+        max_true_peak_db (dBTP, with "lufs" only) bounds the gain by every clip's true peak, as audio.normalize(...,
+        max_true_peak_db=...) does; given without "lufs", or no finite number: ValueError before any GPU work."""
         from . import audio as _audio
         self._check_bandwidth(bandwidth_id)
         norm = _audio.normalize_args("encode_codes", normalize, target_db, target_lufs)
+        ceiling = _audio.ceiling_arg("encode_codes", normalize, max_true_peak_db)
         if norm is not None or return_scales:
             if norm is None:
                 raise ValueError("encode_codes: return_scales needs normalize")
@@ -675,7 +679,8 @@ class WavTokenizer(_BatchedCalls, nn.Module):
             assert audio_input.dim() == 2, "expected audio of shape (B, T)"
             dev = self._ensure_engine()
             rows = self._as_input(audio_input, dev).clone()
-            scales = _audio.normalize_rows(rows, [rows.shape[1]] * rows.shape[0], *norm, sample_rate=self.codec_rate)
+            scales = _audio.normalize_rows(rows, [rows.shape[1]] * rows.shape[0], *norm, sample_rate=self.codec_rate,
+                                            max_true_peak_db=ceiling)
             codes = self.encode_codes(rows, n_q=n_q)
             return (codes, scales) if return_scales else codes
         if n_q is not None:

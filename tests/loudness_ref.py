@@ -1,5 +1,5 @@
 """Definition, bounds and C-ABI wrappers for the loudness kernels (csrc/loudness.hip: wt_loudness, wt_normalize_rows_lufs):
-tests/test_loudness_host.py, test_loudness_op.py and test_loudness_calls.py share them.
+tests/test_loudness_host.py, test_loudness_op.py, test_loudness_calls.py and test_loudness_rates.py share them.
 
 The definition is ITU-R BS.1770-4 / EBU R 128 integrated loudness as include/wavtokenizer_amd.h states it, here in float64 with
 scipy.signal.lfilter and numpy: K-weighting (two biquads, coefficients computed for the clip's integer rate), blocks of 400 ms on a
@@ -8,7 +8,11 @@ the blocks that passed the first.
 
 The bound the GPU is held to is the error of the SAME definition evaluated with a sequential fp32 lfilter (fp32 coefficients,
 fp32 state, the squares summed in float64) against float64, or two fp32 ulps of the result where that is larger (the result is
-stored as fp32: half an ulp is spent on that alone).  The device runs the recurrence in fp64 and is expected far inside."""
+stored as fp32: half an ulp is spent on that alone).  The device runs the recurrence in fp64 and is expected far inside.
+
+A second, tighter bound (bound64; tests/test_loudness_rates.py) takes the fp32 lfilter out of it: two fp32 ulps plus four times
+the distance between the definition and a float64 stand-in of the device's chunked evaluation (weighted_chunked), measured per
+clip.  Where the fp32 lfilter is off by 10^-2 LU (content under the high pass at 96 kHz and above), that distance is 10^-7."""
 import ctypes
 import math
 
@@ -54,20 +58,100 @@ def lufs(z):
         return -0.691 + 10.0 * np.log10(z)
 
 
-def loudness(x, fs: int, dtype=np.float64):
+def weighted(x, fs: int, dtype=np.float64) -> np.ndarray:
+    """The K-weighted channels of x, (n,) or (C, n) with C <= 2, as (C, n): a sequential lfilter in dtype."""
+    x = np.atleast_2d(np.asarray(x))
+    assert x.shape[0] in (1, 2)
+    (b1, a1), (b2, a2) = kweight(fs)
+    out = []
+    for ch in x:
+        y = lfilter(b1.astype(dtype), a1.astype(dtype), ch.astype(dtype))
+        y = lfilter(b2.astype(dtype), a2.astype(dtype), y.astype(dtype))
+        assert y.dtype == dtype
+        out.append(y)
+    return np.stack(out)
+
+
+def _step(c, s, x):
+    """One sample through both biquads (transposed direct form II) for every column: s (4, K) moves on, the weighted samples return."""
+    y1 = c[0] * x + s[0]
+    s[0] = c[1] * x + s[1] - c[3] * y1
+    s[1] = c[2] * x - c[4] * y1
+    y2 = c[5] * y1 + s[2]
+    s[2] = c[6] * y1 + s[3] - c[8] * y2
+    s[3] = c[7] * y1 - c[9] * y2
+    return y2
+
+
+def weighted_chunked(x, fs: int, chunk: int) -> np.ndarray:
+    """The K-weighted channels of x as (C, n) in float64, evaluated the way the device orders the work, not the way the definition
+    reads: every chunk of `chunk` samples is walked from zero state; the end states z_k go through s_{k+1} = M s_k + z_k,
+    M = A^chunk, by a log-step scan with M^(2^i) inside groups of 64 chunks, the groups' totals are chained with M^64, the start
+    state of chunk 64 g + l is M^l carry_g + the scan's value of its left neighbour; then every chunk is walked again from its
+    start state.  Plain numpy products and sums (no fused multiply-add), all chunks of a channel at once: its distance from the
+    sequential float64 lfilter is what the reordering alone costs in float64 (bound64)."""
+    x = np.atleast_2d(np.asarray(x)).astype(np.float64)
+    assert x.shape[0] in (1, 2) and chunk >= 1 and chunk & (chunk - 1) == 0
+    c = coefficients10(fs)
+    A = np.zeros((4, 4))
+    for j in range(4):
+        s = np.zeros((4, 1))
+        s[j] = 1.0
+        _step(c, s, np.zeros(1))
+        A[:, j] = s[:, 0]
+    M = A
+    for _ in range(chunk.bit_length() - 1):
+        M = M @ M
+    P = [M]
+    for _ in range(6):
+        P.append(P[-1] @ P[-1])                                 # P[i] = M^(2^i); P[6] = M^64
+    n = x.shape[1]
+    K = -(-n // chunk)
+    G = -(-K // 64)
+    out = []
+    for ch in x:
+        xs = np.zeros(G * 64 * chunk)
+        xs[:n] = ch
+        xs = xs.reshape(G * 64, chunk).T                        # (chunk, chunks): one row per step of the walk
+        s = np.zeros((4, G * 64))
+        for t in range(chunk):
+            _step(c, s, xs[t])
+        s[:, K:] = 0.0                                          # (chunks past the clip carry nothing)
+        z = s.T.reshape(G, 64, 4).copy()
+        for i in range(6):
+            d = 1 << i
+            z[:, d:] = z[:, :-d] @ P[i].T + z[:, d:]
+        carry = np.zeros((G, 4))
+        run = np.zeros(4)
+        for g in range(G):
+            carry[g] = run
+            run = P[6] @ run + z[g, 63]
+        v = np.repeat(carry[:, None, :], 64, axis=1)            # M^l carry_g, l in binary
+        lane = np.arange(64)
+        for i in range(6):
+            bit = ((lane >> i) & 1).astype(bool)
+            v[:, bit] = v[:, bit] @ P[i].T
+        v[:, 1:] += z[:, :-1]
+        s = v.reshape(G * 64, 4).T.copy()
+        y = np.empty((chunk, G * 64))
+        for t in range(chunk):
+            y[t] = _step(c, s, xs[t])
+        out.append(y.T.reshape(-1)[:n])
+    return np.stack(out)
+
+
+def loudness(x, fs: int, dtype=np.float64, y=None):
     """(L, threshold, gated blocks, l_j (J,)) of x, (n,) or (C, n) with C <= 2; dtype is the filter's arithmetic (float64: the
-    definition; float32: the evaluation the bound is taken from)."""
+    definition; float32: the evaluation the bound is taken from); with y (C, n), the K-weighted channels are taken from there."""
     x = np.atleast_2d(np.asarray(x))
     assert x.shape[0] in (1, 2)
     n = x.shape[1]
-    (b1, a1), (b2, a2) = kweight(fs)
+    y = weighted(x, fs, dtype) if y is None else y
+    assert y.shape == x.shape
     J = blocks(n, fs)
     z = np.zeros(J, np.float64)
     for ch in range(x.shape[0]):
-        y = lfilter(b1.astype(dtype), a1.astype(dtype), x[ch].astype(dtype))
-        y = lfilter(b2.astype(dtype), a2.astype(dtype), y.astype(dtype))
-        assert y.dtype == dtype
-        q = y.astype(np.float64) ** 2
+        q = y[ch].astype(np.float64) ** 2
         for j in range(J):
             lo, hi = j * fs // 10, (j + 4) * fs // 10
             z[j] += q[lo:hi].sum() / (hi - lo)
@@ -89,6 +173,15 @@ def bound(want64: float, got32: float) -> float:
     if not math.isfinite(want64):
         return 0.0
     return max(abs(got32 - want64), 2.0 * ulp32(want64))
+
+
+def bound64(want64: float, standin64: float) -> float:
+    """What a value of a device that filters in fp64 may differ from float64 by: two fp32 ulps of the value (it is stored as fp32)
+    plus four times what the chunked evaluation in float64 (weighted_chunked) differs from the sequential one by (four: the
+    device's order of products and sums inside a step is not the stand-in's)."""
+    if not math.isfinite(want64):
+        return 0.0
+    return 2.0 * ulp32(want64) + 4.0 * abs(standin64 - want64)
 
 
 def gate_margin(x, fs: int) -> float:

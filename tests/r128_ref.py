@@ -13,7 +13,6 @@ import math
 
 import numpy as np
 import torch
-from scipy.signal import lfilter
 
 from tests import loudness_ref as R
 
@@ -32,11 +31,11 @@ def taps(F: int) -> np.ndarray:
     return (np.sinc((j - 24.0) / F) * 0.5 * (1.0 - np.cos(2.0 * np.pi * j / 48.0))).astype(np.float32)
 
 
-def true_peak(x, fs: int):
+def true_peak(x, fs: int, F: int = None):
     """(true peak, sample peak, bound) of x, (n,) or (C, n): linear, in float64 on the fp32 taps; bound is what an fp32 evaluation
-    of any interpolated value may differ from float64 by."""
+    of any interpolated value may differ from float64 by.  F: the oversampling factor where it is not to be the rate's."""
     x = np.atleast_2d(np.asarray(x)).astype(np.float64)
-    F = factor(fs)
+    F = factor(fs) if F is None else F
     sp = float(np.abs(x).max())
     if F == 1:
         return sp, sp, 0.0
@@ -76,20 +75,20 @@ def select(z_sorted: np.ndarray):
     return z_sorted[lo], z_sorted[hi]
 
 
-def short_term(x, fs: int, dtype=np.float64):
-    """(z_j, s_j) of the S windows of x, (n,) or (C, n); dtype is the filter's arithmetic, sums are float64."""
+def short_term(x, fs: int, dtype=np.float64, y=None):
+    """(z_j, s_j) of the S windows of x, (n,) or (C, n); dtype is the filter's arithmetic, sums are float64; with y (C, n), the
+    K-weighted channels are taken from there."""
     x = np.atleast_2d(np.asarray(x))
     n = x.shape[1]
-    (b1, a1), (b2, a2) = R.kweight(fs)
     S = short_term_blocks(n, fs)
     z = np.zeros(S, np.float64)
     if S == 0:
         return z, R.lufs(z)
+    y = R.weighted(x, fs, dtype) if y is None else y
+    assert y.shape == x.shape
     edges = np.array([j * fs // 10 for j in range(S + WINDOW)], dtype=np.int64)
     for ch in range(x.shape[0]):
-        y = lfilter(b1.astype(dtype), a1.astype(dtype), x[ch].astype(dtype))
-        y = lfilter(b2.astype(dtype), a2.astype(dtype), y.astype(dtype))
-        q = y.astype(np.float64) ** 2
+        q = y[ch].astype(np.float64) ** 2
         seg = np.add.reduceat(q[:edges[-1]], edges[:-1])
         win = np.convolve(seg, np.ones(WINDOW), "valid")        # 30 terms each (no running sum: a quiet window after loud ones would cancel)
         z += win[:S] / (edges[WINDOW:] - edges[:-WINDOW])[:S]

@@ -203,3 +203,24 @@ def test_the_reference_reads_the_standards_sine():
     # the bound: the fp32 evaluation's error, at least two ulps
     assert R.bound(-23.0, -23.0) == 2 * R.ulp32(-23.0) == 2.0 ** -18 and R.bound(-23.0, -23.001) == pytest.approx(0.001)
     assert R.bound(-math.inf, -math.inf) == 0.0
+
+
+def test_the_chunked_stand_in_is_the_sequential_filter_in_another_order():
+    """loudness_ref.weighted_chunked (what bound64 is taken from) against the sequential float64 lfilter: more than 64 groups of
+    64 chunks at 192 kHz on content under the high pass, where the carry across groups matters; a short stereo clip; a chunk of 32."""
+    from wavtokenizer_amd import _capi
+    C = int(_capi.lib.wt_loudness_chunk())
+    fs, n = 192000, 65 * 64 * C + 17
+    x = R.make_low_clip(n, fs, seed=5)
+    y, yc = R.weighted(x, fs), R.weighted_chunked(x, fs, C)
+    assert yc.shape == y.shape == (1, n) and yc.dtype == np.float64
+    assert np.abs(yc - y).max() <= 1e-7 * np.abs(y).max()
+    assert np.abs(yc - y).max() > 0                            # (another order: not the same text run twice)
+    L, Lc = R.loudness(x, fs)[0], R.loudness(x, fs, y=yc)[0]
+    assert 4.0 * abs(Lc - L) < R.ulp32(L)
+    s = np.stack([R.make_clip(3 * C + 5, seed=6), R.make_clip(3 * C + 5, seed=7)])
+    for chunk in (C, 32):
+        assert np.abs(R.weighted_chunked(s, 8001, chunk) - R.weighted(s, 8001)).max() <= 1e-12
+    # bound64: two ulps and four times the stand-in's distance
+    assert R.bound64(-23.0, -23.0) == 2.0 ** -18 and R.bound64(-23.0, -23.0 + 1e-7) == pytest.approx(2.0 ** -18 + 4e-7, rel=1e-6)
+    assert R.bound64(-math.inf, -math.inf) == 0.0

@@ -60,28 +60,45 @@ def cmnd(fr, dtype=np.float64):
     return dp
 
 
+def candidates(dp, threshold=THRESHOLD):
+    """[F][291]: the lags in [30, 320] under the threshold that are a local minimum (<= left, < right)."""
+    cur, le, ri = dp[:, LAG_LO:LAG_HI + 1], dp[:, LAG_LO - 1:LAG_HI], dp[:, LAG_LO + 1:LAG_HI + 2]
+    return (cur < threshold) & (cur <= le) & (cur < ri)
+
+
 def pick(dp, threshold=THRESHOLD):
     """Per frame the lag: the first in [30, 320] under the threshold that is a local minimum (<= left, < right), else the smallest
     lag that attains the minimum over the range."""
-    cur, le, ri = dp[:, LAG_LO:LAG_HI + 1], dp[:, LAG_LO - 1:LAG_HI], dp[:, LAG_LO + 1:LAG_HI + 2]
-    ok = (cur < threshold) & (cur <= le) & (cur < ri)
-    return LAG_LO + np.where(ok.any(axis=1), ok.argmax(axis=1), cur.argmin(axis=1))
+    ok = candidates(dp, threshold)
+    return LAG_LO + np.where(ok.any(axis=1), ok.argmax(axis=1), dp[:, LAG_LO:LAG_HI + 1].argmin(axis=1))
 
 
-def refine(dp, lag, dtype=np.float64):
-    """(f0, periodicity) of the parabola through d' at lag - 1, lag, lag + 1."""
+def parabola(dp, lag, dtype=np.float64):
+    """(a, b, c, den, off) of the parabola through d' at lag - 1, lag, lag + 1: off = 0 where den = a - 2 b + c is not positive."""
     i = np.arange(dp.shape[0])
     a, b, c = dp[i, lag - 1], dp[i, lag], dp[i, lag + 1]
     den = (a - dtype(2) * b + c).astype(dtype)
     with np.errstate(divide="ignore", invalid="ignore"):
         off = np.where(den > 0, np.clip((dtype(0.5) * (a - c)).astype(dtype) / den, -0.5, 0.5), 0).astype(dtype)
-    f0 = (dtype(RATE) / (lag.astype(dtype) + off)).astype(dtype)
+    return a, b, c, den, off
+
+
+def from_offset(lag, a, b, c, off, dtype=np.float64):
+    """(f0, periodicity) of a lag and an offset on its parabola."""
+    f0 = (dtype(RATE) / (np.asarray(lag).astype(dtype) + off)).astype(dtype)
     per = np.clip(dtype(1) - (b - (dtype(0.25) * (a - c)).astype(dtype) * off), 0, 1).astype(dtype)
     return f0, per
 
 
-def loudness(fr, dtype=np.float64):
-    """Per frame the mean over the 513 bins of max(10 log10 max(S, 1e-10), clip maximum - 80) + A - 20."""
+def refine(dp, lag, dtype=np.float64):
+    """(f0, periodicity) of the parabola through d' at lag - 1, lag, lag + 1."""
+    a, b, c, _, off = parabola(dp, lag, dtype)
+    return from_offset(lag, a, b, c, off, dtype)
+
+
+def loudness(fr, dtype=np.float64, one_frame_clips=False):
+    """Per frame the mean over the 513 bins of max(10 log10 max(S, 1e-10), clip maximum - 80) + A - 20; with one_frame_clips every
+    row of fr is a clip of its own, and the maximum is the row's."""
     if dtype == np.float64:
         X = np.fft.rfft(fr * window64()[None, :], axis=1)
         S = X.real ** 2 + X.imag ** 2
@@ -90,7 +107,7 @@ def loudness(fr, dtype=np.float64):
         X = torch.fft.rfft(torch.from_numpy((fr * window64().astype(dtype)[None, :]).astype(dtype)), dim=1)
         S = (X.real ** 2 + X.imag ** 2).numpy().astype(dtype)
     db = (dtype(10) * np.log10(np.maximum(S, dtype(1e-10)))).astype(dtype)
-    db = np.maximum(db, db.max() - dtype(80))
+    db = np.maximum(db, (db.max(axis=1, keepdims=True) if one_frame_clips else db.max()) - dtype(80))
     lv = ((db + a_weighting64().astype(dtype)[None, :]).astype(dtype) - dtype(20)).astype(dtype)
     return lv.mean(axis=1, dtype=dtype)
 
@@ -102,16 +119,33 @@ def gate(f0, per_raw, loud, silence=SILENCE, unvoiced=UNVOICED):
 
 
 class Track:
-    """Everything about one clip at one precision: dp, lag, f0_raw, per_raw, loud, f0 (NaN: unvoiced), per."""
+    """Everything about one clip at one precision: dp, lag, f0_raw, per_raw, loud, f0 (NaN: unvoiced), per.  With one_frame_clips x is
+    [N][1024]: N clips of one frame each, kept as the N frames of one track (the loudness floor is each clip's own).  d' and the
+    loudness do not depend on the thresholds: at() gives the track at other thresholds without computing them again."""
 
-    def __init__(self, x, dtype=np.float64, threshold=THRESHOLD, silence=SILENCE, unvoiced=UNVOICED):
-        fr = frames(x, dtype)
-        self.dp = cmnd(fr, dtype)
+    def __init__(self, x, dtype=np.float64, threshold=THRESHOLD, silence=SILENCE, unvoiced=UNVOICED, one_frame_clips=False):
+        if isinstance(x, Track):
+            dtype, self.dp, self.loud = x.dtype, x.dp, x.loud
+        elif isinstance(x, tuple):                                  # (dtype, d', loudness) of some frames of another track
+            dtype, self.dp, self.loud = x
+        else:
+            fr = np.asarray(x, dtype) if one_frame_clips else frames(x, dtype)
+            assert fr.ndim == 2 and fr.shape[1] == WIN
+            self.dp = cmnd(fr, dtype)
+            self.loud = loudness(fr, dtype, one_frame_clips)
+        self.dtype, self.n, self.setting = dtype, self.dp.shape[0], (threshold, silence, unvoiced)
         self.lag = pick(self.dp, dtype(threshold))
         self.f0_raw, self.per_raw = refine(self.dp, self.lag, dtype)
-        self.loud = loudness(fr, dtype)
+        _, _, _, self.den, self.off = parabola(self.dp, self.lag, dtype)
         self.f0, self.per = gate(self.f0_raw, self.per_raw, self.loud, dtype(silence), dtype(unvoiced))
-        self.n = fr.shape[0]
+        self.fallback = ~candidates(self.dp, dtype(threshold)).any(axis=1)        # no candidate: the minimum over the range
+
+    def at(self, threshold=THRESHOLD, silence=SILENCE, unvoiced=UNVOICED):
+        return Track(self, threshold=threshold, silence=silence, unvoiced=unvoiced)
+
+    def take(self, keep):
+        """The track of the frames keep alone (for a track of one-frame clips: of those clips), at the same thresholds."""
+        return Track((self.dtype, self.dp[keep], self.loud[keep]), self.dtype, *self.setting)
 
 
 def pair_metrics(f0, per, f0_hat, per_hat, dtype=np.float64):
@@ -148,40 +182,75 @@ def admissible_lags(dp_row, guard, threshold=THRESHOLD):
     return lags[ok | (cur <= cur.min() + guard)]
 
 
+DEN_GUARDS = 4.0                                # |den| and |a - c| are sums of three and two d' values: their guard is 4 x d's
+
+
+def answers(dp_row, lags, guard=None, got_f0=None):
+    """(f0, periodicity) arrays: the float64 answers of a frame at the given lags.  With a guard, a lag whose |den| = |a - 2 b + c|
+    lies within DEN_GUARDS x guard also gives the answers of off = 0 and off = 0.5 sign(a - c) (den may come out on either side of
+    0, and a tiny positive den drives the offset into its clamp), and, where |a - c| lies within DEN_GUARDS x guard as well, of the
+    offset in [-0.5, 0.5] nearest to the one got_f0 has at that lag (the quotient of two open numbers).  Pitch and periodicity of
+    one answer come from one offset."""
+    lags = np.asarray(lags)
+    dp = np.repeat(dp_row[None, :], len(lags), 0)
+    a, b, c, den, off = parabola(dp, lags)
+    sel, offs = [np.arange(len(lags))], [off]
+    if guard is not None:
+        o = np.nonzero(np.abs(den) <= DEN_GUARDS * guard)[0]
+        sel += [o, o]
+        offs += [np.zeros(len(o)), 0.5 * np.sign(a - c)[o]]
+        free = o[np.abs(a - c)[o] <= DEN_GUARDS * guard]
+        if got_f0 is not None and len(free):
+            sel.append(free)
+            offs.append(np.clip(RATE / float(got_f0) - lags[free], -0.5, 0.5))
+    sel, offs = np.concatenate(sel), np.concatenate(offs)
+    return from_offset(lags[sel], a[sel], b[sel], c[sel], offs)
+
+
 def decisions(t: "Track", guard, guard_db, threshold=THRESHOLD, silence=SILENCE, unvoiced=UNVOICED):
-    """Per frame of a float64 track: (lag_open, gate_open).  lag_open: more than one admissible lag inside guard (d' against the
-    threshold or a neighbour at a lag the search reaches, or a tie of the fallback minimum).  gate_open: the periodicity within
-    guard of unvoiced_threshold (for any admissible lag) or the loudness within guard_db of silence_threshold."""
-    lag_open, gate_open = np.zeros(t.n, bool), np.zeros(t.n, bool)
+    """Per frame of a float64 track: (lag_open, gate_open, den_open).  lag_open: more than one admissible lag inside guard (d' against
+    the threshold or a neighbour at a lag the search reaches, or a tie of the fallback minimum).  den_open: |den| of the parabola
+    within DEN_GUARDS x guard at an admissible lag (its sign decides between off = 0 and the quotient).  gate_open: the periodicity
+    of an admissible answer within guard of unvoiced_threshold or the loudness within guard_db of silence_threshold."""
+    lag_open, gate_open, den_open = np.zeros(t.n, bool), np.zeros(t.n, bool), np.zeros(t.n, bool)
     for f in range(t.n):
         adm = admissible_lags(t.dp[f], guard, threshold)
         lag_open[f] = len(adm) != 1 or adm[0] != t.lag[f]
-        pers = refine(np.repeat(t.dp[f][None, :], len(adm), 0), adm)[1] if lag_open[f] else t.per_raw[f:f + 1]
+        den = t.dp[f][adm - 1] - 2.0 * t.dp[f][adm] + t.dp[f][adm + 1]
+        den_open[f] = bool((np.abs(den) <= DEN_GUARDS * guard).any())
+        pers = answers(t.dp[f], adm, guard)[1]
+        if den_open[f]:                                             # (a free offset: the periodicity is linear in it, the ends bound it)
+            a, b, c = t.dp[f][adm - 1], t.dp[f][adm], t.dp[f][adm + 1]
+            pers = np.concatenate([pers] + [from_offset(adm, a, b, c, np.full(len(adm), o))[1] for o in (-0.5, 0.5)])
         gate_open[f] = bool((np.abs(pers - unvoiced) <= guard).any()) or abs(t.loud[f] - silence) <= guard_db
-    return lag_open, gate_open
+    return lag_open, gate_open, den_open
 
 
-def tap_errors(got_f0, got_per, got_loud, t: "Track", lag_open):
-    """(periodicity error, cents error, loudness error in dB): the largest over the frames; a frame with an open lag decision is
-    held against the admissible answer nearest to what it gave (per and cents), and every frame counts for the loudness."""
-    e_per, e_cents = 0.0, 0.0
+def frame_errors(got_f0, got_per, got_loud, t: "Track", lag_open, den_open=None, guard=None):
+    """Per frame ([3][F]: periodicity error, cents error, loudness error in dB) and the float64 values they were taken against
+    ([3][F]: periodicity, f0, loudness).  A frame with an open lag decision is held against the answer, of any lag, nearest to
+    what it gave (per and cents), one with an open den decision (den_open and its guard given) against the nearest of answers() at
+    its lag."""
+    want = np.stack([t.per_raw, t.f0_raw, t.loud]).astype(np.float64)
     for f in range(t.n):
-        if lag_open[f]:
-            lags = np.arange(LAG_LO, LAG_HI + 1)
-            f0s, pers = refine(np.repeat(t.dp[f][None, :], len(lags), 0), lags)
+        if lag_open[f] or (den_open is not None and den_open[f]):
+            lags = np.arange(LAG_LO, LAG_HI + 1) if lag_open[f] else t.lag[f:f + 1]
+            f0s, pers = answers(t.dp[f], lags, guard if den_open is not None else None, got_f0[f])
             k = int(np.abs(1200.0 * np.log2(float(got_f0[f]) / f0s)).argmin())
-            f0, per = f0s[k], pers[k]
-        else:
-            f0, per = t.f0_raw[f], t.per_raw[f]
-        e_per = max(e_per, abs(float(got_per[f]) - per))
-        e_cents = max(e_cents, abs(1200.0 * np.log2(float(got_f0[f]) / f0)))
-    return e_per, e_cents, float(np.abs(np.asarray(got_loud, np.float64) - t.loud).max())
+            want[0, f], want[1, f] = pers[k], f0s[k]
+    got_f0, got_per, got_loud = (np.asarray(v, np.float64) for v in (got_f0, got_per, got_loud))
+    return np.stack([np.abs(got_per - want[0]), np.abs(1200.0 * np.log2(got_f0 / want[1])), np.abs(got_loud - want[2])]), want
+
+
+def tap_errors(got_f0, got_per, got_loud, t: "Track", lag_open, den_open=None, guard=None):
+    """(periodicity error, cents error, loudness error in dB): the largest of frame_errors() over the frames."""
+    return tuple(float(v) for v in frame_errors(got_f0, got_per, got_loud, t, lag_open, den_open, guard)[0].max(axis=1))
 
 
 def admissible(got_f0, got_per_raw, f, t: "Track", guard, bar_per, bar_cents, threshold=THRESHOLD):
     """Whether frame f's (f0, ungated periodicity) is one of the answers its admissible lags give in float64, within the bars."""
     adm = admissible_lags(t.dp[f], guard, threshold)
-    f0s, pers = refine(np.repeat(t.dp[f][None, :], len(adm), 0), adm)
+    f0s, pers = answers(t.dp[f], adm, guard, got_f0[f])
     return bool(((np.abs(1200.0 * np.log2(float(got_f0[f]) / f0s)) <= bar_cents) & (np.abs(float(got_per_raw[f]) - pers) <= bar_per)).any())
 
 
@@ -306,31 +375,46 @@ BAR_FACTOR, GUARD_FACTOR, OPEN_CAP = 4.0, 10.0, 0.02
 class Cases:
     """The test signals with their float64 tracks, computed once: the bars of the three taps (BAR_FACTOR x what the fp32 stand-in
     reaches on these signals against float64), the guards (GUARD_FACTOR x the bars), the frames whose decisions lie inside them,
-    and the pairs (clip, twin) with the stand-in's pair error."""
+    and the pairs (clip, twin) with the stand-in's pair error.
+    With base (the cases at the default thresholds) and setting = (threshold, silence, unvoiced): the same signals at that setting.
+    d' and the loudness are the base's, as are the guards (the error of d' and of the loudness does not depend on a threshold);
+    the lags, the parabolas, the gates, the decisions, the stand-in's errors and with them the bars are the setting's own."""
 
-    def __init__(self, clips=CLIPS, snrs=SNRS):
-        self.signals, self.pairs = [], []
-        for T, seed in clips:
-            x = recipe(T, seed)
-            self.signals.append(x)
-            for snr in snrs:
-                self.pairs.append((len(self.signals) - 1 - snrs.index(snr), len(self.signals)))
-                self.signals.append(decoded(x, snr, seed))
-        self.t64 = [Track(x) for x in self.signals]
-        self.t32 = [Track(x, np.float32) for x in self.signals]
-        # the stand-in's errors, a frame where it found another lag held against the nearest answer
+    def __init__(self, clips=CLIPS, snrs=SNRS, setting=(THRESHOLD, SILENCE, UNVOICED), base=None):
+        self.setting = tuple(setting)
+        if base is None:
+            self.signals, self.pairs = [], []
+            for T, seed in clips:
+                x = recipe(T, seed)
+                self.signals.append(x)
+                for snr in snrs:
+                    self.pairs.append((len(self.signals) - 1 - snrs.index(snr), len(self.signals)))
+                    self.signals.append(decoded(x, snr, seed))
+            self.t64 = [Track(x, np.float64, *setting) for x in self.signals]
+            self.t32 = [Track(x, np.float32, *setting) for x in self.signals]
+        else:
+            self.signals, self.pairs = base.signals, base.pairs
+            self.t64, self.t32 = [t.at(*setting) for t in base.t64], [t.at(*setting) for t in base.t32]
+            self.guard, self.guard_db = base.guard, base.guard_db
+            opened = [decisions(t, self.guard, self.guard_db, *setting) for t in self.t64]
+        # the stand-in's errors, a frame where it found another lag held against the nearest answer (and at a setting of its own,
+        # where the guards are known beforehand, a frame with an open den against the nearest of its answers)
         flipped = [a.lag != b.lag for a, b in zip(self.t64, self.t32)]
-        worst = np.max([tap_errors(s.f0_raw, s.per_raw, s.loud, t, fl) for t, s, fl in zip(self.t64, self.t32, flipped)], axis=0)
+        den = [None] * len(flipped) if base is None else [o[2] for o in opened]
+        worst = np.max([tap_errors(s.f0_raw, s.per_raw, s.loud, t, fl, d, None if base is None else self.guard)
+                        for t, s, fl, d in zip(self.t64, self.t32, flipped, den)], axis=0)
         self.standin = tuple(float(v) for v in worst)
         self.bar_per, self.bar_cents, self.bar_db = (BAR_FACTOR * v for v in self.standin)
-        self.guard, self.guard_db = GUARD_FACTOR * self.bar_per, GUARD_FACTOR * self.bar_db
-        opened = [decisions(t, self.guard, self.guard_db) for t in self.t64]
-        self.lag_open, self.gate_open = [o[0] for o in opened], [o[1] for o in opened]
-        self.open = [a | b for a, b in opened]
+        if base is None:
+            self.guard, self.guard_db = GUARD_FACTOR * self.bar_per, GUARD_FACTOR * self.bar_db
+            opened = [decisions(t, self.guard, self.guard_db, *setting) for t in self.t64]
+        self.lag_open, self.gate_open, self.den_open = ([o[k] for o in opened] for k in range(3))
+        self.open = [a | b | c for a, b, c in opened]
+        self.new_den_open = [int((c & ~(a | b)).sum()) for a, b, c in opened]    # frames that only the den decision opens
         self.standin_flips_covered = all(bool((lo | ~fl).all()) for lo, fl in zip(self.lag_open, flipped))
         self.open_fraction = [float(o.mean()) for o in self.open]
         # the stand-in's pair error: its fp32 reduction of its own tracks against float64 on its decisions at the open frames
-        self.standin_pair = np.zeros(3)
+        self.standin_pair, self.base_standin_pair = np.zeros(3), (np.zeros(3) if base is None else base.standin_pair)
         for i, j in self.pairs:
             got = pair_metrics(self.t32[i].f0, self.t32[i].per, self.t32[j].f0, self.t32[j].per, np.float32)
             self.standin_pair = np.maximum(self.standin_pair, metric_error(got, self.pair_want(i, j, self.t32[i], self.t32[j])))
@@ -342,11 +426,128 @@ class Cases:
         return pair_metrics(f0, per, g0, qer)
 
     def pair_bar(self, want):
-        """BAR_FACTOR x the stand-in's pair error, and never under BAR_FACTOR half-units of fp32 at the value: the result is an fp32."""
+        """BAR_FACTOR x the stand-in's pair error, and never under BAR_FACTOR half-units of fp32 at the value: the result is an fp32.
+        At a setting of its own the stand-in's pair error is the larger of the setting's and the default thresholds': the error
+        of an fp32 reduction over the same six pairs does not depend on a threshold, each figure is the largest of six samples
+        of it (3.6e-5 .. 1.6e-4 cents over the grid where the taps err alike), and the default one is the yardstick these pairs
+        have in tests/test_pitch_op.py; a setting whose taps err more (threshold 10: lag 30 in noise) adds its own."""
         want = np.where(np.isnan(want), 0.0, np.abs(want))
-        return BAR_FACTOR * np.maximum(self.standin_pair, 2.0 ** -24 * want)
+        return BAR_FACTOR * np.maximum(np.maximum(self.standin_pair, self.base_standin_pair), 2.0 ** -24 * want)
 
 
 @functools.lru_cache(maxsize=None)
 def cases():
     return Cases()
+
+
+# (threshold, silence, unvoiced) of the threshold grid: the fallback on every frame and on none, thresholds around the default,
+# and gates that silence most of a clip, voice everything and voice nothing
+SETTINGS = ((0.0, -60.0, 0.5), (0.05, -60.0, 0.5), (0.3, -60.0, 0.5), (1.0, -60.0, 0.5), (10.0, -60.0, 0.5),
+            (0.15, -40.0, 0.21), (0.15, -80.0, 0.9), (0.15, -50.0, 0.0), (0.15, -70.0, 1.0))
+
+
+@functools.lru_cache(maxsize=None)
+def cases_at(setting):
+    return Cases(setting=setting, base=cases())
+
+
+# ------------------------------------------------------------------------------------------------ every lag and the range's edges
+EVERY = dict(silence=-1e30, unvoiced=-1.0)      # a call in which no frame is silent or unvoiced: f0 is the raw pitch of every frame
+
+
+def edge_tone(period, seed, K, noise=2e-3, T=WIN):
+    """K partials 0.3 / k of a tone with the given period in samples, phases drawn in order, over white noise."""
+    rng = np.random.default_rng(seed)
+    n = np.arange(T, dtype=np.float64)
+    x = np.zeros(T)
+    for k in range(1, K + 1):
+        x += 0.3 / k * np.sin(2.0 * np.pi * k * n / period + rng.uniform(0, 2.0 * np.pi))
+    return (x + noise * rng.standard_normal(T)).astype(np.float32)
+
+
+# (period, seed, K).  The sweep: the .3 / .8 fractions keep d'(P) and d'(P +- 1) apart (at .0 / .5 nearly half of the frames tie);
+# periods under 30 resolve to their subharmonic, periods past 320.5 to lag 320 with the offset in its clamp.  The pool of low tones
+# (11.4 .. 49.8 Hz, under the search range): d' is nearly straight at lag 320 and den about 1e-6, of either sign.
+SWEEP = tuple((28.8 + 0.5 * i, 100 + i, 3) for i in range(591))
+LOW_POOL = tuple((float(p), 5000 + p, 1) for p in range(LAG_HI + 1, 1401))
+HALF_UNIT = 2.0 ** -24                          # of fp32, relative: the least a bar may be is BAR_FACTOR of these at the value
+
+
+class EdgeSet:
+    """One-frame clips (edge_tone) as one track of N frames in float64 and in the fp32 stand-in, with the decisions under the
+    recipe clips' guards in a call in which nothing is gated (EVERY).  sure_only keeps the clips whose frame is sure under every
+    guard (the selection runs here, from the pool, every time) and remembers what the pool showed.  The bars are the set's own:
+    BAR_FACTOR x the stand-in's error on the set, never under BAR_FACTOR half-units of fp32 at the value."""
+
+    def __init__(self, tones, recipe: "Cases", sure_only=False):
+        self.guard, self.guard_db = guard, guard_db = recipe.guard, recipe.guard_db
+        self.signals = [edge_tone(*t) for t in tones]
+        self.t64 = Track(np.stack(self.signals), one_frame_clips=True, **EVERY)
+        self.t32 = Track(np.stack(self.signals), np.float32, one_frame_clips=True, **EVERY)
+        self.lag_open, self.gate_open, self.den_open = decisions(self.t64, guard, guard_db, THRESHOLD, **EVERY)
+        self.pool_n = len(tones)
+        same = self.t32.lag == self.t64.lag
+        self.pool_den_flips = same & ((self.t32.den > 0) != (self.t64.den > 0))      # the stand-in's den on the other side of 0
+        self.pool_den_flips_covered = bool((self.den_open | ~self.pool_den_flips).all())
+        self.pool_den_near = int((np.abs(self.t64.den) <= DEN_GUARDS * guard).sum())
+        if sure_only:
+            keep = np.nonzero(~(self.lag_open | self.gate_open | self.den_open))[0]
+            self.signals = [self.signals[k] for k in keep]
+            self.t64, self.t32 = self.t64.take(keep), self.t32.take(keep)
+            self.lag_open, self.gate_open, self.den_open = self.lag_open[keep], self.gate_open[keep], self.den_open[keep]
+        self.open = self.lag_open | self.gate_open | self.den_open
+        self.sure = ~self.open
+        self.flipped = self.t32.lag != self.t64.lag
+        self.standin_flips_covered = bool((self.lag_open | ~self.flipped).all())
+        err, _ = frame_errors(self.t32.f0_raw, self.t32.per_raw, self.t32.loud, self.t64, self.lag_open | self.flipped, self.den_open, guard)
+        self.standin = tuple(float(v) for v in err.max(axis=1))
+        # a set cannot buy itself a looser bar than the recipe clips': where its stand-in errs more, the recipe's error sets the bar
+        # (the loudness does, by a percent or by a quarter from one CPU to the next: its stand-in is the platform's fp32 FFT, and
+        # the largest of a few hundred frames' errors moves with the frames)
+        self.recipe_standin = recipe.standin
+        self.bar_base = np.minimum(np.array(self.standin), np.array(recipe.standin))
+
+    def errors(self, got_f0, got_per, got_loud):
+        """([3][N] errors of a result against float64, [3][N] bars): periodicity, cents, loudness in dB; the open frames against
+        the nearest of their admissible answers."""
+        err, want = frame_errors(got_f0, got_per, got_loud, self.t64, self.lag_open, self.den_open, self.guard)
+        units = np.stack([np.abs(want[0]), np.full(self.t64.n, 1200.0 / np.log(2.0)), np.abs(want[2])]) * HALF_UNIT
+        return err, BAR_FACTOR * np.maximum(self.bar_base[:, None], units)
+
+    def not_admissible(self, got_f0, got_per):
+        """The open frames whose answer is none of those their admissible lags give, within the bars."""
+        _, bars = self.errors(self.t64.f0_raw, self.t64.per_raw, self.t64.loud)
+        return [int(f) for f in np.nonzero(self.open)[0]
+                if not admissible(got_f0, got_per, f, self.t64, self.guard, bars[0, f], bars[1, f])]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep():
+    return EdgeSet(SWEEP, cases())
+
+
+@functools.lru_cache(maxsize=None)
+def low_tones():
+    return EdgeSet(LOW_POOL, cases(), sure_only=True)
+
+
+TIE_LAGS = (31, 35, 36, 97, 319, 320)           # the first and the last lag of a lane (the neighbour comes from another lane), the range's end
+
+
+def tie_clip(lag):
+    """One frame of zeros with one sample of 0.5 at 703 + lag.  Every number of the search is exact in any precision: d is 0 up to
+    the lag and 0.25 behind it, so d' is 1 (the rule for a running sum of 0) up to the lag, lag + 1 at lag + 1, and falls from
+    there towards 1 without a local minimum.  Under a threshold over 1 the one candidate is the lag itself, on d'(lag) <=
+    d'(lag - 1) with both sides equal and d'(lag) < d'(lag + 1); the parabola gives off = -0.5 and a periodicity clipped to 1.
+    (At lag 320 the right neighbour is d'(321).)  A search that wants d'(lag) < d'(lag - 1) finds no candidate and falls back to
+    lag 30, the smallest lag at the minimum."""
+    x = np.zeros(WIN, np.float32)
+    x[TERMS + lag] = 0.5
+    return x
+
+
+def pr_zero_pair():
+    """(reference, estimate), 34 frames: a sweep-like tone of 2400 samples and 4000 of near-silence, in the two orders.  The reference
+    is voiced in its first frames only and the estimate in its last: TP = 0, FP > 0, FN > 0."""
+    tone_, quiet = edge_tone(100.3, 7, 3, T=2400), (1e-5 * np.random.default_rng(9).standard_normal(4000)).astype(np.float32)
+    return np.concatenate([tone_, quiet]), np.concatenate([quiet, tone_])

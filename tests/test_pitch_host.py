@@ -213,3 +213,109 @@ def test_reference_recipe_moves_all_three_outputs():
     good, bad = R.periodicity_metrics64(x, R.decoded(x, 30, 0)), R.periodicity_metrics64(x, R.decoded(x, 0, 0))
     assert good[2] == 1.0 and good[1] < 1.0 and good[0] < 0.06
     assert 0.8 < bad[2] < 0.99 and bad[1] > 100.0 and bad[0] > 0.2
+
+
+# ------------------------------------------------------------------------------------------------ what tests/test_pitch_range.py rests on
+def test_reference_recipe_clips_show_no_frame_opened_by_the_den_decision_alone():
+    c = R.cases()
+    assert c.new_den_open == [0] * len(c.signals) and min(float(np.abs(t.den).min()) for t in c.t64) > 10 * R.DEN_GUARDS * c.guard
+    assert c.standin_flips_covered and max(c.open_fraction) <= R.OPEN_CAP
+
+
+def test_reference_sweep_reaches_every_lag_with_a_sure_frame():
+    s, c = R.sweep(), R.cases()
+    t, sure = s.t64, s.sure
+    assert t.n == 591 and set(t.lag[sure].tolist()) == set(range(R.LAG_LO, R.LAG_HI + 1))           # 291 distinct sure lags
+    assert int((sure & (t.lag == R.LAG_HI)).sum()) >= 5 and int((sure & (t.lag == R.LAG_LO)).sum()) >= 2
+    assert int((sure & (t.off == 0.5)).sum()) >= 5 and float(s.open.mean()) <= R.OPEN_CAP
+    assert tuple(t.lag[:2]) == (58, 59)                             # periods 28.8 and 29.3: under the range, found as their subharmonics
+    assert not s.flipped.any() and s.standin_flips_covered and s.pool_den_flips_covered
+    # the stand-in errs no more here than on the recipe clips: the YIN taps, whose arithmetic is numpy's own.  The loudness stand-in
+    # is the platform's fp32 FFT, and the largest of some hundred frames' errors lands on either side of the recipe clips' from one
+    # CPU to the next (1.005 and 1.29 times it on two machines): there the bar is held to the smaller of the two instead (EdgeSet)
+    assert s.standin[0] <= c.standin[0] and s.standin[1] <= c.standin[1], (s.standin, c.standin)
+    assert bool((s.bar_base <= np.array(c.standin)).all()) and bool((s.bar_base <= np.array(s.standin)).all())
+
+
+def test_reference_low_tones_take_both_clamps_and_the_den_not_positive_branch():
+    s, c = R.low_tones(), R.cases()
+    t = s.t64
+    assert s.pool_n == 1080 and t.n >= 100 and bool(s.sure.all())
+    assert int((t.den < 0).sum()) >= 30 and int((t.off == 0.5).sum()) >= 20 and int((t.off == -0.5).sum()) >= 20
+    assert bool((t.off[t.den < 0] == 0).all()) and bool(((t.den < 0) | (np.abs(t.off) == 0.5)).all())
+    assert set(t.lag.tolist()) == {R.LAG_LO, R.LAG_HI} and bool(t.fallback.all())
+    assert not s.flipped.any() and s.standin_flips_covered
+    # the pool is where the stand-in's den falls on the other side of 0: every such frame lies inside the den guard, and so is left out
+    assert int(s.pool_den_flips.sum()) >= 1 and s.pool_den_flips_covered and s.pool_den_near > s.pool_n // 2
+    assert s.standin[0] <= c.standin[0] and s.standin[1] <= c.standin[1], (s.standin, c.standin)           # (the loudness: as above)
+    assert bool((s.bar_base <= np.array(c.standin)).all()) and bool((s.bar_base <= np.array(s.standin)).all())
+
+
+def test_reference_den_decision_gives_the_answers_on_both_sides():
+    """A d' that falls in a straight line to lag 320, as under a tone below the range, bent by 1e-6 at lag 321 either way: float64
+    gives the clamp or off = 0, the frame is den_open, and it is held against off = 0 and the clamp on the side of a - c alone."""
+    c = R.cases()
+    for eps, off64 in ((1e-6, 0.5), (-1e-6, 0.0), (0.0, 0.0)):
+        dp = (1.5 - 0.002 * np.arange(R.MAX_LAG + 1))[None, :].copy()
+        dp[0, R.MAX_LAG] += eps
+        t = R.Track((np.float64, dp, np.zeros(1)), np.float64, R.THRESHOLD, **R.EVERY)
+        assert t.lag[0] == R.LAG_HI and t.fallback[0] and t.off[0] == off64 and abs(t.den[0] - eps) < 1e-12
+        lag_open, gate_open, den_open = R.decisions(t, c.guard, c.guard_db, R.THRESHOLD, **R.EVERY)
+        assert den_open[0] and not lag_open[0] and not gate_open[0]
+        for off, ok in ((0.0, True), (0.5, True), (-0.5, False), (0.25, False)):
+            f0, per = R.from_offset(t.lag, dp[:, 319], dp[:, 320], dp[:, 321], off)
+            e = R.tap_errors(f0, per, t.loud, t, lag_open, den_open, c.guard)
+            assert (e[0] < 1e-12 and e[1] < 1e-9) == ok and R.admissible(f0, per, 0, t, c.guard, c.bar_per, c.bar_cents) == ok, (eps, off, e)
+        if off64:                                                   # without the den decision the clamp is the one answer
+            f0, per = R.from_offset(t.lag, dp[:, 319], dp[:, 320], dp[:, 321], 0.0)
+            assert R.tap_errors(f0, per, t.loud, t, lag_open)[1] > 2.0            # 2.7 cents at lag 320
+    # a - c within its guard as well: the quotient of two open numbers, any offset in [-0.5, 0.5], pitch and periodicity from one
+    dp = np.full((1, R.MAX_LAG + 1), 0.9)
+    dp[0, R.LAG_LO - 1:R.LAG_LO + 2] = (0.80006, 0.8, 0.80005)
+    t = R.Track((np.float64, dp, np.zeros(1)), np.float64, R.THRESHOLD, **R.EVERY)
+    lag_open, _, den_open = R.decisions(t, c.guard, c.guard_db, R.THRESHOLD, **R.EVERY)
+    assert t.lag[0] == R.LAG_LO and den_open[0] and not lag_open[0]
+    for off in (-0.5, -0.2, 0.0, 0.37, 0.5):
+        f0, per = R.from_offset(t.lag, dp[:, R.LAG_LO - 1], dp[:, R.LAG_LO], dp[:, R.LAG_LO + 1], off)
+        e = R.tap_errors(f0, per, t.loud, t, lag_open, den_open, c.guard)
+        assert e[0] < 1e-12 and e[1] < 1e-9, (off, e)
+        assert R.tap_errors(f0, per + 1e-4, t.loud, t, lag_open, den_open, c.guard)[0] > 9e-5
+
+
+@pytest.mark.parametrize("setting", R.SETTINGS)
+def test_reference_threshold_grid_keeps_the_open_frames_under_the_cap(setting):
+    c = R.cases_at(setting)
+    assert max(c.open_fraction) <= R.OPEN_CAP, c.open_fraction
+    assert c.standin_flips_covered and c.guard == R.cases().guard
+    threshold, silence, unvoiced = setting
+    if threshold == 0.0:
+        assert all(bool(t.fallback.all()) for t in c.t64)
+    if threshold == 10.0:
+        assert not any(bool(t.fallback.any()) for t in c.t64) and int(((c.t64[3].lag == R.LAG_LO) & ~c.open[3]).sum()) >= 5
+    if setting == (0.15, -40.0, 0.21):
+        assert float((c.t64[0].loud < silence).mean()) > 0.5
+    if unvoiced == 1.0:
+        assert all(bool(np.isnan(t.f0).all()) for t in c.t64)
+        assert all(np.isnan(R.pair_metrics(c.t64[i].f0, c.t64[i].per, c.t64[j].f0, c.t64[j].per)[1:]).all() for i, j in c.pairs)
+
+
+def test_reference_pair_with_precision_and_recall_zero():
+    c = R.cases()
+    ref, est = R.pr_zero_pair()
+    a, b = R.Track(ref), R.Track(est)
+    va, vb = ~np.isnan(a.f0), ~np.isnan(b.f0)
+    assert not any(np.logical_or.reduce(R.decisions(t, c.guard, c.guard_db)).any() for t in (a, b))
+    assert a.n == 34 and int((va & vb).sum()) == 0 and int((~va & vb).sum()) > 0 and int((va & ~vb).sum()) > 0
+    m = R.pair_metrics(a.f0, a.per, b.f0, b.per)
+    assert m[0] > 0.5 and np.isnan(m[1]) and np.isnan(m[2])
+
+
+def test_reference_tie_clips_rest_on_the_left_neighbour_being_allowed_to_tie():
+    x = np.stack([R.tie_clip(lag) for lag in R.TIE_LAGS])
+    for dtype in (np.float64, np.float32):
+        t = R.Track(x, dtype, threshold=10.0, one_frame_clips=True, **R.EVERY)
+        assert tuple(t.lag) == R.TIE_LAGS and not t.fallback.any() and bool((t.off == -0.5).all()) and bool((t.per_raw == 1).all())
+        for k, lag in enumerate(R.TIE_LAGS):
+            assert bool((t.dp[k, 1:lag + 1] == 1).all()) and t.dp[k, lag + 1] == lag + 1 and bool((np.diff(t.dp[k, lag + 1:]) < 0).all())
+        strict = R.candidates(t.dp, dtype(10.0)) & (t.dp[:, R.LAG_LO:R.LAG_HI + 1] < t.dp[:, R.LAG_LO - 1:R.LAG_HI])
+        assert not strict.any()                                     # with < on the left there is no candidate at all: lag 30 by the fallback

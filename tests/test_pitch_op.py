@@ -4,9 +4,9 @@ workspace pre-filled, against the float64 definition (tests/pitch_ref.py).
 The bars are measured, never taken from the kernel: per tap (ungated periodicity, f0 in cents, loudness in dB) 4 x what the fp32
 stand-in of tests/pitch_ref.py reaches against float64 on the same signals on the CPU (the factor covers a different but fixed
 summation order).  A frame whose float64 margin to a decision (d' against the threshold or a neighbour, a tie of the fallback
-minimum, the periodicity against unvoiced_threshold, the loudness against silence_threshold) lies inside a guard of 10 x the bar may
-come out either way: it is held against the admissible answers only, and the float64 pair metrics take the kernel's decisions at
-such frames.  At most 2 % of a clip's frames may be treated so: above that the test fails.
+minimum, the parabola's den against 0, the periodicity against unvoiced_threshold, the loudness against silence_threshold) lies
+inside a guard of 10 x the bar (4 guards for den, a sum of three d') may come out either way: it is held against the admissible
+answers only, and the float64 pair metrics take the kernel's decisions at such frames.  At most 2 % of a clip's frames may be treated so: above that the test fails.
 Measured on an MI355X: profiles/pitch_error.txt."""
 from types import SimpleNamespace
 
@@ -28,6 +28,7 @@ def cases():
     assert 1e-7 < c.standin[0] < 1e-5 and c.standin[1] < 0.05 and 1e-7 < c.standin[2] < 1e-3
     assert c.standin_flips_covered                                  # the stand-in itself changes its mind at open frames only
     assert max(c.open_fraction) <= R.OPEN_CAP, c.open_fraction
+    assert c.new_den_open == [0] * len(c.signals)                   # the sign of the parabola's den is open at no frame of its own
     return c
 
 
@@ -98,11 +99,11 @@ def test_lengths_at_the_frame_edges(cases):
     assert intact and [len(g[0]) for g in got] == [1, 1, 2, 63, 64, 64]
     for c, (f0, per, raw, loud) in zip(clips, got):
         t = R.Track(c)
-        lag_open, gate_open = R.decisions(t, cases.guard, cases.guard_db)
+        lag_open, gate_open, den_open = R.decisions(t, cases.guard, cases.guard_db)
         f0_raw = np.where(np.isnan(f0), t.f0_raw, f0)
-        e = R.tap_errors(f0_raw, raw, loud, t, lag_open)
+        e = R.tap_errors(f0_raw, raw, loud, t, lag_open, den_open, cases.guard)
         assert e[0] <= cases.bar_per and e[1] <= cases.bar_cents and e[2] <= cases.bar_db, (len(c), e)
-        sure = ~(lag_open | gate_open)
+        sure = ~(lag_open | gate_open | den_open)
         assert np.array_equal(np.isnan(f0)[sure], np.isnan(t.f0)[sure]), len(c)
     # a frame's YIN values depend on its 1024 samples alone (the loudness does not: the floor is the clip's)
     assert np.array_equal(got[0][2], got[2][2][:1]) and np.array_equal(got[3][2], got[4][2][:63]) and np.array_equal(got[4][2], got[5][2])

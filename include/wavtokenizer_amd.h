@@ -127,7 +127,9 @@ enum {
                                       operands below the f16 limit 65504.  Costs a pass per buffer; never graph-replayed */
     WT_PLAN_FLAG_MIXED_LENGTH = 64,/* WT_PLAN_ENCODE: clips of different lengths in one call (wt_encode_mixed); `len` is the padded
                                       length.  Only the shipped route takes it: refused together with UNFUSED, FP32_GEMM,
-                                      KEEP_STAGES or RANGE_REPORT, with the encoder site on fp32, or for weights without S32 copies */
+                                      KEEP_STAGES or RANGE_REPORT, with the encoder site on fp32, for weights without S32 copies,
+                                      or for a model whose first encoder ratio (the last of `ratios`) is neither 2 nor 4: the
+                                      stage-1 kernel that holds the down conv is the one that takes per-clip lengths */
     WT_PLAN_FLAG_F16_GEMM = 128,   /* the decode kinds (WT_PLAN_DECODE, _MIXED, _CODES, _CODES_MIXED): half-precision inference mode for
                                       callers that hold codes and want audio.  Every dense layer that runs on split-f16 operands
                                       multiplies their f16 hi halves alone: one f16 MFMA per product instead of three, fp32
@@ -160,7 +162,12 @@ const char* wt_version(void);
 
 /* Replaces: WavTokenizer.from_pretrained0802's load_state_dict (decoder/pretrained.py:95-114)
  * plus the weight_norm pre-forward hook of every SConv1d (encoder/modules/conv.py:25-34), done
- * once here: w = g * v / ||v||.  Copies, folds and packs the weights into HBM on `device`. */
+ * once here: w = g * v / ||v||.  Copies, folds and packs the weights into HBM on `device`.
+ * Architectures taken: four ratios of 1 .. 16 each (a down conv has 2 * ratio taps, the GEMM kernels gather 32); num_quantizers 1 .. 32; input_channels 512; dim 256, 512, 768 or 1024;
+ * intermediate_dim a multiple of 32; num_layers 1 .. 32; adanorm_num_embeddings >= 1; vq_bins a multiple of 4; n_fft % 4 == 0,
+ * a multiple of hop_length with n_fft - hop_length even.  Anything else is refused here (and by wt_model_create_packed and
+ * wt_packed_info) with WT_ERR_INVALID and a message that names the field, before any HIP call: an architecture that loads has
+ * kernels for every step of every plan. */
 int  wt_model_create(const wt_arch* arch, const wt_tensor* tensors, int32_t n_tensors, int32_t device,
                      wt_model** out);
 void wt_model_destroy(wt_model* m);

@@ -31,9 +31,14 @@ class _BatchedCalls:
         """Whether the side of the model that plan kind belongs to runs the route a mixed-length plan takes (the shipped split-f16
         one): no fp32 GEMMs, no unfused debug plan, no debug taps or range report, none of the kind's range sites on fp32, and
         weights that fit the split-f16 form (the conditions build_encode / build_decode check; a plan refused in spite of them
-        is an error, not a fallback).  set_gemm_precision("f16") is on the route: the mixed plans launch the same GEMMs."""
+        is an error, not a fallback).  set_gemm_precision("f16") is on the route: the mixed plans launch the same GEMMs.
+        The encoder side also needs the architecture's first stage on the kernel that holds its down conv (resblock16.hip: a
+        first encoder ratio of 2 or 4): it is the one stage-1 form that takes per-clip lengths, so a model with another first
+        ratio (a build_encode condition like the rest) encodes its clips one at a time."""
         off_route = (_capi.WT_PLAN_FLAG_FP32_GEMM | _capi.WT_PLAN_FLAG_UNFUSED | _capi.WT_PLAN_FLAG_KEEP_STAGES |
                      _capi.WT_PLAN_FLAG_RANGE_REPORT)
+        if kind == _capi.WT_PLAN_ENCODE and self._arch.enc_ratios[0] not in (2, 4):
+            return False
         return not (self._plan_flags & off_route) and not self._sites(kind) and bool(lib.wt_model_split_ok(self._engine.model))
 
     def _guarded_mixed(self, kind: int, B: int, thunk, dev: torch.device):
@@ -116,7 +121,9 @@ class _BatchedCalls:
         same bits as encode_infer(wavs[i][None]).  Clips are sorted by length and grouped (mixed_length.group_clips: at most
         64 per call, padded to a coarse bucket so that calls share plans and graphs); clips shorter than the mixed-length
         plan's minimum, and every clip while the encoder runs off its shipped route (set_gemm_precision("f32"), an fp32
-        encoder site after a range fallback, the unfused debug plans), run one at a time through encode_infer."""
+        encoder site after a range fallback, the unfused debug plans), run one at a time through encode_infer.  So does every
+        clip of a model whose first encoder ratio (the last of arch.ratios) is neither 2 nor 4: the mixed-length plan needs the
+        stage-1 kernel that holds the down conv (_route_ok)."""
         from .mixed_length import group_clips
         dev = self._ensure_engine()
         self._check_bandwidth(bandwidth_id)
@@ -343,7 +350,8 @@ class _BatchedCalls:
         Per group of encode_infer_many's grouping (on the resampled lengths): one upload of the group's CPU clips, one ragged
         ingest launch, one mixed-length encode without a feature tensor, one launch that hands out the codes.  Clips under the
         mixed-length plans' minimum, and every clip while the encoder is off its shipped route, are ingested the same way and
-        encoded one at a time.  Argument errors raise ValueError before any GPU work.
+        encoded one at a time; a model whose first encoder ratio (the last of arch.ratios) is neither 2 nor 4 is always off it
+        (_route_ok: no stage-1 kernel that takes per-clip lengths).  Argument errors raise ValueError before any GPU work.
         n_q, an int in [1, num_quantizers]: residual VQ with the first n_q codebooks, clip i's codes the bits of
         encode_codes(..., n_q=n_q).  Returns [codes (n_q, 1, L_i)], views into one flat tensor laid out [n_q][sum L_i];
         packed=True returns (that tensor as (n_q, sum L_i), offsets).  Per group one ingest, one mixed-length residual VQ encode

@@ -501,7 +501,14 @@ static int launch16s_tiled(const GemmArgs& a, hipStream_t s) {
             case 9: return launch16s_form<HI, 128, 64, 4, 1, 3, EPI, OUT>(a, s);
             default: break;
         }
-        if (a.N <= 64) return launch16s_form<HI, 256, 64, 8, 1, 3, EPI, OUT>(a, s);      // narrow outputs (down conv 1)
+        if (a.N <= 64) {      // narrow outputs (down conv 1)
+            // the 256-row tile's two [taps][256] offset tables fit beside its stages and bias cache up to 19 taps; a stage-1 down
+            // conv of more (a first encoder ratio of 10 .. 16 off the fused kernel) takes the 128-row tile, which holds 32
+            const size_t need = 3ull * (256 + 64) * 128 + 2ull * a.taps * 256 * sizeof(unsigned) + (a.A2 ? 2ull * 256 * sizeof(unsigned) : 0) +
+                                2048;      // (launch16s_one's smem and pc_bytes of this form)
+            if (need <= 160 * 1024) return launch16s_form<HI, 256, 64, 8, 1, 3, EPI, OUT>(a, s);
+            return launch16s_form<HI, 128, 64, 4, 1, 3, EPI, OUT>(a, s);
+        }
         // a handful of clips (M of a few hundred rows): with 128-column tiles fewer than 32 CUs would each walk the whole
         // K loop alone, so the problem is cut into 32-column tiles instead (4x the workgroups, a third of the work per
         // K step).  Every tile shape accumulates K in the same order: results do not depend on the choice

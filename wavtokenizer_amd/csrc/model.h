@@ -365,6 +365,7 @@ size_t model_export_bytes(const wt_model* M);
 int model_export(const wt_model* M, void* buf, size_t n);
 int model_import(wt_model* M, const void* buf, size_t n);        // M->device set; allocates and uploads
 int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint64_t* arch_hash);
+std::string arch_refusal(const wt_arch& a);                      // empty: an architecture every plan kind has kernels for; else the refusal, naming the field
 // every device array of the model that a plan can read, by name (wt_model_weight_info): the arrays of the one walk
 enum : int { WFMT_F32 = 0, WFMT_S32 = 1, WFMT_LSTM_F16 = 2, WFMT_LSTM_PERSIST = 3 };
 struct WeightEntry {

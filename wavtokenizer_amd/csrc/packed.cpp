@@ -211,14 +211,36 @@ struct Validator {
 
 static int bad_image(const std::string& what) { set_error("packed image: " + what + " does not match the architecture in its header"); return WT_ERR_INVALID; }
 
+// The architectures this library runs: the one rule of wt_model_create, wt_model_create_packed and wt_packed_info, made before
+// any HIP call.  What passes here has kernels for every step of every plan kind; what does not is refused when the model is
+// created, never at plan creation or at a launch.  Returns the refusal (it names the field), empty when the architecture is taken.
+std::string arch_refusal(const wt_arch& a) {
+    if (a.n_ratios < 1 || a.n_ratios > 8) return "n_ratios out of range";
+    // a stage's down conv has 2 * ratio taps and both GEMM engines gather at most 32 (check_gemm16s, launch_gemm: the tap
+    // tables' share of LDS): a ratio above 16 loaded and then failed at the conv's launch
+    for (int i = 0; i < a.n_ratios; ++i) if (a.ratios[i] < 1 || a.ratios[i] > 16) return "ratios: every ratio must be 1 .. 16 (a down conv has 2 * ratio taps; the GEMM kernels gather at most 32)";
+    if ((32 << a.n_ratios) != 512) return "ratios: the encoder width after the last ratio must be 512 (32 * 2^n_ratios: four ratios)";          // mult * nf == H
+    if (a.num_quantizers < 1 || a.num_quantizers > 32) return "num_quantizers must be 1 .. 32 (encode_infer uses the first codebook: vq.py:137 forces n_q = 1; codes_to_features sums up to num_quantizers of them)";
+    if (a.input_channels != 512) return "input_channels must be 512 (SEANet dimension)";
+    // the row kernels (dwconv + LayerNorm, AdaLayerNorm: launch_rownorm) are built for these four widths
+    if (a.dim != 256 && a.dim != 512 && a.dim != 768 && a.dim != 1024) return "dim must be 256, 512, 768 or 1024";
+    if (a.intermediate_dim < 32 || a.intermediate_dim % 32) return "intermediate_dim must be a positive multiple of 32";
+    if (a.num_layers < 1 || a.num_layers > 32) return "num_layers must be 1 .. 32 (one range site per ConvNeXt block)";
+    if (a.adanorm_num_embeddings < 1) return "adanorm_num_embeddings must be >= 1: only the AdaLayerNorm backbone is implemented";
+    // the shipped encode plan runs the VQ distances on gemm16s.hip, whose argmax epilogue reads |e|^2 four columns at a time
+    if (a.vq_bins < 4 || a.vq_bins % 4) return "vq_bins must be a positive multiple of 4 (the VQ distance kernel takes four codebook columns at a time)";
+    if (a.n_fft < 4 || a.hop_length < 1) return "n_fft must be >= 4 and hop_length >= 1";
+    if (a.n_fft % a.hop_length || a.n_fft % 2 || (a.n_fft - a.hop_length) % 2) return "n_fft must be an even multiple of hop_length (the ISTFT kernel; n_fft and n_fft - hop_length even)";
+    if (a.n_fft % 4) return "n_fft % 4 must be 0 (the ISTFT kernel takes the spectrum in quarters)";
+    return {};
+}
+
 // what the walk takes for granted of the header's architecture
 static int check_arch(const wt_arch& a) {
-    if (a.n_ratios < 1 || a.n_ratios > 8 || a.num_quantizers < 1 || a.num_quantizers > 32 || a.input_channels != 512 || a.dim % 256 || a.intermediate_dim % 32 ||
-        a.num_layers < 1 || a.num_layers > 32 || a.adanorm_num_embeddings < 1 || a.vq_bins < 4 || a.vq_bins % 4 || a.n_fft < 4 || a.hop_length < 1) return bad_image("the architecture itself");
-    for (int i = 0; i < a.n_ratios; ++i) if (a.ratios[i] < 1 || a.ratios[i] > 64) return bad_image("a ratio");
-    if ((32 << a.n_ratios) != 512) return bad_image("the encoder tail");          // mult * nf == H
-    if (a.n_fft % 4 || a.n_fft % a.hop_length) return bad_image("n_fft / hop_length");
-    return WT_OK;
+    const std::string why = arch_refusal(a);
+    if (why.empty()) return WT_OK;
+    set_error("packed image: " + why + " (the architecture in its header)");
+    return WT_ERR_INVALID;
 }
 static int validate_imported(const wt_model* M) {
     if (int rc = check_arch(M->arch)) return rc;
@@ -383,6 +405,7 @@ int packed_info(const void* buf, size_t n, wt_arch* arch, int32_t* version, uint
     if (arch_hash) *arch_hash = h.arch_hash;
     if (h.version != PACK_VERSION) { set_error("packed image: layout version " + std::to_string(h.version) + ", this library reads " + std::to_string(PACK_VERSION)); return WT_ERR_INVALID; }
     if (h.arch_hash != arch_hash_of(h.arch)) { set_error("packed image: architecture hash mismatch (corrupt header)"); return WT_ERR_INVALID; }
+    if (int rc = check_arch(h.arch)) return rc;
     // every term is checked against what is left of the file before it is added: nothing here can wrap
     size_t left = n - sizeof(PackHeader);
     if (h.n_allocs > (1u << 16) || h.n_allocs * 8 > left) { set_error("packed image: truncated (allocation table)"); return WT_ERR_INVALID; }

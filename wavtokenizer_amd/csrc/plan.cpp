@@ -401,7 +401,8 @@ int build_encode(wt_plan* P) {
         for (const ResStage& st : M->stages) ok = ok && st.c3.k == 3 && st.sc.k == 1;     // (the geometry step's k3 / 1x1 convs)
         if (!ok) {
             set_error("mixed-length plans run only the shipped split-f16 encoder route: not with WT_PLAN_FLAG_UNFUSED, "
-                      "FP32_GEMM, KEEP_STAGES or RANGE_REPORT, an encoder range site on fp32, or weights without S32 copies");
+                      "FP32_GEMM, KEEP_STAGES or RANGE_REPORT, an encoder range site on fp32, weights without S32 copies, or a first "
+                      "encoder ratio other than 2 or 4 (no stage-1 kernel with the down conv)");
             return WT_ERR_INVALID;
         }
         P->min_clip = 1024;              // resblock16_down_fusable: the fused stage-1 kernel's shortest clip

@@ -505,7 +505,7 @@ int build_splits(wt_model* M) {
     // loaded into the full module tree: they only decide how the SEANetDecoder plan runs
     auto conv32sd = [&](ConvW& c) { return (c.cin % 32) ? 0 : add_s32(M, c.w, (long)c.cout * c.k * c.cin, &c.s32, &M->sd_s32_ok, true); };
     for (ResStage& st : M->stages) {            // encoder chain on S32 operands (build_encode)
-        if (st.down.cin % 32 == 0 && st.down.k == 2 * st.r && st.down.k <= 32) {
+        if (st.down.cin % 32 == 0 && st.down.k == 2 * st.r) {       // (k <= 32: arch_refusal takes ratios to 16, the GEMMs' 32 taps)
             // k = 2 * stride: every input frame feeds two output frames (taps j and j + stride).  Packing the taps as
             // (0, r, 1, r+1, ...) puts those two reads in adjacent K steps
             const long n = (long)st.down.cout * st.down.k * st.down.cin;
